@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- throughput of the SSE hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N = 1)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]         (N = 1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,6 +18,11 @@ data-path collective).  A secondary, separately timed leg measures the
 ranking-scale scoring path of configs[3] in weak form: 8192 queries against a
 row-sharded synthetic index (1.25 M x 256 rows per GPU), per-shard top-10,
 RCCL all-gather of the per-shard lists, k-way merge (`scoring_leg`).
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds everything else, as before:
+the secondary legs (the scoring leg above, split-bf16 and mid-batch encode, single-query latency, train step, recipe
+shapes, text-CNN, real rows, config sweep), the CPU baseline, the oracle parity spot check and the full legs file.
+--dump-outputs DIR writes the last timed step's encodings and top-10 scores / ids (rank 0) as DIR/*.npy.
 
 Prints ONE JSON line on rank 0.
 """
@@ -634,9 +639,10 @@ def _leg(d, ms_key, roof=None, **extra):
     return out
 
 
-def compact_headline(full):
+def compact_headline(full, with_legs=True):
     """The ONE line the driver parses: the contract keys, `roofline` and `cpu_baseline` without prose, and one compact
-    number set per secondary leg.  Everything else is in LEGS_FILE (and on the BENCH_LEGS line printed before it)."""
+    number set per secondary leg.  Everything else is in LEGS_FILE (and on the BENCH_LEGS line printed before it).
+    with_legs=False (a plain run, no secondary legs): the contract keys and `roofline` only."""
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data", "config", "cosine_scores_per_s", "top1_match_vs_oracle", "encode_max_abs_err_vs_oracle",
             "speedup_vs_cpu_baseline", "rccl_ranks_seen", "shard_bounds")
@@ -650,6 +656,8 @@ def compact_headline(full):
         line["cpu_baseline"] = {k: _r(cb.get(k), 6) for k in ("value", "unit", "cores", "kind", "host_cores", "replicas",
                                                                "threads_per_replica", "host_cpu_model", "scoring_scores_per_s")}
         line["cpu_baseline"]["sample"] = str(cb.get("sample", ""))[:160]
+    if not with_legs:
+        return json.dumps(line, separators=(",", ":"))
     legs = {}
     g = full.get
     if g("scoring_leg"):
@@ -714,14 +722,16 @@ def compact_headline(full):
     return text
 
 
-def emit(full):
-    """Full legs -> LEGS_FILE and an earlier, non-'{'-leading stdout line; the compact headline is the LAST line."""
-    try:
-        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-        with open(os.path.join(ROOT, LEGS_FILE), "w") as f:
-            json.dump(full, f, indent=1)
-    except OSError:
-        pass
+def emit(full, with_legs=True):
+    """Full legs -> LEGS_FILE and an earlier, non-'{'-leading stdout line; the compact headline is the LAST line.
+    with_legs=False (a plain run): the headline line alone."""
+    if with_legs:
+        try:
+            os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+            with open(os.path.join(ROOT, LEGS_FILE), "w") as f:
+                json.dump(full, f, indent=1)
+        except OSError:
+            pass
     # RCCL (NCCL_DEBUG=VERSION on the GPU boxes) prints its banner through C stdio, which would otherwise be
     # flushed at exit, AFTER this line: push it out first so that the JSON line is the last line of stdout
     try:
@@ -729,8 +739,32 @@ def emit(full):
         ctypes.CDLL(None).fflush(None)
     except Exception:
         pass
-    print("BENCH_LEGS " + json.dumps(full), flush=True)
-    print(compact_headline(full), flush=True)
+    if with_legs:
+        print("BENCH_LEGS " + json.dumps(full), flush=True)
+    print(compact_headline(full, with_legs=with_legs), flush=True)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, src_enc, top_s, top_i):
+    """--dump-outputs: what the timed path handed back in its last step -- the l2-normalised source encodings and the
+    top-10 scores and row ids per query -- as out_dir/<name>.npy (float32 / float64; ids < 2^53 are exact in float64).
+    When the batch would take more than DUMP_MAX_BYTES, the same fixed, seeded sample of rows is written from every
+    array, and its row numbers as sample_rows.npy."""
+    import numpy as np
+    arrays = {"src_enc": src_enc.cpu().numpy().astype(np.float32),
+              "top_scores": top_s.cpu().numpy().astype(np.float64),
+              "top_ids": top_i.cpu().numpy().astype(np.float64)}
+    rows = arrays["src_enc"].shape[0]
+    per_row = sum(a[0].nbytes for a in arrays.values())
+    if rows * per_row > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.RandomState(0).choice(rows, (DUMP_MAX_BYTES - 4096) // (per_row + 8), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["sample_rows"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def main():
@@ -752,7 +786,17 @@ def main():
     ap.add_argument("--no-shapes-leg", action="store_true")
     ap.add_argument("--no-realdata-leg", action="store_true")
     ap.add_argument("--no-sweep-leg", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs, the CPU baseline and the oracle parity check, and write the full legs "
+                         "to %s; a plain run times the headline steps only" % LEGS_FILE)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed (encodings, top-10 scores and ids) to DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:               # a plain run: setup, warm-up, the timed steps, the outputs, the headline line
+        for leg in ("cpu_baseline", "scoring_leg", "train_leg", "x3_leg", "cnn_leg", "shapes_leg", "realdata_leg", "sweep_leg"):
+            setattr(args, "no_" + leg, True)
 
     global PMC
     PMC = pmc_summary()
@@ -787,7 +831,7 @@ def main():
 
     # proof that RCCL saw every rank: an all-reduce of ones over the job's process group
     rccl_ranks_seen = 1
-    if use_dist:
+    if use_dist and args.full:
         ones = torch.ones(1, dtype=torch.float32, device=dev)
         dist.all_reduce(ones)
         rccl_ranks_seen = int(ones.item())
@@ -843,10 +887,12 @@ def main():
 
     value = world * B * args.steps / dt
     achieved_tflops = B * FLOP_PER_SEQ / (enc_ms_avg * 1e-3) / 1e12
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, src_enc, top_s, top_i)
 
-    # ---- parity spot check inside the bench: top-1 ids vs the float64 oracle on a sample
-    top1_match = None
-    if rank == 0:
+    # ---- parity spot check inside the bench (--full): top-1 ids vs the float64 oracle on a sample
+    top1_match = enc_err = None
+    if rank == 0 and args.full:
         from oracle import sse_oracle as O
         p = {k: v for k, v in m.get_variables().items()}
         ids_s = src_ids[:48].cpu().numpy()
@@ -1147,9 +1193,6 @@ def main():
                        "batch_per_gpu": B, "seq_len": T, "targets": N_TARGETS, "parallelism": "dp%d" % world,
                        "weights": "random-init (reference initialisers, seed 0)"},
             "cosine_scores_per_s": value * N_TARGETS,
-            "rccl_ranks_seen": rccl_ranks_seen,
-            "shard_bounds": shard_bounds,
-            "top1_match_vs_oracle": top1_match, "encode_max_abs_err_vs_oracle": enc_err,
             "roofline": {"kernel": "lstm_fwd_kernel<2>", "bound": "mfma", "achieved": achieved_tflops,
                          "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": achieved_tflops / PEAK_F32_MFMA_TFLOPS,
                          "traffic": traffic, "traffic_unit": "bytes/launch (PMC: (2 x FETCH_SIZE + WRITE_SIZE) x 1024, separate rocprofv3 "
@@ -1163,6 +1206,9 @@ def main():
                          "avg_kernel_ms": enc_ms_avg,
                          "algorithmic_flop_per_launch": B * FLOP_PER_SEQ},
         }
+        if args.full:
+            line.update({"rccl_ranks_seen": rccl_ranks_seen, "shard_bounds": shard_bounds,
+                         "top1_match_vs_oracle": top1_match, "encode_max_abs_err_vs_oracle": enc_err})
         if scoring is not None:
             line["scoring_leg"] = scoring
             line["scoring_leg_fp32_candidates"] = scoring_fp32
@@ -1185,7 +1231,7 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
             line["speedup_vs_cpu_baseline"] = value / line["cpu_baseline"]["value"]
-        emit(line)
+        emit(line, with_legs=args.full)
     if use_dist:
         dist.destroy_process_group()
 

@@ -94,3 +94,41 @@ def test_headline_line_stays_small_and_keeps_the_contract_keys():
     text = bench.compact_headline(fat)
     d = json.loads(text)
     assert len(text) <= bench.HEADLINE_MAX_BYTES and d["legs_truncated"] and "roofline" in d and "cpu_baseline" in d
+
+
+def test_plain_headline_has_no_legs():
+    """A plain run (no --full) prints the contract keys and `roofline` alone: no legs, no legs file named."""
+    full = json.load(open(os.path.join(bench.ROOT, "profiles", "r05z_bench.json")))
+    plain = {k: v for k, v in full.items() if k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+                                                    "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
+                                                    "cosine_scores_per_s", "roofline")}
+    d = json.loads(bench.compact_headline(plain, with_legs=False))
+    assert set(d) == set(plain) and "legs" not in d and "legs_file" not in d
+    assert d["ms_per_step"] == float("%.7g" % full["ms_per_step"]) and d["metric"] == full["metric"]
+
+
+def test_dump_outputs_writes_float_arrays_and_caps_the_size(tmp_path):
+    import numpy as np
+    import torch
+    rng = np.random.RandomState(0)
+    enc = torch.from_numpy(rng.standard_normal((300, 256)).astype(np.float32))
+    sc = torch.from_numpy(rng.standard_normal((300, 10)))
+    ids = torch.from_numpy(rng.randint(0, 571, size=(300, 10)).astype(np.int64))
+    bench.dump_outputs(str(tmp_path / "small"), enc, sc, ids)
+    got = {n: np.load(str(tmp_path / "small" / (n + ".npy"))) for n in ("src_enc", "top_scores", "top_ids")}
+    assert sorted(os.listdir(str(tmp_path / "small"))) == ["src_enc.npy", "top_ids.npy", "top_scores.npy"]
+    assert got["src_enc"].dtype == np.float32 and np.array_equal(got["src_enc"], enc.numpy())
+    assert got["top_scores"].dtype == np.float64 and np.array_equal(got["top_scores"], sc.numpy())
+    assert got["top_ids"].dtype == np.float64 and np.array_equal(got["top_ids"], ids.numpy())
+    # a batch past the cap: the same seeded rows of every array, and their row numbers
+    rows = bench.DUMP_MAX_BYTES // (256 * 4) + 1000
+    big = torch.arange(rows, dtype=torch.float32)[:, None].repeat(1, 256)
+    big_ids = torch.arange(rows, dtype=torch.int64)[:, None].repeat(1, 10)
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), big, big_ids.double(), big_ids)
+    total = sum(os.path.getsize(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a")))
+    assert total <= bench.DUMP_MAX_BYTES
+    keep = np.load(str(tmp_path / "a" / "sample_rows.npy"))
+    assert np.array_equal(keep, np.load(str(tmp_path / "b" / "sample_rows.npy"))) and np.all(np.diff(keep) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "a" / "src_enc.npy"))[:, 0], keep)
+    assert np.array_equal(np.load(str(tmp_path / "a" / "top_ids.npy"))[:, 3], keep)
