@@ -30,6 +30,18 @@ struct Variable {
   float *grad = nullptr;    // gradient of the current step (allocated by the first train step)
 };
 
+// pad-prefix table: state after p leading PAD steps, p = 0..T ([T+1][width] each), recorded by the kernel that reads it
+struct PadTable {
+  float *h = nullptr, *c = nullptr;
+  int T = 0;
+  bool valid = false;
+  void release() {
+    if (h) (void)hipFree(h);
+    if (c) (void)hipFree(c);
+    h = c = nullptr;
+  }
+};
+
 struct Encoder {
   int kernel = -1, bias = -1, proj = -1;  // variable indices
   int H = 0, Hp = 0, UB = 0, KGx = 0, KGh = 0, Ep = 0;
@@ -41,19 +53,11 @@ struct Encoder {
   unsigned short *Wx3 = nullptr;  // option lstm_x3: hi / lo bf16 fragment copies of the kernel matrix
   bool x3_valid = false;
   unsigned short *Wx3t = nullptr;  // option train_fwd_x3: the same copies with the h part in unit order (training forward)
-  float *pad_h_x3 = nullptr, *pad_c_x3 = nullptr;  // pad-prefix table of the lstm_x3 path ([pad_T_x3+1][Hp])
-  int pad_T_x3 = 0;
-  bool pad_valid_x3 = false;
   int shares_lstm_with = -1;  // shared-encoder: target reuses the source LSTM packing
   bool generic = false;       // shape outside the fused kernels' layouts: every encode / train step of this encoder runs lstm_generic.hip
-  // pad-prefix table: state after p leading PAD steps, p = 0..pad_T ([pad_T+1][Hp] each)
-  float *pad_h = nullptr, *pad_c = nullptr;
-  int pad_T = 0;
-  bool pad_valid = false;
-  // the same table for the few-sequences kernel (lstm_small.hip), produced by that kernel ([pad_T_small+1][H])
-  float *pad_h_small = nullptr, *pad_c_small = nullptr;
-  int pad_T_small = 0;
-  bool pad_valid_small = false;
+  // pad-prefix tables of the LSTM owner: matrix kernel (lstm_fwd.hip, Hp wide), few-sequences kernel (lstm_small.hip, H wide;
+  // the two cluster kernels share its arithmetic and read it too), lstm_x3 path (Hp wide)
+  PadTable pad_fwd, pad_small, pad_x3;
 };
 
 struct DevBuf {  // grow-only device scratch; freed with its owner (handle / TrainState)
@@ -196,8 +200,6 @@ struct sse_handle {
   size_t pin_cap = 0;
   int32_t score_seq = 0;  // call number the re-scoring pass stores into the pinned completion flags (ScoreMirror)
   DevBuf s_pb, s_cthr, s_cslot, s_ccnt, s_cbuf;  // per-split bounds; collect path: thresholds, slots, counters, row buffers
-  const int32_t *cur_row_map = nullptr;  // set by sse_encode around its launch
-  bool cur_padded_hint = false;          // ... together with this: the batch's mean leading-PAD count is >= T / 4
   // training
   float lr = 0.9f;
   int64_t global_step = 0;
@@ -300,6 +302,14 @@ static int emb_cols(const sse_config &c) {
   return c.network_mode == SSE_MODE_SOURCE_ONLY_CNN ? round_up(c.embedding_size, 4) : round_up(c.embedding_size + 1, 8);
 }
 
+Encoder &lstm_owner(sse_handle *h, Encoder &e) { return e.shares_lstm_with >= 0 ? h->enc[e.shares_lstm_with] : e; }
+
+// the layouts and pad-prefix tables made from the LSTM weights on demand: stale once the weights change
+void invalidate_derived(Encoder &e) {
+  e.waug_valid = e.wc_valid = e.x3_valid = false;
+  e.pad_fwd.valid = e.pad_small.valid = e.pad_x3.valid = false;
+}
+
 // (re)build the kernel-facing layouts from the master variables
 // the packed projections alone (what a train step whose LSTM kernels all run on split operands reads of these layouts):
 // the embedding pad, the fp32 kernel fragments and the CNN layouts stay stale (packed_dirty) until an encode needs them
@@ -328,12 +338,7 @@ int ensure_packed(sse_handle *h, hipStream_t st) {
   for (int s = 0; s < 2; ++s) {
     Encoder &e = h->enc[s];
     if (e.H <= 0 || e.kernel < 0 || e.generic) continue;
-    e.pad_valid = false;
-    e.pad_valid_small = false;
-    e.waug_valid = false;
-    e.wc_valid = false;
-    e.x3_valid = false;
-    e.pad_valid_x3 = false;
+    invalidate_derived(e);
     const int KG = e.KGx + e.KGh;
     if (e.shares_lstm_with < 0) {
       if (!e.Wp) HIPCHECK(h, hipMalloc((void **)&e.Wp, (size_t)(e.Hp / 32) * KG * 4 * 256 * sizeof(float)));
@@ -388,7 +393,7 @@ int pack_train_fp32(sse_handle *h, TrainState &ts, int nside, hipStream_t st) {
     for (int s = 0; s < 2; ++s) {
       Encoder &e = h->enc[s];
       if (e.H <= 0 || e.kernel < 0) continue;
-      e.pad_valid = e.pad_valid_small = e.waug_valid = e.wc_valid = e.x3_valid = e.pad_valid_x3 = false;
+      invalidate_derived(e);
       const int KG = e.KGx + e.KGh;
       if (e.shares_lstm_with < 0) {
         if (!e.Wp) HIPCHECK(h, hipMalloc((void **)&e.Wp, (size_t)(e.Hp / 32) * KG * 4 * 256 * sizeof(float)));
@@ -440,45 +445,31 @@ void fill_fwd_args(sse_handle *h, Encoder &e, LstmFwdArgs &a) {
   a.cu_count = h->cu_count;  // (set by sse_create)
 }
 
-// state after p leading PAD steps for p = 0..T: one all-PAD row through the SAME kernel
-// (bit-identical arithmetic), recorded step by step
-int ensure_pad_table(sse_handle *h, int side, int T, hipStream_t st) {
-  Encoder &e = h->enc[side];
-  Encoder &own = e.shares_lstm_with >= 0 ? h->enc[e.shares_lstm_with] : e;
-  if (!(own.pad_valid && own.pad_T >= T)) {
-    const int Tt = T > h->cfg.max_seq_length ? T : h->cfg.max_seq_length;
-    if (own.pad_T < Tt || !own.pad_h) {
-      if (own.pad_h) HIPCHECK(h, hipFree(own.pad_h));
-      if (own.pad_c) HIPCHECK(h, hipFree(own.pad_c));
-      own.pad_h = own.pad_c = nullptr;
-      HIPCHECK(h, hipMalloc((void **)&own.pad_h, (size_t)(Tt + 1) * own.Hp * sizeof(float)));
-      HIPCHECK(h, hipMalloc((void **)&own.pad_c, (size_t)(Tt + 1) * own.Hp * sizeof(float)));
-      own.pad_T = Tt;
-    }
-    HIPCHECK(h, hipMemsetAsync(own.pad_h, 0, (size_t)(Tt + 1) * own.Hp * sizeof(float), st));
-    HIPCHECK(h, hipMemsetAsync(own.pad_c, 0, (size_t)(Tt + 1) * own.Hp * sizeof(float), st));
-    if (reserve(h, h->s_zero, (size_t)Tt * sizeof(int32_t) + (size_t)h->cfg.encoding_size * sizeof(float))) return 1;
-    HIPCHECK(h, hipMemsetAsync(h->s_zero.p, 0, (size_t)Tt * sizeof(int32_t), st));
-    LstmFwdArgs a;
-    fill_fwd_args(h, own, a);
-    a.ids = (const int32_t *)h->s_zero.p;
-    a.out = (float *)((char *)h->s_zero.p + (size_t)Tt * sizeof(int32_t));
-    a.B = 1;
-    a.T = Tt;
-    a.normalize = 0;
-    a.rec_h = own.pad_h;
-    a.rec_c = own.pad_c;
-    HIPCHECK(h, launch_lstm_fwd(a, own.Hp, st));
-    own.pad_valid = true;
+// State after p leading PAD steps for p = 0..T: one all-PAD row through the kernel that reads the table (bit-identical
+// arithmetic), recorded step by step.  record(ids, out, Tt) launches that row: Tt zero ids, scratch output, rec_h / rec_c = t.
+template <class Record>
+int ensure_pad_table(sse_handle *h, PadTable &t, int width, int T, hipStream_t st, Record record) {
+  if (t.valid && t.T >= T) return 0;
+  const int Tt = T > h->cfg.max_seq_length ? T : h->cfg.max_seq_length;
+  const size_t bytes = (size_t)(Tt + 1) * width * sizeof(float);
+  if (t.T < Tt || !t.h) {
+    if (t.h) HIPCHECK(h, hipFree(t.h));
+    if (t.c) HIPCHECK(h, hipFree(t.c));
+    t.h = t.c = nullptr;
+    HIPCHECK(h, hipMalloc((void **)&t.h, bytes));
+    HIPCHECK(h, hipMalloc((void **)&t.c, bytes));
+    t.T = Tt;
   }
-  e.pad_h = own.pad_h;
-  e.pad_c = own.pad_c;
+  HIPCHECK(h, hipMemsetAsync(t.h, 0, bytes, st));
+  HIPCHECK(h, hipMemsetAsync(t.c, 0, bytes, st));
+  if (reserve(h, h->s_zero, (size_t)Tt * sizeof(int32_t) + (size_t)h->cfg.encoding_size * sizeof(float))) return 1;
+  HIPCHECK(h, hipMemsetAsync(h->s_zero.p, 0, (size_t)Tt * sizeof(int32_t), st));
+  if (record((const int32_t *)h->s_zero.p, (float *)((char *)h->s_zero.p + (size_t)Tt * sizeof(int32_t)), Tt)) return 1;
+  t.valid = true;
   return 0;
 }
 
-int ensure_waug(sse_handle *h, int side, hipStream_t st) {
-  Encoder &e = h->enc[side];
-  Encoder &own = e.shares_lstm_with >= 0 ? h->enc[e.shares_lstm_with] : e;
+int ensure_waug(sse_handle *h, Encoder &own, hipStream_t st) {
   if (own.waug_valid) return 0;
   const int E = h->cfg.embedding_size;
   if (!own.Waug) HIPCHECK(h, hipMalloc((void **)&own.Waug, lstm_small_waug_floats(E, own.H) * sizeof(float)));
@@ -487,11 +478,12 @@ int ensure_waug(sse_handle *h, int side, hipStream_t st) {
   return 0;
 }
 
-void fill_small_args(sse_handle *h, Encoder &e, LstmSmallArgs &a) {
+// LstmSmallArgs / LstmPersistArgs: the few-sequences kernel and the single-query cluster kernel read the same operands
+template <class Args>
+void fill_small_args(sse_handle *h, Encoder &e, Args &a) {
   const sse_config &c = h->cfg;
-  Encoder &own = e.shares_lstm_with >= 0 ? h->enc[e.shares_lstm_with] : e;
   a.emb = h->vars[0].dev;
-  a.Waug = own.Waug;
+  a.Waug = lstm_owner(h, e).Waug;
   a.M = h->vars[e.proj].dev;
   a.err = h->err_flag;
   a.V = c.vocab_size;
@@ -501,38 +493,22 @@ void fill_small_args(sse_handle *h, Encoder &e, LstmSmallArgs &a) {
   a.pad_stride = e.H;
 }
 
-// pad-prefix table of the few-sequences kernel: one all-PAD row through THAT kernel (its own arithmetic, bit for bit)
-int ensure_pad_table_small(sse_handle *h, int side, int T, hipStream_t st) {
-  Encoder &e = h->enc[side];
-  Encoder &own = e.shares_lstm_with >= 0 ? h->enc[e.shares_lstm_with] : e;
-  if (own.pad_valid_small && own.pad_T_small >= T) return 0;
-  const int Tt = T > h->cfg.max_seq_length ? T : h->cfg.max_seq_length;
-  if (own.pad_T_small < Tt || !own.pad_h_small) {
-    if (own.pad_h_small) HIPCHECK(h, hipFree(own.pad_h_small));
-    if (own.pad_c_small) HIPCHECK(h, hipFree(own.pad_c_small));
-    own.pad_h_small = own.pad_c_small = nullptr;
-    HIPCHECK(h, hipMalloc((void **)&own.pad_h_small, (size_t)(Tt + 1) * own.H * sizeof(float)));
-    HIPCHECK(h, hipMalloc((void **)&own.pad_c_small, (size_t)(Tt + 1) * own.H * sizeof(float)));
-    own.pad_T_small = Tt;
-  }
-  HIPCHECK(h, hipMemsetAsync(own.pad_h_small, 0, (size_t)(Tt + 1) * own.H * sizeof(float), st));
-  HIPCHECK(h, hipMemsetAsync(own.pad_c_small, 0, (size_t)(Tt + 1) * own.H * sizeof(float), st));
-  if (reserve(h, h->s_zero, (size_t)Tt * sizeof(int32_t) + (size_t)h->cfg.encoding_size * sizeof(float))) return 1;
-  HIPCHECK(h, hipMemsetAsync(h->s_zero.p, 0, (size_t)Tt * sizeof(int32_t), st));
-  if (ensure_waug(h, side, st)) return 1;
-  LstmSmallArgs a;
-  // the LSTM of `own` with any projection of that cell size (the table only records h, c)
-  fill_small_args(h, own, a);
-  a.ids = (const int32_t *)h->s_zero.p;
-  a.out = (float *)((char *)h->s_zero.p + (size_t)Tt * sizeof(int32_t));
-  a.B = 1;
-  a.T = Tt;
-  a.normalize = 0;
-  a.rec_h = own.pad_h_small;
-  a.rec_c = own.pad_c_small;
-  HIPCHECK(h, launch_lstm_small(a, st));
-  own.pad_valid_small = true;
-  return 0;
+// pad-prefix table of the few-sequences kernel (lstm_small.hip); both cluster kernels share its arithmetic and read it too
+int ensure_pad_table_small(sse_handle *h, Encoder &own, int T, hipStream_t st) {
+  return ensure_pad_table(h, own.pad_small, own.H, T, st, [&](const int32_t *ids, float *out, int Tt) {
+    if (ensure_waug(h, own, st)) return 1;
+    LstmSmallArgs a;
+    fill_small_args(h, own, a);  // the LSTM of `own` with any projection of that cell size (the table only records h, c)
+    a.ids = ids;
+    a.out = out;
+    a.B = 1;
+    a.T = Tt;
+    a.normalize = 0;
+    a.rec_h = own.pad_small.h;
+    a.rec_c = own.pad_small.c;
+    HIPCHECK(h, launch_lstm_small(a, st));
+    return 0;
+  });
 }
 
 // Batches the MFMA cluster kernel (lstm_cluster.hip) takes: 33 rows up to lstm_cluster_chunks launches of lstm_cluster_rows
@@ -557,21 +533,47 @@ static int ensure_cu_count(sse_handle *h) {
   return 0;
 }
 
-// Would encode_dev_locked hand a batch of this shape to the MFMA cluster kernel RIGHT NOW?  One test for the launch path and
-// for the host-side pad-prefix row sort (which the cluster kernel does not want and the matrix kernel does): shape, the
-// back-off counter after a give-up, the device's CU count and the LDS fit all enter (the sort used to be
-// switched off by the shape alone, so a backed-off or small device lost the pad skip silently).
-static bool cluster_takes(sse_handle *h, const Encoder &e, int B, int T) {
+// what the caller of one inference encode knows beyond the ids
+struct EncodeRequest {
+  const int32_t *row_map = nullptr;  // host pad-prefix row sort (encode_host_ids_locked): row b of the kernels is caller row row_map[b]
+  bool padded_hint = false;          // ... with it: the batch's mean leading-PAD count is >= T / 4
+  bool allow_cluster = true;         // false: the re-run of a batch whose cluster-kernel launch gave up (encode_fallback_locked)
+};
+
+enum class LstmPath { Persist, Cluster, Small, X3, Fwd, Error /* h->err is set */ };
+
+// The LSTM kernel that runs an inference encode of B x T ids of encoder e, first match wins.  The only reader of the
+// back-off after a give-up (cluster_skip): an eligible call of a backed-off kernel counts it down and goes on to the next
+// candidate.  dry_run: report the choice only, count nothing down -- the host-side pad-prefix row sort asks ahead of the call
+// whether the cluster kernel, which does not want the sort, will take the batch (shape, back-off, the device's CU
+// count and the LDS fit all enter).
+LstmPath choose_lstm_path(sse_handle *h, const Encoder &e, int B, int T, const EncodeRequest &rq, bool dry_run = false) {
   const sse_config &c = h->cfg;
-  if (h->cur_row_map || lstm_small_lds_bytes(c.embedding_size, e.H, c.encoding_size) > 160 * 1024) return false;
-  if (!(B > 32 && B <= cluster_row_limit(h, e) && T <= lstm_persist_max_steps() &&
-        lstm_cluster_ok(c.embedding_size, e.H, c.encoding_size)))
-    return false;
-  if (h->cluster_skip[1] > 0) return false;
-  if (ensure_cu_count(h)) return false;
-  const int per = std::min(h->lstm_cluster_rows, lstm_cluster_max_rows());
-  const int ncl = (std::min(B, per) + 63) / 64;
-  return (ncl <= 8 ? 128 : 256) <= h->cu_count;
+  const bool small_ok = !rq.row_map && lstm_small_lds_bytes(c.embedding_size, e.H, c.encoding_size) <= 160 * 1024;
+  // one to a few queries: the single-query cluster kernel, with every workgroup of the launch resident at once (at most half
+  // the CUs are asked for)
+  if (rq.allow_cluster && small_ok && B <= h->lstm_persist_rows && B <= lstm_persist_max_rows() && T <= lstm_persist_max_steps()) {
+    if (h->cluster_skip[0] > 0) {
+      if (!dry_run) --h->cluster_skip[0];
+    } else {
+      const int nwg = lstm_persist_nwg(c.embedding_size, e.H, c.encoding_size);
+      if (ensure_cu_count(h)) return LstmPath::Error;
+      if (nwg > 0 && 8 * nwg * 2 <= h->cu_count) return LstmPath::Persist;
+    }
+  }
+  // mid-size batches: the MFMA cluster kernel, one CU per workgroup (a failed CU-count query is a silent "no" here)
+  if (rq.allow_cluster && small_ok && B > 32 && B <= cluster_row_limit(h, e) && T <= lstm_persist_max_steps() &&
+      lstm_cluster_ok(c.embedding_size, e.H, c.encoding_size)) {
+    if (h->cluster_skip[1] > 0) {
+      if (!dry_run) --h->cluster_skip[1];
+    } else if (!ensure_cu_count(h)) {
+      const int ncl = (std::min(B, std::min(h->lstm_cluster_rows, lstm_cluster_max_rows())) + 63) / 64;
+      if ((ncl <= 8 ? 128 : 256) <= h->cu_count) return LstmPath::Cluster;
+    }
+  }
+  if (B <= h->lstm_small_rows && small_ok) return LstmPath::Small;
+  if (x3_applies(h, e)) return LstmPath::X3;
+  return LstmPath::Fwd;
 }
 
 // Inference encode of an encoder whose shape is outside the fused kernels' layouts: lstm_generic.hip, row chunks sized so
@@ -634,8 +636,216 @@ static int device_pad_sort(sse_handle *h, int side, const int32_t *ids, int B, i
   return 0;
 }
 
-int encode_dev_locked(sse_handle *h, int side, const int32_t *ids, int B, int T, int normalize, float *out,
-                      hipStream_t st) {
+// Tag epoch of the next launch of a cluster kernel on its exchange buffer (need bytes): a fresh or re-sized buffer, or a 20-bit
+// epoch that ran out, first has all its tags set to "never written".
+int next_epoch(sse_handle *h, DevBuf &xchg, uint32_t &epoch, size_t need, hipStream_t st, uint32_t *next) {
+  if (epoch == 0 || epoch >= (1u << 20) - 1 || need > xchg.cap) {
+    if (reserve(h, xchg, need)) return 1;
+    HIPCHECK(h, hipMemsetAsync(xchg.p, 0, xchg.cap, st));
+    epoch = 0;
+  }
+  *next = ++epoch;
+  return 0;
+}
+
+// testing aid (option lstm_persist_inject_miss): after a cluster-kernel launch, pretend a workgroup never arrived
+int inject_miss(sse_handle *h, hipStream_t st) {
+  static const int32_t four = 4;
+  if (h->persist_inject) HIPCHECK(h, hipMemcpyAsync(h->err_flag, &four, sizeof four, hipMemcpyHostToDevice, st));
+  return 0;
+}
+
+// one to a few queries (sse_demo / webserver): a cluster of workgroups with the weights resident in LDS, see lstm_persist.hip
+int encode_persist(sse_handle *h, int side, const int32_t *ids, int B, int T, int normalize, float *out, hipStream_t st) {
+  Encoder &e = h->enc[side], &own = lstm_owner(h, e);
+  if (ensure_waug(h, own, st)) return 1;
+  LstmPersistArgs pa;
+  fill_small_args(h, e, pa);
+  pa.ids = ids;
+  pa.out = out;
+  pa.B = B;
+  pa.T = T;
+  pa.normalize = normalize ? 1 : 0;
+  if (h->pad_skip && T > 1) {
+    if (ensure_pad_table_small(h, own, T, st)) return 1;  // same arithmetic, same table
+    pa.pad_h = own.pad_small.h;
+    pa.pad_c = own.pad_small.c;
+  }
+  const size_t nhx = lstm_persist_hx_words(e.H), nraw = lstm_persist_raw_words(h->cfg.encoding_size);
+  if (next_epoch(h, h->s_persist, h->persist_epoch, (nhx + nraw) * sizeof(unsigned long long), st, &pa.epoch)) return 1;
+  pa.write_through = h->lstm_cluster_wt;
+  pa.plain_launch = h->lstm_cluster_coop ? 0 : 1;
+  pa.hx = (unsigned long long *)h->s_persist.p;
+  pa.rawx = pa.hx + nhx;
+  HIPCHECK(h, launch_lstm_persist(pa, st));
+  return inject_miss(h, st);
+}
+
+// mid-size batches (the evaluator's 600, the index builder's 1000): the hidden units of every 64-row tile spread over a
+// cluster of 16 compute units, weights in LDS, h_t exchanged per step (lstm_cluster.hip); launches of lstm_cluster_rows rows
+int encode_cluster(sse_handle *h, int side, const int32_t *ids, int B, int T, int normalize, float *out, hipStream_t st) {
+  const sse_config &c = h->cfg;
+  Encoder &e = h->enc[side], &own = lstm_owner(h, e);
+  if (!own.wc_valid) {
+    if (!own.Wc) HIPCHECK(h, hipMalloc((void **)&own.Wc, lstm_cluster_weight_floats(c.embedding_size, own.H) * sizeof(float)));
+    HIPCHECK(h, launch_pack_lstm_cluster(h->vars[own.kernel].dev, h->vars[own.bias].dev, c.embedding_size, own.H, own.Wc, st));
+    own.wc_valid = true;
+  }
+  LstmClusterArgs ca;
+  ca.emb = h->emb_pad;
+  ca.Wc = own.Wc;
+  ca.Mp = e.Mp;
+  ca.err = h->err_flag;
+  ca.T = T;
+  ca.V = c.vocab_size;
+  ca.E = c.embedding_size;
+  ca.Ep = e.Ep;
+  ca.KGx = e.KGx;
+  ca.H = e.H;
+  ca.Hp = e.H <= 128 ? 128 : 256;
+  ca.KGh = ca.Hp / 8;
+  ca.S = c.encoding_size;
+  ca.NTS = (c.encoding_size + 31) / 32;
+  ca.normalize = normalize ? 1 : 0;
+  if (h->pad_skip && T > 1) {
+    if (ensure_pad_table_small(h, own, T, st)) return 1;  // lstm_small's table: the same arithmetic
+    ca.pad_h = own.pad_small.h;
+    ca.pad_c = own.pad_small.c;
+    ca.pad_stride = e.H;
+  }
+  ca.write_through = h->lstm_cluster_wt;
+  ca.plain_launch = h->lstm_cluster_coop ? 0 : 1;
+  ca.drop_wg = h->lstm_cluster_drop;
+  const int per = std::min(h->lstm_cluster_rows, lstm_cluster_max_rows());
+  const size_t nhx = lstm_cluster_hx_words(e.H), nsx = lstm_cluster_sx_words();
+  for (int c0 = 0; c0 < B; c0 += per) {  // launches of the same stream reuse the exchange buffers under new epochs
+    if (next_epoch(h, h->s_cluster, h->cluster_epoch, (nhx + nsx) * sizeof(unsigned long long), st, &ca.epoch)) return 1;
+    ca.hx = (unsigned long long *)h->s_cluster.p;
+    ca.sx = ca.hx + nhx;
+    ca.ids = ids + (size_t)c0 * T;
+    ca.out = out + (size_t)c0 * c.encoding_size;
+    ca.B = std::min(per, B - c0);
+    HIPCHECK(h, launch_lstm_cluster(ca, st));
+  }
+  return inject_miss(h, st);
+}
+
+// a handful of sequences (demo / web query, last batch of an index build): GEMV on the vector ALUs, see lstm_small.hip
+int encode_small(sse_handle *h, int side, const int32_t *ids, int B, int T, int normalize, float *out, hipStream_t st) {
+  Encoder &e = h->enc[side], &own = lstm_owner(h, e);
+  if (ensure_waug(h, own, st)) return 1;
+  LstmSmallArgs sa;
+  fill_small_args(h, e, sa);
+  sa.ids = ids;
+  sa.out = out;
+  sa.B = B;
+  sa.T = T;
+  sa.normalize = normalize ? 1 : 0;
+  if (h->pad_skip && T > 1) {
+    if (ensure_pad_table_small(h, own, T, st)) return 1;
+    sa.pad_h = own.pad_small.h;
+    sa.pad_c = own.pad_small.c;
+  }
+  HIPCHECK(h, launch_lstm_small(sa, st));
+  return 0;
+}
+
+// opt-in: the gate GEMMs on the bf16 matrix pipe with hi + lo split operands (lstm_fwd_x3.hip); ~1e-5 from the fp32 path
+int encode_x3(sse_handle *h, int side, const int32_t *ids, int B, int T, int normalize, float *out, const EncodeRequest &rq,
+              hipStream_t st) {
+  const sse_config &c = h->cfg;
+  Encoder &e = h->enc[side], &own = lstm_owner(h, e);
+  const int E = c.embedding_size;
+  if (!own.x3_valid || !h->emb16_valid) {
+    if (!own.Wx3) HIPCHECK(h, hipMalloc((void **)&own.Wx3, lstm_x3_weight_elems(E, own.Hp) * sizeof(unsigned short)));
+    if (!h->emb16) HIPCHECK(h, hipMalloc((void **)&h->emb16, lstm_x3_emb_elems(c.vocab_size, E) * sizeof(unsigned short)));
+    HIPCHECK(h, launch_pack_lstm_x3(h->vars[own.kernel].dev, h->vars[own.bias].dev, h->vars[0].dev, c.vocab_size, E, own.H,
+                                    own.Hp, own.Wx3, h->emb16_valid ? nullptr : h->emb16, 0, st));
+    own.x3_valid = true;
+    h->emb16_valid = true;
+  }
+  LstmX3Args xa;
+  xa.ids = ids;
+  xa.emb16 = h->emb16;
+  xa.Wx3 = own.Wx3;
+  xa.Mp = e.Mp;
+  xa.out = out;
+  xa.err = h->err_flag;
+  xa.B = B;
+  xa.T = T;
+  xa.V = c.vocab_size;
+  xa.KGX = lstm_x3_kgx(E);
+  xa.H = e.H;
+  xa.S = c.encoding_size;
+  xa.NTS = (c.encoding_size + 31) / 32;
+  xa.normalize = normalize ? 1 : 0;
+  xa.row_map = rq.row_map;
+  bool padded = false;
+  if (device_pad_sort(h, side, ids, B, T, st, &xa.row_map, &padded)) return 1;
+  if (h->pad_skip && T > 1) {
+    if (ensure_pad_table(h, own.pad_x3, own.Hp, T, st, [&](const int32_t *zero_ids, float *scratch, int Tt) {
+          LstmX3Args ta = xa;
+          ta.ids = zero_ids;
+          ta.out = scratch;
+          ta.B = 1;
+          ta.T = Tt;
+          ta.normalize = 0;
+          ta.row_map = nullptr;
+          ta.rec_h = own.pad_x3.h;
+          ta.rec_c = own.pad_x3.c;
+          HIPCHECK(h, launch_lstm_fwd_x3(ta, st));
+          return 0;
+        }))
+      return 1;
+    xa.pad_h = own.pad_x3.h;
+    xa.pad_c = own.pad_x3.c;
+  }
+  HIPCHECK(h, launch_lstm_fwd_x3(xa, st));
+  return 0;
+}
+
+// the MFMA matrix kernel (lstm_fwd.hip / lstm_fwd_gs.hip): any batch
+int encode_fwd(sse_handle *h, int side, const int32_t *ids, int B, int T, int normalize, float *out, const EncodeRequest &rq,
+               hipStream_t st) {
+  Encoder &e = h->enc[side], &own = lstm_owner(h, e);
+  LstmFwdArgs a;
+  fill_fwd_args(h, e, a);
+  a.ids = ids;
+  a.out = out;
+  a.B = B;
+  a.T = T;
+  a.normalize = normalize ? 1 : 0;
+  a.row_map = rq.row_map;
+  bool padded_hint = rq.padded_hint;
+  if (device_pad_sort(h, side, ids, B, T, st, &a.row_map, &padded_hint)) return 1;
+  if (h->pad_skip && T > 1) {
+    if (ensure_pad_table(h, own.pad_fwd, own.Hp, T, st, [&](const int32_t *zero_ids, float *scratch, int Tt) {
+          LstmFwdArgs ta;
+          fill_fwd_args(h, own, ta);
+          ta.ids = zero_ids;
+          ta.out = scratch;
+          ta.B = 1;
+          ta.T = Tt;
+          ta.normalize = 0;
+          ta.rec_h = own.pad_fwd.h;
+          ta.rec_c = own.pad_fwd.c;
+          HIPCHECK(h, launch_lstm_fwd(ta, own.Hp, st));
+          return 0;
+        }))
+      return 1;
+    a.pad_h = own.pad_fwd.h;
+    a.pad_c = own.pad_fwd.c;
+    // a heavily left-padded batch sorted by pad count (sse_encode's host path knows both): tiles differ in length, the finer
+    // 32-row granularity with two workgroups per CU balances them better -- crosslingual index build 2.96 -> 2.64 ms, queries
+    // 1.24 -> 0.84 ms (profiles/r05_notes.txt)
+    if (padded_hint && a.row_map && e.Hp <= 256) a.force_rows = 32;
+  }
+  HIPCHECK(h, launch_lstm_fwd(a, e.Hp, st));
+  return 0;
+}
+
+int encode_dev_locked(sse_handle *h, int side, const int32_t *ids, int B, int T, int normalize, float *out, hipStream_t st,
+                      const EncodeRequest &rq = EncodeRequest()) {
   const sse_config &c = h->cfg;
   if (side != SSE_SIDE_SOURCE && side != SSE_SIDE_TARGET) return fail(h, "side must be 0 (source) or 1 (target)");
   if (B < 0 || T < 1) return fail(h, "bad batch shape B=%d T=%d", B, T);
@@ -676,240 +886,15 @@ int encode_dev_locked(sse_handle *h, int side, const int32_t *ids, int B, int T,
   if (e.kernel < 0) return fail(h, "network mode has no %s sequence encoder (sse_model.py:231-233)", side ? "target" : "source");
   if (e.generic) return encode_generic_locked(h, e, ids, B, T, normalize, out, st);
   if (ensure_packed(h, st)) return 1;
-  const bool small_ok = !h->cur_row_map && lstm_small_lds_bytes(c.embedding_size, e.H, c.encoding_size) <= 160 * 1024;
-  bool persist_shape = small_ok && B <= h->lstm_persist_rows && B <= lstm_persist_max_rows() && T <= lstm_persist_max_steps();
-  if (persist_shape && h->cluster_skip[0] > 0) {  // backing off after a launch that gave up
-    --h->cluster_skip[0];
-    persist_shape = false;
+  switch (choose_lstm_path(h, e, B, T, rq)) {
+    case LstmPath::Persist: return encode_persist(h, side, ids, B, T, normalize, out, st);
+    case LstmPath::Cluster: return encode_cluster(h, side, ids, B, T, normalize, out, st);
+    case LstmPath::Small: return encode_small(h, side, ids, B, T, normalize, out, st);
+    case LstmPath::X3: return encode_x3(h, side, ids, B, T, normalize, out, rq, st);
+    case LstmPath::Fwd: return encode_fwd(h, side, ids, B, T, normalize, out, rq, st);
+    case LstmPath::Error: break;
   }
-  if (persist_shape) {
-    // one to a few queries (sse_demo / webserver): a cluster of workgroups with the weights resident in LDS, see
-    // lstm_persist.hip.  Needs every workgroup of the launch resident at once: at most half the CUs are asked for.
-    const int nwg = lstm_persist_nwg(c.embedding_size, e.H, c.encoding_size);
-    if (ensure_cu_count(h)) return 1;
-    if (nwg > 0 && 8 * nwg * 2 <= h->cu_count) {
-      if (ensure_waug(h, side, st)) return 1;
-      LstmSmallArgs sa;
-      fill_small_args(h, e, sa);
-      LstmPersistArgs pa;
-      pa.emb = sa.emb;
-      pa.Waug = sa.Waug;
-      pa.M = sa.M;
-      pa.err = sa.err;
-      pa.V = sa.V;
-      pa.E = sa.E;
-      pa.H = sa.H;
-      pa.S = sa.S;
-      pa.pad_stride = sa.pad_stride;
-      pa.ids = ids;
-      pa.out = out;
-      pa.B = B;
-      pa.T = T;
-      pa.normalize = normalize ? 1 : 0;
-      if (h->pad_skip && T > 1) {
-        if (ensure_pad_table_small(h, side, T, st)) return 1;  // same arithmetic, same table
-        Encoder &own = e.shares_lstm_with >= 0 ? h->enc[e.shares_lstm_with] : e;
-        pa.pad_h = own.pad_h_small;
-        pa.pad_c = own.pad_c_small;
-      }
-      const size_t nhx = lstm_persist_hx_words(e.H), nraw = lstm_persist_raw_words(c.encoding_size);
-      const size_t need = (nhx + nraw) * sizeof(unsigned long long);
-      if (h->persist_epoch == 0 || h->persist_epoch >= (1u << 20) - 1 || need > h->s_persist.cap) {
-        // fresh (or re-sized, or the 20-bit epoch ran out): all tags to "never written"
-        if (reserve(h, h->s_persist, need)) return 1;
-        HIPCHECK(h, hipMemsetAsync(h->s_persist.p, 0, h->s_persist.cap, st));
-        h->persist_epoch = 0;
-      }
-      pa.epoch = ++h->persist_epoch;
-      pa.write_through = h->lstm_cluster_wt;
-      pa.plain_launch = h->lstm_cluster_coop ? 0 : 1;
-      pa.hx = (unsigned long long *)h->s_persist.p;
-      pa.rawx = pa.hx + nhx;
-      HIPCHECK(h, launch_lstm_persist(pa, st));
-      if (h->persist_inject) {  // testing aid: pretend a workgroup of the cluster never arrived
-        static const int32_t four = 4;
-        HIPCHECK(h, hipMemcpyAsync(h->err_flag, &four, sizeof four, hipMemcpyHostToDevice, st));
-      }
-      return 0;
-    }
-  }
-  const bool cluster_shape = cluster_takes(h, e, B, T);
-  if (!cluster_shape && h->cluster_skip[1] > 0 && small_ok && B > 32 && B <= cluster_row_limit(h, e) &&
-      T <= lstm_persist_max_steps() && lstm_cluster_ok(c.embedding_size, e.H, c.encoding_size))
-    --h->cluster_skip[1];  // an eligible call spent backing off
-  if (cluster_shape) {
-    // mid-size batches (the evaluator's 600, the index builder's 1000): the hidden units of every 64-row tile spread over a
-    // cluster of 16 compute units, weights in LDS, h_t exchanged per step (lstm_cluster.hip); needs one CU per workgroup
-    const int per = std::min(h->lstm_cluster_rows, lstm_cluster_max_rows());
-    {
-      Encoder &own = e.shares_lstm_with >= 0 ? h->enc[e.shares_lstm_with] : e;
-      if (!own.wc_valid) {
-        if (!own.Wc) HIPCHECK(h, hipMalloc((void **)&own.Wc, lstm_cluster_weight_floats(c.embedding_size, own.H) * sizeof(float)));
-        HIPCHECK(h, launch_pack_lstm_cluster(h->vars[own.kernel].dev, h->vars[own.bias].dev, c.embedding_size, own.H, own.Wc, st));
-        own.wc_valid = true;
-      }
-      LstmClusterArgs ca;
-      ca.ids = ids;
-      ca.emb = h->emb_pad;
-      ca.Wc = own.Wc;
-      ca.Mp = e.Mp;
-      ca.out = out;
-      ca.err = h->err_flag;
-      ca.B = B;
-      ca.T = T;
-      ca.V = c.vocab_size;
-      ca.E = c.embedding_size;
-      ca.Ep = e.Ep;
-      ca.KGx = e.KGx;
-      ca.H = e.H;
-      ca.Hp = e.H <= 128 ? 128 : 256;
-      ca.KGh = ca.Hp / 8;
-      ca.S = c.encoding_size;
-      ca.NTS = (c.encoding_size + 31) / 32;
-      ca.normalize = normalize ? 1 : 0;
-      if (h->pad_skip && T > 1) {
-        if (ensure_pad_table_small(h, side, T, st)) return 1;  // lstm_small's table: the same arithmetic
-        ca.pad_h = own.pad_h_small;
-        ca.pad_c = own.pad_c_small;
-        ca.pad_stride = e.H;
-      }
-      const size_t nhx = lstm_cluster_hx_words(e.H), nsx = lstm_cluster_sx_words();
-      const size_t need = (nhx + nsx) * sizeof(unsigned long long);
-      if (h->cluster_epoch == 0 || h->cluster_epoch >= (1u << 20) - 1 || need > h->s_cluster.cap) {
-        if (reserve(h, h->s_cluster, need)) return 1;
-        HIPCHECK(h, hipMemsetAsync(h->s_cluster.p, 0, h->s_cluster.cap, st));
-        h->cluster_epoch = 0;
-      }
-      ca.write_through = h->lstm_cluster_wt;
-      ca.plain_launch = h->lstm_cluster_coop ? 0 : 1;
-      ca.drop_wg = h->lstm_cluster_drop;
-      ca.hx = (unsigned long long *)h->s_cluster.p;
-      ca.sx = ca.hx + nhx;
-      for (int c0 = 0; c0 < B; c0 += per) {  // launches of the same stream reuse the exchange buffers under new epochs
-        if (h->cluster_epoch >= (1u << 20) - 1) {
-          HIPCHECK(h, hipMemsetAsync(h->s_cluster.p, 0, h->s_cluster.cap, st));
-          h->cluster_epoch = 0;
-        }
-        ca.epoch = ++h->cluster_epoch;
-        ca.ids = ids + (size_t)c0 * T;
-        ca.out = out + (size_t)c0 * c.encoding_size;
-        ca.B = std::min(per, B - c0);
-        HIPCHECK(h, launch_lstm_cluster(ca, st));
-      }
-      if (h->persist_inject) {  // testing aid: pretend a workgroup of the cluster never arrived
-        static const int32_t four = 4;
-        HIPCHECK(h, hipMemcpyAsync(h->err_flag, &four, sizeof four, hipMemcpyHostToDevice, st));
-      }
-      return 0;
-    }
-  }
-  if (B <= h->lstm_small_rows && small_ok) {
-    // a handful of sequences (demo / web query, last batch of an index build): GEMV on the vector ALUs, see lstm_small.hip
-    if (ensure_waug(h, side, st)) return 1;
-    LstmSmallArgs sa;
-    fill_small_args(h, e, sa);
-    sa.ids = ids;
-    sa.out = out;
-    sa.B = B;
-    sa.T = T;
-    sa.normalize = normalize ? 1 : 0;
-    if (h->pad_skip && T > 1) {
-      if (ensure_pad_table_small(h, side, T, st)) return 1;
-      Encoder &own = e.shares_lstm_with >= 0 ? h->enc[e.shares_lstm_with] : e;
-      sa.pad_h = own.pad_h_small;
-      sa.pad_c = own.pad_c_small;
-    }
-    HIPCHECK(h, launch_lstm_small(sa, st));
-    return 0;
-  }
-  if (x3_applies(h, e)) {  // (tiny cells: nothing to gain, and their raw
-    // encodings can be small enough for the 2e-6 absolute error to matter after normalisation)
-    // opt-in: the gate GEMMs on the bf16 matrix pipe with hi + lo split operands (lstm_fwd_x3.hip); ~1e-5 from the fp32 path
-    Encoder &own = e.shares_lstm_with >= 0 ? h->enc[e.shares_lstm_with] : e;
-    const int E = c.embedding_size;
-    if (!own.x3_valid || !h->emb16_valid) {
-      if (!own.Wx3) HIPCHECK(h, hipMalloc((void **)&own.Wx3, lstm_x3_weight_elems(E, own.Hp) * sizeof(unsigned short)));
-      if (!h->emb16) HIPCHECK(h, hipMalloc((void **)&h->emb16, lstm_x3_emb_elems(c.vocab_size, E) * sizeof(unsigned short)));
-      HIPCHECK(h, launch_pack_lstm_x3(h->vars[own.kernel].dev, h->vars[own.bias].dev, h->vars[0].dev, c.vocab_size, E, own.H,
-                                      own.Hp, own.Wx3, h->emb16_valid ? nullptr : h->emb16, 0, st));
-      own.x3_valid = true;
-      h->emb16_valid = true;
-    }
-    LstmX3Args xa;
-    xa.ids = ids;
-    xa.emb16 = h->emb16;
-    xa.Wx3 = own.Wx3;
-    xa.Mp = e.Mp;
-    xa.out = out;
-    xa.err = h->err_flag;
-    xa.B = B;
-    xa.T = T;
-    xa.V = c.vocab_size;
-    xa.KGX = lstm_x3_kgx(E);
-    xa.H = e.H;
-    xa.S = c.encoding_size;
-    xa.NTS = (c.encoding_size + 31) / 32;
-    xa.normalize = normalize ? 1 : 0;
-    xa.row_map = h->cur_row_map;
-    {
-      bool padded_x3 = false;
-      if (device_pad_sort(h, side, ids, B, T, st, &xa.row_map, &padded_x3)) return 1;
-    }
-    if (h->pad_skip && T > 1) {
-      // pad-prefix table of THIS path: one all-PAD row through the same kernel, recorded step by step
-      if (!(own.pad_valid_x3 && own.pad_T_x3 >= T)) {
-        const int Tt = T > c.max_seq_length ? T : c.max_seq_length;
-        if (own.pad_T_x3 < Tt || !own.pad_h_x3) {
-          if (own.pad_h_x3) HIPCHECK(h, hipFree(own.pad_h_x3));
-          if (own.pad_c_x3) HIPCHECK(h, hipFree(own.pad_c_x3));
-          own.pad_h_x3 = own.pad_c_x3 = nullptr;
-          HIPCHECK(h, hipMalloc((void **)&own.pad_h_x3, (size_t)(Tt + 1) * own.Hp * sizeof(float)));
-          HIPCHECK(h, hipMalloc((void **)&own.pad_c_x3, (size_t)(Tt + 1) * own.Hp * sizeof(float)));
-          own.pad_T_x3 = Tt;
-        }
-        HIPCHECK(h, hipMemsetAsync(own.pad_h_x3, 0, (size_t)(Tt + 1) * own.Hp * sizeof(float), st));
-        HIPCHECK(h, hipMemsetAsync(own.pad_c_x3, 0, (size_t)(Tt + 1) * own.Hp * sizeof(float), st));
-        if (reserve(h, h->s_zero, (size_t)Tt * sizeof(int32_t) + (size_t)c.encoding_size * sizeof(float))) return 1;
-        HIPCHECK(h, hipMemsetAsync(h->s_zero.p, 0, (size_t)Tt * sizeof(int32_t), st));
-        LstmX3Args ta = xa;
-        ta.ids = (const int32_t *)h->s_zero.p;
-        ta.out = (float *)((char *)h->s_zero.p + (size_t)Tt * sizeof(int32_t));
-        ta.B = 1;
-        ta.T = Tt;
-        ta.normalize = 0;
-        ta.row_map = nullptr;
-        ta.rec_h = own.pad_h_x3;
-        ta.rec_c = own.pad_c_x3;
-        HIPCHECK(h, launch_lstm_fwd_x3(ta, st));
-        own.pad_valid_x3 = true;
-      }
-      xa.pad_h = own.pad_h_x3;
-      xa.pad_c = own.pad_c_x3;
-    }
-    HIPCHECK(h, launch_lstm_fwd_x3(xa, st));
-    return 0;
-  }
-  LstmFwdArgs a;
-  fill_fwd_args(h, e, a);
-  a.ids = ids;
-  a.out = out;
-  a.B = B;
-  a.T = T;
-  a.normalize = normalize ? 1 : 0;
-  a.row_map = h->cur_row_map;
-  bool padded_hint = h->cur_padded_hint;
-  if (device_pad_sort(h, side, ids, B, T, st, &a.row_map, &padded_hint)) return 1;
-  if (h->pad_skip && T > 1) {
-    if (ensure_pad_table(h, side, T, st)) return 1;
-    a.pad_h = e.pad_h;
-    a.pad_c = e.pad_c;
-    // a heavily left-padded batch sorted by pad count (sse_encode's host path knows both): tiles differ in length, the finer
-    // 32-row granularity with two workgroups per CU balances them better -- crosslingual index build 2.96 -> 2.64 ms, queries
-    // 1.24 -> 0.84 ms (profiles/r05_notes.txt)
-    if (padded_hint && a.row_map && e.Hp <= 256) a.force_rows = 32;
-  }
-  HIPCHECK(h, launch_lstm_fwd(a, e.Hp, st));
-  return 0;
+  return 1;
 }
 
 // bits: (optional) receives the raw flag; a flag that is exactly bit 2 (cluster kernel: a workgroup did not arrive) is then
@@ -1493,16 +1478,13 @@ void sse_destroy(sse_handle *h) {
     Encoder &e = h->enc[s];
     if (e.shares_lstm_with < 0) {
       if (e.Wp) hipFree(e.Wp);
-      if (e.pad_h) (void)hipFree(e.pad_h);
-      if (e.pad_c) (void)hipFree(e.pad_c);
       if (e.Waug) (void)hipFree(e.Waug);
       if (e.Wc) (void)hipFree(e.Wc);
       if (e.Wx3) (void)hipFree(e.Wx3);
       if (e.Wx3t) (void)hipFree(e.Wx3t);
-      if (e.pad_h_x3) (void)hipFree(e.pad_h_x3);
-      if (e.pad_c_x3) (void)hipFree(e.pad_c_x3);
-      if (e.pad_h_small) (void)hipFree(e.pad_h_small);
-      if (e.pad_c_small) (void)hipFree(e.pad_c_small);
+      e.pad_fwd.release();
+      e.pad_small.release();
+      e.pad_x3.release();
     }
     if (e.Mp) hipFree(e.Mp);
   }
@@ -1611,13 +1593,9 @@ static int ensure_pin(sse_handle *h, size_t need) {
 static int encode_fallback_locked(sse_handle *h, int side, int32_t B, int32_t T, int32_t normalize, hipStream_t st) {
   h->persist_fallbacks += 1;
   h->cluster_skip[B <= 32 ? 0 : 1] = h->cluster_backoff >= 0 ? h->cluster_backoff : 16;  // a time-out costs 10 ms: do not pay it on every call of a busy device
-  const int keep = h->lstm_persist_rows, keep_c = h->lstm_cluster_rows;
-  h->lstm_persist_rows = 0;
-  h->lstm_cluster_rows = 0;
-  const int rc = encode_dev_locked(h, side, (const int32_t *)h->s_ids.p, B, T, normalize, (float *)h->s_out.p, st);
-  h->lstm_persist_rows = keep;
-  h->lstm_cluster_rows = keep_c;
-  if (rc) return 1;
+  EncodeRequest rq;
+  rq.allow_cluster = false;
+  if (encode_dev_locked(h, side, (const int32_t *)h->s_ids.p, B, T, normalize, (float *)h->s_out.p, st, rq)) return 1;
   return check_err_flag(h, st);
 }
 
@@ -1631,9 +1609,11 @@ static int encode_host_ids_locked(sse_handle *h, int side, const int32_t *ids_ho
   // Group rows by their leading-PAD count (left-padded inputs, sse_index.py:79-85) so that every
   // 64-row tile can skip its whole common PAD prefix; results are scattered back in caller order.
   const bool lstm_side = h->cfg.network_mode != SSE_MODE_SOURCE_ONLY_CNN && !(side == SSE_SIDE_TARGET && h->tgt_table >= 0);
-  const int32_t *row_map_dev = nullptr;
-  const bool to_cluster = lstm_side && h->enc[side].kernel >= 0 && cluster_takes(h, h->enc[side], B, T);  // (takes rows as they come)
-  if (h->pad_skip && lstm_side && B > 64 && B > h->lstm_small_rows && !to_cluster && !h->enc[side].generic) {
+  EncodeRequest rq;
+  const Encoder &e = h->enc[side];
+  const bool to_cluster = lstm_side && e.kernel >= 0 && !e.generic &&  // (the cluster kernel takes rows as they come)
+                          choose_lstm_path(h, e, B, T, rq, /*dry_run=*/true) == LstmPath::Cluster;
+  if (h->pad_skip && lstm_side && B > 64 && B > h->lstm_small_rows && !to_cluster && !e.generic) {
     // counting sort of the row numbers by leading-PAD count, shortest prefix first (the tiles with the most steps left are
     // dispatched first; see pack.hip, pad_lead_kernel)
     std::vector<int32_t> lead(B), start(T + 2, 0), order(B);
@@ -1648,18 +1628,14 @@ static int encode_host_ids_locked(sse_handle *h, int side, const int32_t *ids_ho
     for (int b = 0; b < B; ++b) order[start[lead[b]]++] = b;
     int64_t lead_sum = 0;
     for (int b = 0; b < B; ++b) lead_sum += lead[b];
-    h->cur_padded_hint = lead_sum * 4 >= (int64_t)B * T;
+    rq.padded_hint = lead_sum * 4 >= (int64_t)B * T;
     if (reserve(h, h->s_map, (size_t)B * sizeof(int32_t))) return 1;
     HIPCHECK(h, hipMemcpyAsync(h->s_map.p, order.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIPCHECK(h, hipStreamSynchronize(st));  // `order` is a local
-    row_map_dev = (const int32_t *)h->s_map.p;
+    rq.row_map = (const int32_t *)h->s_map.p;
   }
   HIPCHECK(h, hipMemcpyAsync(h->s_ids.p, ids_host, (size_t)B * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  h->cur_row_map = row_map_dev;
-  int rc = encode_dev_locked(h, side, (const int32_t *)h->s_ids.p, B, T, normalize, (float *)h->s_out.p, st);
-  h->cur_row_map = nullptr;
-  h->cur_padded_hint = false;
-  if (rc) return 1;
+  if (encode_dev_locked(h, side, (const int32_t *)h->s_ids.p, B, T, normalize, (float *)h->s_out.p, st, rq)) return 1;
   if (defer_check) return 0;
   int32_t bits = 0;
   if (check_err_flag(h, st, &bits)) return 1;
@@ -2729,7 +2705,7 @@ static int train_grads_locked(sse_handle *h, const int32_t *src_ids_host, const 
     a.h_last = (float *)ts.h_last[s].p;
     if (fwd_x3[s]) {
       // the gate GEMMs as three bf16 MFMAs on hi + lo split operands (lstm_fwd_x3.hip, TRAIN): same tapes, same outputs
-      Encoder &own = e.shares_lstm_with >= 0 ? h->enc[e.shares_lstm_with] : e;
+      Encoder &own = lstm_owner(h, e);
       if (e.shares_lstm_with < 0 && s != 0) {  // (side 0 was packed ahead of the fork together with the embedding table)
         if (!own.Wx3t) HIPCHECK(h, hipMalloc((void **)&own.Wx3t, lstm_x3_weight_elems(E, own.Hp) * sizeof(unsigned short)));
         if (!h->emb16) HIPCHECK(h, hipMalloc((void **)&h->emb16, lstm_x3_emb_elems(V, E) * sizeof(unsigned short)));
