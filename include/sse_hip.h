@@ -96,6 +96,12 @@ int sse_encode_dev(sse_handle *h, int side, const int32_t *ids_dev, int32_t B, i
  * of that side saw padding, 32-row tiles while its mean prefix was >= T / 4), 2 = always, 0 = off.  Counter "pad_sorted_calls".
  * "lstm_gate_split" (default 1): inference encodes of cell sizes <= 128 at 64-row tiles (batches above 8192 rows) run the
  * gate-split kernel (one gate per wave, two phase-shifted 32-row groups per workgroup); bit-identical to 0.
+ * "lstm_x_table" (default 1): LSTM encodes on the matrix kernel with 129 .. 512 hidden units start every step's gate
+ * accumulators from a per-token table of x projections (the embedding row and bias through the kernel matrix, built once per
+ * weight change by the recurrence's own MFMA chain) instead of recomputing them; bit-identical to 0.  1 = (re)build the
+ * table when a batch holds at least as many tokens as the vocabulary (B * T >= vocab_size), use it while it is valid;
+ * 2 = always build; 0 = off.  "lstm_x_table_mb" (default 256): largest table built, in MiB (vocab_size * 16 * cell size
+ * bytes, rounded up to 32 units); above it the embedding-gather path runs.  Counter "lstm_x_table_builds".
  * "score_two_pass_min_rows" / "score_two_pass_rows" (defaults 49152 / 524288): sse_score_topk* on an index of that many rows
  * with >= 1024 queries, k <= 16 and bf16 candidates ranks by a max-only sweep -> per-query threshold -> collect sweep -> float64
  * select instead of the list sweep: the same exact ids and score bits; max 0 = off.  Counter "score_two_pass_calls".

@@ -63,6 +63,8 @@ size_t lstm_fwd_lds_bytes(int KGx, int KGh, int RT) {
   const int xb = lstm_fwd_x_double(KGx, KGh, RT) ? 2 : 1;
   return (size_t)(xb * RT * KGx + 2 * RT * KGh) * 256 * sizeof(float) + 64 * 4 * sizeof(float);
 }
+// x-table path (XT): no x tiles, only h [2 bufs][RT][KGh][256] + red
+static size_t lstm_fwd_xt_lds_bytes(int KGh, int RT) { return (size_t)(2 * RT * KGh) * 256 * sizeof(float) + 64 * 4 * sizeof(float); }
 
 // v_exp_f32 (2^x) + v_rcp_f32 (1 ulp); plain `/` or __fdividef would expand to the ~10-instruction IEEE division
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504089f * x)); }
@@ -145,9 +147,13 @@ __device__ __forceinline__ void gemm_pass(__amdgpu_buffer_rsrc_t wr, int voff, i
 //   <1,1,1>  Hp = 256, 32 rows: wave w owns unit block w      (half the per-step latency: used
 //            when the batch cannot fill the chip with 64-row tiles)
 //   <1,1,2>  Hp = 512, 32 rows: wave w owns unit blocks w and w+8
-template <int RT, int MT, int UBW, bool TRAIN, bool LIN, bool SPL = false, bool TSW = false>
+// XT (inference, with LIN): the x part of every gate accumulator comes from the per-token table a.xtab (lstm_xtable.hip:
+// the same MFMA chain over the same operands, so the same bits) instead of the embedding gather and the KGx x k-groups of
+// each pass; the passes then run the h k-groups only, and step 0 (h_{-1} = 0) runs no MFMA at all.  No x tiles in LDS.
+template <int RT, int MT, int UBW, bool TRAIN, bool LIN, bool SPL = false, bool TSW = false, bool XT = false>
 __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
   static_assert(!TSW || TRAIN, "TSW is the training forward in the inference orientation");
+  static_assert(!XT || (!TRAIN && LIN && !SPL), "the x table is an inference path of the linear LDS layout");
   constexpr int NTHR = LSTM_THREADS;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int ROWS = RT * 32;                 // sequences per workgroup
@@ -192,18 +198,19 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
   const int fidx = SPL ? ub0 : mt0;  // hand-over flag of this wave's (unit block | row tile)
   const int KGx = a.KGx, KGh = a.KGh, KG = KGx + KGh, T = a.T;
   const int KGhe = (a.KGhe > 0 && a.KGhe < KGh) ? a.KGhe : KGh;
+  const int KGxs = XT ? 0 : KGx, KGs = KGxs + KGh;  // k-groups of a row tile held in LDS
   // LDS.  LIN (x double-buffered, fits 160 KiB): A tiles [2 bufs][RT][KG][256], the x part of
   // a row tile followed by its h part, so a k-loop walks one linear array.  Otherwise:
   // x [RT][KGx][256] single-buffered, then h [2 bufs][RT][KGh][256].
   constexpr bool XD = LIN;
   auto xptr = [&](int buf, int mt) -> float * {
-    return LIN ? smem + (size_t)((buf * RT + mt) * KG) * 256 : smem + (size_t)(mt * KGx) * 256;
+    return LIN ? smem + (size_t)((buf * RT + mt) * KGs) * 256 : smem + (size_t)(mt * KGx) * 256;
   };
   auto hptr = [&](int buf, int mt) -> float * {
-    return LIN ? smem + (size_t)((buf * RT + mt) * KG + KGx) * 256
+    return LIN ? smem + (size_t)((buf * RT + mt) * KGs + KGxs) * 256
                : smem + (size_t)(RT * KGx + (buf * RT + mt) * KGh) * 256;
   };
-  float *red = smem + (size_t)(LIN ? 2 * RT * KG : RT * KGx + 2 * RT * KGh) * 256;  // [ROWS][NWR] (>= 8 floats)
+  float *red = smem + (size_t)(LIN ? 2 * RT * KGs : RT * KGx + 2 * RT * KGh) * 256;  // [ROWS][NWR] (>= 8 floats)
   const int b0 = blockIdx.x * ROWS;
   int *pass_flag = reinterpret_cast<int *>(red + 16);  /* LDS atomics, not volatile: see gs_flag_min4 in lstm_fwd_gs.hip */  // split3: [row tile] = steps whose i,j pass is parked
   if (tid < 8) pass_flag[tid] = 0;
@@ -216,6 +223,22 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
   const int32_t *id_row = a.ids + (size_t)(row_ok ? (a.row_map ? a.row_map[b0 + xr] : b0 + xr) : 0) * T;
   auto fetch_id = [&](int t) -> int {
     int id = row_ok ? id_row[t] : 0;
+    if (id < 0 || id >= a.V) {
+      atomicOr(a.err, 1);
+      id = 0;
+    }
+    return id;
+  };
+  // XT: the sequences this lane's accumulators hold (column lane & 31 of row tile mt0 + m): their token ids select the
+  // table rows; every id goes through fetch_id's range check (and error flag) once, before it is used
+  int xt_row[MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    const int r = b0 + (mt0 + m) * 32 + (lane & 31);
+    xt_row[m] = XT && r < a.B ? (a.row_map ? a.row_map[r] : r) : -1;
+  }
+  auto xt_id = [&](int m, int t) -> int { return xt_row[m] >= 0 ? a.ids[(size_t)xt_row[m] * T + t] : 0; };
+  auto xt_check = [&](int id) -> int {
     if (id < 0 || id >= a.V) {
       atomicOr(a.err, 1);
       id = 0;
@@ -269,7 +292,10 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
   }
 
   // --- prologue: x_{t0} -> x buffer (t0 & 1), h_{t0-1} = state after t0 PAD steps (0 when t0 = 0)
-  {
+  int xid[MT];  // XT: checked token ids of step t
+#pragma unroll
+  for (int m = 0; m < MT; ++m) xid[m] = XT ? xt_check(xt_id(m, t0)) : 0;
+  if constexpr (!XT) {
     const int id = fetch_id(t0);
     const float *src = a.emb + (size_t)id * a.Ep;
     for (int kg = xq; kg < KGx; kg += TPR) {
@@ -287,6 +313,8 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
         tape_x(t0, kg, lo, hi);
       }
     }
+  }
+  {
     const int Hp = KGh * 8;
     for (int i = tid; i < RT * KGh * 256; i += NTHR) {  // all row tiles of buffer t0 & 1
       const int mt = i / (KGh * 256), e = i % (KGh * 256);
@@ -333,6 +361,31 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
       const_cast<float *>(a.Wp), 0, (KGh / 4) * KG * 4096, 0x00020000);
   const int wvoff = lane * 16;
 
+  // gate accumulators of a pass (zero, or XT: the x part from the table)
+  auto acc_init = [&](f32x16(&acc)[MT][2], const int (&id)[MT], int ub, int q) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      if constexpr (XT) {
+        const float *src = a.xtab + (((size_t)id[m] * a.xtab_ub + ub) * 4 + q) * 32 + (lane >> 5) * 16;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const f32x4 v0 = *reinterpret_cast<const f32x4 *>(src + 4 * i), v1 = *reinterpret_cast<const f32x4 *>(src + 32 + 4 * i);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            acc[m][0][4 * i + e] = v0[e];
+            acc[m][1][4 * i + e] = v1[e];
+          }
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          acc[m][0][r] = 0.0f;
+          acc[m][1][r] = 0.0f;
+        }
+      }
+    }
+  };
+
   FW_CLK_DECL
   for (int t = t0; t < T; ++t) {
     FW_CLK(0)
@@ -341,7 +394,10 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
     const bool have_next = (t + 1) < T;
     int nid = 0;
     f32x4 nlo = {0, 0, 0, 0}, nhi = {0, 0, 0, 0};
-    if (have_next) {
+    int xnid[MT];  // XT: raw ids of step t+1, checked at the end of the step (the load has the whole step to land)
+#pragma unroll
+    for (int m = 0; m < MT; ++m) xnid[m] = XT && have_next ? xt_id(m, t + 1) : 0;
+    if (!XT && have_next) {
       nid = fetch_id(t + 1);
       if (xq < KGx) {
         const float *src = a.emb + (size_t)nid * a.Ep + xq * 8;
@@ -411,7 +467,7 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
       // >= KGhe are skipped): nothing to compute.  Training keeps it (the tapes cover all Hp units).
       if (!TRAIN && a.H > 0 && ub * 32 >= a.H) {
         // (the wave still delivers its share of the x_{t+1} gather, which normally rides between the two passes)
-        if (u == 0 && XD && have_next) {
+        if (u == 0 && XD && !XT && have_next) {
           if (xq < KGx) x_store(nxt, xq, nlo, nhi);
           for (int kg = xq + TPR; kg < KGx; kg += TPR) {
             const float *src = a.emb + (size_t)nid * a.Ep + kg * 8;
@@ -438,20 +494,22 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
       // pass A: gates i, j  ->  pij = sigmoid(i) * tanh(j)      (BasicLSTMCell, TF 1.x)
       // pij is parked in the (still unused) h_t slots of the other h buffer -- same (row, unit)
       // coordinates -- instead of 16*MT registers held across pass B.
-      // (accumulators start at 0: the bias arrives through the constant-1 column of x, see the file header)
+      // (accumulators start at 0: the bias arrives through the constant-1 column of x, see the file header.  XT: they start
+      // from the table, i.e. the state after the x k-groups, and the pass runs the h k-groups -- none in step 0)
       f32x16 g[MT][2];
       float *hdst[MT];
-#pragma unroll
-      for (int m = 0; m < MT; ++m) {
-        hdst[m] = hptr(nxt, mt0 + m) + hoff;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          g[m][0][r] = 0.0f;
-          g[m][1][r] = 0.0f;
+      auto pass = [&](int soff, f32x16(&acc)[MT][2]) {
+        if constexpr (XT) {
+          if (t > 0) gemm_pass<MT, true, SWAP>(wr, wvoff, soff + KGx * 4096, ha, ha, 0, KGhe, acc);
+        } else {
+          gemm_pass<MT, LIN, SWAP>(wr, wvoff, soff, xa, ha, KGx, kend, acc);
         }
-      }
+      };
+#pragma unroll
+      for (int m = 0; m < MT; ++m) hdst[m] = hptr(nxt, mt0 + m) + hoff;
+      if (!XT || do_a) acc_init(g, xid, ub, 0);
       FW_CLK(1)
-      if (do_a) gemm_pass<MT, LIN, SWAP>(wr, wvoff, wsoff, xa, ha, KGx, kend, g);
+      if (do_a) pass(wsoff, g);
       FW_CLK(2)
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
@@ -494,7 +552,7 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
         __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
         if (lane == 0) __hip_atomic_store(pass_flag + fidx, t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
-      if (u == 0 && XD && have_next) {
+      if (u == 0 && XD && !XT && have_next) {
         // x_{t+1}: its buffer was last read in step t-1, so it can be written as soon as the
         // prefetch has landed (frees the staging registers before pass B)
         if (xq < KGx) x_store(nxt, xq, nlo, nhi);
@@ -505,15 +563,9 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
         tape_x(t + 1, xq, nlo, nhi);  // TSW: x columns of the next step's A-tape (zeros where xq >= KGx)
       }
       // pass B: gates f (+1 folded into the bias), o -> c' = c*sigmoid(f) + pij ; h' = tanh(c')*sigmoid(o)
-#pragma unroll
-      for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          g[m][0][r] = 0.0f;
-          g[m][1][r] = 0.0f;
-        }
+      if (!XT || do_b) acc_init(g, xid, ub, 2);
       FW_CLK(3)
-      if (do_b) gemm_pass<MT, LIN, SWAP>(wr, wvoff, wsoff + 2048, xa, ha, KGx, kend, g);
+      if (do_b) pass(wsoff + 2048, g);
       FW_CLK(4)
       if (do_b && !do_a) {  // split3: the i,j pass of this (block, row tile) comes from the partner wave
         while (__hip_atomic_load(pass_flag + fidx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < t + 1) __builtin_amdgcn_s_sleep(2);
@@ -600,6 +652,9 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
     if (XD) {
       __syncthreads();  // h_t complete and visible; h_{t-1} / x_t no longer needed
       FW_CLK(7)
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+        if (XT && have_next) xid[m] = xt_check(xnid[m]);
     } else {
       __syncthreads();
       if (have_next) {
@@ -709,13 +764,13 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
   }
 }
 
-template <int RT, int MT, int UBW, bool TRAIN, bool LIN, bool SPL, bool TSW = false>
+template <int RT, int MT, int UBW, bool TRAIN, bool LIN, bool SPL, bool TSW = false, bool XT = false>
 static hipError_t launch_one(const LstmFwdArgs &a, size_t lds, hipStream_t stream) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(lstm_fwd_kernel<RT, MT, UBW, TRAIN, LIN, SPL, TSW>),
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(lstm_fwd_kernel<RT, MT, UBW, TRAIN, LIN, SPL, TSW, XT>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   const dim3 grid(a.NT32 > 0 ? a.NT32 / RT : (a.B + RT * 32 - 1) / (RT * 32)), block(LSTM_THREADS);
-  hipLaunchKernelGGL((lstm_fwd_kernel<RT, MT, UBW, TRAIN, LIN, SPL, TSW>), grid, block, lds, stream, a);
+  hipLaunchKernelGGL((lstm_fwd_kernel<RT, MT, UBW, TRAIN, LIN, SPL, TSW, XT>), grid, block, lds, stream, a);
 #ifdef SSE_FWD_CLOCK
   {
     static int n = 0;
@@ -739,6 +794,12 @@ static hipError_t launch_cfg(const LstmFwdArgs &a_in, hipStream_t stream) {
   a.xdouble = lstm_fwd_x_double(a.KGx, a.KGh, RT) ? 1 : 0;
   const size_t lds = lstm_fwd_lds_bytes(a.KGx, a.KGh, RT);
   const bool train = a.tape_g != nullptr;
+  if constexpr (!SPL && !(RT == 2 && MT == 1)) {  // inference with the x table (the Hp = 256 / 512 configurations)
+    if (!train && a.xtab != nullptr) {
+      if (a.xtab_ub != (a.H > 0 ? (a.H + 31) / 32 : a.KGh / 4)) return hipErrorInvalidValue;
+      return launch_one<RT, MT, UBW, false, true, false, false, true>(a, lstm_fwd_xt_lds_bytes(a.KGh, RT), stream);
+    }
+  }
   if (train && a.tape_swap) {
     if (a.tape_a_split) return hipErrorInvalidValue;  // the register-built A-tape is fp32
     return a.xdouble ? launch_one<RT, MT, UBW, true, true, SPL, true>(a, lds, stream)
@@ -779,6 +840,7 @@ hipError_t launch_lstm_fwd(const LstmFwdArgs &a, int Hp, hipStream_t stream) {
     if (Hp <= 256 && (r == 32 || r == 64)) rows = r;
   }
   if (rows == 64 && a.NT32 > 0 && (a.NT32 & 1)) return hipErrorInvalidValue;  // tapes are laid out per 32-row tile
+  if (Hp == 128 && a.xtab != nullptr) return hipErrorInvalidValue;  // no x-table path at Hp = 128
   if (Hp == 128 && rows == 64 && a.gate_split && a.tape_g == nullptr && a.rec_h == nullptr && a.NTS <= 16 &&
       lstm_fwd_gs_ok(a.KGx, a.KGh, a.H > 0 ? a.H : Hp)) {
     const char *ev = getenv("SSE_FWD_GS");  // measurement aid: 0 = lstm_fwd_kernel<2,1,1>

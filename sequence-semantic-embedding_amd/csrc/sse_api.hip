@@ -58,6 +58,10 @@ struct Encoder {
   // pad-prefix tables of the LSTM owner: matrix kernel (lstm_fwd.hip, Hp wide), few-sequences kernel (lstm_small.hip, H wide;
   // the two cluster kernels share its arithmetic and read it too), lstm_x3 path (Hp wide)
   PadTable pad_fwd, pad_small, pad_x3;
+  // x-projection table of the LSTM owner (lstm_xtable.hip): per token, the gate accumulators after the x k-groups; read by
+  // lstm_fwd_kernel's table path (Hp = 256 / 512 inference)
+  float *xtab = nullptr;
+  bool xtab_valid = false;
 };
 
 struct DevBuf {  // grow-only device scratch; freed with its owner (handle / TrainState)
@@ -153,6 +157,14 @@ struct sse_handle {
   int lstm_cluster_wt = 0;      // option "lstm_cluster_write_through": force the any-placement publish path (tests)
   int lstm_cluster_drop = 0;    // option "lstm_cluster_drop_wg": one workgroup of the cluster kernel exits at once (tests)
   int lstm_small_rows = 1024; // option "lstm_small_rows": batches up to this many rows take the few-sequences LSTM kernel
+  // option "lstm_x_table": encodes on the matrix kernel at Hp = 256 / 512 start every step's gate accumulators from a per-token
+  // table of x projections instead of recomputing them (bit-identical).  1 (default): the table is (re)built when a batch
+  // brings at least as many tokens as the vocabulary (B * T >= V), so small batches between weight updates never pay for a
+  // rebuild; 2: always built; 0: off.  Option "lstm_x_table_mb": the largest table built, in MiB (default 256, the Infinity
+  // Cache of an MI355X); larger ones take the embedding-gather path.  Counter "lstm_x_table_builds".
+  int lstm_x_table = 1;
+  int lstm_x_table_mb = 256;
+  int64_t x_table_builds = 0;
   bool score_small_index = true;  // option "score_small_index": many queries against <= 1024 rows skip the list sweep (launch_score_small_index)
   bool score_bf16 = true;    // option "score_bf16" (default on): candidate pass on the bf16 matrix pipe; results stay exact
   void *idxp16 = nullptr;    // bf16 fragment copy of the index (built on demand)
@@ -308,6 +320,7 @@ Encoder &lstm_owner(sse_handle *h, Encoder &e) { return e.shares_lstm_with >= 0 
 void invalidate_derived(Encoder &e) {
   e.waug_valid = e.wc_valid = e.x3_valid = false;
   e.pad_fwd.valid = e.pad_small.valid = e.pad_x3.valid = false;
+  e.xtab_valid = false;
 }
 
 // (re)build the kernel-facing layouts from the master variables
@@ -804,6 +817,32 @@ int encode_x3(sse_handle *h, int side, const int32_t *ids, int B, int T, int nor
   return 0;
 }
 
+// *use = the x-projection table of the LSTM owner serves this B x T batch: the lstm_x_table policy wants it and it is valid or
+// has just been (re)built on st.  Otherwise the caller takes the embedding-gather path.
+int ensure_x_table(sse_handle *h, Encoder &own, int B, int T, hipStream_t st, bool *use) {
+  *use = false;
+  if (h->lstm_x_table == 0 || own.Hp < 256) return 0;
+  const int64_t V = h->cfg.vocab_size;
+  const int UBt = (own.H + 31) / 32;
+  const size_t bytes = lstm_xtable_floats(V, UBt) * sizeof(float);
+  if (bytes > ((size_t)h->lstm_x_table_mb << 20)) return 0;
+  if (own.xtab_valid) {
+    *use = true;
+    return 0;
+  }
+  if (h->lstm_x_table == 1 && (int64_t)B * T < V) return 0;
+  if (!own.xtab && hipMalloc((void **)&own.xtab, bytes) != hipSuccess) {
+    (void)hipGetLastError();  // out of device memory: the embedding-gather path needs no table
+    own.xtab = nullptr;
+    return 0;
+  }
+  HIPCHECK(h, launch_lstm_xtable(h->emb_pad, own.Wp, V, own.Ep, own.KGx, own.KGh, UBt, own.xtab, st));
+  own.xtab_valid = true;
+  h->x_table_builds += 1;
+  *use = true;
+  return 0;
+}
+
 // the MFMA matrix kernel (lstm_fwd.hip / lstm_fwd_gs.hip): any batch
 int encode_fwd(sse_handle *h, int side, const int32_t *ids, int B, int T, int normalize, float *out, const EncodeRequest &rq,
                hipStream_t st) {
@@ -839,6 +878,12 @@ int encode_fwd(sse_handle *h, int side, const int32_t *ids, int B, int T, int no
     // 32-row granularity with two workgroups per CU balances them better -- crosslingual index build 2.96 -> 2.64 ms, queries
     // 1.24 -> 0.84 ms (profiles/r05_notes.txt)
     if (padded_hint && a.row_map && e.Hp <= 256) a.force_rows = 32;
+  }
+  bool use_xt = false;
+  if (ensure_x_table(h, own, B, T, st, &use_xt)) return 1;
+  if (use_xt) {
+    a.xtab = own.xtab;
+    a.xtab_ub = (own.H + 31) / 32;
   }
   HIPCHECK(h, launch_lstm_fwd(a, e.Hp, st));
   return 0;
@@ -1485,6 +1530,7 @@ void sse_destroy(sse_handle *h) {
       e.pad_fwd.release();
       e.pad_small.release();
       e.pad_x3.release();
+      if (e.xtab) (void)hipFree(e.xtab);
     }
     if (e.Mp) hipFree(e.Mp);
   }
@@ -1802,6 +1848,10 @@ int sse_get_counter(sse_handle *h, const char *name, int64_t *value) {
     *value = h->pad_sorted_calls;
     return 0;
   }
+  if (strcmp(name, "lstm_x_table_builds") == 0) {  // x-projection tables built (option lstm_x_table)
+    *value = h->x_table_builds;
+    return 0;
+  }
   if (strcmp(name, "lstm_coop_refused") == 0) {  // process-wide: cooperative launches refused by the runtime (plain launch taken)
     *value = (int64_t)lstm_coop_refused();
     return 0;
@@ -1944,6 +1994,16 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value) {
   if (strcmp(name, "lstm_small_rows") == 0) {
     if (value < 0) return fail(h, "lstm_small_rows must be >= 0");
     h->lstm_small_rows = value;
+    return 0;
+  }
+  if (strcmp(name, "lstm_x_table") == 0) {
+    if (value < 0 || value > 2) return fail(h, "lstm_x_table must be 0 (off), 1 (batches with B * T >= vocab_size) or 2 (always)");
+    h->lstm_x_table = value;
+    return 0;
+  }
+  if (strcmp(name, "lstm_x_table_mb") == 0) {
+    if (value < 0) return fail(h, "lstm_x_table_mb must be >= 0");
+    h->lstm_x_table_mb = value;
     return 0;
   }
   return fail(h, "unknown option '%s'", name);

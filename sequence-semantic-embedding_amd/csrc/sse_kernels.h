@@ -134,6 +134,10 @@ struct LstmFwdArgs {
   const float *pad_h = nullptr, *pad_c = nullptr;
   const int32_t *row_map = nullptr;  // optional: logical row b reads ids / writes out at row row_map[b]
   float *rec_h = nullptr, *rec_c = nullptr;
+  // Inference, Hp = 256 / 512: per-token x projections (launch_lstm_xtable) -- the gate accumulators after the x k-groups
+  // are loaded from here instead of being recomputed from the embedding row.  nullptr: embedding-gather path.
+  const float *xtab = nullptr;
+  int32_t xtab_ub = 0;  // unit blocks per token in xtab (ceil(H / 32))
   // training only (nullptr for inference): tapes consumed by the backward kernels
   float *tape_g = nullptr;  // [T][NT32][4][UB][5][4][64][4] gate activations + c, accumulator layout: lane l, register r at word
                             // (r >> 2) * 256 + 4 l + (r & 3) of its 1024-word block (16-byte pieces per lane)
@@ -149,6 +153,12 @@ size_t lstm_fwd_lds_bytes(int KGx, int KGh, int RT);
 bool lstm_fwd_x_double(int KGx, int KGh, int RT);
 int lstm_fwd_rows_per_wg(int Hp, int B, int tiles_elsewhere = 0, int cus = 0 /* 0: 256 */);
 hipError_t launch_lstm_fwd(const LstmFwdArgs &a, int Hp, hipStream_t stream);
+// x-projection table of lstm_fwd_kernel's table path (lstm_xtable.hip): for every token v < V and live unit block ub < UBt,
+// the four gate tiles' accumulators after the KGx x k-groups of the packed kernel Wp, in the inference accumulator layout
+// [V][UBt][4 gates][lane >> 5][16 registers] fp32, built with the recurrence's own MFMA chain (bit-identical)
+size_t lstm_xtable_floats(int64_t V, int UBt);
+hipError_t launch_lstm_xtable(const float *emb /* [V][Ep] padded */, const float *Wp, int64_t V, int Ep, int KGx, int KGh, int UBt,
+                              float *table, hipStream_t stream);
 // small cells (H <= 128), inference, 64-row tiles: lstm_fwd_gs.hip
 size_t lstm_fwd_gs_lds_bytes(int KGx, int NB);
 bool lstm_fwd_gs_ok(int KGx, int KGh, int H);
