@@ -30,10 +30,11 @@ struct Variable {
   float *grad = nullptr;    // gradient of the current step (allocated by the first train step)
 };
 
-// pad-prefix table: state after p leading PAD steps, p = 0..T ([T+1][width] each), recorded by the kernel that reads it
+// pad-prefix table: state after p leading PAD steps, p = 0..T ([T+1][width] each), recorded by the kernel that reads it.
+// T is what the latest recording covers; the buffers hold cap + 1 rows (cap >= T: a shorter re-recording keeps them).
 struct PadTable {
   float *h = nullptr, *c = nullptr;
-  int T = 0;
+  int T = 0, cap = 0;
   bool valid = false;
   void release() {
     if (h) (void)hipFree(h);
@@ -465,19 +466,22 @@ int ensure_pad_table(sse_handle *h, PadTable &t, int width, int T, hipStream_t s
   if (t.valid && t.T >= T) return 0;
   const int Tt = T > h->cfg.max_seq_length ? T : h->cfg.max_seq_length;
   const size_t bytes = (size_t)(Tt + 1) * width * sizeof(float);
-  if (t.T < Tt || !t.h) {
+  t.valid = false;
+  if (t.cap < Tt || !t.h) {
     if (t.h) HIPCHECK(h, hipFree(t.h));
     if (t.c) HIPCHECK(h, hipFree(t.c));
     t.h = t.c = nullptr;
+    t.cap = 0;
     HIPCHECK(h, hipMalloc((void **)&t.h, bytes));
     HIPCHECK(h, hipMalloc((void **)&t.c, bytes));
-    t.T = Tt;
+    t.cap = Tt;
   }
   HIPCHECK(h, hipMemsetAsync(t.h, 0, bytes, st));
   HIPCHECK(h, hipMemsetAsync(t.c, 0, bytes, st));
   if (reserve(h, h->s_zero, (size_t)Tt * sizeof(int32_t) + (size_t)h->cfg.encoding_size * sizeof(float))) return 1;
   HIPCHECK(h, hipMemsetAsync(h->s_zero.p, 0, (size_t)Tt * sizeof(int32_t), st));
   if (record((const int32_t *)h->s_zero.p, (float *)((char *)h->s_zero.p + (size_t)Tt * sizeof(int32_t)), Tt)) return 1;
+  t.T = Tt;  // rows beyond Tt (an earlier, longer recording) are stale: a later, longer T records again
   t.valid = true;
   return 0;
 }
@@ -546,28 +550,29 @@ static int ensure_cu_count(sse_handle *h) {
   return 0;
 }
 
+enum class LstmPath { Unset, Persist, Cluster, Small, X3, Fwd, Error /* h->err is set */ };
+
 // what the caller of one inference encode knows beyond the ids
 struct EncodeRequest {
   const int32_t *row_map = nullptr;  // host pad-prefix row sort (encode_host_ids_locked): row b of the kernels is caller row row_map[b]
   bool padded_hint = false;          // ... with it: the batch's mean leading-PAD count is >= T / 4
   bool allow_cluster = true;         // false: the re-run of a batch whose cluster-kernel launch gave up (encode_fallback_locked)
+  LstmPath path = LstmPath::Unset;   // set: choose_lstm_path already ran for this call (encode_host_ids_locked, before its sort)
 };
-
-enum class LstmPath { Persist, Cluster, Small, X3, Fwd, Error /* h->err is set */ };
 
 // The LSTM kernel that runs an inference encode of B x T ids of encoder e, first match wins.  The only reader of the
 // back-off after a give-up (cluster_skip): an eligible call of a backed-off kernel counts it down and goes on to the next
-// candidate.  dry_run: report the choice only, count nothing down -- the host-side pad-prefix row sort asks ahead of the call
-// whether the cluster kernel, which does not want the sort, will take the batch (shape, back-off, the device's CU
-// count and the LDS fit all enter).
-LstmPath choose_lstm_path(sse_handle *h, const Encoder &e, int B, int T, const EncodeRequest &rq, bool dry_run = false) {
+// candidate.  Called once per encode: the host-side pad-prefix row sort asks before it sorts, because the cluster kernel
+// takes rows as they come (shape, back-off, the device's CU count and the LDS fit all enter), and hands the
+// answer on in EncodeRequest::path; every other encode asks in encode_dev_locked.
+LstmPath choose_lstm_path(sse_handle *h, const Encoder &e, int B, int T, const EncodeRequest &rq) {
   const sse_config &c = h->cfg;
   const bool small_ok = !rq.row_map && lstm_small_lds_bytes(c.embedding_size, e.H, c.encoding_size) <= 160 * 1024;
   // one to a few queries: the single-query cluster kernel, with every workgroup of the launch resident at once (at most half
   // the CUs are asked for)
   if (rq.allow_cluster && small_ok && B <= h->lstm_persist_rows && B <= lstm_persist_max_rows() && T <= lstm_persist_max_steps()) {
     if (h->cluster_skip[0] > 0) {
-      if (!dry_run) --h->cluster_skip[0];
+      --h->cluster_skip[0];
     } else {
       const int nwg = lstm_persist_nwg(c.embedding_size, e.H, c.encoding_size);
       if (ensure_cu_count(h)) return LstmPath::Error;
@@ -578,7 +583,7 @@ LstmPath choose_lstm_path(sse_handle *h, const Encoder &e, int B, int T, const E
   if (rq.allow_cluster && small_ok && B > 32 && B <= cluster_row_limit(h, e) && T <= lstm_persist_max_steps() &&
       lstm_cluster_ok(c.embedding_size, e.H, c.encoding_size)) {
     if (h->cluster_skip[1] > 0) {
-      if (!dry_run) --h->cluster_skip[1];
+      --h->cluster_skip[1];
     } else if (!ensure_cu_count(h)) {
       const int ncl = (std::min(B, std::min(h->lstm_cluster_rows, lstm_cluster_max_rows())) + 63) / 64;
       if ((ncl <= 8 ? 128 : 256) <= h->cu_count) return LstmPath::Cluster;
@@ -931,12 +936,13 @@ int encode_dev_locked(sse_handle *h, int side, const int32_t *ids, int B, int T,
   if (e.kernel < 0) return fail(h, "network mode has no %s sequence encoder (sse_model.py:231-233)", side ? "target" : "source");
   if (e.generic) return encode_generic_locked(h, e, ids, B, T, normalize, out, st);
   if (ensure_packed(h, st)) return 1;
-  switch (choose_lstm_path(h, e, B, T, rq)) {
+  switch (rq.path != LstmPath::Unset ? rq.path : choose_lstm_path(h, e, B, T, rq)) {
     case LstmPath::Persist: return encode_persist(h, side, ids, B, T, normalize, out, st);
     case LstmPath::Cluster: return encode_cluster(h, side, ids, B, T, normalize, out, st);
     case LstmPath::Small: return encode_small(h, side, ids, B, T, normalize, out, st);
     case LstmPath::X3: return encode_x3(h, side, ids, B, T, normalize, out, rq, st);
     case LstmPath::Fwd: return encode_fwd(h, side, ids, B, T, normalize, out, rq, st);
+    case LstmPath::Unset:
     case LstmPath::Error: break;
   }
   return 1;
@@ -1657,9 +1663,11 @@ static int encode_host_ids_locked(sse_handle *h, int side, const int32_t *ids_ho
   const bool lstm_side = h->cfg.network_mode != SSE_MODE_SOURCE_ONLY_CNN && !(side == SSE_SIDE_TARGET && h->tgt_table >= 0);
   EncodeRequest rq;
   const Encoder &e = h->enc[side];
-  const bool to_cluster = lstm_side && e.kernel >= 0 && !e.generic &&  // (the cluster kernel takes rows as they come)
-                          choose_lstm_path(h, e, B, T, rq, /*dry_run=*/true) == LstmPath::Cluster;
-  if (h->pad_skip && lstm_side && B > 64 && B > h->lstm_small_rows && !to_cluster && !e.generic) {
+  if (lstm_side && e.kernel >= 0 && !e.generic) {  // the kernel, chosen once: the cluster kernel takes rows as they come
+    rq.path = choose_lstm_path(h, e, B, T, rq);
+    if (rq.path == LstmPath::Error) return 1;
+  }
+  if (h->pad_skip && lstm_side && B > 64 && B > h->lstm_small_rows && rq.path != LstmPath::Cluster && !e.generic) {
     // counting sort of the row numbers by leading-PAD count, shortest prefix first (the tiles with the most steps left are
     // dispatched first; see pack.hip, pad_lead_kernel)
     std::vector<int32_t> lead(B), start(T + 2, 0), order(B);
