@@ -252,7 +252,9 @@ int sse_train_step(sse_handle *h, const int32_t *src_ids_host, const int32_t *tg
  * bit-identical on every rank.  sse_train_set_grad_arena lets the caller own
  * the buffer (e.g. a torch tensor handed to torch.distributed.all_reduce);
  * NULL returns to a library-owned one.  sse_train_step == grads(rows_global =
- * B) + apply. */
+ * B) + apply.  sse_train_grads[_rows] fails (no gradients pending, so a
+ * following sse_train_apply changes nothing) on a token id, corpus row or
+ * free-target-matrix row out of range, whatever the shape, path or network mode. */
 /* The stream the train-step entry points (sse_train_step[_rows], sse_train_grads[_rows], sse_train_apply) enqueue on;
  * NULL (the default) is the null stream.  The two encoders of a step run on internal side streams forked from and joined
  * to this stream, so a caller that orders other work against it (torch.distributed orders a collective against torch's

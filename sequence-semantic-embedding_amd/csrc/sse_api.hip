@@ -2524,8 +2524,10 @@ static int train_grads_generic_locked(sse_handle *h, const int32_t *src_ids_host
                                    (float *)ts.gen_hl[s].p, h->err_flag, st));
     HIPCHECK(h, launch_gen_project((const float *)ts.gen_hl[s].p, (const float *)ts.gen_MT[s].p, d, S, (float *)ts.raw[s].p, st));
   }
-  // (no host round trip here any more: gen_dx_scatter_kernel validates the ids itself, as rows_scatter_kernel and cnn_dx_kernel do;
-  // the forward raised the error flag, the update is cancelled on the device and sse_train_apply reports it)
+  // token ids / target rows out of range: gen_dx_scatter_kernel validates the ids itself, as rows_scatter_kernel and cnn_dx_kernel
+  // do, so the fused step (sse_train_step) reads the flag once with the loss and cancels its update on the device; sse_train_grads
+  // reads it now, as the other two paths do, so that a rank with a bad id fails here instead of only in its own sse_train_apply
+  if (!ts.defer_err && check_err_flag(h, st)) return 1;
   // ---- loss, train accuracy, d(raw encodings)
   if (reserve(h, ts.row_loss, (size_t)B * sizeof(float))) return 1;
   if (reserve(h, ts.row_acc, (size_t)B * sizeof(float))) return 1;
