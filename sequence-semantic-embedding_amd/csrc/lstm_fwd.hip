@@ -33,6 +33,7 @@
 // The bias is not added separately: the padded embedding table carries a constant 1.0 in column E
 // and the packed kernel the bias (forget-bias folded in) in k-row E, so it rides in the GEMM.
 #include <cstdlib>
+#include <type_traits>
 
 #include "sse_kernels.h"
 
@@ -88,10 +89,16 @@ __device__ __forceinline__ f32x4 wload(__amdgpu_buffer_rsrc_t r, int voff, int s
 // the partner's MFMAs double the cover -- but a wave that runs its pass while the partner is in its gate epilogue or waits at
 // the barrier had 8*MT*64 cycles to hide an L2 round trip: clock64 showed such passes at 73 % of the matrix rate at MT = 1.)
 // The accumulation order is k-group by k-group as before: results are bit-identical.
-// kbeg: first k-group.
-template <int MT, bool LIN, bool SWAP, int R = (MT == 1 ? 4 : 3), bool PRIO = true>
+// kbeg: first k-group.  tail(): issued right after the ring's last load, ahead of the MFMAs of the last groups (the x-table
+// prefetch of the next pass): vector-memory loads return in order for vmcnt, so loads issued there are younger than every
+// ring load and no counted wait of the ring waits for them.
+struct NoTail {
+  __device__ void operator()() const {}
+};
+template <int MT, bool LIN, bool SWAP, int R = (MT == 1 ? 4 : 3), bool PRIO = true, typename Tail = NoTail>
 __device__ __forceinline__ void gemm_pass(__amdgpu_buffer_rsrc_t wr, int voff, int soff, const float *const (&xa)[MT],
-                                          const float *const (&ha)[MT], int KGx, int kend, f32x16 (&acc)[MT][2], int kbeg = 0) {
+                                          const float *const (&ha)[MT], int KGx, int kend, f32x16 (&acc)[MT][2], int kbeg = 0,
+                                          const Tail &tail = Tail{}) {
   auto a_frag = [&](int m, int kg) -> f32x4 {
     if constexpr (LIN) return *reinterpret_cast<const f32x4 *>(xa[m] + kg * 256);
     return *reinterpret_cast<const f32x4 *>(kg < KGx ? xa[m] + kg * 256 : ha[m] + (kg - KGx) * 256);
@@ -132,6 +139,11 @@ __device__ __forceinline__ void gemm_pass(__amdgpu_buffer_rsrc_t wr, int voff, i
 #pragma unroll
       for (int m = 0; m < MT; ++m) af[s][m] = a_frag(m, kn);
     }
+  }
+  if constexpr (!std::is_same_v<Tail, NoTail>) {
+    __builtin_amdgcn_sched_barrier(0);
+    tail();
+    __builtin_amdgcn_sched_barrier(0);
   }
   // the last kend % R groups: their operands are stages 0 .. already loaded
 #pragma unroll
@@ -360,31 +372,52 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
   const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float *>(a.Wp), 0, (KGh / 4) * KG * 4096, 0x00020000);
   const int wvoff = lane * 16;
+  // XT: the table [V][xtab_ub][4 gates][lane >> 5][16] through a buffer descriptor too (the launcher keeps it below 2 GiB):
+  // per lane one 32-bit byte offset per token, the unit block and gate in the scalar offset, the rest immediates
+  const __amdgpu_buffer_rsrc_t xtr = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float *>(a.xtab), 0, XT ? a.V * a.xtab_ub * 512 : 0, 0x00020000);
+  // gate tiles q, q + 1 of unit block ub for the tokens id[]: the accumulators a pass starts from (4 x 2 x 16 B per m)
+  auto xt_load = [&](f32x16(&acc)[MT][2], const int (&id)[MT], int ub, int q) {
+    const int soff = __builtin_amdgcn_readfirstlane(ub * 512 + q * 128);
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      const int voff = id[m] * (a.xtab_ub * 512) + (lane >> 5) * 64;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const f32x4 v0 = wload(xtr, voff + 16 * i, soff), v1 = wload(xtr, voff + 128 + 16 * i, soff);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          acc[m][0][4 * i + e] = v0[e];
+          acc[m][1][4 * i + e] = v1[e];
+        }
+      }
+    }
+  };
 
   // gate accumulators of a pass (zero, or XT: the x part from the table)
   auto acc_init = [&](f32x16(&acc)[MT][2], const int (&id)[MT], int ub, int q) {
+    if constexpr (XT) {
+      xt_load(acc, id, ub, q);
+    } else {
 #pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      if constexpr (XT) {
-        const float *src = a.xtab + (((size_t)id[m] * a.xtab_ub + ub) * 4 + q) * 32 + (lane >> 5) * 16;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const f32x4 v0 = *reinterpret_cast<const f32x4 *>(src + 4 * i), v1 = *reinterpret_cast<const f32x4 *>(src + 32 + 4 * i);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            acc[m][0][4 * i + e] = v0[e];
-            acc[m][1][4 * i + e] = v1[e];
-          }
-        }
-      } else {
+      for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           acc[m][0][r] = 0.0f;
           acc[m][1][r] = 0.0f;
         }
-      }
     }
   };
+
+  // XT step-ahead schedule (PF): every pass starts from table fragments loaded one pass earlier -- pass B's (into gb) right
+  // after pass A's k-loop issued its last ring load, the next pass A's (into ga: the next unit block, or step t+1 with ids
+  // checked first) right after pass B's.  Epilogue A, epilogue B and the barrier cover their latency instead of the head of
+  // the pass.  Costs a second accumulator set (16 * 2 * MT VGPRs): <2,2,1> 181 -> 239 VGPRs, still two waves per SIMD.
+  // <1,1,1> (128 -> 158) and <1,1,2> (151 -> 180) would drop to 3 / 2 waves per SIMD: they keep loading at the pass head.
+  constexpr bool PF = XT && RT == 2 && MT == 2 && UBW == 1;
+  const bool live0 = !(a.H > 0 && ub0 * 32 >= a.H);  // this wave computes at least one unit block (live blocks are a prefix)
+  f32x16 ga[MT][2], gb[MT][2];  // accumulators of pass A / pass B (PF: filled one pass ahead)
+  if (PF && live0) xt_load(ga, xid, ub0, 0);
 
   FW_CLK_DECL
   for (int t = t0; t < T; ++t) {
@@ -394,7 +427,7 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
     const bool have_next = (t + 1) < T;
     int nid = 0;
     f32x4 nlo = {0, 0, 0, 0}, nhi = {0, 0, 0, 0};
-    int xnid[MT];  // XT: raw ids of step t+1, checked at the end of the step (the load has the whole step to land)
+    int xnid[MT];  // XT: raw ids of step t+1, checked before their first use (the load has a pass or more to land)
 #pragma unroll
     for (int m = 0; m < MT; ++m) xnid[m] = XT && have_next ? xt_id(m, t + 1) : 0;
     if (!XT && have_next) {
@@ -496,20 +529,41 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
       // coordinates -- instead of 16*MT registers held across pass B.
       // (accumulators start at 0: the bias arrives through the constant-1 column of x, see the file header.  XT: they start
       // from the table, i.e. the state after the x k-groups, and the pass runs the h k-groups -- none in step 0)
-      f32x16 g[MT][2];
       float *hdst[MT];
-      auto pass = [&](int soff, f32x16(&acc)[MT][2]) {
+      auto pass = [&](int soff, f32x16(&acc)[MT][2], const auto &tail) {
         if constexpr (XT) {
-          if (t > 0) gemm_pass<MT, true, SWAP>(wr, wvoff, soff + KGx * 4096, ha, ha, 0, KGhe, acc);
+          if (t > 0) gemm_pass<MT, true, SWAP>(wr, wvoff, soff + KGx * 4096, ha, ha, 0, KGhe, acc, 0, tail);
+          else tail();
         } else {
           gemm_pass<MT, LIN, SWAP>(wr, wvoff, soff, xa, ha, KGx, kend, acc);
         }
       };
+      auto tail_a = [&] {  // PF: pass B's table fragments
+        if constexpr (PF) xt_load(gb, xid, ub, 2);
+      };
+      auto tail_b = [&] {  // PF: the next pass A's -- the next live unit block of this step, else step t+1 (ids checked first)
+        if constexpr (PF) {
+          if (u + 1 < UBW && (a.H <= 0 || (ub + 8) * 32 < a.H)) {
+            xt_load(ga, xid, ub + 8, 0);
+          } else if (have_next) {
+#pragma unroll
+            for (int m = 0; m < MT; ++m) xid[m] = xt_check(xnid[m]);
+            xt_load(ga, xid, ub0, 0);
+          } else {
+            // last step: no prefetch.  Overwrite the spent pass-A accumulators anyway, or they would stay live through
+            // pass B into the loop's back edge (64 VGPRs at <2,2,1>: spills)
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+#pragma unroll
+              for (int r = 0; r < 16; ++r) ga[m][0][r] = ga[m][1][r] = 0.0f;
+          }
+        }
+      };
 #pragma unroll
       for (int m = 0; m < MT; ++m) hdst[m] = hptr(nxt, mt0 + m) + hoff;
-      if (!XT || do_a) acc_init(g, xid, ub, 0);
+      if (!PF && (!XT || do_a)) acc_init(ga, xid, ub, 0);
       FW_CLK(1)
-      if (do_a) pass(wsoff, g);
+      if (do_a) pass(wsoff, ga, tail_a);
       FW_CLK(2)
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
@@ -520,8 +574,8 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
             f32x4 pij, si4, tj4;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              si4[e] = fast_sigmoid(g[m][0][q4 * 4 + e]);
-              tj4[e] = fast_tanh(g[m][1][q4 * 4 + e]);
+              si4[e] = fast_sigmoid(ga[m][0][q4 * 4 + e]);
+              tj4[e] = fast_tanh(ga[m][1][q4 * 4 + e]);
               pij[e] = si4[e] * tj4[e];
             }
             *reinterpret_cast<f32x4 *>(hdst[m] + q4 * 256) = pij;
@@ -537,8 +591,8 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const int r = q4 * 4 + e;
-              si4[e] = fast_sigmoid(g[m][0][r]);
-              tj4[e] = fast_tanh(g[m][1][r]);
+              si4[e] = fast_sigmoid(ga[m][0][r]);
+              tj4[e] = fast_tanh(ga[m][1][r]);
               hdst[m][mfma_row(r, lane) << 2] = si4[e] * tj4[e];
             }
             if constexpr (TRAIN) {
@@ -563,9 +617,9 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
         tape_x(t + 1, xq, nlo, nhi);  // TSW: x columns of the next step's A-tape (zeros where xq >= KGx)
       }
       // pass B: gates f (+1 folded into the bias), o -> c' = c*sigmoid(f) + pij ; h' = tanh(c')*sigmoid(o)
-      if (!XT || do_b) acc_init(g, xid, ub, 2);
+      if (!PF && (!XT || do_b)) acc_init(gb, xid, ub, 2);
       FW_CLK(3)
-      if (do_b) pass(wsoff + 2048, g);
+      if (do_b) pass(wsoff + 2048, gb, tail_b);
       FW_CLK(4)
       if (do_b && !do_a) {  // split3: the i,j pass of this (block, row tile) comes from the partner wave
         while (__hip_atomic_load(pass_flag + fidx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < t + 1) __builtin_amdgcn_s_sleep(2);
@@ -583,8 +637,8 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const int r = q4 * 4 + e;
-              const float sf = fast_sigmoid(g[m][0][r]);
-              const float so = fast_sigmoid(g[m][1][r]);
+              const float sf = fast_sigmoid(gb[m][0][r]);
+              const float so = fast_sigmoid(gb[m][1][r]);
               const float cn = c[u][m][r] * sf + pij[e];
               c[u][m][r] = cn;
               hv4[e] = fast_tanh(cn) * so;
@@ -600,8 +654,8 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
                 const int r = q4 * 4 + e;
-                sf4[e] = fast_sigmoid(g[m][0][r]);  // (the values computed above: common subexpressions)
-                so4[e] = fast_sigmoid(g[m][1][r]);
+                sf4[e] = fast_sigmoid(gb[m][0][r]);  // (the values computed above: common subexpressions)
+                so4[e] = fast_sigmoid(gb[m][1][r]);
                 cn4[e] = c[u][m][r];
               }
               __builtin_nontemporal_store(sf4, reinterpret_cast<f32x4 *>(tp[m] + 2048 + q4 * 256));
@@ -626,8 +680,8 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const int r = q4 * 4 + e;
-              const float sf = fast_sigmoid(g[m][0][r]);
-              const float so = fast_sigmoid(g[m][1][r]);
+              const float sf = fast_sigmoid(gb[m][0][r]);
+              const float so = fast_sigmoid(gb[m][1][r]);
               const float cn = c[u][m][r] * sf + hdst[m][mfma_row(r, lane) << 2];
               c[u][m][r] = cn;
               const float hv = fast_tanh(cn) * so;
@@ -654,7 +708,7 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
       FW_CLK(7)
 #pragma unroll
       for (int m = 0; m < MT; ++m)
-        if (XT && have_next) xid[m] = xt_check(xnid[m]);
+        if (XT && !(PF && live0) && have_next) xid[m] = xt_check(xnid[m]);  // (PF: checked before the prefetch)
     } else {
       __syncthreads();
       if (have_next) {
@@ -797,6 +851,7 @@ static hipError_t launch_cfg(const LstmFwdArgs &a_in, hipStream_t stream) {
   if constexpr (!SPL && !(RT == 2 && MT == 1)) {  // inference with the x table (the Hp = 256 / 512 configurations)
     if (!train && a.xtab != nullptr) {
       if (a.xtab_ub != (a.H > 0 ? (a.H + 31) / 32 : a.KGh / 4)) return hipErrorInvalidValue;
+      if ((int64_t)a.V * a.xtab_ub * 512 > INT32_MAX) return hipErrorInvalidValue;  // buffer offsets are 32-bit (ensure_x_table)
       return launch_one<RT, MT, UBW, false, true, false, false, true>(a, lstm_fwd_xt_lds_bytes(a.KGh, RT), stream);
     }
   }

@@ -830,7 +830,7 @@ int ensure_x_table(sse_handle *h, Encoder &own, int B, int T, hipStream_t st, bo
   const int64_t V = h->cfg.vocab_size;
   const int UBt = (own.H + 31) / 32;
   const size_t bytes = lstm_xtable_floats(V, UBt) * sizeof(float);
-  if (bytes > ((size_t)h->lstm_x_table_mb << 20)) return 0;
+  if (bytes > ((size_t)h->lstm_x_table_mb << 20) || bytes > (size_t)INT32_MAX) return 0;  // (lstm_fwd reads it with 32-bit offsets)
   if (own.xtab_valid) {
     *use = true;
     return 0;
