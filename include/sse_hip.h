@@ -207,6 +207,10 @@ int sse_merge_topk_strided_dev(sse_handle *h, const double *in_scores_dev, const
  *   sse_allgather_merge_topk_dev  this rank's [Q][k] lists (global row ids) -> ONE ncclAllGather of the packed
  *       (float64 score bits | int64 ids) words on `stream` -> k-way merge: the unsharded result on every rank;
  *   sse_score_topk_sharded_dev    sse_score_topk_dev on this rank's shard (rows set with id_base = shard offset) + the above;
+ *       LIMIT: k is handed to the shard sweep as it is, so k <= the rows of EVERY rank's shard (and no rank without rows):
+ *       a 571-row index over 8 ranks takes k <= 71.  A host that needs more ranks min(k, rows) per shard, pads the lists to k
+ *       with (-inf, INT64_MAX) and calls sse_allgather_merge_topk_dev -- the merge never emits a padding slot while the shards
+ *       together hold >= k rows (sharded.py::ShardedIndex does this over torch.distributed);
  *   sse_rccl_get_unique_id / sse_rccl_comm_init_rank / sse_rccl_comm_destroy: thin conveniences over ncclGetUniqueId /
  *       ncclCommInitRank / ncclCommDestroy for hosts without an RCCL binding of their own (id128: the 128-byte ncclUniqueId;
  *       rank 0 creates it and hands it to the other ranks by whatever channel the host has -- file, socket, MPI).

@@ -9,7 +9,11 @@ bit-identical on every rank and equals the single-process step on the concatenat
 The reference trains in one process (sse_train.py:170-172); this is the exchange step a multi-GPU job adds.
 The engine is anything with train_grad_count / train_bind_arena / train_grads / train_apply: the HIP handle
 (sequence-semantic-embedding_amd/_lib.py) in the product, the numpy oracle in the CPU `gloo` tests.
-torch / torch.distributed are plumbing only.
+torch / torch.distributed are plumbing only.  The collectives go through collectives.py: RCCL as is under `nccl`, staged
+through the host under any other backend (ranks as processes on one GPU).
+
+Known property: every rank must reach every collective of a step.  A rank whose train_grads raises (a bad token id, say)
+leaves the step before the all-reduce while its peers wait in it until the process group's timeout; the caller ends the job.
 """
 
 
@@ -45,12 +49,12 @@ class DataParallelTrainer(object):
         """(sum, max) of the ranks' row counts: one tiny all-gather (both are needed: the loss is a mean over the sum,
         the packed embedding exchange is sized by the max)."""
         import torch
-        import torch.distributed as dist
+        from .collectives import all_gather_into
         if self.world == 1:
             return int(local_rows), int(local_rows)
         t = torch.tensor([int(local_rows)], dtype=torch.int64, device=self.arena.device)
         out = torch.empty(self.world, dtype=torch.int64, device=self.arena.device)
-        dist.all_gather_into_tensor(out, t, group=self.group)
+        all_gather_into(out, t, group=self.group)
         out = out.cpu()
         return int(out.sum()), int(out.max())
 
@@ -61,7 +65,7 @@ class DataParallelTrainer(object):
         (the reference's truncated batches, data.py:98) leave it None.
         by_rows: src_ids / tgt_ids are row numbers into the corpora uploaded with engine.corpus_upload."""
         import torch
-        import torch.distributed as dist
+        from .collectives import all_reduce_
         if self.arena.is_cuda and hasattr(self.engine, "set_stream"):
             # the train step runs on the library's own streams forked from / joined to ONE stream, and torch.distributed
             # orders the collective against torch's CURRENT stream: hand that stream to the library (sse_set_stream)
@@ -84,7 +88,7 @@ class DataParallelTrainer(object):
             if self._use_sparse(rows_global, src_ids, by_rows):
                 self._exchange_sparse(rows_cap, self._seq_len(src_ids, by_rows))
             else:
-                dist.all_reduce(self.arena, group=self.group)      # ONE collective per step (sum)
+                all_reduce_(self.arena, group=self.group)          # ONE collective per step (sum)
                 self.last_exchange = "dense"
         return self.engine.train_apply()
 
@@ -116,20 +120,20 @@ class DataParallelTrainer(object):
         order by the engine (HIP kernels behind the C ABI: sse_train_pack / unpack_embedding_grad) -- no torch kernels, no
         host synchronisation."""
         import torch
-        import torch.distributed as dist
+        from .collectives import all_gather_into, all_reduce_
         off, V, E = self.emb_slice
         cap = max(1, min(V, 2 * int(rows_cap) * int(T)))
         n = self.engine.dp_packed_floats(cap)
         if self._packed is None or self._packed.numel() != n or self._gathered.numel() != n * self.world:
             self._packed = torch.zeros(n, dtype=torch.float32, device=self.arena.device)
             self._gathered = torch.zeros(n * self.world, dtype=torch.float32, device=self.arena.device)
-        works = [dist.all_reduce(part, group=self.group, async_op=True)          # everything but the embedding block
+        works = [all_reduce_(part, group=self.group, async_op=True)              # everything but the embedding block
                  for part in (self.arena[:off], self.arena[off + V * E:]) if part.numel()]
         self.engine.dp_pack_embedding(cap, self._packed)
         if self.world == 1 and not self.always_reduce:
             self._gathered.copy_(self._packed)
         else:
-            dist.all_gather_into_tensor(self._gathered, self._packed, group=self.group)
+            all_gather_into(self._gathered, self._packed, group=self.group)
         self.engine.dp_unpack_embedding(self._gathered, self.world, cap)
         for w in works:
             w.wait()

@@ -10,6 +10,11 @@ block i runs on RCCL's stream while block i+1 sweeps the shard.  Every library
 call is enqueued on torch's CURRENT stream (passed explicitly), which is also
 the stream torch.distributed orders its collectives against.
 
+Any 1 <= k <= n_total is served: a shard with r < k rows (the 571-row demo index over 8 ranks at k = 100; an EMPTY
+shard when n_total < world) scores min(k, r) and pads its list to k with (-inf, INT64_MAX) before the gather.  The
+merge ranks such a slot behind every real row and, because the shards together hold >= k real rows, never writes one
+into the result.  Under a backend other than `nccl` the gather is staged through the host (collectives.py).
+
 The reference has no distributed code at all; this is the one real exchange
 step of the hot path.  torch / torch.distributed are plumbing only.
 """
@@ -31,6 +36,7 @@ def all_gather_topk(local_scores, local_ids, group=None, force=False):
     nccl backend, CPU with gloo); returns ([P,Q,k] scores, [P,Q,k] ids), shard-major."""
     import torch
     import torch.distributed as dist
+    from .collectives import all_gather_into
     world = dist.get_world_size(group)
     gs = torch.empty((world,) + tuple(local_scores.shape), dtype=local_scores.dtype, device=local_scores.device)
     gi = torch.empty((world,) + tuple(local_ids.shape), dtype=local_ids.dtype, device=local_ids.device)
@@ -39,8 +45,8 @@ def all_gather_topk(local_scores, local_ids, group=None, force=False):
         gi[0].copy_(local_ids)
         return gs, gi
     if local_scores.is_cuda:
-        dist.all_gather_into_tensor(gs, local_scores.contiguous(), group=group)
-        dist.all_gather_into_tensor(gi, local_ids.contiguous(), group=group)
+        all_gather_into(gs, local_scores.contiguous(), group=group)
+        all_gather_into(gi, local_ids.contiguous(), group=group)
     else:                                   # gloo: list form
         dist.all_gather(list(gs.unbind(0)), local_scores.contiguous(), group=group)
         dist.all_gather(list(gi.unbind(0)), local_ids.contiguous(), group=group)
@@ -58,16 +64,23 @@ class ShardedIndex(object):
         self.start, self.end = shard_bounds(n_total, world)[rank]
 
     def set_local_rows(self, rows):
-        """rows: CUDA float32 tensor [end-start, S] -- this rank's shard, already on its GPU."""
+        """rows: CUDA float32 tensor [end-start, S] -- this rank's shard, already on its GPU.  A rank without rows
+        (n_total < world) passes its [0, S] tensor: nothing is uploaded, score_topk contributes an empty list."""
         if rows.shape[0] != self.end - self.start:
             raise ValueError("shard of rank %d must have %d rows, got %d" % (self.rank, self.end - self.start, rows.shape[0]))
-        self.handle.index_set_dev(rows.data_ptr(), rows.shape[0], rows.shape[1], id_base=self.start)
+        if rows.shape[0] > 0:
+            self.handle.index_set_dev(rows.data_ptr(), rows.shape[0], rows.shape[1], id_base=self.start)
 
     def score_topk(self, queries, k, block=8192):
         """queries: CUDA float32 [Q,S] (identical on every rank).  Returns the global
-        top-k (scores float64 [Q,k], row ids int64 [Q,k]) on every rank."""
+        top-k (scores float64 [Q,k], row ids int64 [Q,k]) on every rank, for any 1 <= k <= n_total (ValueError
+        otherwise, on every rank alike and before any collective)."""
         import torch
         import torch.distributed as dist
+        from .collectives import all_gather_into
+        k = int(k)
+        if not 1 <= k <= self.n_total:
+            raise ValueError("k=%d must be in [1, n_total=%d]" % (k, self.n_total))
         Q = queries.shape[0]
         dev = queries.device
         stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
@@ -77,16 +90,27 @@ class ShardedIndex(object):
             self.handle.score_topk_dev(queries.data_ptr(), Q, k, fs.data_ptr(), fi.data_ptr(), stream)
             return fs, fi
         world = dist.get_world_size(self.group)
+        kl = min(k, self.end - self.start)                                 # what this shard can rank: the library takes k <= rows
         pending = None                                                     # (work, gathered, q0, n) of the previous block
         for q0 in list(range(0, Q, block)) + [None]:
             if q0 is not None:
                 n = min(block, Q - q0)
                 loc = torch.empty((2, n, k), dtype=torch.int64, device=dev)
-                self.handle.score_topk_dev(queries[q0:q0 + n].data_ptr(), n, k, loc[0].data_ptr(), loc[1].data_ptr(), stream)
+                if kl == k:
+                    self.handle.score_topk_dev(queries[q0:q0 + n].data_ptr(), n, k, loc[0].data_ptr(), loc[1].data_ptr(), stream)
+                else:
+                    # short shard: slots kl .. k-1 of every list hold (-inf, INT64_MAX); the library's packed [n, kl]
+                    # result is spread into the k-wide rows by a strided device copy on the same stream
+                    loc[0].view(torch.float64).fill_(float("-inf"))
+                    loc[1].fill_(torch.iinfo(torch.int64).max)
+                    if kl > 0:
+                        short = torch.empty((2, n, kl), dtype=torch.int64, device=dev)
+                        self.handle.score_topk_dev(queries[q0:q0 + n].data_ptr(), n, kl, short[0].data_ptr(), short[1].data_ptr(), stream)
+                        loc[:, :, :kl].copy_(short)
                 g = torch.empty((world * 2, n, k), dtype=torch.int64, device=dev)   # concatenation along dim 0 (gloo and nccl)
                 # one collective for scores and ids; async: RCCL's stream waits for the sweep just enqueued, the host
                 # goes on to enqueue the next block's sweep
-                work = dist.all_gather_into_tensor(g, loc, group=self.group, async_op=True)
+                work = all_gather_into(g, loc, group=self.group, async_op=True)
                 nxt = (work, g, loc, q0, n)
             else:
                 nxt = None
@@ -103,7 +127,9 @@ class RcclShardedIndex(object):
     """The same sharded index WITHOUT torch.distributed: the exchange is the library's own entry point
     (sse_score_topk_sharded_dev: shard sweep -> ONE ncclAllGather of the packed lists -> k-way merge, all on one stream)
     over an RCCL communicator created through the C ABI.  What a reference-side integration that must not import torch
-    uses; the host moves the 128-byte unique id from rank 0 to the other ranks itself."""
+    uses; the host moves the 128-byte unique id from rank 0 to the other ranks itself.
+    Limit: k <= the rows of EVERY shard (sse_score_topk_sharded_dev passes k to the shard sweep unchanged), and no shard
+    may be empty; ShardedIndex pads short shards instead."""
 
     def __init__(self, handle, rank, world, n_total, unique_id):
         self.handle, self.rank, self.world = handle, int(rank), int(world)

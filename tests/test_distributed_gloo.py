@@ -86,10 +86,14 @@ class _CpuShardHandle(object):
         return np.frombuffer(buf, dtype=dtype).reshape(shape)
 
     def index_set_dev(self, ptr, n, S, id_base=0, stream=0):
+        if n <= 0:
+            raise ValueError("empty index")                         # as sse_index_set_dev
         self.rows, self.base = self._view(ptr, (n, S), np.float32).astype(np.float64), id_base
 
     def score_topk_dev(self, q_ptr, Q, k, s_ptr, i_ptr, stream=0):
         from oracle import sse_oracle as O
+        if not 1 <= k <= self.rows.shape[0]:
+            raise ValueError("k=%d must be in [1, N=%d]" % (k, self.rows.shape[0]))   # as sse_score_topk_dev
         sc, ids = O.topk(O.scores_f64(self._view(q_ptr, (Q, self.S), np.float32), self.rows), k)
         self._view(s_ptr, (Q, k), np.float64)[:] = sc
         self._view(i_ptr, (Q, k), np.int64)[:] = ids + self.base
@@ -113,6 +117,8 @@ def _sharded_worker(rank, world, port, q_np, t_np, k, out_dir, block=16):
     sh = sse_amd.ShardedIndex(_CpuShardHandle(t_np.shape[1]), rank, world, t_np.shape[0])
     rows = torch.from_numpy(t_np[sh.start:sh.end].copy())
     sh.set_local_rows(rows)
+    with pytest.raises(ValueError):                                       # on every rank, before any collective
+        sh.score_topk(torch.from_numpy(q_np.copy()), t_np.shape[0] + 1, block=block)
     s, i = sh.score_topk(torch.from_numpy(q_np.copy()), k, block=block)   # 37 queries -> 3 blocks, gathers overlapped
     np.savez(os.path.join(out_dir, "sh%d.npz" % rank), s=s.numpy(), i=i.numpy())
     dist.barrier()
@@ -151,6 +157,26 @@ def test_eight_rank_sharded_index_uneven_blocks_and_shards(tmp_path):
     assert wids[3, :2].tolist() == [50, 51]
     for r in range(world):
         z = np.load(os.path.join(str(tmp_path), "sh%d.npz" % r))
+        assert np.array_equal(z["i"], wids) and np.abs(z["s"] - wsc).max() < 1e-12
+
+
+@pytest.mark.parametrize("Q,N,k,block", [(33, 25, 10, 8), (5, 2, 2, 8)], ids=["short", "empty"])
+def test_three_rank_shards_shorter_than_k(tmp_path, Q, N, k, block):
+    """Any 1 <= k <= n_total: 25 rows over 3 ranks are shards of 9 / 8 / 8 rows, all shorter than k = 10; 2 rows over 3 ranks
+    leave rank 2 without a row.  The stand-in handle refuses k > its rows and an empty upload as the library does, so the
+    product has to score min(k, rows) per shard and pad the list with (-inf, INT64_MAX); none of the padding reaches the
+    result, which is the unsharded ranking."""
+    from oracle import sse_oracle as O
+    rng = np.random.RandomState(N)
+    S, world = 16, 3
+    q = rng.standard_normal((Q, S)).astype(np.float32)
+    t = rng.standard_normal((N, S)).astype(np.float32)
+    port = _free_port()
+    mp.spawn(_sharded_worker, args=(world, port, q, t, k, str(tmp_path), block), nprocs=world, join=True)
+    wsc, wids = O.topk(O.scores_f64(q, t.astype(np.float64)), k)
+    for r in range(world):
+        z = np.load(os.path.join(str(tmp_path), "sh%d.npz" % r))
+        assert np.isfinite(z["s"]).all() and z["i"].max() < N
         assert np.array_equal(z["i"], wids) and np.abs(z["s"] - wsc).max() < 1e-12
 
 
