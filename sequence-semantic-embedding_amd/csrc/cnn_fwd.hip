@@ -16,6 +16,7 @@
 #define CNN_THREADS 512
 // sequences per workgroup: 8, or 4 when 8 embedded sequences (+ the training keys) do not fit the 160 KB of LDS
 // (e.g. the reference's default T = 80 with the arg-max tape)
+// rule (cnn_pick_nb): 8 while (8*T + 5) * Ep <= 36,348 floats for inference, <= 31,740 for training (T * Ep up to ~4,540 / ~3,960)
 #define CNN_SG 4   // sequences per wave work item (one B fragment feeds 4 MFMAs)
 
 struct CnnArgs {

@@ -12,21 +12,65 @@ import pytest
 
 from oracle import sse_oracle as O
 from tests.util import (GRAD_BARS_EXACT, GRAD_BARS_SPLIT, LOSS_REL_EXACT, LOSS_REL_SPLIT, arena_grads, check_grads,
-                        check_tail, make_pair, model_params, oracle_params, random_ids, reference_apply, reference_grads)
+                        check_tail, model_params, oracle_params, random_ids, reference_apply, reference_grads)
 
 pytestmark = pytest.mark.gpu
 
 
-def _case(cid, mode, V, E, Hs, Ht, S, T, B, N=13, batch="paired", opts=None, rows_factor=1, by_rows=False, seed=0):
+def _case(cid, mode, V, E, Hs, Ht, S, T, B, N=13, batch="paired", opts=None, rows_factor=1, by_rows=False, seed=0, **extra):
     opts = dict(opts or {})
     split = any(opts.get(k) for k in ("train_fwd_x3", "train_bwd_x3", "train_dk_x3"))
     return pytest.param(dict(id=cid, mode=mode, V=V, E=E, Hs=Hs, Ht=Ht, S=S, T=T, B=B, N=N, batch=batch, opts=opts, split=split,
-                             rows_factor=rows_factor, by_rows=by_rows, seed=seed), id=cid)
+                             rows_factor=rows_factor, by_rows=by_rows, seed=seed, **extra), id=cid)
+
+
+def _cnn(cid, V, E, S, T, B, N=17, seed=0, bf16=False, **kw):
+    """A text-CNN case.  Extra keys: distinct = D (batch kind "tiled": D distinct sequences tiled over the batch), conv_bias = v
+    (every conv bias set to v), dead = (lo, hi) (the share of pooled features that are exactly 0 must lie in [lo, hi]),
+    bars = a bar of the case's own, var_bars = {variable: bars}."""
+    return _case(cid, "source_only_cnn", V, E, 96, 96, S, T, B, N=N, seed=seed, opts=dict(cnn_bf16=1) if bf16 else None, **kw)
 
 
 def _x3(fwd, bwd, dk):
     return dict(train_fwd_x3=fwd, train_bwd_x3=bwd, train_dk_x3=dk)
 
+
+# Text-CNN, one case per backward branch.  The kernel a case takes, read from the launchers: cnn_dw_kernel<R,X16> with R = 8
+# (T <= 64), 12 (T <= 96), 0 (longer), X16 = bf16 with even E; dX by cnn_dx_mfma_kernel<ceil(T/32), ceil(E/32)> in bf16 mode up
+# to T = 96, else by the gather cnn_dx_kernel + dx_hot_reduce; NCH = min(ceil(B/32), 128) chunks; the training forward
+# conv_pool_kernel<true,NB> / conv_pool_bf16_kernel<NB,true> with NB = 8 sequences per workgroup while T * Ep <= ~3,940 (fp32,
+# Ep = E rounded up to 4) or T * Ep8 <= ~7,900 (bf16), else 4.  Seeds searched on the CPU so that no max-pool is within 1e-5 of
+# a tie and no pooled feature within 1e-5 of 0 (both asserted).  Left out on purpose: ids_fit == false with T <= 96 (the
+# chunk's ids no longer in LDS), which needs B above about 17,800 at T = 96.
+CNN_CASES = [
+    _cnn("cnn-t5", 60, 8, 16, 5, 24, N=64, seed=1),                       # ONE position for width 5; dw<8,false>; conv_pool<true,8>
+    _cnn("cnn-e3", 80, 3, 24, 12, 10, seed=4),                           # E < 4 (Ep 4): k-groups mostly padding
+    _cnn("cnn-t80-e50", 200, 50, 64, 80, 26, N=33, seed=6),              # reference default T; dw<12,false>; conv_pool<true,4>
+    _cnn("cnn-t96-e64", 150, 64, 64, 96, 20, seed=3),                    # dw<12,false> at its upper edge; E 64 (the training limit)
+    _cnn("cnn-t140-e64", 150, 64, 32, 140, 8),                   # dw<0,false>; training forward ~750 B below its LDS limit
+    _cnn("cnn-t150-e50", 120, 50, 32, 150, 12, seed=2),                  # dw<0,false>; 5 position tiles
+    _cnn("cnn-b9", 90, 24, 64, 20, 9, batch="unpaired", seed=7),         # odd B: DW_G tail, partial dX workgroup, Bp padding rows
+    _cnn("cnn-chunks", 90, 24, 64, 20, 200, N=400, batch="tiled", distinct=24, seed=2),        # 7 chunks, the last one partial; reduce order
+    # chunk cap: per = 33, chunks 125-127 empty.  A bar of its own: the float32 oracle itself is 1.47e-6 norm-relative (conv-
+    # maxpool-4/b; every conv variable and the embedding ~1.2e-6 alike) / 4.13e-6 per element (word_embedding) from float64 here
+    # -- the 4100-term float32 sums -- so 10x that, rounded up, instead of 25x 4e-7; still well inside GRAD_BARS_SPLIT
+    _cnn("cnn-b4100", 90, 16, 32, 12, 4100, N=6000, batch="tiled", distinct=24, seed=15, bars=(1.5e-5, 4.2e-5)),
+    _cnn("cnn-hot", 90, 24, 64, 20, 40, N=64, batch="cnn-hot", seed=12),        # hot_part + dx_hot_reduce, all-PAD pair, one repeated id
+    _cnn("cnn-dead", 90, 24, 64, 20, 10, conv_bias=-0.15, dead=(0.3, 0.7)),     # ReLU mask in db / dW / dX
+    _cnn("cnn-all-dead", 90, 24, 64, 20, 10, conv_bias=-10.0, dead=(1.0, 1.0)), # zero encodings through the 1e-12 clamp
+    _cnn("cnn-rows-global-3b", 90, 24, 64, 20, 10, rows_factor=3, seed=2),      # this rank's share of a mean over 3 B rows
+    _cnn("cnn-by-rows", 90, 24, 64, 20, 10, by_rows=True, seed=2),       # sse_train_grads_rows: uploaded source corpus, free-matrix rows
+    _cnn("cnn-bf16-11", 90, 24, 64, 20, 10, bf16=True),          # dx_mfma<1,1>; dw<8,true>
+    _cnn("cnn-bf16-12", 200, 50, 64, 30, 16, N=33, bf16=True, seed=7),   # dx_mfma<1,2>
+    _cnn("cnn-bf16-21", 200, 32, 64, 40, 16, N=33, bf16=True, seed=4),   # dx_mfma<2,1>
+    _cnn("cnn-bf16-31", 200, 30, 64, 96, 12, N=33, bf16=True, seed=1),   # dx_mfma<3,1>; dw<12,true>
+    _cnn("cnn-bf16-32", 200, 50, 64, 80, 26, N=33, bf16=True, seed=9),   # dx_mfma<3,2>; dw<12,true>
+    _cnn("cnn-bf16-e25", 200, 25, 64, 33, 18, N=33, bf16=True, seed=3),  # odd E: x16 false, dw<8,false> rounding while staging; dx_mfma<2,1>
+    _cnn("cnn-bf16-t100", 200, 50, 64, 100, 12, N=33, bf16=True, seed=1),               # gather dX over rounded filters; dw<0,true>
+    _cnn("cnn-bf16-t96-e64", 150, 64, 64, 96, 16, bf16=True, seed=2),    # dw<12,true>, dx_mfma<3,2> at both upper edges
+    _cnn("cnn-bf16-t140-e64", 150, 64, 32, 140, 8, bf16=True, seed=3),   # conv_pool_bf16<4,true> (T * Ep8 = 8,960); dw<0,true>; gather dX
+    _cnn("cnn-bf16-chunks", 90, 24, 64, 20, 200, N=400, batch="tiled", distinct=24, bf16=True, seed=30),   # chunks through dx_mfma, hot_part[workgroup]
+]
 
 CASES = [
     # configs[1] shape: paired (B % 128 == 0: source forward and dK on B/2 rows, dk_gemm2 pair) and the same batch unpaired
@@ -65,6 +109,7 @@ CASES = [
     # CNN: cnn_dw, cnn_dx(_mfma); seeds chosen so that no max-pool is within rounding of a tie (asserted below)
     _case("cnn", "source_only_cnn", 90, 24, 96, 96, 64, 20, 10, N=17, seed=1),
     _case("cnn-bf16", "source_only_cnn", 200, 50, 96, 96, 64, 33, 26, N=33, opts=dict(cnn_bf16=1), seed=0),
+] + CNN_CASES + [
     # BPTT edges, repeated / hot ids (dx_hot_reduce, the atomics scatter), labels all 1
     _case("t1", "dual-encoder", 100, 16, 64, 64, 32, 1, 64),
     _case("t2", "shared-encoder", 100, 16, 64, 64, 32, 2, 64),
@@ -78,9 +123,14 @@ CASES = [
 
 
 def case_params(c):
-    """(model params, oracle parameter dict) of a case: what make_pair loads into the GPU model."""
+    """(model params, oracle parameter dict) of a case: what _model loads into the GPU model."""
     params = model_params(c["mode"], c["V"], c["E"], c["Hs"], c["Ht"], c["S"], c["T"], N=c["N"], lr=0.9)
-    return params, oracle_params(params, seed=3 + c["seed"])
+    p = oracle_params(params, seed=3 + c["seed"])
+    if c.get("conv_bias") is not None:             # lowered conv biases: dead filters (pooled value exactly 0)
+        for k in p:
+            if k.endswith("/b"):
+                p[k] = np.full_like(p[k], c["conv_bias"])
+    return params, p
 
 
 def _ids(rng, B, T, V):
@@ -95,12 +145,14 @@ def case_batch(c):
     rng = np.random.RandomState(11 + c["seed"])
     B, T, V = c["B"], c["T"], c["V"]
     kind = c["batch"]
+    if kind in ("tiled", "cnn-hot"):               # the CNN-only kinds draw in an order of their own; every other kind as before
+        return _cnn_batch(c, rng)
     src = _ids(rng, B, T, V) if kind == "unpaired" else np.repeat(_ids(rng, B // 2, T, V), 2, axis=0)
     if c["mode"] in ("source-encoder-only", "source_only_cnn"):
         tgt = rng.randint(0, c["N"], size=B).astype(np.int32)
     else:
         tgt = _ids(rng, B, T, V)
-    z = np.tile(np.array([1.0, 0.0], np.float32), B // 2)
+    z = np.tile(np.array([1.0, 0.0], np.float32), (B + 1) // 2)[:B]     # odd B (unpaired only): one more positive row
     if kind == "edges":
         src[0:2] = 0                               # an all-PAD pair
         tgt[0] = 0
@@ -117,10 +169,45 @@ def case_batch(c):
     return src, tgt, z
 
 
+def _cnn_batch(c, rng):
+    """tiled: c["distinct"] (<= 24) distinct sequences repeated over the batch, target rows and labels drawn per row -- the
+    near-tie preconditions cannot hold for thousands of random sequences (the smallest gap over B * 576 features shrinks like
+    1 / B), while the weight gradients still sum a different g per row over every chunk.
+    cnn-hot: 80 % of the tokens PAD / EOS (the hot rows of the embedding scatter), an all-PAD pair, a pair of one repeated id."""
+    B, T, V, N = c["B"], c["T"], c["V"], c["N"]
+    if c["batch"] == "tiled":
+        D = c["distinct"]
+        assert D <= 24
+        src = _ids(rng, D, T, V)[np.arange(B) % D]
+        tgt = rng.randint(0, N, size=B).astype(np.int32)
+        return src, tgt, (rng.uniform(size=B) < 0.5).astype(np.float32)
+    half = _ids(rng, B // 2, T, V)
+    hot = rng.uniform(size=half.shape) < 0.8
+    half[hot] = rng.randint(0, 2, size=int(hot.sum()))
+    half[0] = 0
+    half[2] = 9
+    src = np.repeat(half, 2, axis=0)
+    tgt = rng.randint(0, N, size=B).astype(np.int32)
+    return src, tgt, np.tile(np.array([1.0, 0.0], np.float32), B // 2)
+
+
+def cnn_min_positive_pool(params, src, bf16):
+    """Smallest strictly positive pooled feature (inf if there is none): a feature that is 1e-8 here and 0 on the device (or
+    the reverse) switches a whole window of gradient on or off."""
+    pool = O.cnn_forward(params, np.unique(src, axis=0), bf16=bf16)
+    return float(pool[pool > 0].min()) if (pool > 0).any() else np.inf
+
+
+def cnn_dead_share(params, src, bf16):
+    """Share of the pooled features that are exactly 0 (ReLU closed at every position)."""
+    return float(np.mean(O.cnn_forward(params, src, bf16=bf16) == 0))
+
+
 def cnn_min_pool_gap(params, src, bf16):
     """Smallest (best - second best) over every sequence and filter whose pooled value is > 0, second best taken over the
-    positions whose value differs from the best (bit-equal values come from equal windows: the same gradient either way)."""
-    _, tape = O.cnn_forward(params, src, keep_tape=True, bf16=bf16)
+    positions whose value differs from the best (bit-equal values come from equal windows: the same gradient either way).
+    Taken over the distinct sequences: a sequence's pooling does not depend on its batch."""
+    _, tape = O.cnn_forward(params, np.unique(src, axis=0), keep_tape=True, bf16=bf16)
     gap = np.inf
     for _, hconv in tape:
         h = hconv.astype(np.float64)
@@ -132,9 +219,28 @@ def cnn_min_pool_gap(params, src, bf16):
     return gap
 
 
+def cnn_preconditions(c, p, src):
+    """What makes the comparison meaningful in CNN mode (asserted here and in the CPU self-test): float32 and float64 agree on
+    which position wins every max-pool and on whether the winner is above 0; and the share of dead features the case is for."""
+    if c["mode"] != "source_only_cnn":
+        return
+    bf16 = bool(c["opts"].get("cnn_bf16"))
+    assert cnn_min_pool_gap(p, src, bf16) > 1e-5
+    assert cnn_min_positive_pool(p, src, bf16) > 1e-5
+    if c.get("dead"):
+        lo, hi = c["dead"]
+        assert lo <= cnn_dead_share(p, src, bf16) <= hi
+
+
+def case_bars(c):
+    return c.get("bars") or (GRAD_BARS_SPLIT if c["split"] else GRAD_BARS_EXACT)
+
+
 def _model(c):
-    params, _ = case_params(c)
-    m, p = make_pair(params, seed=3 + c["seed"])
+    import sse_amd
+    params, p = case_params(c)
+    m = sse_amd.SSEModel(params)
+    m.set_variables(p)
     for k, v in c["opts"].items():
         m.handle.set_option(k, v)
     return params, m, p
@@ -147,20 +253,25 @@ def test_raw_gradients_and_apply_match_float64(c):
     B = len(z)
     rows_global = c["rows_factor"] * B
     cnn_bf16 = bool(c["opts"].get("cnn_bf16"))
-    if c["mode"] == "source_only_cnn":
-        assert cnn_min_pool_gap(p, src, cnn_bf16) > 1e-5
-    bars = GRAD_BARS_SPLIT if c["split"] else GRAD_BARS_EXACT
+    cnn_preconditions(c, p, src)
+    bars = case_bars(c)
     want, want_tail = reference_grads(p, params, src, tgt, z, rows_global, cnn_bf16=cnn_bf16)
     if c["by_rows"]:
         order = np.random.RandomState(5).permutation(B).astype(np.int32)
         inv = np.argsort(order).astype(np.int32)    # row numbers into the shuffled corpora that give back the batch
         m.handle.corpus_upload(0, src[order])
-        m.handle.corpus_upload(1, tgt[order])
-        got, tail = arena_grads(m, inv, inv, z, rows_global, rows=True)
+        if tgt.ndim == 2:
+            m.handle.corpus_upload(1, tgt[order])
+            got, tail = arena_grads(m, inv, inv, z, rows_global, rows=True)
+        else:                                       # table modes: the target side stays row numbers of the free matrix
+            got, tail = arena_grads(m, inv, tgt, z, rows_global, rows=True)
     else:
         got, tail = arena_grads(m, src, tgt, z, rows_global)
-    errs = check_grads(got, want, bars, what="%s: " % c["id"])
+    errs = check_grads(got, want, bars, what="%s: " % c["id"], var_bars=c.get("var_bars"))
     check_tail(tail, want_tail, bars, LOSS_REL_SPLIT if c["opts"].get("train_fwd_x3") else LOSS_REL_EXACT)
+    if c.get("dead") == (1.0, 1.0):                 # nothing alive: the clamp's 1e6 slope reaches only masked features
+        for name in want:
+            assert not want[name].any() and not np.asarray(got[name]).any(), name
     # rows of the lookup tables that the batch never touches: exactly zero
     touched = {"word_embedding": np.unique(np.concatenate([src.ravel(), tgt.ravel()]) if tgt.ndim == 2 else src.ravel())}
     if "target_embedding/tgt_seq_embedding" in got:
@@ -229,3 +340,47 @@ def test_train_grads_reports_a_bad_id_on_every_path(case):
     got, tail = arena_grads(m, src, tgt, z)
     check_grads(got, want, GRAD_BARS_EXACT)
     check_tail(tail, want_tail, GRAD_BARS_EXACT, LOSS_REL_EXACT)
+
+
+@pytest.mark.parametrize("bf16,start", [(False, 150), (True, 300)], ids=["fp32", "bf16"])
+def test_largest_accepted_cnn_shape_matches_float64(bf16, start):
+    """E = 64 (the training limit): T walked down from one the library rejects to the first it accepts -- the boundary is the
+    library's, not restated here.  A rejection is a host-side check whose message names LDS, never a launch error.  At the
+    accepted T (every LDS tile of the training forward and of cnn_dw_kernel<0,*> as full as it gets) the raw gradients are held
+    to the exact bar like any other case; the seed is the first whose batch meets the near-tie preconditions, and the float32
+    oracle has to be 10x inside the bar there, as tests/test_grad_check.py asserts for the listed cases."""
+    import sse_amd
+    c = dict(id="cnn-largest-%s" % ("bf16" if bf16 else "fp32"), mode="source_only_cnn", V=150, E=64, Hs=96, Ht=96, S=32, B=6,
+             N=17, batch="paired", opts=dict(cnn_bf16=1) if bf16 else {}, split=False, rows_factor=1, by_rows=False, seed=0)
+    rejected = 0
+    for T in range(start, 4, -1):
+        c["T"] = T
+        params, m, p = _model(c)
+        src, tgt, z = case_batch(c)
+        try:
+            arena_grads(m, src, tgt, z)
+        except sse_amd.SSEError as e:
+            assert "LDS" in str(e), str(e)
+            rejected += 1
+            continue
+        break
+    assert rejected > 0, "T = %d was expected to be rejected" % start
+    print("largest accepted T for E = 64 (%s): %d" % ("bf16" if bf16 else "fp32", T))
+    for seed in range(16):
+        c["seed"] = seed
+        params, p = case_params(c)
+        src, tgt, z = case_batch(c)
+        if cnn_min_pool_gap(p, src, bf16) > 1e-5 and cnn_min_positive_pool(p, src, bf16) > 1e-5:
+            break
+    cnn_preconditions(c, p, src)
+    want, want_tail = reference_grads(p, params, src, tgt, z, cnn_bf16=bf16)
+    f32, f32_tail = reference_grads(p, params, src, tgt, z, cnn_bf16=bf16, float64=False)
+    check_grads(f32, want, (GRAD_BARS_EXACT[0] / 10, GRAD_BARS_EXACT[1] / 10), what="float32 oracle: ")
+    params, m, p = _model(c)
+    got, tail = arena_grads(m, src, tgt, z)
+    errs = check_grads(got, want, GRAD_BARS_EXACT, what="%s T %d: " % (c["id"], T))
+    check_tail(tail, want_tail, GRAD_BARS_EXACT, LOSS_REL_EXACT)
+    rel_name = max(errs, key=lambda n: errs[n][0])
+    elem_name = max(errs, key=lambda n: errs[n][1])
+    print("GRADERR %s T %d seed %d: norm %.2e (%s), element %.2e (%s)"
+          % (c["id"], T, seed, errs[rel_name][0], rel_name, errs[elem_name][1], elem_name))

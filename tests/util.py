@@ -150,11 +150,14 @@ def grad_error(got, want):
     return float(np.linalg.norm(d)) / n, float(ad.max()) / m, worst
 
 
-def check_grads(got, want, bars, what=""):
-    """Asserts every variable within bars = (norm-relative, max-element-relative); returns {variable: (rel, elem)}.
+def check_grads(got, want, bars, what="", var_bars=None):
+    """Asserts every variable within bars = (norm-relative, max-element-relative), a variable named in var_bars within the
+    bars given there; returns {variable: (rel, elem)}.
     A failure names the variable, both numbers, the bars and the worst index with its two values."""
     errs, bad = {}, []
+    case_bars = bars
     for name in sorted(want):
+        bars = (var_bars or {}).get(name, case_bars)
         g = np.asarray(got[name]).reshape(want[name].shape)
         rel, elem, worst = grad_error(g, want[name])
         errs[name] = (rel, elem)
