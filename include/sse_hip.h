@@ -151,7 +151,15 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value);
  * can be in the exact top-k).  "score_bruteforce_queries": queries that fell through to the one-workgroup-per-query
  * float64 sweep (k > 1024, or more than 4096 rows within the fp32 bound of the k-th score).
  * "lstm_persist_fallbacks": host-buffer encodes re-run on the few-sequences kernel (see option lstm_persist_rows).
- * "lstm_coop_refused" (process-wide): cooperative launches the runtime refused -- the plain launch was taken instead. */
+ * "lstm_coop_refused" (process-wide): cooperative launches the runtime refused -- the plain launch was taken instead.
+ * Which kernel an LSTM inference encode was sent to, one count per encode (a host-buffer encode that falls back after a
+ * cluster give-up counts twice: the kernel that gave up and the one that re-ran it): "lstm_path_persist" (single-query
+ * cluster kernel), "lstm_path_cluster" (MFMA cluster kernel), "lstm_path_small" (few-sequences kernel), "lstm_path_x3"
+ * (split-bf16 matrix kernel), "lstm_path_generic" (any-shape path), "lstm_path_fwd" (fp32 matrix kernel).  Of the matrix
+ * kernel's encodes: "lstm_fwd_rows32" / "lstm_fwd_rows64" (rows per workgroup; they add up to lstm_path_fwd),
+ * "lstm_fwd_gate_split" (the gate-split kernel for small cells; the others ran the unit-block kernel), "lstm_fwd_x_table"
+ * (gate accumulators from the x-projection table; the others gathered embedding rows).  The pad-prefix table builds a
+ * kernel does for itself are not counted. */
 int sse_get_counter(sse_handle *h, const char *name, int64_t *value);
 
 /* tf.nn.l2_normalize(x, dim=-1) on device rows (sse_model.py:282-283). */

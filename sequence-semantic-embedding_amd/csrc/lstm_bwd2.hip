@@ -22,8 +22,6 @@
 #include "sse_kernels.h"
 #include "train.h"
 
-__device__ __forceinline__ float b2_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008178f * x)); }
-
 struct LstmBwd2Args {
   const float *tape_g;   // forward gate tape, lane = sequence accumulator layout (LstmFwdArgs::tape_swap)
   const float *dh_last;  // [Bp][Hp]
@@ -166,7 +164,7 @@ __global__ __launch_bounds__(NW * 64) void lstm_bwd2_kernel(LstmBwd2Args a) {
           const int r = q4 * 4 + e;
           const float si = tg[0][r], tj = tg[1][r], sf = tg[2][r], so = tg[3][r];
           const float cprev = (t > 0) ? tcp[r] : 0.0f;
-          const float tc = b2_tanh(tcn[r]);
+          const float tc = sse_tanh(tcn[r]);
           const float dhv = dh[r];
           const float dov = dhv * tc;
           const float dcv = dc[r] + dhv * so * (1.0f - tc * tc);

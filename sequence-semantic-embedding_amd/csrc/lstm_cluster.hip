@@ -50,9 +50,6 @@ typedef unsigned int lc_u32x4 __attribute__((ext_vector_type(4)));
 typedef float lc_f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int lc_u32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ float lc_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504089f * x)); }
-__device__ __forceinline__ float lc_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008178f * x)); }
-
 __device__ __forceinline__ void lc_publish(unsigned long long *p, float v, unsigned int tag) {
   __hip_atomic_store(p, ((unsigned long long)tag << 32) | __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -323,9 +320,9 @@ __global__ __launch_bounds__(LC_NT) void lstm_cluster_kernel(LstmClusterArgs a) 
       if (active) {
         // BasicLSTMCell gates (forget bias folded into the packed bias row), lane-local; i*j is rounded before it meets
         // c*f as in the matrix kernel (which parks the product between its two passes)
-        const float pW = __fmul_rn(lc_sigmoid(acc[0]), lc_tanh(acc[1]));
-        cW = __builtin_fmaf(cW, lc_sigmoid(acc[2]), pW);
-        const float hW = lc_tanh(cW) * lc_sigmoid(acc[3]);
+        const float pW = __fmul_rn(sse_sigmoid(acc[0]), sse_tanh(acc[1]));
+        cW = __builtin_fmaf(cW, sse_sigmoid(acc[2]), pW);
+        const float hW = sse_tanh(cW) * sse_sigmoid(acc[3]);
         // half (unit offset + 2 or not) of the 16-byte piece (k-group, slot lane >> 4, sequence): 8 bytes per lane
         const int off = pbase + ((((uW >> 3) * 4 + (lane >> 4)) * 16) + s16w) * 16 + (qW & 1) * 8;
         const lc_u32x2 w = {__float_as_uint(hW), tag};

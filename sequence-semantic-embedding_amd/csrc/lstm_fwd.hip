@@ -67,9 +67,8 @@ size_t lstm_fwd_lds_bytes(int KGx, int KGh, int RT) {
 // x-table path (XT): no x tiles, only h [2 bufs][RT][KGh][256] + red
 static size_t lstm_fwd_xt_lds_bytes(int KGh, int RT) { return (size_t)(2 * RT * KGh) * 256 * sizeof(float) + 64 * 4 * sizeof(float); }
 
-// v_exp_f32 (2^x) + v_rcp_f32 (1 ulp); plain `/` or __fdividef would expand to the ~10-instruction IEEE division
-__device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504089f * x)); }
-__device__ __forceinline__ float fast_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008178f * x)); }
+// (sigmoid / tanh: sse_sigmoid / sse_tanh of sse_kernels.h -- v_exp_f32 (2^x) + v_rcp_f32 (1 ulp); plain `/` or __fdividef
+// would expand to the ~10-instruction IEEE division)
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -574,8 +573,8 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
             f32x4 pij, si4, tj4;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              si4[e] = fast_sigmoid(ga[m][0][q4 * 4 + e]);
-              tj4[e] = fast_tanh(ga[m][1][q4 * 4 + e]);
+              si4[e] = sse_sigmoid(ga[m][0][q4 * 4 + e]);
+              tj4[e] = sse_tanh(ga[m][1][q4 * 4 + e]);
               pij[e] = si4[e] * tj4[e];
             }
             *reinterpret_cast<f32x4 *>(hdst[m] + q4 * 256) = pij;
@@ -591,8 +590,8 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const int r = q4 * 4 + e;
-              si4[e] = fast_sigmoid(ga[m][0][r]);
-              tj4[e] = fast_tanh(ga[m][1][r]);
+              si4[e] = sse_sigmoid(ga[m][0][r]);
+              tj4[e] = sse_tanh(ga[m][1][r]);
               hdst[m][mfma_row(r, lane) << 2] = si4[e] * tj4[e];
             }
             if constexpr (TRAIN) {
@@ -637,11 +636,11 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const int r = q4 * 4 + e;
-              const float sf = fast_sigmoid(gb[m][0][r]);
-              const float so = fast_sigmoid(gb[m][1][r]);
+              const float sf = sse_sigmoid(gb[m][0][r]);
+              const float so = sse_sigmoid(gb[m][1][r]);
               const float cn = c[u][m][r] * sf + pij[e];
               c[u][m][r] = cn;
-              hv4[e] = fast_tanh(cn) * so;
+              hv4[e] = sse_tanh(cn) * so;
               if (a.rec_h != nullptr && blockIdx.x == 0 && mt0 + m == 0 && (lane & 31) == 0) {
                 // sequence 0 of the launch: state after t+1 steps (used to build the pad-prefix table)
                 a.rec_h[(size_t)(t + 1) * (KGh * 8) + ub * 32 + mfma_row(r, lane)] = hv4[e];
@@ -654,8 +653,8 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
                 const int r = q4 * 4 + e;
-                sf4[e] = fast_sigmoid(gb[m][0][r]);  // (the values computed above: common subexpressions)
-                so4[e] = fast_sigmoid(gb[m][1][r]);
+                sf4[e] = sse_sigmoid(gb[m][0][r]);  // (the values computed above: common subexpressions)
+                so4[e] = sse_sigmoid(gb[m][1][r]);
                 cn4[e] = c[u][m][r];
               }
               __builtin_nontemporal_store(sf4, reinterpret_cast<f32x4 *>(tp[m] + 2048 + q4 * 256));
@@ -680,11 +679,11 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmFwdArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const int r = q4 * 4 + e;
-              const float sf = fast_sigmoid(gb[m][0][r]);
-              const float so = fast_sigmoid(gb[m][1][r]);
+              const float sf = sse_sigmoid(gb[m][0][r]);
+              const float so = sse_sigmoid(gb[m][1][r]);
               const float cn = c[u][m][r] * sf + hdst[m][mfma_row(r, lane) << 2];
               c[u][m][r] = cn;
-              const float hv = fast_tanh(cn) * so;
+              const float hv = sse_tanh(cn) * so;
               hdst[m][mfma_row(r, lane) << 2] = hv;  // h_t, A-fragment order
               sf4[e] = sf;
               so4[e] = so;
@@ -887,23 +886,31 @@ int lstm_fwd_rows_per_wg(int Hp, int B, int tiles_elsewhere, int cus) {
   return 64;
 }
 
-hipError_t launch_lstm_fwd(const LstmFwdArgs &a, int Hp, hipStream_t stream) {
+// The kernel launch_lstm_fwd runs for (a, Hp): rows per workgroup (32 / 64), + LSTM_FWD_GATE_SPLIT (lstm_fwd_gs.hip), + LSTM_FWD_X_TABLE
+// (gate accumulators from the x-projection table).  The launcher dispatches on this value, the C-ABI layer counts it.
+int lstm_fwd_variant(const LstmFwdArgs &a, int Hp) {
   int rows = lstm_fwd_rows_per_wg(Hp, a.B, a.tiles_elsewhere, a.cu_count);
   if (Hp <= 256 && (a.force_rows == 32 || a.force_rows == 64)) rows = a.force_rows;
   if (const char *ev = getenv("SSE_FWD_ROWS")) {  // measurement aid
     const int r = atoi(ev);
     if (Hp <= 256 && (r == 32 || r == 64)) rows = r;
   }
-  if (rows == 64 && a.NT32 > 0 && (a.NT32 & 1)) return hipErrorInvalidValue;  // tapes are laid out per 32-row tile
-  if (Hp == 128 && a.xtab != nullptr) return hipErrorInvalidValue;  // no x-table path at Hp = 128
   if (Hp == 128 && rows == 64 && a.gate_split && a.tape_g == nullptr && a.rec_h == nullptr && a.NTS <= 16 &&
       lstm_fwd_gs_ok(a.KGx, a.KGh, a.H > 0 ? a.H : Hp)) {
     const char *ev = getenv("SSE_FWD_GS");  // measurement aid: 0 = lstm_fwd_kernel<2,1,1>
-    if (!(ev && atoi(ev) == 0)) {
-      LstmFwdArgs g = a;
-      if (g.H <= 0) g.H = Hp;
-      return launch_lstm_fwd_gs(g, stream);
-    }
+    if (!(ev && atoi(ev) == 0)) return rows | LSTM_FWD_GATE_SPLIT;
+  }
+  return rows | (Hp != 128 && a.tape_g == nullptr && a.xtab != nullptr ? LSTM_FWD_X_TABLE : 0);
+}
+
+hipError_t launch_lstm_fwd(const LstmFwdArgs &a, int Hp, hipStream_t stream) {
+  const int variant = lstm_fwd_variant(a, Hp), rows = variant & (32 | 64);
+  if (rows == 64 && a.NT32 > 0 && (a.NT32 & 1)) return hipErrorInvalidValue;  // tapes are laid out per 32-row tile
+  if (Hp == 128 && a.xtab != nullptr) return hipErrorInvalidValue;  // no x-table path at Hp = 128
+  if (variant & LSTM_FWD_GATE_SPLIT) {
+    LstmFwdArgs g = a;
+    if (g.H <= 0) g.H = Hp;
+    return launch_lstm_fwd_gs(g, stream);
   }
   if (Hp == 128) return rows == 32 ? launch_cfg<1, 1, 1, true>(a, stream) : launch_cfg<2, 1, 1>(a, stream);
   if (Hp == 256) return rows == 32 ? launch_cfg<1, 1, 1>(a, stream) : launch_cfg<2, 2, 1>(a, stream);

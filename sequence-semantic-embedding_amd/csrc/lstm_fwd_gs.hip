@@ -56,9 +56,6 @@ __device__ long long g_gs_clk[8 * 8];
 
 namespace {
 
-__device__ __forceinline__ float gs_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504089f * x)); }
-__device__ __forceinline__ float gs_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008178f * x)); }
-
 __device__ __forceinline__ f32x4 gs_wload(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
 }
@@ -96,7 +93,7 @@ __device__ __forceinline__ void gs_tail(const f32x16 (&acc)[NB], f32x4 (&c)[NB],
     for (int j = 0; j < 4; ++j) {
       f32x4 v;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (Q == 1) ? gs_tanh(acc[b][j * 4 + e]) : gs_sigmoid(acc[b][j * 4 + e]);
+      for (int e = 0; e < 4; ++e) v[e] = (Q == 1) ? sse_tanh(acc[b][j * 4 + e]) : sse_sigmoid(acc[b][j * 4 + e]);
       if (j == Q) own[b] = v;
       else *reinterpret_cast<f32x4 *>(ex + ((Q * NB + b) * 3 + gs_slot(j, Q)) * 256 + lane * 4) = v;
     }
@@ -124,7 +121,7 @@ __device__ __forceinline__ void gs_tail(const f32x16 (&acc)[NB], f32x4 (&c)[NB],
       asm volatile("" : "+v"(pij));  // a rounded product, as the other kernels park it in LDS: c' = fma(c, sf, pij)
       const float cn = c[b][e] * gv[2][e] + pij;
       c[b][e] = cn;
-      hv[e] = gs_tanh(cn) * gv[3][e];
+      hv[e] = sse_tanh(cn) * gv[3][e];
     }
     *reinterpret_cast<f32x4 *>(hb + (4 * b + Q) * 256 + lane * 4) = hv;  // h_t, A-fragment order: k-group 4 b + Q
   }

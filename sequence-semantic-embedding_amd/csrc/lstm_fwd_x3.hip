@@ -36,9 +36,6 @@
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float x3_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504089f * x)); }
-__device__ __forceinline__ float x3_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008178f * x)); }
-
 __host__ __device__ static inline unsigned short x3_bf16(float f) {  // round to nearest even (finite inputs)
   unsigned u;
   __builtin_memcpy(&u, &f, 4);
@@ -330,8 +327,8 @@ __global__ __launch_bounds__(X3_THREADS) void lstm_fwd_x3_kernel(LstmX3Args a) {
         f32x4 pij, si4, tj4;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          si4[e] = x3_sigmoid(g[m][0][q4 * 4 + e]);
-          tj4[e] = x3_tanh(g[m][1][q4 * 4 + e]);
+          si4[e] = sse_sigmoid(g[m][0][q4 * 4 + e]);
+          tj4[e] = sse_tanh(g[m][1][q4 * 4 + e]);
           pij[e] = si4[e] * tj4[e];
         }
         if constexpr (TRAIN) {
@@ -368,11 +365,11 @@ __global__ __launch_bounds__(X3_THREADS) void lstm_fwd_x3_kernel(LstmX3Args a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int r = q4 * 4 + e;
-          const float sf = x3_sigmoid(g[m][0][r]);
-          const float so = x3_sigmoid(g[m][1][r]);
+          const float sf = sse_sigmoid(g[m][0][r]);
+          const float so = sse_sigmoid(g[m][1][r]);
           const float cn = c[m][r] * sf + pij[e];
           c[m][r] = cn;
-          hv[r] = x3_tanh(cn) * so;
+          hv[r] = sse_tanh(cn) * so;
           sf4[e] = sf;
           so4[e] = so;
           cn4[e] = cn;

@@ -30,9 +30,6 @@
 #define LP_WAIT_TICKS 1000000  // 10 ms of the 100 MHz wall clock without the awaited word: give up (error bit 2)
 #define LP_EPT 8     // exchange elements per thread per step: RB * H / NT (H <= 512)
 
-__device__ __forceinline__ float lp_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504089f * x)); }
-__device__ __forceinline__ float lp_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008178f * x)); }
-
 // exchange element: {float value, uint32 tag} as one 64-bit word, agent scope (the device-coherent level of the memory
 // system; no cache write-back / invalidate fences are needed around single-copy-atomic 64-bit accesses)
 __device__ __forceinline__ void lp_publish(unsigned long long *p, float v, unsigned int tag) {
@@ -229,14 +226,14 @@ __global__ __launch_bounds__(LP_NT) void lstm_persist_kernel(LstmPersistArgs a) 
     __syncthreads();  // gates complete; nobody reads the operand rows any more
     if (wv == 0) {
       if (lane_on && lb < nb) {
-        const float si = lp_sigmoid(gs[lane]);
-        const float tj = lp_tanh(gs[64 + lane]);
-        const float sf = lp_sigmoid(gs[128 + lane]);
-        const float so = lp_sigmoid(gs[192 + lane]);
+        const float si = sse_sigmoid(gs[lane]);
+        const float tj = sse_tanh(gs[64 + lane]);
+        const float sf = sse_sigmoid(gs[128 + lane]);
+        const float so = sse_sigmoid(gs[192 + lane]);
         const float pij = __fmul_rn(si, tj);  // the matrix kernel parks this product (rounded) between its two passes
         c = __builtin_fmaf(c, sf, pij);
         const int slot = (((t + 1) & 1) * LP_RB + lb) * H + u0 + lu;
-        const float hv = lp_tanh(c) * so;
+        const float hv = sse_tanh(c) * so;
         if (wthrough) {
           lp_publish(hx + slot, hv, epoch | (unsigned)(t + 1));
         } else {

@@ -19,9 +19,6 @@
 
 #define LS_RB 4  // sequences per workgroup
 
-__device__ __forceinline__ float ls_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504089f * x)); }
-__device__ __forceinline__ float ls_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008178f * x)); }
-
 // ring slots d = 0 .. D-1 of one pass over the ring, by template recursion: the slot index must be a compile-time
 // constant (a rolled loop indexes the register ring dynamically, i.e. through scratch memory)
 template <int CPT> struct ColVec;
@@ -169,14 +166,14 @@ __global__ __launch_bounds__(NT) void lstm_small_kernel(LstmSmallArgs a) {
       if (e < LS_RB * H) {
         const int b = e / H, unit = e - b * H;
         const float *g = gs + b * N4;
-        const float si = ls_sigmoid(g[unit]);
-        const float tj = ls_tanh(g[H + unit]);
-        const float sf = ls_sigmoid(g[2 * H + unit]);
-        const float so = ls_sigmoid(g[3 * H + unit]);
+        const float si = sse_sigmoid(g[unit]);
+        const float tj = sse_tanh(g[H + unit]);
+        const float sf = sse_sigmoid(g[2 * H + unit]);
+        const float so = sse_sigmoid(g[3 * H + unit]);
         const float pij = __fmul_rn(si, tj);           // the matrix kernel parks this product (rounded) between its two passes
         const float cn = __builtin_fmaf(c[j], sf, pij);
         c[j] = cn;
-        const float hv = ls_tanh(cn) * so;
+        const float hv = sse_tanh(cn) * so;
         av[b * KA + KX + unit] = hv;
         if (a.rec_h != nullptr && blockIdx.x == 0 && b == 0) {  // sequence 0: the pad-prefix table of THIS kernel
           a.rec_h[(size_t)(t + 1) * a.pad_stride + unit] = hv;

@@ -112,6 +112,13 @@ struct TrainState {
 
 }  // namespace
 
+// sse_handle::lstm_path_calls: one entry per kernel an encode can be sent to, then what the matrix kernel's launcher picked
+enum { PATH_PERSIST, PATH_CLUSTER, PATH_SMALL, PATH_X3, PATH_GENERIC, PATH_FWD, PATH_FWD_ROWS32, PATH_FWD_ROWS64, PATH_FWD_GS, PATH_FWD_XT,
+       PATH_COUNT };
+static const char *const LSTM_PATH_NAMES[PATH_COUNT] = {"lstm_path_persist", "lstm_path_cluster", "lstm_path_small", "lstm_path_x3",
+                                                "lstm_path_generic", "lstm_path_fwd", "lstm_fwd_rows32", "lstm_fwd_rows64",
+                                                "lstm_fwd_gate_split", "lstm_fwd_x_table"};
+
 struct sse_handle {
   sse_config cfg;
   std::mutex mu;
@@ -140,6 +147,8 @@ struct sse_handle {
   int32_t *pad_stat = nullptr;  // pinned host words the device stores to: [side] {call number, class 0 / 1 / 2}
   int32_t pad_seq = 0;
   int64_t pad_sorted_calls = 0;  // counter "pad_sorted_calls"
+  // counters "lstm_path_*" / "lstm_fwd_*": LSTM inference encodes by the kernel they were sent to (LSTM_PATH_NAMES, same order)
+  int64_t lstm_path_calls[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   bool lstm_x3 = false;       // option "lstm_x3": large inference encodes (Hp = 256) on the bf16 matrix pipe with split operands
   unsigned short *emb16 = nullptr;  // split embedding table of that path
   bool emb16_valid = false;
@@ -890,6 +899,10 @@ int encode_fwd(sse_handle *h, int side, const int32_t *ids, int B, int T, int no
     a.xtab = own.xtab;
     a.xtab_ub = (own.H + 31) / 32;
   }
+  const int variant = lstm_fwd_variant(a, e.Hp);
+  h->lstm_path_calls[(variant & 64) ? PATH_FWD_ROWS64 : PATH_FWD_ROWS32] += 1;
+  if (variant & LSTM_FWD_GATE_SPLIT) h->lstm_path_calls[PATH_FWD_GS] += 1;
+  if (variant & LSTM_FWD_X_TABLE) h->lstm_path_calls[PATH_FWD_XT] += 1;
   HIPCHECK(h, launch_lstm_fwd(a, e.Hp, st));
   return 0;
 }
@@ -934,14 +947,17 @@ int encode_dev_locked(sse_handle *h, int side, const int32_t *ids, int B, int T,
   }
   Encoder &e = h->enc[side];
   if (e.kernel < 0) return fail(h, "network mode has no %s sequence encoder (sse_model.py:231-233)", side ? "target" : "source");
-  if (e.generic) return encode_generic_locked(h, e, ids, B, T, normalize, out, st);
+  if (e.generic) {
+    h->lstm_path_calls[PATH_GENERIC] += 1;
+    return encode_generic_locked(h, e, ids, B, T, normalize, out, st);
+  }
   if (ensure_packed(h, st)) return 1;
   switch (rq.path != LstmPath::Unset ? rq.path : choose_lstm_path(h, e, B, T, rq)) {
-    case LstmPath::Persist: return encode_persist(h, side, ids, B, T, normalize, out, st);
-    case LstmPath::Cluster: return encode_cluster(h, side, ids, B, T, normalize, out, st);
-    case LstmPath::Small: return encode_small(h, side, ids, B, T, normalize, out, st);
-    case LstmPath::X3: return encode_x3(h, side, ids, B, T, normalize, out, rq, st);
-    case LstmPath::Fwd: return encode_fwd(h, side, ids, B, T, normalize, out, rq, st);
+    case LstmPath::Persist: h->lstm_path_calls[PATH_PERSIST] += 1; return encode_persist(h, side, ids, B, T, normalize, out, st);
+    case LstmPath::Cluster: h->lstm_path_calls[PATH_CLUSTER] += 1; return encode_cluster(h, side, ids, B, T, normalize, out, st);
+    case LstmPath::Small: h->lstm_path_calls[PATH_SMALL] += 1; return encode_small(h, side, ids, B, T, normalize, out, st);
+    case LstmPath::X3: h->lstm_path_calls[PATH_X3] += 1; return encode_x3(h, side, ids, B, T, normalize, out, rq, st);
+    case LstmPath::Fwd: h->lstm_path_calls[PATH_FWD] += 1; return encode_fwd(h, side, ids, B, T, normalize, out, rq, st);
     case LstmPath::Unset:
     case LstmPath::Error: break;
   }
@@ -1858,6 +1874,11 @@ int sse_get_counter(sse_handle *h, const char *name, int64_t *value) {
   }
   if (strcmp(name, "lstm_x_table_builds") == 0) {  // x-projection tables built (option lstm_x_table)
     *value = h->x_table_builds;
+    return 0;
+  }
+  for (int i = 0; i < PATH_COUNT; ++i) {  // LSTM inference encodes by kernel
+    if (strcmp(name, LSTM_PATH_NAMES[i]) != 0) continue;
+    *value = h->lstm_path_calls[i];
     return 0;
   }
   if (strcmp(name, "lstm_coop_refused") == 0) {  // process-wide: cooperative launches refused by the runtime (plain launch taken)

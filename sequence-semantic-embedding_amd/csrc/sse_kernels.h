@@ -108,6 +108,28 @@ __device__ static inline void sse_quad_transpose(f32x4 &v, int lane) {
 #endif
 }
 
+// ---------------------------------------------------------------------------
+// Activations of every fused LSTM kernel (inference, training forward, BPTT recompute): ONE definition, so that the kernels
+// keep one instruction sequence and stay bit-identical to each other.
+// sigmoid(x) = rcp(1 + exp2(-x log2 e)): absolute error ~1e-7 on a result in (0, 1), which is relative accuracy too wherever
+// it matters (a sigmoid near 0 multiplies something).
+// tanh(x) = 1 - 2 rcp(1 + exp2(2 x log2 e)) has the same ABSOLUTE error, but its result goes through 0: for small |x| it is
+// the difference of two numbers near 1 and loses every digit (|x| = 1e-3: 1e-4 relative, 1e-6: nothing left), while the
+// reference's float32 tanh is accurate relative to the result.  Below SSE_TANH_SMALL the odd Taylor polynomial
+// x (1 - x^2/3 + 2 x^4/15 - 17 x^6/315) takes over.  The threshold 0.25 balances the two: the polynomial's truncation,
+// 62/2835 x^8, reaches 3.4e-7 relative there, the exponential form ~1e-7 / 0.245 = 4e-7 (0.125 would leave it at 9e-7; a
+// float32 emulation with exact exp2 and division gives 3.9e-7 and 3.8e-7, tests/test_lstm_forward_check.py).  Both are
+// computed and one is selected (v_cndmask): no branch.
+// ---------------------------------------------------------------------------
+#define SSE_TANH_SMALL 0.25f
+__device__ __forceinline__ float sse_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504089f * x)); }
+__device__ __forceinline__ float sse_tanh(float x) {
+  const float big = 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008178f * x));
+  const float x2 = x * x;
+  const float p = __builtin_fmaf(x2, __builtin_fmaf(x2, __builtin_fmaf(x2, -17.0f / 315.0f, 2.0f / 15.0f), -1.0f / 3.0f), 1.0f);
+  return __builtin_fabsf(x) < SSE_TANH_SMALL ? x * p : big;
+}
+
 // ------------------------------ LSTM forward -------------------------------
 struct LstmFwdArgs {
   const int32_t *ids;   // [B][T]
@@ -153,6 +175,8 @@ size_t lstm_fwd_lds_bytes(int KGx, int KGh, int RT);
 bool lstm_fwd_x_double(int KGx, int KGh, int RT);
 int lstm_fwd_rows_per_wg(int Hp, int B, int tiles_elsewhere = 0, int cus = 0 /* 0: 256 */);
 hipError_t launch_lstm_fwd(const LstmFwdArgs &a, int Hp, hipStream_t stream);
+enum { LSTM_FWD_GATE_SPLIT = 1, LSTM_FWD_X_TABLE = 2 };
+int lstm_fwd_variant(const LstmFwdArgs &a, int Hp);  // the kernel launch_lstm_fwd picks: 32 | 64 rows, + the flags above
 // x-projection table of lstm_fwd_kernel's table path (lstm_xtable.hip): for every token v < V and live unit block ub < UBt,
 // the four gate tiles' accumulators after the KGx x k-groups of the packed kernel Wp, in the inference accumulator layout
 // [V][UBt][4 gates][lane >> 5][16 registers] fp32, built with the recurrence's own MFMA chain (bit-identical)

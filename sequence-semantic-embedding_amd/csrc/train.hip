@@ -20,10 +20,6 @@
 
 #include "sse_kernels.h"
 
-
-__device__ __forceinline__ float fast_tanh_t(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008178f * x)); }
-__device__ __forceinline__ float fast_sigmoid_t(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504089f * x)); }
-
 // ---------------------------------------------------------------------------
 // Loss: one wave per pair row.  sse_model.py:282-283,290,298,302.
 struct LossArgs {
@@ -65,7 +61,7 @@ __global__ void loss_kernel(LossArgs a) {
   const float cosv = st * rs * rt;           // reduce_sum(ns * nt)
   const float x = 64.0f * cosv;
   const float z = a.labels[row];
-  const float sg = fast_sigmoid_t(x);
+  const float sg = sse_sigmoid(x);
   if (lane == 0) {
     // weighted_cross_entropy_with_logits, pos_weight = 1
     a.row_loss[row] = (1.0f - z) * x + log1pf(expf(-fabsf(x))) + fmaxf(-x, 0.0f);
@@ -354,7 +350,7 @@ __global__ __launch_bounds__(NW * 64) void lstm_bwd_kernel(LstmBwdArgs a) {
         const float si = tg[u][0][r], tj = tg[u][1][r], sf = tg[u][2][r], so = tg[u][3][r];
         const float cn = tcn[u][r];
         const float cprev = (t > 0) ? tcp[u][r] : 0.0f;
-        const float tc = fast_tanh_t(cn);
+        const float tc = sse_tanh(cn);
         const float dhv = dh[u][r];
         const float dov = dhv * tc;
         const float dcv = dc[u][r] + dhv * so * (1.0f - tc * tc);

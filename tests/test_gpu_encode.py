@@ -11,6 +11,18 @@ pytestmark = pytest.mark.gpu
 
 TOL = 1e-4
 
+
+def _ran(h, before, **moved):
+    """The LSTM path counters named (include/sse_hip.h) moved by the given amounts since `before` = _paths(h)."""
+    now = _paths(h)
+    got = {n: now[n] - before[n] for n in moved}
+    assert got == moved, (got, moved)
+
+
+def _paths(h):
+    return {n: h.get_counter(n) for n in ("lstm_path_persist", "lstm_path_cluster", "lstm_path_small", "lstm_path_fwd",
+                                          "lstm_fwd_rows32", "lstm_fwd_rows64", "lstm_fwd_gate_split", "lstm_fwd_x_table")}
+
 CASES = [
     # mode, V, E, Hs, Ht, S, T, B
     ("dual-encoder", 500, 50, 256, 256, 256, 32, 70),      # BASELINE configs[1] shape
@@ -152,9 +164,18 @@ def test_cluster_kernel_equals_the_other_kernels(mode, V, E, Hs, Ht, S, T):
         for side, enc in (("src", m.encode_source), ("tgt", m.encode_target)):
             for normalize in (True, False):
                 m.handle.set_option("lstm_persist_rows", 0)
+                n0 = _paths(m.handle)
                 ref = enc(ids, normalize=normalize)
+                _ran(m.handle, n0, lstm_path_small=1, lstm_path_persist=0)
                 m.handle.set_option("lstm_persist_rows", 32)
+                n0 = _paths(m.handle)
                 got = enc(ids, normalize=normalize)
+                # cells above 256 units need 32 workgroups per cluster, 8 x 32 x 2 = 512 compute units for the chooser's
+                # co-residency rule: on a 256-CU device they stay on the few-sequences kernel
+                if (Hs if side == "src" else Ht) <= 256:
+                    _ran(m.handle, n0, lstm_path_persist=1, lstm_path_small=0)
+                else:
+                    _ran(m.handle, n0, lstm_path_persist=0, lstm_path_small=1)
                 assert np.array_equal(got, ref), (B, side, normalize, np.abs(got - ref).max())
                 m.handle.set_option("pad_skip", 0)
                 assert np.array_equal(enc(ids, normalize=normalize), ref)
@@ -397,7 +418,9 @@ def test_cluster_kernel_with_workgroups_that_own_no_hidden_unit(H, S):
     rng = np.random.RandomState(7)
     for it in range(20):
         ids = random_ids(rng, 1 + it % 7, 9, 120, 0.5)
+        n0 = _paths(m.handle)
         got = m.encode_source(ids)
+        _ran(m.handle, n0, lstm_path_persist=1, lstm_path_small=0)
         m.handle.set_option("lstm_persist_rows", 0)
         want = m.encode_source(ids)
         m.handle.set_option("lstm_persist_rows", 32)
@@ -483,12 +506,15 @@ def test_mfma_cluster_kernel_equals_the_other_kernels(mode, V, E, Hs, Ht, S, T):
                 m.handle.set_option("lstm_cluster_rows", 0)
                 ref = enc(ids, normalize=normalize)                                   # few-sequences kernel
                 m.handle.set_option("lstm_cluster_rows", 1024)
+                n0 = _paths(m.handle)
                 got = enc(ids, normalize=normalize)
+                _ran(m.handle, n0, lstm_path_cluster=1, lstm_path_small=0, lstm_path_fwd=0)
                 assert np.array_equal(got, ref), (B, side, normalize, np.abs(got - ref).max())
                 # the any-placement publish path (write-through stores; taken when a cluster is not on one XCD)
                 m.handle.set_option("lstm_cluster_write_through", 1)
                 got_wt = enc(ids, normalize=normalize)
                 m.handle.set_option("lstm_cluster_write_through", 0)
+                _ran(m.handle, n0, lstm_path_cluster=2, lstm_path_small=0, lstm_path_fwd=0)
                 assert np.array_equal(got_wt, ref), (B, side, normalize, "write-through")
             if B in (65, 600):
                 m.handle.set_option("pad_skip", 0)
@@ -498,7 +524,9 @@ def test_mfma_cluster_kernel_equals_the_other_kernels(mode, V, E, Hs, Ht, S, T):
         if B == 600:
             m.handle.set_option("lstm_small_rows", 0)
             m.handle.set_option("lstm_cluster_rows", 0)
+            n0 = _paths(m.handle)
             mat = m.encode_source(ids)                                                # 32-row matrix tiles
+            _ran(m.handle, n0, lstm_path_fwd=1, lstm_fwd_rows32=1, lstm_path_cluster=0)
             m.handle.set_option("lstm_small_rows", 1024)
             m.handle.set_option("lstm_cluster_rows", 1024)
             assert np.array_equal(m.encode_source(ids), mat)
@@ -648,9 +676,11 @@ def test_single_query_with_odd_pad_prefix_never_gives_up():
     for npad in range(0, 15):
         ids = random_ids(rng, 3, 16, 200)
         ids[:, :npad] = 0
+        n0 = _paths(m.handle)
         first = m.encode_source(ids)
         for _ in range(20):
             assert np.array_equal(m.encode_source(ids), first)
+        _ran(m.handle, n0, lstm_path_persist=21, lstm_path_small=0)
         m.handle.set_option("lstm_persist_rows", 0)
         m.handle.set_option("lstm_cluster_rows", 0)
         assert np.array_equal(m.encode_source(ids), first)
@@ -670,7 +700,12 @@ def test_small_cells_at_64_row_tiles_are_bit_identical_to_the_other_kernels(H):
     ids = random_ids(rng, 9000, 20, 400, pad_frac=0.6)
     for pad_skip in (1, 0):
         m.handle.set_option("pad_skip", pad_skip)
+        n0 = _paths(m.handle)
         big = m.encode_source(ids)
+        if pad_skip:          # (the host entry sorts this padded batch by prefix and then asks for 32-row tiles: padded_hint)
+            _ran(m.handle, n0, lstm_path_fwd=1)
+        else:
+            _ran(m.handle, n0, lstm_path_fwd=1, lstm_fwd_rows64=1, lstm_fwd_gate_split=1)
         assert np.abs(big[:300] - O.encode(p, params, "src", ids[:300])).max() <= TOL
         pick = np.concatenate([np.arange(0, 40), np.arange(4480, 4520), np.arange(8960, 9000)])
         m.handle.set_option("lstm_persist_rows", 0)
@@ -762,8 +797,10 @@ def test_gate_split_kernel_is_bit_identical_to_the_unit_block_kernel(H, S, T, B)
                 h.set_option("lstm_gate_split", gs)
                 for norm in (True, False):
                     out.zero_()
+                    n0 = _paths(h)
                     h.encode_dev(side, d.data_ptr(), B, T, norm, out.data_ptr())
                     h.synchronize()
+                    _ran(h, n0, lstm_path_fwd=1, lstm_fwd_rows64=1, lstm_fwd_gate_split=gs)
                     res[(side, skip, gs, norm)] = out.cpu().numpy().copy()
             for norm in (True, False):
                 assert np.array_equal(res[(side, skip, 1, norm)], res[(side, skip, 0, norm)]), (side, skip, norm)

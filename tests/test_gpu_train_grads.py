@@ -90,6 +90,9 @@ CASES = [
     _case("e32", "dual-encoder", 300, 32, 96, 64, 40, 7, 66),
     _case("e63", "dual-encoder", 300, 63, 128, 256, 64, 9, 128),
     _case("e64", "dual-encoder", 300, 64, 128, 256, 64, 9, 128),
+    # zero LSTM biases (the reference initialiser) and a small embedding: cell states ~1e-3, where the training forward's and the
+    # BPTT recompute's tanh (sse_tanh, shared with the inference kernels) takes its small-argument branch; fused fp32 path
+    _case("small-preactivations", "dual-encoder", 300, 50, 128, 128, 64, 10, 128, zero_bias=True, emb_scale=1e-2),
     # first-generation kernels (lstm_bwd_kernel, dx_kernel, bias partials)
     _case("gen1-c1", "dual-encoder", 400, 50, 256, 256, 256, 16, 128, opts=dict(train_gen1=1)),
     _case("gen1-shared96", "shared-encoder", 300, 40, 96, 96, 50, 50, 64, opts=dict(train_gen1=1)),
@@ -125,7 +128,9 @@ CASES = [
 def case_params(c):
     """(model params, oracle parameter dict) of a case: what _model loads into the GPU model."""
     params = model_params(c["mode"], c["V"], c["E"], c["Hs"], c["Ht"], c["S"], c["T"], N=c["N"], lr=0.9)
-    p = oracle_params(params, seed=3 + c["seed"])
+    p = oracle_params(params, seed=3 + c["seed"], bias_scale=0.0 if c.get("zero_bias") else 0.2)
+    if c.get("emb_scale"):
+        p["word_embedding"] = (p["word_embedding"] * np.float32(c["emb_scale"])).astype(np.float32)
     if c.get("conv_bias") is not None:             # lowered conv biases: dead filters (pooled value exactly 0)
         for k in p:
             if k.endswith("/b"):

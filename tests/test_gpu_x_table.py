@@ -20,10 +20,13 @@ def _matrix_kernel_only(h):
 
 def _both(m, enc, ids, normalize):
     """(x-table path, embedding-gather path) encodings of one batch."""
+    n = m.handle.get_counter("lstm_fwd_x_table")
     m.handle.set_option("lstm_x_table", 2)
     fast = enc(ids, normalize=normalize)
+    assert m.handle.get_counter("lstm_fwd_x_table") == n + 1       # the matrix kernel's table path ran ...
     m.handle.set_option("lstm_x_table", 0)
     full = enc(ids, normalize=normalize)
+    assert m.handle.get_counter("lstm_fwd_x_table") == n + 1       # ... and here its embedding gather
     m.handle.set_option("lstm_x_table", 1)
     return fast, full
 

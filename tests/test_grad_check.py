@@ -37,6 +37,22 @@ def test_float32_oracle_passes_every_bar_with_10x_margin(c):
     check_tail(tail, want_tail, margin, (LOSS_REL_SPLIT if c["opts"].get("train_fwd_x3") else LOSS_REL_EXACT) / 10)
 
 
+def test_small_preactivation_case_is_as_small_as_intended():
+    """Zero LSTM biases and an embedding of +-2.5e-3: every cell state, hence every argument of the cell-output tanh, stays
+    below 1e-2 -- deep inside the range where the fused kernels' tanh is a polynomial -- and the gradients are not all zero."""
+    c = next(c.values[0] for c in CASES if c.id == "small-preactivations")
+    params, p = case_params(c)
+    src, tgt, z = case_batch(c)
+    assert not c["opts"] and not any(p[k].any() for k in p if k.endswith("/bias"))
+    for scope, ids in (("source_encoder", src), ("target_encoder", tgt)):
+        name = scope + "/rnn/basic_lstm_cell/"
+        h, tape = O.lstm_forward(p["word_embedding"], p[name + "kernel"], p[name + "bias"], ids, keep_tape=True)
+        cmax = max(float(np.abs(np.arctanh(rec[6].astype(np.float64))).max()) for rec in tape)
+        assert 1e-5 < cmax < 1e-2, (scope, cmax)
+    want, _ = reference_grads(p, params, src, tgt, z)
+    assert all(np.abs(g).max() > 0 for g in want.values())
+
+
 def test_oracle_float64_restores_the_float32_oracle_on_error():
     with pytest.raises(ZeroDivisionError):
         with oracle_float64():
