@@ -138,7 +138,14 @@ int sse_encode_dev(sse_handle *h, int side, const int32_t *ids_dev, int32_t B, i
  * isolated kernel durations; same results).
  * "score_small_index" (default 1): >= 1024 queries against <= 1024 index rows (index dimensions 249 .. 256, 57 .. 64,
  * 49 .. 56: the evaluator's shape, sse_evaluator.py:104-112) are scored by one launch that forms all N scores per query and
- * selects the 16 best exactly, instead of the list sweep; identical results.  "lstm_cluster_coop" (default 1): the cluster
+ * selects the 16 best exactly, instead of the list sweep; identical results.  "score_small_x3" (default 1): that launch
+ * forms its candidate scores from split-bf16 operands (hi = bf16(x), lo = bf16(x - hi); q.t ~ qh.th + qh.tl + ql.th on the bf16
+ * matrix pipe, a sixth of the fp32 matrix cycles; the split image of the index is built once when the index is set).  The
+ * scores only pick 16 candidates and bound the rows left out: every score returned is the float64 re-scoring and every id
+ * follows the float64 order, certified with the bound (2^-15 (1 + 2^-6) + 2 (3 S + 2) 2^-24 (1 + 2^-5)) |q| max|t| (1.26e-4
+ * at S = 256; fp32 candidates: 3.1e-5), so results are identical; a query whose 10th .. 16th scores sit closer than that
+ * takes the collect path (counter "score_collect_queries").  Rows or queries of norm below 2^-100 are outside the bound's
+ * claim.  0 = fp32 candidates (v_mfma_f32_32x32x2_f32).  "lstm_cluster_coop" (default 1): the cluster
  * encoder kernels are launched cooperatively (co-residency guaranteed by the runtime; ~20 us per call on ROCm 7.2; 0 =
  * plain launch, the give-up / fall-back path alone).  "lstm_cluster_backoff" (default -1 = automatic): eligible calls that go
  * straight to the kernels needing no co-residency after a cluster launch gave up (a give-up costs 10 ms); automatic arms 16

@@ -266,6 +266,9 @@ __global__ __launch_bounds__(SC_THREADS) void score_topk_kernel(ScoreArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform (SGPR): tile numbers and load offsets derive from it
   const int KG = a.KG;
+  if constexpr (COLLECT) {
+    if (a.uncert && *a.uncert == 0) return;  // every query certified: nothing to collect (uniform)
+  }
 
   // XCD-aware decode: workgroups of one XCD (blockIdx % 8) sweep the same index
   // range so that the range is fetched into that XCD's L2 once.
@@ -978,6 +981,38 @@ hipError_t launch_frag32_to_bf16(const float *idxp, int64_t NT, int KG, void *ou
   return hipGetLastError();
 }
 
+// the resident fp32 fragment index -> split-bf16 image [NT][KB][hi 1 KiB | lo 1 KiB], KB = ceil(KG/2): lane (row, k octet)
+// owns k = 16 kb + 8 (lane >> 5) + 0 .. 7 of its row, the A operand of v_mfma_f32_32x32x16_bf16 (k-groups past KG: zeros)
+__global__ void frag32_to_split_bf16_kernel(const f32x4 *__restrict__ in, int KG, int KB, int64_t total8, sse_u32x4 *__restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total8; i += (int64_t)gridDim.x * blockDim.x) {
+    const int l = (int)(i & 63);
+    const int64_t blk = i >> 6;
+    const int kb = (int)(blk % KB);
+    const int64_t tile = blk / KB;
+    const int kg = kb * 2 + (l >> 5), r = l & 31;
+    f32x4 lo4 = {0, 0, 0, 0}, hi4 = {0, 0, 0, 0};
+    if (kg < KG) {
+      lo4 = in[((size_t)tile * KG + kg) * 64 + r];
+      hi4 = in[((size_t)tile * KG + kg) * 64 + 32 + r];
+    }
+    const float v[8] = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
+    sse_u32x4 h, lw;
+    sse_split8(v, h, lw);
+    out[(size_t)blk * 128 + l] = h;
+    out[(size_t)blk * 128 + 64 + l] = lw;
+  }
+}
+
+hipError_t launch_frag32_to_split_bf16(const float *idxp, int64_t NT, int KG, void *out, hipStream_t stream) {
+  const int KB = (KG + 1) / 2;
+  const int64_t total8 = NT * KB * 64;
+  if (total8 == 0) return hipSuccess;
+  const int64_t blocks = (total8 + 255) / 256;
+  hipLaunchKernelGGL(frag32_to_split_bf16_kernel, dim3((int)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, stream,
+                     reinterpret_cast<const f32x4 *>(idxp), KG, KB, total8, reinterpret_cast<sse_u32x4 *>(out));
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // Small-index scorer (see SmallIndexArgs).  16384 queries x 571 targets -- the scoring half of the headline step, the
 // evaluator's shape (sse_evaluator.py:104-112) -- took 110 us in the list sweep (+ 7 us of packing) for ~30 us of fp32 MFMA
@@ -1180,6 +1215,104 @@ __global__ __launch_bounds__(256) void score_small_index_kernel(SmallIndexArgs a
     si_select4<16>(a, sc, NP, NT, qt, w * 8 + 4, lane SI_CLK_ARGS);
   }
 }
+// The same scorer on split-bf16 operands (SmallIndexArgs::idx_x3): q.t ~ qh.th + qh.tl + ql.th, three
+// v_mfma_f32_32x32x16_bf16 per 16 k (48 x 32 cycles per tile against 128 x 64 of the fp32 form).  The queries are split in
+// registers as they are read (KB x (4 hi + 4 lo) VGPRs: what the fp32 fragments take), the index comes as the hi | lo image
+// launch_frag32_to_split_bf16 built when the index was set.  With a sixth of the matrix cycles the index fragments' way
+// from L2 is what paces the phase: they are read four k-blocks ahead THROUGH the tile boundary (the next tile's first
+// blocks under this tile's last MFMAs), or every tile would start with an exposed L2 round trip.  Accumulator layout,
+// LDS score tile, padding and selection: as above.
+template <int KB>
+__global__ __launch_bounds__(256) void score_small_index_x3_kernel(SmallIndexArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float si_sc[];  // scores [32 queries][NP]
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int NT = a.NT, NP = NT * 32 + 1;
+  const int qt = blockIdx.x;
+  float *sc = si_sc;
+  SC_CLK_DECL
+  // this lane's query fragments (lane (k octet, query): 8 consecutive k per k-block), split as they arrive
+  sse_u32x4 bh[KB], bl[KB];
+  {
+    const int row = qt * 32 + (lane & 31), kb0 = (lane >> 5) * 8;
+    const float *src = a.q_rows + (size_t)(row < a.Q ? row : 0) * a.S + kb0;
+    const bool vec = (a.S & 3) == 0 && (reinterpret_cast<uintptr_t>(a.q_rows) & 15) == 0 && KB * 16 <= a.S;  // (uniform)
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+      float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (vec) {
+        const f32x4 v0 = *reinterpret_cast<const f32x4 *>(src + kb * 16), v1 = *reinterpret_cast<const f32x4 *>(src + kb * 16 + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          v[e] = v0[e];
+          v[4 + e] = v1[e];
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (kb * 16 + kb0 + e < a.S) v[e] = src[kb * 16 + e];
+      }
+      if (row >= a.Q) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = 0.0f;
+      }
+      sse_split8(v, bh[kb], bl[kb]);
+    }
+  }
+  SC_CLK(0)
+  {
+    constexpr int D = KB < 4 ? KB : 4;  // k-blocks in flight
+    static_assert(KB % D == 0, "the ring index must be static");
+    const sse_u32x4 *img = reinterpret_cast<const sse_u32x4 *>(a.idx_x3) + lane;
+    const sse_u32x4 *ap = img + (size_t)(w < NT ? w : 0) * KB * 128;
+    sse_u32x4 ah[D], al[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      ah[d] = ap[d * 128];
+      al[d] = ap[d * 128 + 64];
+    }
+    for (int t = w; t < NT; t += 4) {
+      const sse_u32x4 *apn = img + (size_t)(t + 4 < NT ? t + 4 : t) * KB * 128;  // (the last tile re-reads itself: never used)
+      f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb) {
+        __builtin_amdgcn_sched_barrier(0);  // (pinned as in the fp32 kernel: the refills otherwise sink behind the block)
+        const bf16x8_t xh = __builtin_bit_cast(bf16x8_t, ah[kb % D]), xl = __builtin_bit_cast(bf16x8_t, al[kb % D]);
+        const bf16x8_t yh = __builtin_bit_cast(bf16x8_t, bh[kb]), yl = __builtin_bit_cast(bf16x8_t, bl[kb]);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, yh, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, yl, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl, yh, acc, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        const sse_u32x4 *nx = (kb + D < KB) ? ap + (kb + D) * 128 : apn + (kb + D - KB) * 128;
+        ah[kb % D] = nx[0];
+        al[kb % D] = nx[64];
+      }
+      const int rb = t * 32 + 4 * (lane >> 5);
+      float *col = sc + (lane & 31) * NP;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = rb + (r & 3) + 8 * (r >> 2);
+        col[row] = (row < a.N) ? acc[r] : NEG_INF;  // (the zero padding of the last tile)
+      }
+      ap = apn;
+    }
+  }
+  SC_CLK(1)
+  __syncthreads();
+  SC_CLK(2)
+  if (NT * 32 <= 640) {
+    si_select4<10>(a, sc, NP, NT, qt, w * 8, lane SI_CLK_ARGS);
+    SC_CLK(3)
+    si_select4<10>(a, sc, NP, NT, qt, w * 8 + 4, lane SI_CLK_ARGS);
+    SC_CLK(4)
+#ifdef SSE_SCORE_CLOCK
+    if (blockIdx.x == gridDim.x / 2 && lane == 0)
+      for (int i = 0; i < 8; ++i) g_score_clk[w * 8 + i] = ck_[i];
+#endif
+  } else {
+    si_select4<16>(a, sc, NP, NT, qt, w * 8, lane SI_CLK_ARGS);
+    si_select4<16>(a, sc, NP, NT, qt, w * 8 + 4, lane SI_CLK_ARGS);
+  }
+}
 bool score_small_index_applies(int Q, int KG, int64_t NT) {
   // many queries only: a single query's workgroup would walk all tiles alone (0.09 ms against 0.05 for the list sweep)
   // index dimensions 249 .. 256 (configs[1]), 57 .. 64 (the reference's default encoding_size, sse_train.py:67), 49 .. 56 (its
@@ -1196,9 +1329,10 @@ hipError_t launch_score_small_index(const SmallIndexArgs &a, hipStream_t stream)
     hipLaunchKernelGGL(kernel, grid, block, lds, stream, a);
     return hipGetLastError();
   };
+  if (a.idx_x3 && a.KG != 32) return go(score_small_index_x3_kernel<4>);  // (7 k-groups: the image's last octets are zeros)
   if (a.KG == 8) return go(score_small_index_kernel<8>);
   if (a.KG == 7) return go(score_small_index_kernel<7>);
-  const hipError_t e32 = go(score_small_index_kernel<32>);
+  const hipError_t e32 = a.idx_x3 ? go(score_small_index_x3_kernel<16>) : go(score_small_index_kernel<32>);
   if (e32 != hipSuccess) return e32;
 #ifdef SSE_SCORE_CLOCK
   if (a.Q >= 8192) {
@@ -1384,6 +1518,7 @@ __global__ __launch_bounds__(RS_THREADS) void rescore_kernel(RescoreArgs a) {
   __shared__ double s_qn[RS_THREADS / 64];
   extern __shared__ __attribute__((aligned(16))) unsigned long long s_key[];  // [NC] (dynamic: keeps occupancy for small NC)
   const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if (a.uncert_clear && q == 0 && tid == 0) *a.uncert_clear = 0;  // the next call's word (see RescoreArgs::uncert)
   if (a.q_count && q >= *a.q_count) return;  // compacted second chance: slots past the set (uniform per workgroup)
   const int qo = a.qmap ? a.qmap[q] : q;     // where this slot's results go
   const float *ps = a.part_scores + (size_t)q * a.NC;
@@ -1563,6 +1698,7 @@ __global__ __launch_bounds__(RS_THREADS) void rescore_kernel(RescoreArgs a) {
       t = fmax(fmax(s_ex[0], s_ex[1]), fmax(s_ex[2], s_ex[3]));
       const bool ok = (nwin_all <= RS_MAXWIN) && (nwin >= a.k) && ((double)mmax + (double)eps_q < t);
       a.cert[qo] = ok ? 1 : 0;
+      if (!ok && a.uncert) atomicAdd(a.uncert, 1);
       // t = exact score of the k-th best candidate (-inf with fewer than k): a lower bound of the true k-th best, so
       // every exact top-k row has fp32 score >= t - eps32*|q| (the collect pass gathers exactly those)
       if (a.col_thr) a.col_thr[qo] = ok ? __builtin_inff() : __double2float_rd(t - (double)(a.eps32 * qnorm));
@@ -1597,6 +1733,7 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {
 __global__ __launch_bounds__(256) void rescore_small_kernel(RescoreArgs a) {
   const int lane = threadIdx.x & 63;
   const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (a.uncert_clear && blockIdx.x == 0 && threadIdx.x == 0) *a.uncert_clear = 0;  // the next call's word (see RescoreArgs::uncert)
   if (q >= a.Q) return;
   if (a.q_count && q >= *a.q_count) return;  // compacted second chance: slots past the set (uniform per wave)
   const int qo = a.qmap ? a.qmap[q] : q;
@@ -1682,6 +1819,7 @@ __global__ __launch_bounds__(256) void rescore_small_kernel(RescoreArgs a) {
   if (lane == 0) {
     const bool ok = (nwin >= a.k) && ((double)mmax + (double)eps_q < theta);
     a.cert[qo] = ok ? 1 : 0;
+    if (!ok && a.uncert) atomicAdd(a.uncert, 1);
     if (a.col_thr) a.col_thr[qo] = ok ? __builtin_inff() : __double2float_rd(theta - (double)(a.eps32 * qnorm));
     if (a.col_slot) {
       a.col_slot[qo] = ok ? -1 : qo;
@@ -1734,13 +1872,12 @@ struct ExactArgs {
   int32_t k_off, k_total;  // they land at columns [k_off, k_off + k) of rows of k_total columns; when
                            // k_off > 0 only rows ranked AFTER column k_off-1 are considered (next page)
   unsigned long long *served;  // diagnostic counter (device) or nullptr: +1 per query computed here (first page)
+  const int32_t *uncert;       // optional, see SelectArgs::uncert
 };
 
-__global__ __launch_bounds__(EX_THREADS) void exact_topk_kernel(ExactArgs a) {
-  __shared__ double s_sc[EX_THREADS / 64][SC_KC];
-  __shared__ int64_t s_id[EX_THREADS / 64][SC_KC];
-  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  if (a.cert && a.cert[q]) return;
+__device__ __forceinline__ void exact_topk_query(const ExactArgs a, const int q, double (*s_sc)[SC_KC],
+                                                 int64_t (*s_id)[SC_KC]) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   if (a.served && tid == 0 && a.k_off == 0) atomicAdd(a.served, 1ull);
   const float *qrow = a.q + (size_t)q * a.S;
   const int KG = (a.S + 7) / 8;
@@ -1787,29 +1924,62 @@ __global__ __launch_bounds__(EX_THREADS) void exact_topk_kernel(ExactArgs a) {
   }
   __syncthreads();
   if (tid == 0) {
-    int pos[EX_THREADS / 64] = {0, 0, 0, 0};
+    unsigned pos4 = 0;  // the four lists' positions, a byte each (<= 16): no indexed private array, no scratch
+    auto pos = [&](int p) { return (int)((pos4 >> (8 * p)) & 0xFFu); };
     for (int o = 0; o < a.k; ++o) {
       int best = -1;
       for (int p = 0; p < EX_THREADS / 64; ++p) {
-        if (pos[p] >= SC_KC || s_id[p][pos[p]] < 0) continue;
-        if (best < 0 || before(s_sc[p][pos[p]], s_id[p][pos[p]], s_sc[best][pos[best]], s_id[best][pos[best]])) best = p;
+        if (pos(p) >= SC_KC || s_id[p][pos(p)] < 0) continue;
+        if (best < 0 || before(s_sc[p][pos(p)], s_id[p][pos(p)], s_sc[best][pos(best)], s_id[best][pos(best)])) best = p;
       }
-      a.out_scores[(size_t)q * a.k_total + a.k_off + o] = s_sc[best][pos[best]];
-      a.out_ids[(size_t)q * a.k_total + a.k_off + o] = a.id_base + s_id[best][pos[best]];
-      ++pos[best];
+      a.out_scores[(size_t)q * a.k_total + a.k_off + o] = s_sc[best][pos(best)];
+      a.out_ids[(size_t)q * a.k_total + a.k_off + o] = a.id_base + s_id[best][pos(best)];
+      pos4 += 1u << (8 * best);
     }
+  }
+}
+__global__ __launch_bounds__(EX_THREADS) void exact_topk_kernel(ExactArgs a) {  // one workgroup per query
+  __shared__ double s_sc[EX_THREADS / 64][SC_KC];
+  __shared__ int64_t s_id[EX_THREADS / 64][SC_KC];
+  const int q = blockIdx.x;
+  if (a.cert && a.cert[q]) return;
+  exact_topk_query(a, q, s_sc, s_id);
+}
+// The follow-up launch of a scoring call (ExactArgs::uncert set): a bounded grid, workgroup b takes queries b, b + gridDim.x,
+// ...  `open` flags of up to 256 of them are fetched side by side first: a chain of dependent reads would cost a round trip
+// per query.  (A kernel of its own: the loop costs the one above 20 registers and a wave of occupancy.)
+__global__ __launch_bounds__(EX_THREADS) void exact_topk_strided_kernel(ExactArgs a) {
+  __shared__ double s_sc[EX_THREADS / 64][SC_KC];
+  __shared__ int64_t s_id[EX_THREADS / 64][SC_KC];
+  __shared__ unsigned char s_open[EX_THREADS];
+  if (a.uncert && *a.uncert == 0) return;  // every query certified by the re-scoring pass (uniform)
+  {
+    const long long q = (long long)blockIdx.x + (long long)threadIdx.x * gridDim.x;
+    s_open[threadIdx.x] = (q < a.Q) && !(a.cert && a.cert[q]);
+  }
+  __syncthreads();
+  int it = 0;
+#pragma nounroll
+  for (int q = blockIdx.x; q < a.Q; q += gridDim.x, ++it) {
+    const bool open = it < EX_THREADS ? s_open[it] != 0 : !(a.cert && a.cert[q]);  // (uniform)
+    if (!open) continue;
+    exact_topk_query(a, q, s_sc, s_id);
+    __syncthreads();  // thread 0 has read the lists before the next query's overwrite them
   }
 }
 
 hipError_t launch_exact_topk(const float *q, const float *idxp, const double *idx64, const int32_t *cert,
                              double *out_scores, int64_t *out_ids, int64_t id_base, int64_t N, int Q, int S,
-                             int k, hipStream_t stream, unsigned long long *served) {
+                             int k, hipStream_t stream, unsigned long long *served, const int32_t *uncert, int grid_cap) {
   // k <= 16: one pass (the certified-failure path).  Larger k: pages of 16, each pass a full
   // float64 sweep restricted to rows ranked after the previous page (exact, slow, rarely used:
   // the reference's consumers read <= 10 columns, sse_evaluator.py:95,112)
   for (int off = 0; off < k; off += SC_KC) {
-    ExactArgs a{q, idxp, idx64, cert, out_scores, out_ids, id_base, N, Q, S, (k - off < SC_KC) ? k - off : SC_KC, off, k, served};
-    hipLaunchKernelGGL(exact_topk_kernel, dim3(Q), dim3(EX_THREADS), 0, stream, a);
+    ExactArgs a{q, idxp, idx64, cert, out_scores, out_ids, id_base, N, Q, S, (k - off < SC_KC) ? k - off : SC_KC, off, k, served, uncert};
+    // with the word: a bounded grid (its workgroups leave at once as a rule); without: a workgroup per query, as ever
+    const int grid = (uncert && grid_cap > 0 && grid_cap < Q) ? grid_cap : Q;
+    if (grid < Q) hipLaunchKernelGGL(exact_topk_strided_kernel, dim3(grid), dim3(EX_THREADS), 0, stream, a);
+    else hipLaunchKernelGGL(exact_topk_kernel, dim3(Q), dim3(EX_THREADS), 0, stream, a);
   }
   return hipGetLastError();
 }
@@ -1953,9 +2123,8 @@ hipError_t launch_lane_max_threshold(const float *q, const float *lane_max, int 
 
 // One workgroup per collected query: float64 scores of its rows (the reference's arithmetic, wave_exact_dot as in the
 // re-scoring pass: bit-identical values), sorted (score descending, then lower row id), first k out.
-__global__ __launch_bounds__(256) void select_topk_kernel(SelectArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned long long sel_smem[];
-  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+__device__ __forceinline__ void select_topk_query(const SelectArgs &a, const int q, unsigned long long *sel_smem) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int slot = a.col_slot[q];
   if (slot < 0) return;
   const int n = a.col_cnt[slot];
@@ -2014,12 +2183,32 @@ __global__ __launch_bounds__(256) void select_topk_kernel(SelectArgs a) {
     if (a.served) atomicAdd(a.served, 1ull);
   }
 }
+// (the queries of a workgroup and their `open` flags: as in exact_topk_kernel)
+__global__ __launch_bounds__(256) void select_topk_kernel(SelectArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long sel_smem[];
+  __shared__ unsigned char s_open[256];
+  if (a.uncert && *a.uncert == 0) return;  // every query certified by the re-scoring pass (uniform)
+  {
+    const long long q = (long long)blockIdx.x + (long long)threadIdx.x * gridDim.x;
+    s_open[threadIdx.x] = (q < a.Q) && a.col_slot[q] >= 0;
+  }
+  __syncthreads();
+  int it = 0;
+#pragma nounroll
+  for (int q = blockIdx.x; q < a.Q; q += gridDim.x, ++it) {
+    const bool open = it < 256 ? s_open[it] != 0 : a.col_slot[q] >= 0;  // (uniform)
+    if (!open) continue;
+    select_topk_query(a, q, sel_smem);
+    __syncthreads();  // the sort area is free for the next query
+  }
+}
 hipError_t launch_select_topk(const SelectArgs &a, hipStream_t st) {
   if (a.col_cap > SSE_COLLECT_CAP) return hipErrorInvalidValue;
   const size_t lds = (size_t)a.col_cap * (sizeof(unsigned long long) + sizeof(int));
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(select_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(select_topk_kernel, dim3(a.Q), dim3(256), lds, st, a);
+  const int grid = (a.uncert && a.grid_cap > 0 && a.grid_cap < a.Q) ? a.grid_cap : a.Q;
+  hipLaunchKernelGGL(select_topk_kernel, dim3(grid), dim3(256), lds, st, a);
   return hipGetLastError();
 }
 

@@ -176,11 +176,13 @@ struct sse_handle {
   int lstm_x_table_mb = 256;
   int64_t x_table_builds = 0;
   bool score_small_index = true;  // option "score_small_index": many queries against <= 1024 rows skip the list sweep (launch_score_small_index)
+  bool score_small_x3 = true;     // option "score_small_x3": the small-index scorer forms its candidates from split-bf16 operands (idx_x3; wider r.eps)
   bool score_bf16 = true;    // option "score_bf16" (default on): candidate pass on the bf16 matrix pipe; results stay exact
   void *idxp16 = nullptr;    // bf16 fragment copy of the index (built on demand)
   size_t idxp16_cap = 0;
   bool idxp16_valid = false;
   bool fb_cnt_init = false;
+  int uncert_word = 0;       // which word of the pair behind the counters the current scoring call counts its uncertified queries in
   bool cnn_bf16 = false;     // option "cnn_bf16": source_only_cnn inference with bf16 storage / fp32 accumulation
   unsigned short *emb_bf16 = nullptr, *cnn_Wc16 = nullptr, *cnn_Mx3 = nullptr;
   int lstm_train_rows = 0;   // option "lstm_train_rows": 0 = automatic, 32 / 64 = rows per workgroup of the training forward (Hp = 256)
@@ -204,6 +206,8 @@ struct sse_handle {
   double *idx64 = nullptr;
   DevBuf idx_rm;            // row-major f32 copy of a SMALL index (re-scoring gathers, RescoreArgs::idx_rm); valid: idx_rm_valid
   bool idx_rm_valid = false;
+  DevBuf idx_x3;            // split-bf16 image of idxp for the small-index scorer (SmallIndexArgs::idx_x3), rebuilt with every index
+  bool idx_x3_valid = false;  // that score_small_index_applies can serve (<= 1024 rows: <= 1 MiB); valid: idx_x3_valid
   int64_t idx_N = 0, idx_base = 0;
   int idx_S = 0;
   float idx_norm_max = 1.0f;
@@ -1004,6 +1008,14 @@ int index_from_dev_rows(sse_handle *h, const float *rows_dev, int64_t N, int S, 
   if (reserve(h, h->s_tmp2, 16)) return 1;
   HIPCHECK(h, hipMemsetAsync(h->s_tmp2.p, 0, 4, st));
   HIPCHECK(h, launch_pack_rows_norm(rows_dev, N, S, h->idxp, (float *)h->s_tmp2.p, st));
+  // the small-index scorer's split-bf16 image: once per index, from the fragment copy just written (the index is resident
+  // and constant from call to call); an index it cannot serve leaves no image behind
+  h->idx_x3_valid = false;
+  if (score_small_index_applies(1024, KG, NT)) {
+    if (reserve(h, h->idx_x3, (size_t)NT * ((KG + 1) / 2) * 2048)) return 1;
+    HIPCHECK(h, launch_frag32_to_split_bf16(h->idxp, NT, KG, h->idx_x3.p, st));
+    h->idx_x3_valid = true;
+  }
   float n2 = 0;
   HIPCHECK(h, hipMemcpyAsync(&n2, h->s_tmp2.p, 4, hipMemcpyDeviceToHost, st));
   HIPCHECK(h, hipStreamSynchronize(st));
@@ -1065,9 +1077,10 @@ static int choose_nsplit(int NQ, int QB, int64_t NT) {
 // diagnostic counters on the device: [0] queries whose bf16-candidate result missed its certificate, [1] queries served
 // by the collect path, [2] queries that fell through to the float64 brute force
 static int ensure_counters(sse_handle *h, hipStream_t st) {
-  if (reserve(h, h->s_fb_cnt, 4 * sizeof(unsigned long long))) return 1;
+  // four diagnostic counters, then the pair of "queries left uncertified" words (RescoreArgs::uncert)
+  if (reserve(h, h->s_fb_cnt, 6 * sizeof(unsigned long long))) return 1;
   if (!h->fb_cnt_init) {
-    HIPCHECK(h, hipMemsetAsync(h->s_fb_cnt.p, 0, 4 * sizeof(unsigned long long), st));
+    HIPCHECK(h, hipMemsetAsync(h->s_fb_cnt.p, 0, 6 * sizeof(unsigned long long), st));
     h->fb_cnt_init = true;
   }
   return 0;
@@ -1205,6 +1218,7 @@ int score_dev_locked(sse_handle *h, const float *q, int Q, int k, double *out_s,
   // many queries against a small index (the evaluator's 16384 x 571): one launch forms all N scores per query and selects the
   // 16 best exactly (launch_score_small_index) instead of the list sweep
   const bool small_idx = h->score_small_index && !bf && score_small_index_applies(Q, KG, NT);
+  const bool small_x3 = small_idx && h->score_small_x3 && h->idx_x3_valid;
   const int NC = small_idx ? 16 : nsplit * 16, NCmax = std::max(nsplit, nsplit2) * 16;
   const int KG16 = (S + 15) / 16;
   if (bf && !h->idxp16_valid) {
@@ -1328,6 +1342,7 @@ int score_dev_locked(sse_handle *h, const float *q, int Q, int k, double *out_s,
   if (first) {
     if (small_idx) {
       SmallIndexArgs si{q, h->idxp, a.part_scores, a.part_ids, a.part_bnd, h->idx_N, Q, S, KG, (int)NT};
+      if (small_x3) si.idx_x3 = h->idx_x3.p;
       HIPCHECK(h, launch_score_small_index(si, st));
     } else {
       HIPCHECK(h, launch_score_topk(a, st));
@@ -1355,6 +1370,14 @@ int score_dev_locked(sse_handle *h, const float *q, int Q, int k, double *out_s,
   r.eps = eps32;
   r.eps32 = eps32;
   r.col_thr = (float *)h->s_cthr.p;
+  // the follow-up launches below are queued unconditionally; this word lets their workgroups leave at once (and their grids
+  // stay small) when the re-scoring pass certified every query -- the usual call.  Two words, used in turn: a call's
+  // re-scoring pass zeroes the one the next call will count in.
+  if (first) h->uncert_word ^= 1;
+  int32_t *const uncert = (int32_t *)(counters + 4) + h->uncert_word;
+  const int follow_grid = 2 * (h->cu_count > 0 ? h->cu_count : 256);
+  r.uncert = uncert;
+  r.uncert_clear = (int32_t *)(counters + 4) + (h->uncert_word ^ 1);
   // every query has a collect slot of its own (the usual call): the re-scoring pass hands them out (slot = query for an
   // uncertified one) and zeroes their counters -- no memset / launch_assign_slots between the passes
   const bool own_slots = Q <= POOL;
@@ -1364,6 +1387,15 @@ int score_dev_locked(sse_handle *h, const float *q, int Q, int k, double *out_s,
   }
   // bf16 operands: |q^.t^ - q.t| <= ((1+u)^2 - 1) sum|q_i t_i| <= (2^-8 + 2^-18) |q||t|, u = 2^-9 (round to nearest)
   if (bf) r.eps += (float)(1.02 * (1.0 / 256.0 + 1.0 / 262144.0) * h->idx_norm_max);
+  // split-bf16 candidates of the small-index scorer (DESIGN K6).  bf16 keeps 8 significant bits: hi = rne(x) leaves
+  // |x - hi| <= 2^-8 |x|, lo = rne(x - hi) leaves e = x - hi - lo with |e| <= 2^-17 |x| (and |lo| <= 2^-8 (1 + 2^-9) |x|).  The
+  // dropped terms ql.tl + eq.t + (q - eq).et are <= (2^-16 + 2 * 2^-17)(1 + 2^-7) sum|q_i t_i| <= 2^-15 (1 + 2^-6) |q||t| -- reached
+  // to 2 % by mantissas that sit halfway in both roundings.  The 3 S kept products are exact in fp32 and are added in an order
+  // the matrix pipe chooses: (3 S + 2) additions of <= 2^-24 sum|terms| each (+ the f32 rounding of f64 rows), sum|terms| <=
+  // (1 + 2^-5) sum|q_i t_i|, with the fp32 bound's 2x margin.  1.26e-4 at S = 256 (fp32: 3.1e-5); rows or queries of norm
+  // below 2^-100 are outside the claim (a lo part may underflow bf16's range).
+  if (small_x3)
+    r.eps = (float)(((1.0 + 1.0 / 64.0) / 32768.0 + 2.0 * (3 * S + 2) * 5.97e-8 * (1.0 + 1.0 / 32.0)) * h->idx_norm_max);
   if (first) {
     RescoreArgs rf = r;
     if (mirror) {
@@ -1410,6 +1442,7 @@ int score_dev_locked(sse_handle *h, const float *q, int Q, int k, double *out_s,
     r2.eps = eps32;
     r2.qmap = qmap;
     r2.q_count = qcount;
+    r2.uncert = r2.uncert_clear = nullptr;  // (the word keeps the first pass's count: an upper bound, zero only if nothing is left)
     HIPCHECK(h, launch_rescore(r2, st));
     qp32 = (const float *)h->s_qp32.p;  // (unused by the collect sweep: it reads the rows)
   }
@@ -1435,12 +1468,14 @@ int score_dev_locked(sse_handle *h, const float *q, int Q, int k, double *out_s,
   c.col_cnt = (int32_t *)h->s_ccnt.p;
   c.col_buf = (int32_t *)h->s_cbuf.p;
   c.col_cap = SSE_COLLECT_CAP;
+  c.uncert = uncert;
   HIPCHECK(h, launch_score_topk(c, st));
   SelectArgs sel{q, h->idxp, h->idx64, c.col_slot, c.col_cnt, c.col_buf, SSE_COLLECT_CAP, out_s, out_i, r.cert, h->idx_base, Q, S, k,
-                 counters + 1};
+                 counters + 1, uncert, follow_grid};
   HIPCHECK(h, launch_select_topk(sel, st));
   // last resort (more than SSE_COLLECT_CAP rows within the bound of the k-th score, or no buffer slot left)
-  HIPCHECK(h, launch_exact_topk(q, h->idxp, h->idx64, r.cert, out_s, out_i, h->idx_base, h->idx_N, Q, S, k, st, counters + 2));
+  HIPCHECK(h, launch_exact_topk(q, h->idxp, h->idx64, r.cert, out_s, out_i, h->idx_base, h->idx_N, Q, S, k, st, counters + 2, uncert,
+                                follow_grid));
   return 0;
 }
 
@@ -1905,6 +1940,10 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value) {
   std::lock_guard<std::mutex> lk(h->mu);
   if (strcmp(name, "score_small_index") == 0) {
     h->score_small_index = value != 0;
+    return 0;
+  }
+  if (strcmp(name, "score_small_x3") == 0) {
+    h->score_small_x3 = value != 0;
     return 0;
   }
   if (strcmp(name, "score_bf16") == 0) {

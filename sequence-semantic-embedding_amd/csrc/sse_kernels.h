@@ -319,6 +319,9 @@ struct ScoreArgs {
   // not read and the pack launch in front of the sweep goes away
   const float *q_rows = nullptr;
   int32_t S = 0;
+  // COLLECT sweeps: optional device word, the number of queries the re-scoring pass left uncertified (RescoreArgs::uncert);
+  // zero: every workgroup leaves at once
+  const int32_t *uncert = nullptr;
 };
 hipError_t launch_score_topk(const ScoreArgs &a, hipStream_t stream);
 // two-pass path for mid-size indexes: threshold per query from the lane maxima of a max-only sweep (ScoreArgs::lane_max)
@@ -337,6 +340,9 @@ hipError_t launch_count_uncert(const int32_t *cert, int Q, unsigned long long *c
 hipError_t launch_compact_uncert(const float *q, const int32_t *cert, int Q, int S, int32_t *qmap, int32_t *count, float *qc,
                                  hipStream_t st);
 hipError_t launch_frag32_to_bf16(const float *idxp, int64_t NT, int KG, void *out, hipStream_t stream);
+// fp32 frag32 index -> split-bf16 fragment image [NT][ceil(KG/2)][hi 1 KiB | lo 1 KiB] (frag16 blocks, hi = bf16(x),
+// lo = bf16(x - hi)): the A operand of the small-index scorer's split candidate pass (SmallIndexArgs::idx_x3)
+hipError_t launch_frag32_to_split_bf16(const float *idxp, int64_t NT, int KG, void *out, hipStream_t stream);
 
 #define SSE_COLLECT_CAP 4096   // rows one query can collect (exact path); more -> float64 brute force
 #define SSE_MAX_SELECT_K 1024  // largest k the collect path serves
@@ -377,6 +383,11 @@ struct RescoreArgs {
   // row from 8 cache lines instead of the 64 the fragment order spreads it over.  A lane reads the same four dimensions
   // either way, so the sums -- and the float64 scores -- are bit-identical.
   const float *idx_rm = nullptr;
+  // optional: *uncert += 1 per query left uncertified (the word is zero on entry); the follow-up launches of a call (collect
+  // sweep, select, float64 sweep) read it first and leave when it is zero.  *uncert_clear = 0: the OTHER word of the pair the
+  // host alternates between from call to call -- stream order puts this pass after the previous call's readers of that
+  // word and before the next call's writers, so no memset launch and no "last reader" bookkeeping
+  int32_t *uncert = nullptr, *uncert_clear = nullptr;
 };
 hipError_t launch_rescore(const RescoreArgs &a, hipStream_t stream);
 
@@ -386,6 +397,9 @@ hipError_t launch_rescore(const RescoreArgs &a, hipStream_t stream);
 // launch_score_topk with ONE split (NC = 16), so launch_rescore follows unchanged.  part_bnd[q] = the 16th best (every
 // other row scores <= that), +inf when more than 63 rows tie into the selection (the certificate then fails: next stage).
 // Index dimensions 249 .. 256, 57 .. 64 and 49 .. 56 (the k-groups are a template parameter: the query fragments live in registers).
+// idx_x3 set (option score_small_x3): the scores are formed from split-bf16 operands, q.t ~ qh.th + qh.tl + ql.th on
+// v_mfma_f32_32x32x16_bf16 -- a sixth of the matrix cycles of the fp32 form.  They only pick candidates and bound the rows
+// left out, so the caller widens RescoreArgs::eps to the split bound (DESIGN K6); selection and outputs are the same code.
 struct SmallIndexArgs {
   const float *q_rows;   // [Q][S] fp32 row-major
   const float *idxp;     // frag32 index [NT][KG][256]
@@ -394,6 +408,7 @@ struct SmallIndexArgs {
   float *part_bnd;       // [Q]
   int64_t N;
   int32_t Q, S, KG, NT;
+  const void *idx_x3 = nullptr;  // split-bf16 image of idxp (launch_frag32_to_split_bf16) or nullptr: fp32 candidates
 };
 bool score_small_index_applies(int Q, int KG, int64_t NT);
 hipError_t launch_score_small_index(const SmallIndexArgs &a, hipStream_t stream);
@@ -417,6 +432,10 @@ struct SelectArgs {
   int64_t id_base;
   int32_t Q, S, k;
   unsigned long long *served = nullptr;  // diagnostic counter (device), +1 per query served here
+  // optional (see RescoreArgs::uncert): zero -> nothing to do; with it the launch is grid_cap workgroups walking the
+  // queries in a grid-stride loop instead of one workgroup per query
+  const int32_t *uncert = nullptr;
+  int32_t grid_cap = 0;
 };
 // float64 re-score + sort of the collected rows, first k out (score descending, then lower row id)
 hipError_t launch_select_topk(const SelectArgs &a, hipStream_t st);
@@ -466,7 +485,8 @@ hipError_t launch_row_norm2_max(const float *x, int64_t rows, int cols, float *o
 hipError_t launch_fill(float *p, int64_t n, float v, hipStream_t stream);
 hipError_t launch_exact_topk(const float *q, const float *idxp, const double *idx64, const int32_t *cert,
                              double *out_scores, int64_t *out_ids, int64_t id_base, int64_t N, int Q, int S,
-                             int k, hipStream_t stream, unsigned long long *served = nullptr);
+                             int k, hipStream_t stream, unsigned long long *served = nullptr, const int32_t *uncert = nullptr,
+                             int grid_cap = 0);  // uncert / grid_cap: as in SelectArgs
 
 // ------------------------------ CNN encoder --------------------------------
 // bf16-storage variant (cnn_fwd_bf16.hip): embeddings / filters as bf16, fp32 accumulation, fp32 tail
