@@ -150,7 +150,9 @@ int sse_encode_dev(sse_handle *h, int side, const int32_t *ids_dev, int32_t B, i
  * plain launch, the give-up / fall-back path alone).  "lstm_cluster_backoff" (default -1 = automatic): eligible calls that go
  * straight to the kernels needing no co-residency after a cluster launch gave up (a give-up costs 10 ms); automatic arms 16
  * calls once a give-up was observed (another process on the device, or a refused cooperative launch).  "train_gen1" (default 0): the first-generation fp32 training
- * kernels instead of the round-4 ones (A/B and test aid; same results to fp32 summation order). */
+ * kernels instead of the round-4 ones (A/B and test aid; same results to fp32 summation order).
+ * "eval_chunk_rows" (default 65536; >= 2, rounded down to even): sse_eval_loss* stages and encodes its pair rows in chunks of
+ * at most this many, so that its scratch is bounded for any batch; the result does not depend on the value. */
 int sse_set_option(sse_handle *h, const char *name, int32_t value);
 /* Diagnostic counters (cumulative).  "score_bf16_second_chance_queries": queries whose bf16-candidate result missed
  * its certificate and were re-run with fp32 candidates.  "score_collect_queries": queries served by the collect path
@@ -166,7 +168,8 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value);
  * kernel's encodes: "lstm_fwd_rows32" / "lstm_fwd_rows64" (rows per workgroup; they add up to lstm_path_fwd),
  * "lstm_fwd_gate_split" (the gate-split kernel for small cells; the others ran the unit-block kernel), "lstm_fwd_x_table"
  * (gate accumulators from the x-projection table; the others gathered embedding rows).  The pad-prefix table builds a
- * kernel does for itself are not counted. */
+ * kernel does for itself are not counted.
+ * "eval_paired_calls": sse_eval_loss* calls that ran the source encoder once per pair of rows (option train_pair_dedup). */
 int sse_get_counter(sse_handle *h, const char *name, int64_t *value);
 
 /* tf.nn.l2_normalize(x, dim=-1) on device rows (sse_model.py:282-283). */
@@ -309,6 +312,28 @@ int sse_train_step_rows(sse_handle *h, const int32_t *src_rows_host, const int32
                         const float *labels_host, int32_t B, float *loss, float *train_acc);
 int sse_train_grads_rows(sse_handle *h, const int32_t *src_rows_host, const int32_t *tgt_rows_host,
                          const float *labels_host, int32_t B, int64_t rows_global);
+/* session.run([model.loss, model.train_acc], feed) WITHOUT model.train, and the per-row `binarylogit` cosines
+ * (sse_model.py:290,298,302): loss and accuracy of held-out pairs -- a validation curve, early stopping, a threshold chosen
+ * on labelled pairs, a restored checkpoint checked against the run that wrote it.  Forward only: the arguments mean what
+ * they mean for sse_train_step / sse_train_step_rows (tgt: [B,T] token ids in the dual- and shared-encoder modes, [B] rows
+ * of the free target matrix in source-encoder-only and source_only_cnn; the rows form reads the corpora of
+ * sse_corpus_upload), but both encoders run on the INFERENCE kernels, un-normalised -- every network mode, every shape
+ * an encode accepts, the inference options (lstm_x3, cnn_bf16, pad_skip, lstm_x_table, ...; the train_*_x3 options do not
+ * apply), the lstm_path_* counters counting once per encode -- and there are no BPTT tapes, hence no 2 GiB tape limit.
+ *   sums[3] = { sum of the row losses, sum of the row accuracies, B } in double, rows added in an order that depends on B
+ *       alone: loss = sums[0] / sums[2], train_acc = sums[1] / sums[2]; sums of ranks or slices of a held-out set add up.
+ *   row_cos_host (NULL or [B]) receives cos(src_b, tgt_b), float32; the logit is 64 cos.
+ * Pair rows are staged and encoded in chunks of option eval_chunk_rows; any chunk size gives the same bits.  With option
+ * train_pair_dedup (default 1), an even B and rows 2i, 2i + 1 carrying the same source (data.py:95-115), the source encoder
+ * runs once per pair (counter eval_paired_calls): the same bits again.  The call runs on the stream of sse_set_stream and
+ * synchronises before it returns.  It changes no variable, Adagrad slot, global_step or learning rate, and nothing of a
+ * gradient result pending between sse_train_grads and sse_train_apply (arena, grads_ready): its scratch is its own.
+ * A token id, corpus row or target-matrix row out of range fails with a message, writes no output and leaves the error
+ * flag clear for the next call.  B == 0 returns sums of 0. */
+int sse_eval_loss(sse_handle *h, const int32_t *src_ids_host, const int32_t *tgt_ids_host, const float *labels_host,
+                  int32_t B, int32_t T, double *sums, float *row_cos_host);
+int sse_eval_loss_rows(sse_handle *h, const int32_t *src_rows_host, const int32_t *tgt_rows_host, const float *labels_host,
+                       int32_t B, double *sums, float *row_cos_host);
 /* model.learning_rate.eval(), model.global_step.eval(), learning_rate_decay_op
  * (sse_train.py:181,200; sse_model.py:122-125) */
 int sse_get_learning_rate(sse_handle *h, float *lr);

@@ -70,6 +70,8 @@ SYMBOLS = {
     "sse_corpus_upload": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int32]),
     "sse_train_step_rows": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sse_train_grads_rows": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int64]),
+    "sse_eval_loss": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(C.c_double), _P]),
+    "sse_eval_loss_rows": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(C.c_double), _P]),
     "sse_get_learning_rate": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "sse_set_learning_rate": (C.c_int, [_P, C.c_float]),
     "sse_decay_learning_rate": (C.c_int, [_P]),
@@ -413,6 +415,47 @@ class Handle(object):
         loss, acc = C.c_float(), C.c_float()
         self.check(self.lib.sse_train_apply(self._h, C.byref(loss), C.byref(acc)))
         return float(loss.value), float(acc.value)
+
+    # ---- forward-only loss / accuracy / cosines of held-out pairs (sse_eval_loss*): no update, inference kernels
+    def _eval_call(self, by_rows, src, tgt, labels, want_cos):
+        if by_rows:
+            s, t, z = self._rows_batch(src, tgt, labels)
+        else:
+            s, t, z = self._train_batch(src, tgt, labels)
+            self._check_tgt_kind(t)
+        B = s.shape[0]
+        sums = (C.c_double * 3)()
+        cos = np.empty(B, np.float32) if want_cos else None
+        if by_rows:
+            self.check(self.lib.sse_eval_loss_rows(self._h, _ptr(s), _ptr(t), _ptr(z), B, sums, _ptr(cos) if want_cos else None))
+        else:
+            self.check(self.lib.sse_eval_loss(self._h, _ptr(s), _ptr(t), _ptr(z), B, s.shape[1], sums, _ptr(cos) if want_cos else None))
+        return (float(sums[0]), float(sums[1]), float(sums[2])), cos
+
+    @staticmethod
+    def _eval_result(sums, cos, return_cos):
+        n = sums[2] if sums[2] else 1.0
+        loss, acc = np.float32(sums[0] / n), np.float32(sums[1] / n)
+        return (loss, acc, cos) if return_cos else (loss, acc)
+
+    def eval_loss_sums(self, src_ids, tgt_ids, labels):
+        """(sum of the row losses, sum of the row accuracies, rows) as float64: what ranks or slices of a held-out set add."""
+        return self._eval_call(False, src_ids, tgt_ids, labels, False)[0]
+
+    def eval_loss_rows_sums(self, src_rows, tgt_rows, labels):
+        return self._eval_call(True, src_rows, tgt_rows, labels, False)[0]
+
+    def eval_loss(self, src_ids, tgt_ids, labels, return_cos=False):
+        """Loss and binary accuracy of a batch of pairs as the train step reports them, WITHOUT the step: (np.float32 loss,
+        np.float32 acc), with return_cos also the cosine of every pair row (float32 [B]; the logit is 64 cos)."""
+        sums, cos = self._eval_call(False, src_ids, tgt_ids, labels, return_cos)
+        return self._eval_result(sums, cos, return_cos)
+
+    def eval_loss_rows(self, src_rows, tgt_rows, labels, return_cos=False):
+        """eval_loss by row numbers into the corpora of corpus_upload (tgt: rows of the free target matrix in the modes
+        that have one)."""
+        sums, cos = self._eval_call(True, src_rows, tgt_rows, labels, return_cos)
+        return self._eval_result(sums, cos, return_cos)
 
     # ---- (row id, gradient row) exchange of the word-embedding gradient (data_parallel.py)
     def dp_packed_floats(self, cap):

@@ -226,6 +226,11 @@ struct sse_handle {
   size_t pin_cap = 0;
   int32_t score_seq = 0;  // call number the re-scoring pass stores into the pinned completion flags (ScoreMirror)
   DevBuf s_pb, s_cthr, s_cslot, s_ccnt, s_cbuf;  // per-split bounds; collect path: thresholds, slots, counters, row buffers
+  // forward-only pair loss (sse_eval_loss*, eval_loss.hip).  Option "eval_chunk_rows": pair rows staged and encoded per chunk (even).
+  // Scratch of its own: a gradient result pending between sse_train_grads and sse_train_apply lives in TrainState and the arena.
+  int eval_chunk_rows = 65536;
+  int64_t eval_paired_calls = 0;  // counter "eval_paired_calls": calls that ran the source encoder once per pair of rows
+  DevBuf ev_ids[2], ev_stage, ev_rows[2], ev_labels, ev_raw[2], ev_row, ev_sums;
   // training
   float lr = 0.9f;
   int64_t global_step = 0;
@@ -1907,6 +1912,10 @@ int sse_get_counter(sse_handle *h, const char *name, int64_t *value) {
     *value = h->pad_sorted_calls;
     return 0;
   }
+  if (strcmp(name, "eval_paired_calls") == 0) {  // sse_eval_loss* calls whose source encoder ran once per (positive, negative) pair
+    *value = h->eval_paired_calls;
+    return 0;
+  }
   if (strcmp(name, "lstm_x_table_builds") == 0) {  // x-projection tables built (option lstm_x_table)
     *value = h->x_table_builds;
     return 0;
@@ -1984,6 +1993,11 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value) {
   }
   if (strcmp(name, "train_pair_dedup") == 0) {
     h->train_pair_dedup = value != 0;
+    return 0;
+  }
+  if (strcmp(name, "eval_chunk_rows") == 0) {
+    if (value < 2) return fail(h, "eval_chunk_rows must be >= 2");
+    h->eval_chunk_rows = (int)(value & ~1);  // even: a chunk never splits a (positive, negative) pair of rows
     return 0;
   }
   if (strcmp(name, "train_serial") == 0) {
@@ -3119,6 +3133,122 @@ int sse_train_step(sse_handle *h, const int32_t *src_ids_host, const int32_t *tg
   h->train->defer_err = false;
   if (rc) return 1;
   return train_apply_locked(h, loss, train_acc);
+}
+
+// session.run([model.loss, model.train_acc]) WITHOUT model.train (sse_model.py:290,298,302): both encoders through the
+// inference dispatch (encode_dev_locked, un-normalised: every option, path and shape an encode takes), then eval_loss.hip.
+// by_rows: src / tgt are row numbers into the corpora of sse_corpus_upload.  Chunks of at most eval_chunk_rows pair rows bound
+// the scratch; the per-row values land at the row's position in the call and ONE reduce follows the last chunk, so the result
+// does not depend on the chunk size.  Runs on the stream of sse_set_stream, behind whatever a train step queued there.
+static int eval_loss_locked(sse_handle *h, const int32_t *src_host, const int32_t *tgt_host, const float *labels_host, int32_t B,
+                            int32_t T, bool by_rows, double *sums, float *row_cos_host) {
+  const sse_config &c = h->cfg;
+  if (!sums || B < 0) return fail(h, "bad arguments to the loss evaluation");
+  if (B == 0) {
+    sums[0] = sums[1] = sums[2] = 0.0;
+    return 0;
+  }
+  if (T < 1 || !src_host || !tgt_host || !labels_host) return fail(h, "bad arguments to the loss evaluation");
+  const bool table_tgt = h->tgt_table >= 0;  // source-encoder-only / source_only_cnn: tgt = rows of the free target matrix
+  TrainState *ts = h->train;
+  if (by_rows && !table_tgt && (!ts->corpus[1].p || ts->corpus_T[1] != T))
+    return fail(h, "loss evaluation by rows: no target corpus with T = %d on the device (sse_corpus_upload)", T);
+  const int S = c.encoding_size;
+  hipStream_t st = h->stream;
+
+  // paired batch (data.py:95-115): rows 2i, 2i + 1 carry the same source -> one source-encoder row per pair
+  bool paired = h->train_pair_dedup && B % 2 == 0;
+  for (int i = 0; i < B && paired; i += 2)
+    paired = by_rows ? src_host[i] == src_host[i + 1]
+                     : memcmp(src_host + (size_t)i * T, src_host + (size_t)(i + 1) * T, (size_t)T * sizeof(int32_t)) == 0;
+  if (paired) h->eval_paired_calls += 1;
+
+  const int chunk = std::min<int>(B, h->eval_chunk_rows);  // (even, or the whole batch)
+  const int chunk_src = paired ? chunk / 2 : chunk;
+  if (reserve(h, h->ev_ids[0], (size_t)chunk_src * T * sizeof(int32_t)) || reserve(h, h->ev_raw[0], (size_t)chunk_src * S * sizeof(float)) ||
+      reserve(h, h->ev_labels, (size_t)chunk * sizeof(float)) || reserve(h, h->ev_row, (size_t)3 * B * sizeof(float)) ||
+      reserve(h, h->ev_sums, 3 * sizeof(double)))
+    return 1;
+  if (by_rows && reserve(h, h->ev_rows[0], (size_t)chunk * sizeof(int32_t))) return 1;
+  if (!by_rows && paired && reserve(h, h->ev_stage, (size_t)chunk * T * sizeof(int32_t))) return 1;
+  if ((by_rows || table_tgt) && reserve(h, h->ev_rows[1], (size_t)chunk * sizeof(int32_t))) return 1;
+  if (!table_tgt && (reserve(h, h->ev_ids[1], (size_t)chunk * T * sizeof(int32_t)) || reserve(h, h->ev_raw[1], (size_t)chunk * S * sizeof(float))))
+    return 1;
+  int32_t *ids[2] = {(int32_t *)h->ev_ids[0].p, (int32_t *)h->ev_ids[1].p}, *rows[2] = {(int32_t *)h->ev_rows[0].p, (int32_t *)h->ev_rows[1].p};
+  float *raw[2] = {(float *)h->ev_raw[0].p, (float *)h->ev_raw[1].p};
+  float *row_loss = (float *)h->ev_row.p, *row_acc = row_loss + B, *row_cos = row_acc + B;
+  double *sums_pin = reinterpret_cast<double *>(h->pin_small + 8);
+
+  // the whole call, queued on st (host buffers are the caller's: they outlive the synchronisation below)
+  auto queue = [&](bool allow_cluster) -> int {
+    EncodeRequest rq;
+    rq.allow_cluster = allow_cluster;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+      const int nb = std::min(chunk, B - b0), ns = paired ? nb / 2 : nb, stride = paired ? 2 : 1;
+      if (by_rows) {
+        HIPCHECK(h, hipMemcpyAsync(rows[0], src_host + b0, (size_t)nb * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIPCHECK(h, launch_eval_stage_ids((const int32_t *)ts->corpus[0].p, rows[0], stride, ns, T, ts->corpus_N[0], ids[0], h->err_flag, st));
+      } else if (paired) {
+        HIPCHECK(h, hipMemcpyAsync(h->ev_stage.p, src_host + (size_t)b0 * T, (size_t)nb * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIPCHECK(h, launch_eval_stage_ids((const int32_t *)h->ev_stage.p, nullptr, stride, ns, T, 0, ids[0], h->err_flag, st));
+      } else {
+        HIPCHECK(h, hipMemcpyAsync(ids[0], src_host + (size_t)b0 * T, (size_t)nb * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+      }
+      if (encode_dev_locked(h, SSE_SIDE_SOURCE, ids[0], ns, T, 0, raw[0], st, rq)) return 1;
+      if (table_tgt) {
+        HIPCHECK(h, hipMemcpyAsync(rows[1], tgt_host + b0, (size_t)nb * sizeof(int32_t), hipMemcpyHostToDevice, st));
+      } else {
+        if (by_rows) {
+          HIPCHECK(h, hipMemcpyAsync(rows[1], tgt_host + b0, (size_t)nb * sizeof(int32_t), hipMemcpyHostToDevice, st));
+          HIPCHECK(h, launch_eval_stage_ids((const int32_t *)ts->corpus[1].p, rows[1], 1, nb, T, ts->corpus_N[1], ids[1], h->err_flag, st));
+        } else {
+          HIPCHECK(h, hipMemcpyAsync(ids[1], tgt_host + (size_t)b0 * T, (size_t)nb * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        }
+        if (encode_dev_locked(h, SSE_SIDE_TARGET, ids[1], nb, T, 0, raw[1], st, rq)) return 1;
+      }
+      HIPCHECK(h, hipMemcpyAsync(h->ev_labels.p, labels_host + b0, (size_t)nb * sizeof(float), hipMemcpyHostToDevice, st));
+      const Variable *table = table_tgt ? &h->vars[h->tgt_table] : nullptr;
+      HIPCHECK(h, launch_pair_eval(raw[0], table ? table->dev : raw[1], table ? rows[1] : nullptr, table ? table->rows : 0,
+                                   (const float *)h->ev_labels.p, row_loss + b0, row_acc + b0, row_cos + b0, h->err_flag, nb, S,
+                                   paired ? 1 : 0, st));
+    }
+    HIPCHECK(h, launch_eval_reduce(row_loss, row_acc, B, (double *)h->ev_sums.p, st));
+    HIPCHECK(h, hipMemcpyAsync(sums_pin, h->ev_sums.p, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    return 0;
+  };
+  if (queue(true)) return 1;
+  int32_t bits = 0;
+  if (check_err_flag(h, st, &bits)) return 1;  // (synchronises; an id or a row out of range: reported, flag reset, no outputs)
+  if (bits == 4) {
+    // a cluster-kernel launch gave up (a workgroup did not arrive): the call once more on the kernels that need no co-residency
+    h->persist_fallbacks += 1;
+    h->cluster_skip[0] = h->cluster_skip[1] = h->cluster_backoff >= 0 ? h->cluster_backoff : 16;
+    if (queue(false)) return 1;
+    if (check_err_flag(h, st)) return 1;
+  }
+  if (row_cos_host) {
+    HIPCHECK(h, hipMemcpyAsync(row_cos_host, row_cos, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHECK(h, sync_stream(st));
+  }
+  for (int i = 0; i < 3; ++i) sums[i] = sums_pin[i];
+  return 0;
+}
+
+int sse_eval_loss(sse_handle *h, const int32_t *src_ids_host, const int32_t *tgt_ids_host, const float *labels_host, int32_t B,
+                  int32_t T, double *sums, float *row_cos_host) {
+  if (!h) return 1;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  return eval_loss_locked(h, src_ids_host, tgt_ids_host, labels_host, B, T, false, sums, row_cos_host);
+}
+
+int sse_eval_loss_rows(sse_handle *h, const int32_t *src_rows_host, const int32_t *tgt_rows_host, const float *labels_host,
+                       int32_t B, double *sums, float *row_cos_host) {
+  if (!h) return 1;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  if (!h->train || !h->train->corpus[0].p) return fail(h, "loss evaluation by rows: no source corpus on the device (sse_corpus_upload)");
+  return eval_loss_locked(h, src_rows_host, tgt_rows_host, labels_host, B, h->train->corpus_T[0], true, sums, row_cos_host);
 }
 
 int sse_get_learning_rate(sse_handle *h, float *lr) {

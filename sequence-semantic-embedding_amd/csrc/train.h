@@ -112,3 +112,15 @@ int cnn_dx_mfma_blocks(int B);
 // out[b][0..T) = corpus[rows[b]][0..T)  (rows outside [0, N): error flag bit 1, row 0 used)
 hipError_t launch_gather_id_rows(const int32_t *corpus, const int32_t *rows, int B, int T, int64_t N, int32_t *out,
                                  int32_t *err, hipStream_t st);
+
+// forward-only pair loss (eval_loss.hip; sse_eval_loss / sse_eval_loss_rows)
+// out[b][0..T) = ids[rows ? rows[b * stride] : b * stride][0..T)  (a row number outside [0, N): error flag bit 2, row 0 read)
+hipError_t launch_eval_stage_ids(const int32_t *ids, const int32_t *rows, int stride, int B, int T, int64_t N, int32_t *out,
+                                 int32_t *err, hipStream_t st);
+// row b: loss, accuracy and cosine of (src_raw[paired ? b >> 1 : b], tgt_rows ? tgt_raw[tgt_rows[b]] : tgt_raw[b]); a target row
+// outside [0, N) raises error flag bit 1 and reads nothing out of bounds
+hipError_t launch_pair_eval(const float *src_raw, const float *tgt_raw, const int32_t *tgt_rows, int N, const float *labels,
+                            float *row_loss, float *row_acc, float *row_cos, int32_t *err, int B, int S, int paired,
+                            hipStream_t st);
+// sums[3] = {sum row_loss, sum row_acc, B} as doubles, fixed order for a given B
+hipError_t launch_eval_reduce(const float *row_loss, const float *row_acc, int64_t B, double *sums, hipStream_t st);

@@ -7,7 +7,8 @@ arena" of include/sse_hip.h), then clips by the global norm of the REDUCED gradi
 bit-identical on every rank and equals the single-process step on the concatenated batch up to fp32 summation order.
 
 The reference trains in one process (sse_train.py:170-172); this is the exchange step a multi-GPU job adds.
-The engine is anything with train_grad_count / train_bind_arena / train_grads / train_apply: the HIP handle
+The engine is anything with train_grad_count / train_bind_arena / train_grads / train_apply (and, for eval_loss,
+eval_loss_sums / eval_loss_rows_sums): the HIP handle
 (sequence-semantic-embedding_amd/_lib.py) in the product, the numpy oracle in the CPU `gloo` tests.
 torch / torch.distributed are plumbing only.  The collectives go through collectives.py: RCCL as is under `nccl`, staged
 through the host under any other backend (ranks as processes on one GPU).
@@ -91,6 +92,26 @@ class DataParallelTrainer(object):
                 all_reduce_(self.arena, group=self.group)          # ONE collective per step (sum)
                 self.last_exchange = "dense"
         return self.engine.train_apply()
+
+    def eval_loss(self, src_ids, tgt_ids, labels, by_rows=False):
+        """Forward-only GLOBAL (loss, train_acc) of held-out pairs split over the ranks (any row counts, a rank may hold none):
+        the engine's three float64 sums {row losses, row accuracies, rows} of this rank's rows, ONE all-reduce (sum), the
+        two quotients.  No update, no gradient arena.  The engine needs eval_loss_sums / eval_loss_rows_sums."""
+        import torch
+        from .collectives import all_reduce_
+        if self.arena.is_cuda and hasattr(self.engine, "set_stream"):
+            cur = torch.cuda.current_stream(self.arena.device).cuda_stream
+            if cur != self._stream:
+                self.engine.set_stream(cur)
+                self._stream = cur
+        fn = self.engine.eval_loss_rows_sums if by_rows else self.engine.eval_loss_sums
+        sums = torch.tensor([float(v) for v in fn(src_ids, tgt_ids, labels)], dtype=torch.float64, device=self.arena.device)
+        if self.world > 1 or self.always_reduce:
+            all_reduce_(sums, group=self.group)
+        tot_loss, tot_acc, rows = (float(v) for v in sums.cpu())
+        if rows == 0:
+            return 0.0, 0.0
+        return tot_loss / rows, tot_acc / rows
 
     # ---- (row id, gradient row) exchange of the embedding gradient (SURVEY 8e "Training") ----------------------------
     def _seq_len(self, src_ids, by_rows):

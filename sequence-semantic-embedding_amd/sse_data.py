@@ -174,6 +174,28 @@ class Data(object):
         labels = np.tile(np.array([1.0, 0.0], np.float32), stop - start)
         return src, tgt, labels
 
+    def get_eval_pairs(self, seed=0, target_rows=False):
+        """Held-out pairs for a forward-only loss (Handle.eval_loss): every row of rawEvalCorpus twice, with its first
+        verified target (label 1.0) and with one negative (label 0.0) that is none of the row's positives -- the layout of
+        a train batch.  Returns (src [2n,T] int32, tgt [2n,T] int32 -- or [2n] rows of the free target matrix with
+        target_rows --, labels [2n] float32).  The negatives come from a PRIVATE RandomState(seed): self.rng is not
+        touched, so the train batches of a seeded run do not depend on whether this was called."""
+        rng = np.random.RandomState(seed)
+        n = len(self.rawEvalCorpus)
+        T = self.max_seq_length
+        src = np.zeros((2 * n, T), np.int32)
+        rows = np.zeros(2 * n, np.int64)
+        for i, (tokens, verified) in enumerate(self.rawEvalCorpus):
+            positives = set(verified)
+            neg = self.fullSetTargetIds[rng.randint(0, self.rawnegSetLen)]
+            while neg in positives:
+                neg = self.fullSetTargetIds[rng.randint(0, self.rawnegSetLen)]
+            src[2 * i] = src[2 * i + 1] = tokens
+            rows[2 * i] = self.target_row(verified[0])
+            rows[2 * i + 1] = self.target_row(neg)
+        tgt = rows.astype(np.int32) if target_rows else self._corpus_arrays()[1][rows].reshape(2 * n, T)
+        return src, tgt, np.tile(np.array([1.0, 0.0], np.float32), n)
+
     def corpus_matrices(self):
         """(source corpus [n_pos, T], target corpus [N, T] in fullSetTargetIds order) int32: what sse_corpus_upload
         keeps resident on the device."""

@@ -164,6 +164,7 @@ class SSEModel(object):
         self.similarity = _Sym("similarity")
         self.loss = _Sym("loss")
         self.train_acc = _Sym("train_acc")
+        self.binarylogit = _Sym("binarylogit")       # sse_model.py:290: cos(src_b, tgt_b) per pair row (fetched without model.train)
         self.train = _Sym("train")
         self.learning_rate = _Scalar("learning_rate", lambda: self.handle.learning_rate)
         self.global_step = _Scalar("global_step", lambda: self.handle.global_step)
@@ -243,6 +244,10 @@ class SSEModel(object):
     def train_step(self, src_ids, tgt_ids, labels):
         return self.handle.train_step(src_ids, tgt_ids, labels)
 
+    def eval_loss(self, src_ids, tgt_ids, labels, return_cos=False):
+        """Loss and binary accuracy of held-out pairs, forward only (no update): see Handle.eval_loss."""
+        return self.handle.eval_loss(src_ids, tgt_ids, labels, return_cos=return_cos)
+
     def predict(self, src_ids, tgt_ids, top_n=None):
         """`_def_predict` (sse_model.py:344-352): tf.nn.top_k(similarity, TOP_N) over the batch's
         own targets, then the k scores l2-normalised per row.  Returns (scores float32 [Bs,k],
@@ -300,7 +305,8 @@ class SSEModel(object):
 class Session(object):
     """`tf.Session` stand-in: `run(fetches, feed_dict)` dispatches to the C ABI.
     One train step is executed at most once per run() however many of
-    train/loss/train_acc are fetched, like a TF graph execution."""
+    train/loss/train_acc are fetched, like a TF graph execution; loss /
+    train_acc / binarylogit without train run one forward-only evaluation."""
 
     def __init__(self, model=None):
         self.model = model
@@ -320,13 +326,18 @@ class Session(object):
             raise RuntimeError("Session has no model bound")
         names = [f.name for f in fl]
         cache = {}
-        if any(n in ("train", "loss", "train_acc") for n in names):
+        if "train" in names:
             src, tgt, lab = feed[model._src_input_data], feed[model._tgt_input_data], feed[model._labels]
-            if "train" in names:
-                cache["loss"], cache["train_acc"] = model.train_step(src, tgt, lab)
-            else:
-                raise NotImplementedError("fetching loss/train_acc without model.train is not used by the reference CLIs")
+            cache["loss"], cache["train_acc"] = model.train_step(src, tgt, lab)
             cache["train"] = None
+        elif any(n in ("loss", "train_acc", "binarylogit") for n in names):
+            # no model.train in the fetch list: ONE forward-only evaluation serves all three
+            src, tgt, lab = feed[model._src_input_data], feed[model._tgt_input_data], feed[model._labels]
+            want_cos = "binarylogit" in names
+            res = model.eval_loss(src, tgt, lab, return_cos=want_cos)
+            cache["loss"], cache["train_acc"] = res[0], res[1]
+            if want_cos:
+                cache["binarylogit"] = res[2]
         out = []
         for n in names:
             if n in cache:

@@ -40,6 +40,8 @@ FLAGS = flags.FlagSet("sse_train", [
     ("train_x3", int, 0, "LSTM modes: 0 (default) = float32 MFMA throughout, the reference's arithmetic; 1 = opt in to the forward / "
                          "BPTT / weight-gradient GEMMs of the train step on the bf16 matrix pipe with hi + lo split float32 "
                          "operands (~4e-6 relative per product, ~2x faster)"),
+    ("eval_loss", int, 0, "1: after each epoch's task evaluation, log the forward-only pair loss and binary accuracy of the held-out "
+                          "EvalPairs (each with its first verified target and one sampled negative)"),
 ])
 
 
@@ -103,6 +105,7 @@ def train(f):
     step_time, loss, train_acc = 0.0, 0.0, 0.0
     current_step, previous_accuracies, stop = 0, [], False
     checkpoint_path = os.path.join(f.model_dir, "SSE-LSTM.ckpt")
+    eval_pairs = None                  # --eval_loss: the held-out pairs, built once
     for epoch in range(f.max_epoc):
         epoc_start = time.time()
         for _ in range(int(epoc_steps)):
@@ -151,6 +154,11 @@ def train(f):
                                       idx_file, sess, batchsize=1000, row_of=data.target_row)
             acc1, acc3, acc10 = Evaluator(model, data.rawEvalCorpus, idx_file, sess).eval()
             logging.info("epoc#%d, task specific evaluation: top 1/3/10 accuracies: %f / %f / %f \n\n\n" % (epoch, acc1, acc3, acc10))
+            if f.eval_loss:
+                if eval_pairs is None:
+                    eval_pairs = data.get_eval_pairs(seed=0, target_rows=table_tgt)
+                held_loss, held_acc = model.handle.eval_loss(*eval_pairs)
+                logging.info("held-out pair loss: %f, binary acc: %f (%d pairs)" % (held_loss, held_acc, len(eval_pairs[2])))
         model.save(sess, checkpoint_path + "-epoch-%d" % epoch)
         if previous_accuracies:
             logging.info("So far best ever model training binary accuracy is: %.4f " % max(previous_accuracies))
