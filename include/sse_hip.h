@@ -169,7 +169,8 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value);
  * "lstm_fwd_gate_split" (the gate-split kernel for small cells; the others ran the unit-block kernel), "lstm_fwd_x_table"
  * (gate accumulators from the x-projection table; the others gathered embedding rows).  The pad-prefix table builds a
  * kernel does for itself are not counted.
- * "eval_paired_calls": sse_eval_loss* calls that ran the source encoder once per pair of rows (option train_pair_dedup). */
+ * "eval_paired_calls": sse_eval_loss* calls that ran the source encoder once per pair of rows (option train_pair_dedup).
+ * "score_rank_band_rows" / "score_rank_bruteforce_pairs": see sse_score_rank. */
 int sse_get_counter(sse_handle *h, const char *name, int64_t *value);
 
 /* tf.nn.l2_normalize(x, dim=-1) on device rows (sse_model.py:282-283). */
@@ -195,6 +196,30 @@ int sse_score_topk(sse_handle *h, const float *q_host, int32_t Q, int32_t k, dou
                    int64_t *out_ids);
 int sse_score_topk_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, double *out_scores_dev,
                        int64_t *out_ids_dev, void *stream);
+
+/* Exact rank of labelled targets over the WHOLE index: where row g lands in sse_score_topk(..., k = N) without forming that
+ * list.  Replaces a full getSortedResults row searched for the label (data_utils.py:263-267: np.argsort of all N scores
+ * per query, of which sse_evaluator.py:95,112 then reads 10 columns): what mean reciprocal rank, mean / median rank and
+ * recall at any k need.  Pairs are the unit of work: pair p is query row pair_q[p] (in [0, Q)) and a threshold (score,
+ * pair_id[p]); out_before[p] = the number of rows r of the resident index with score64(q, r) > score, or == score and
+ * id_base + r < pair_id[p] -- the order sse_score_topk ranks by, score64 being the float64 dot product it returns.
+ *   pair_score_in == NULL: every pair_id[p] must be a row of this index (id_base <= id < id_base + N); the score is
+ *     score64(q, that row), bit-identical to what sse_score_topk returns for it, and out_before[p] is the row's 0-based
+ *     rank.  out_score (may be NULL) receives the scores.
+ *   pair_score_in != NULL: the thresholds are (pair_score_in[p], pair_id[p]), the id any int64 -- what a row shard counts
+ *     for a label that lives in another shard.  Counts of shards add: the global rank is their sum.
+ * The counts come from one fp32 MFMA sweep per 4096 pairs (compare-and-count, no lists); only rows whose fp32 score lies
+ * within the certified bound of the threshold are re-scored in float64 (counter "score_rank_band_rows"); a pair with more
+ * than 4096 such rows is counted by a float64 sweep (counter "score_rank_bruteforce_pairs").  Results are exact either way.
+ * Rows or queries of norm below 2^-100 and non-finite input are outside the claim (no fault).
+ * A pair_q out of [0, Q), an id out of range in the first form, or no index: error with a message, no output written, the
+ * handle stays usable.  L == 0 succeeds.  The host form runs on the null stream and synchronises; the _dev form takes
+ * device pointers, enqueues on `stream`, and reports a bad pair through sse_synchronize (like sse_encode_dev). */
+int sse_score_rank(sse_handle *h, const float *q_host, int32_t Q, const int32_t *pair_q, const int64_t *pair_id, int64_t L,
+                   const double *pair_score_in, int64_t *out_before, double *out_score);
+int sse_score_rank_dev(sse_handle *h, const float *q_dev, int32_t Q, const int32_t *pair_q_dev, const int64_t *pair_id_dev,
+                       int64_t L, const double *pair_score_in_dev, int64_t *out_before_dev, double *out_score_dev,
+                       void *stream);
 
 /* encode + score in one call, the encodings never leaving the device: session.run([src_seq_embedding | norm_...])
  * followed by np.dot + getSortedResults[:k] as sse_demo.py:121-129, webserver.py:144-151 (and the three other routes)

@@ -47,6 +47,8 @@ SYMBOLS = {
     "sse_index_set_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, _P]),
     "sse_score_topk": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     "sse_score_topk_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    "sse_score_rank": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P]),
+    "sse_score_rank_dev": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P]),
     "sse_encode_score_topk": (C.c_int, [_P, C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_merge_topk_dev": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_merge_topk_strided_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
@@ -277,6 +279,37 @@ class Handle(object):
 
     def score_topk_dev(self, q_ptr, Q, k, scores_ptr, ids_ptr, stream=0):
         self.check(self.lib.sse_score_topk_dev(self._h, q_ptr, Q, k, scores_ptr, ids_ptr, stream))
+
+    def score_rank(self, queries, pair_q, pair_id, pair_score=None):
+        """Exact rank over the whole resident index: for pair p (query row pair_q[p], row id pair_id[p]) the number of
+        rows ranked before it in score_topk's order.  pair_score=None: pair_id are rows of this index, the result is
+        their 0-based rank and their float64 score.  pair_score given: rows before the threshold (pair_score[p],
+        pair_id[p]), any id -- what a shard counts for a label of another shard.  Returns (before int64 [L], score
+        float64 [L]); the output arrays are handed back untouched (zeros) only on success -- an error raises."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError("queries must be [Q,S]")
+        pq = np.ascontiguousarray(pair_q, dtype=np.int32).reshape(-1)
+        pid = np.ascontiguousarray(pair_id, dtype=np.int64).reshape(-1)
+        if pq.shape != pid.shape:
+            raise ValueError("pair_q and pair_id must both be [L]")
+        L = pq.shape[0]
+        ps = None
+        if pair_score is not None:
+            ps = np.ascontiguousarray(pair_score, dtype=np.float64).reshape(-1)
+            if ps.shape != pq.shape:
+                raise ValueError("pair_score must be [L]")
+        before = np.zeros(L, np.int64)
+        score = np.zeros(L, np.float64) if ps is None else ps.copy()
+        self.check(self.lib.sse_score_rank(self._h, _ptr(q), q.shape[0], _ptr(pq), _ptr(pid), L,
+                                           _ptr(ps) if ps is not None else None, _ptr(before), _ptr(score)))
+        return before, score
+
+    def score_rank_dev(self, q_ptr, Q, pair_q_ptr, pair_id_ptr, L, pair_score_ptr, before_ptr, score_ptr, stream=0):
+        """score_rank on device pointers (pair_score_ptr / score_ptr may be None / 0), enqueued on `stream`; a bad pair
+        is reported by synchronize()."""
+        self.check(self.lib.sse_score_rank_dev(self._h, q_ptr, Q, pair_q_ptr, pair_id_ptr, int(L), pair_score_ptr or None,
+                                               before_ptr, score_ptr or None, stream))
 
     def merge_topk_strided_dev(self, in_s, in_i, shard_stride, P, Q, k, out_s, out_i, stream=0):
         self.check(self.lib.sse_merge_topk_strided_dev(self._h, in_s, in_i, int(shard_stride), P, Q, k, out_s, out_i, stream))

@@ -226,6 +226,11 @@ struct sse_handle {
   size_t pin_cap = 0;
   int32_t score_seq = 0;  // call number the re-scoring pass stores into the pinned completion flags (ScoreMirror)
   DevBuf s_pb, s_cthr, s_cslot, s_ccnt, s_cbuf;  // per-split bounds; collect path: thresholds, slots, counters, row buffers
+  // exact rank of labelled rows (sse_score_rank*, score_rank.hip): per-pair scratch of a chunk (thresholds, fp32 intervals, sure
+  // counts, the call's "bad pair" word), the two counters "score_rank_band_rows" / "score_rank_bruteforce_pairs" on the
+  // device, staging of the host form.  The band buffers are the collect path's (s_ccnt, s_cbuf).
+  DevBuf s_rk, s_rk_cnt, s_rk_in;
+  bool rk_cnt_init = false;
   // forward-only pair loss (sse_eval_loss*, eval_loss.hip).  Option "eval_chunk_rows": pair rows staged and encoded per chunk (even).
   // Scratch of its own: a gradient result pending between sse_train_grads and sse_train_apply lives in TrainState and the arena.
   int eval_chunk_rows = 65536;
@@ -987,6 +992,8 @@ int check_err_flag(sse_handle *h, hipStream_t st, int32_t *bits = nullptr) {
     if (flag & 2) return fail(h, "corpus row out of range in a train step by rows");
     if (flag & 8) return fail(h, "data-parallel embedding-gradient exchange: more touched rows than the packed buffer holds, or a row id "
                                  "out of range in a gathered buffer (sse_train_pack_embedding_grad / sse_train_unpack_embedding_grad)");
+    if (flag & 16) return fail(h, "sse_score_rank_dev: a pair_q out of [0, Q) or, without pair scores, a pair_id that is not a row of "
+                                  "this index; the call wrote no output");
     if (flag & 4) return fail(h, "LSTM cluster kernel: a workgroup of a cluster did not arrive (device oversubscribed?); the "
                                  "host-buffer entry points fall back to the few-sequences kernel by themselves, for "
                                  "sse_encode_dev set option lstm_persist_rows to 0");
@@ -1164,6 +1171,70 @@ static int score_select_locked(sse_handle *h, const float *q, int Q, int k, doub
     // whatever overflowed its buffer: float64 brute force (pages of 16)
     HIPCHECK(h, launch_exact_topk(qc, h->idxp, h->idx64, (const int32_t *)h->s_cert.p, out_s + (size_t)q0 * k,
                                   out_i + (size_t)q0 * k, h->idx_base, h->idx_N, Qc, S, k, st, counters + 2));
+  }
+  return 0;
+}
+
+// sse_score_rank*: every stage of the call queued on `st` (device pointers throughout).  Pairs go in chunks of RANK_POOL: a
+// chunk's pairs are the columns of one count sweep (a pair = one query row of the sweep, so a query with several labels is
+// staged once per label) and own one band buffer each.  Validation runs over ALL pairs first: one bad pair and no kernel of
+// the call writes anything (the flag reaches the host through the device error word, bit 16).
+static int score_rank_dev_locked(sse_handle *h, const float *q, int Q, const int32_t *pair_q, const int64_t *pair_id, int64_t L,
+                                 const double *pair_score_in, int64_t *out_before, double *out_score, hipStream_t st) {
+  if (!h->idxp) return fail(h, "no index uploaded");
+  if (Q < 0 || L < 0) return fail(h, "bad arguments to sse_score_rank");
+  if (L == 0) return 0;
+  if (!q || !pair_q || !pair_id || !out_before || Q == 0) return fail(h, "bad arguments to sse_score_rank");
+  const int RANK_POOL = 4096;
+  const int S = h->idx_S, KG = (S + 7) / 8;
+  const int64_t NT = (h->idx_N + 31) / 32;
+  const int Pmax = (int)std::min<int64_t>(L, RANK_POOL);
+  // per-pair scratch: thr64 [Pmax] | sure [Pmax] | lo [Pmax] | hi [Pmax] | bad
+  if (reserve(h, h->s_rk, (size_t)Pmax * 24 + 16)) return 1;
+  if (reserve(h, h->s_ccnt, (size_t)(Pmax + 1) * sizeof(int32_t))) return 1;
+  if (reserve(h, h->s_cbuf, (size_t)Pmax * SSE_COLLECT_CAP * sizeof(int32_t))) return 1;
+  if (reserve(h, h->s_rk_cnt, 2 * sizeof(unsigned long long))) return 1;
+  if (!h->rk_cnt_init) {
+    HIPCHECK(h, hipMemsetAsync(h->s_rk_cnt.p, 0, 2 * sizeof(unsigned long long), st));
+    h->rk_cnt_init = true;
+  }
+  char *base = (char *)h->s_rk.p;
+  int32_t *bad = (int32_t *)(base + (size_t)Pmax * 24);
+  HIPCHECK(h, hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+  HIPCHECK(h, launch_rank_validate(pair_q, pair_id, L, Q, pair_score_in ? 0 : 1, h->idx_base, h->idx_N, bad, h->err_flag, st));
+  RankArgs a;
+  a.q = q;
+  a.idxp = h->idxp;
+  a.idx64 = h->idx64;
+  a.thr64 = (double *)base;
+  a.sure = (unsigned long long *)(base + (size_t)Pmax * 8);
+  a.lo = (float *)(base + (size_t)Pmax * 16);
+  a.hi = (float *)(base + (size_t)Pmax * 20);
+  a.band_cnt = (int32_t *)h->s_ccnt.p;
+  a.band_buf = (int32_t *)h->s_cbuf.p;
+  a.band_cap = SSE_COLLECT_CAP;
+  a.bad = bad;
+  a.counters = (unsigned long long *)h->s_rk_cnt.p;
+  a.id_base = h->idx_base;
+  a.N = h->idx_N;
+  a.S = S;
+  a.KG = KG;
+  a.NT = (int)NT;
+  a.eps32 = (float)(2.0 * (S + 2) * 5.97e-8 * h->idx_norm_max);
+  for (int64_t p0 = 0; p0 < L; p0 += RANK_POOL) {
+    const int P = (int)std::min<int64_t>(RANK_POOL, L - p0);
+    const int NQ = score_pick_nq(P, S, 0);
+    if (NQ == 0) return fail(h, "index dimension %d does not fit the scoring kernel's LDS query block", S);
+    const int QB = (P + NQ * 32 - 1) / (NQ * 32);
+    a.pair_q = pair_q + p0;
+    a.pair_id = pair_id + p0;
+    a.pair_score_in = pair_score_in ? pair_score_in + p0 : nullptr;
+    a.out_before = out_before + p0;
+    a.out_score = out_score ? out_score + p0 : nullptr;
+    a.P = P;
+    a.NQ = NQ;
+    a.NSPLIT = choose_nsplit(NQ, QB, NT);
+    HIPCHECK(h, launch_score_rank(a, st));
   }
   return 0;
 }
@@ -1929,6 +2000,18 @@ int sse_get_counter(sse_handle *h, const char *name, int64_t *value) {
     *value = (int64_t)lstm_coop_refused();
     return 0;
   }
+  static const char *const rank_names[2] = {"score_rank_band_rows", "score_rank_bruteforce_pairs"};
+  for (int i = 0; i < 2; ++i) {  // sse_score_rank*: rows that needed float64, pairs whose band outgrew its buffer
+    if (strcmp(name, rank_names[i]) != 0) continue;
+    unsigned long long v[2] = {0, 0};
+    if (h->s_rk_cnt.p && h->rk_cnt_init) {
+      HIPCHECK(h, hipSetDevice(h->cfg.device));
+      HIPCHECK(h, hipDeviceSynchronize());
+      HIPCHECK(h, hipMemcpy(v, h->s_rk_cnt.p, sizeof v, hipMemcpyDeviceToHost));
+    }
+    *value = (int64_t)v[i];
+    return 0;
+  }
   static const char *const names[3] = {"score_bf16_second_chance_queries", "score_collect_queries", "score_bruteforce_queries"};
   for (int i = 0; i < 3; ++i) {
     if (strcmp(name, names[i]) != 0) continue;
@@ -2159,6 +2242,52 @@ int sse_score_topk(sse_handle *h, const float *q_host, int32_t Q, int32_t k, dou
   if (reserve(h, h->s_q, (size_t)Q * S * sizeof(float))) return 1;
   HIPCHECK(h, hipMemcpy(h->s_q.p, q_host, (size_t)Q * S * sizeof(float), hipMemcpyHostToDevice));
   return score_to_host_locked(h, (const float *)h->s_q.p, Q, k, out_scores, out_ids);
+}
+
+int sse_score_rank_dev(sse_handle *h, const float *q_dev, int32_t Q, const int32_t *pair_q_dev, const int64_t *pair_id_dev, int64_t L,
+                       const double *pair_score_in_dev, int64_t *out_before_dev, double *out_score_dev, void *stream) {
+  if (!h) return 1;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  return score_rank_dev_locked(h, q_dev, Q, pair_q_dev, pair_id_dev, L, pair_score_in_dev, out_before_dev, out_score_dev,
+                               (hipStream_t)stream);
+}
+
+int sse_score_rank(sse_handle *h, const float *q_host, int32_t Q, const int32_t *pair_q, const int64_t *pair_id, int64_t L,
+                   const double *pair_score_in, int64_t *out_before, double *out_score) {
+  if (!h) return 1;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  if (!h->idxp) return fail(h, "no index uploaded");
+  if (Q < 0 || L < 0) return fail(h, "bad arguments to sse_score_rank");
+  if (L == 0) return 0;
+  if (!q_host || !pair_q || !pair_id || !out_before || Q == 0) return fail(h, "bad arguments to sse_score_rank");
+  // the host has the pairs: checked here, with the offending pair in the message, before anything is queued
+  for (int64_t p = 0; p < L; ++p) {
+    if (pair_q[p] < 0 || pair_q[p] >= Q) return fail(h, "sse_score_rank: pair_q[%lld] = %d is not in [0, Q = %d)", (long long)p, pair_q[p], Q);
+    if (!pair_score_in && (pair_id[p] < h->idx_base || pair_id[p] >= h->idx_base + h->idx_N))
+      return fail(h, "sse_score_rank: pair_id[%lld] = %lld is not a row of this index [%lld, %lld)", (long long)p, (long long)pair_id[p],
+                  (long long)h->idx_base, (long long)(h->idx_base + h->idx_N));
+  }
+  const size_t S = h->idx_S;
+  // staging: queries | pair_id | pair_score_in | out_score | out_before | pair_q (8-byte items first)
+  const size_t qb = ((size_t)Q * S * sizeof(float) + 7) & ~(size_t)7, l8 = (size_t)L * 8, l4 = (size_t)L * 4;
+  if (reserve(h, h->s_rk_in, qb + 4 * l8 + l4)) return 1;
+  char *b = (char *)h->s_rk_in.p;
+  float *d_q = (float *)b;
+  int64_t *d_id = (int64_t *)(b + qb);
+  double *d_in = (double *)(b + qb + l8), *d_sc = (double *)(b + qb + 2 * l8);
+  int64_t *d_bf = (int64_t *)(b + qb + 3 * l8);
+  int32_t *d_pq = (int32_t *)(b + qb + 4 * l8);
+  HIPCHECK(h, hipMemcpy(d_q, q_host, (size_t)Q * S * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHECK(h, hipMemcpy(d_id, pair_id, l8, hipMemcpyHostToDevice));
+  HIPCHECK(h, hipMemcpy(d_pq, pair_q, l4, hipMemcpyHostToDevice));
+  if (pair_score_in) HIPCHECK(h, hipMemcpy(d_in, pair_score_in, l8, hipMemcpyHostToDevice));
+  if (score_rank_dev_locked(h, d_q, Q, d_pq, d_id, L, pair_score_in ? d_in : nullptr, d_bf, d_sc, nullptr)) return 1;
+  if (check_err_flag(h, nullptr)) return 1;
+  HIPCHECK(h, hipMemcpy(out_before, d_bf, l8, hipMemcpyDeviceToHost));
+  if (out_score) HIPCHECK(h, hipMemcpy(out_score, d_sc, l8, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 int sse_merge_topk_strided_dev(sse_handle *h, const double *in_scores_dev, const int64_t *in_ids_dev, int64_t shard_stride,

@@ -413,6 +413,34 @@ struct SmallIndexArgs {
 bool score_small_index_applies(int Q, int KG, int64_t NT);
 hipError_t launch_score_small_index(const SmallIndexArgs &a, hipStream_t stream);
 
+// Exact rank of labelled rows (score_rank.hip): for every pair p of a chunk (query pair_q[p], threshold (score, pair_id[p])) the
+// number of index rows r with before(score64(q, r), id_base + r, score, pair_id[p]).  pair_score_in == nullptr: the score is
+// score64(q, row pair_id[p] - id_base), formed with wave_exact_dot.  Scratch per pair: thr64 / lo / hi / sure / band_cnt
+// [P], band_buf [P][band_cap] (the collect buffers).  *bad != 0 (launch_rank_validate): every kernel leaves at once.
+struct RankArgs {
+  const float *q;               // [Q][S] f32 row-major queries
+  const int32_t *pair_q;        // [P]
+  const int64_t *pair_id;       // [P]
+  const double *pair_score_in;  // [P] or nullptr
+  const float *idxp;            // frag32 index [NT][KG][256]
+  const double *idx64;          // [N][S] f64 rows or nullptr
+  int64_t *out_before;          // [P]
+  double *out_score;            // [P] or nullptr
+  double *thr64;                // [P] threshold scores
+  float *lo, *hi;               // [P] fp32 interval the bound cannot decide
+  unsigned long long *sure;     // [P] rows with fp32 score > hi
+  int32_t *band_cnt, *band_buf;
+  int32_t band_cap;
+  const int32_t *bad;
+  unsigned long long *counters;  // [0] band rows re-scored in float64, [1] pairs counted by the float64 sweep
+  int64_t id_base, N;
+  int32_t S, KG, NT, P, NSPLIT, NQ;
+  float eps32;
+};
+hipError_t launch_rank_validate(const int32_t *pair_q, const int64_t *pair_id, int64_t L, int Q, int need_row, int64_t id_base,
+                                int64_t N, int32_t *bad, int32_t *err_flag, hipStream_t st);
+hipError_t launch_score_rank(const RankArgs &a, hipStream_t st);
+
 // uncertified queries (cert[q] == 0) get collect-buffer slots 0, 1, ... (col_slot[q]; -1 when certified or the pool
 // of `slots` is exhausted); *counter must be zero on entry
 hipError_t launch_assign_slots(const int32_t *cert, int Q, int slots, int32_t *col_slot, int32_t *counter, hipStream_t st);

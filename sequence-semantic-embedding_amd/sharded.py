@@ -123,6 +123,57 @@ class ShardedIndex(object):
         return fs, fi
 
 
+    def rank_of(self, queries, pair_q, pair_id):
+        """Exact global rank of labelled rows: queries CUDA float32 [Q,S], pair_q int32 [L] (query row of pair p), pair_id
+        int64 [L] (GLOBAL row id of its label), identical on every rank.  Returns the int64 [L] ranks -- the position of row
+        pair_id[p] in score_topk(queries, n_total)[pair_q[p]] -- on every rank.  No lists travel: (1) every rank scores and
+        counts the pairs whose row it holds (Handle.score_rank_dev), (2) ONE all-gather hands every rank every pair's
+        float64 score (a rank cannot score a row it does not hold), (3) every rank counts, for the pairs it does not own,
+        the rows of its shard ranked before the threshold (score, id), (4) ONE all-reduce adds the counts.  An empty shard
+        owns no pair and counts nothing.  Bad input raises ValueError on every rank alike, before any collective."""
+        import torch
+        import torch.distributed as dist
+        from .collectives import all_gather_into, all_reduce_
+        dev = queries.device
+        Q, L = int(queries.shape[0]), int(pair_q.shape[0])
+        if pair_id.shape[0] != L or pair_q.dtype != torch.int32 or pair_id.dtype != torch.int64:
+            raise ValueError("pair_q int32 [L] and pair_id int64 [L] are required")
+        out = torch.zeros(L, dtype=torch.int64, device=dev)
+        if L == 0:
+            return out
+        if bool(((pair_q < 0) | (pair_q >= Q) | (pair_id < 0) | (pair_id >= self.n_total)).any().item()):
+            raise ValueError("pair_q must be in [0, Q=%d) and pair_id in [0, n_total=%d)" % (Q, self.n_total))
+        stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
+        queries, pair_q, pair_id = queries.contiguous(), pair_q.contiguous(), pair_id.contiguous()
+        have_rows = self.end > self.start
+        if self.world == 1 and not self.always_gather:
+            self.handle.score_rank_dev(queries.data_ptr(), Q, pair_q.data_ptr(), pair_id.data_ptr(), L, None, out.data_ptr(), None, stream)
+            return out
+        world = dist.get_world_size(self.group)
+        mine = (pair_id >= self.start) & (pair_id < self.end)
+        own, other = torch.nonzero(mine).reshape(-1), torch.nonzero(~mine).reshape(-1)
+        score = torch.zeros(L, dtype=torch.float64, device=dev)
+        if own.numel() > 0:                                               # (1) owned pairs: scores + local ranks
+            pq, pi = pair_q[own].contiguous(), pair_id[own].contiguous()
+            b = torch.empty(own.numel(), dtype=torch.int64, device=dev)
+            sc = torch.empty(own.numel(), dtype=torch.float64, device=dev)
+            self.handle.score_rank_dev(queries.data_ptr(), Q, pq.data_ptr(), pi.data_ptr(), own.numel(), None, b.data_ptr(), sc.data_ptr(), stream)
+            out[own] = b
+            score[own] = sc
+        gathered = torch.empty(world * L, dtype=torch.float64, device=dev)    # (2) concatenation along dim 0, as the lists travel
+        all_gather_into(gathered, score, group=self.group)
+        bounds = torch.tensor([e for _, e in shard_bounds(self.n_total, world)], dtype=torch.int64, device=dev)
+        owner = torch.bucketize(pair_id, bounds, right=True)              # rank whose [start, end) holds the id
+        score = gathered.view(world, L).gather(0, owner.view(1, L)).view(L)
+        if have_rows and other.numel() > 0:                               # (3) the other ranks' pairs: thresholds
+            pq, pi, ps = pair_q[other].contiguous(), pair_id[other].contiguous(), score[other].contiguous()
+            b = torch.empty(other.numel(), dtype=torch.int64, device=dev)
+            self.handle.score_rank_dev(queries.data_ptr(), Q, pq.data_ptr(), pi.data_ptr(), other.numel(), ps.data_ptr(), b.data_ptr(), None, stream)
+            out[other] = b
+        all_reduce_(out, group=self.group)                                # (4)
+        return out
+
+
 class RcclShardedIndex(object):
     """The same sharded index WITHOUT torch.distributed: the exchange is the library's own entry point
     (sse_score_topk_sharded_dev: shard sweep -> ONE ncclAllGather of the packed lists -> k-way merge, all on one stream)

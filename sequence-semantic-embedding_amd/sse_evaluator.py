@@ -48,6 +48,26 @@ def topk_accuracy(topk, labels, ranked_idx):
     return hit / float(ranked_idx.shape[0])
 
 
+def rank_metrics_from_ranks(ranks, top_n=(1, 3, 10), batch=600):
+    """Ranking metrics from the exact 0-based ranks of every source's labels (a list of int arrays, label order):
+    mrr = mean over sources of 1 / (1 + best rank among its labels); mean_rank / median_rank of 1 + best rank;
+    tight_acc[i] = share of a source's labels with rank < top_n[i], averaged per batch of `batch` sources, the batch means
+    averaged UNWEIGHTED -- the arithmetic of topk_tight_accuracy + Evaluator.eval, so the values are equal to eval()'s."""
+    best = np.array([int(min(r)) for r in ranks], dtype=np.int64)
+    tight = []
+    for n in top_n:
+        accs = []
+        for b0 in range(0, len(ranks), batch):
+            rows = ranks[b0:b0 + batch]
+            total = 0.0
+            for r in rows:
+                total += sum(1.0 for v in r if v < n) / len(r)
+            accs.append(total / float(len(rows)))
+        tight.append(np.mean(accs))
+    return {"mrr": float(np.mean(1.0 / (1.0 + best))), "mean_rank": float(np.mean(1.0 + best)),
+            "median_rank": float(np.median(1.0 + best)), "tight_acc": tight}
+
+
 class Evaluator(object):
     def __init__(self, model, eval_corpus, tgtIndexFile, session):
         self.model = model
@@ -79,6 +99,33 @@ class Evaluator(object):
             _, idx = h.encode_score_topk(0, ids, True, k)
             out.extend(idx[b0:b0 + batch] for b0 in range(0, len(ids), batch))
         return out
+
+    def ranks(self, batch=600):
+        """Exact 0-based rank of every eval source's labels over the WHOLE index (label order; int64 arrays): the position
+        each label has in the full getSortedResults row (data_utils.py:263-267) that the reference never looks past column
+        10 of.  Sources are encoded as ranked() encodes them (same chunks, same bits); the count runs on the device
+        (Handle.score_rank), nothing of size Q x N is formed."""
+        h = self.model.handle
+        if h.index_gen != self._index_gen:      # as in ranked()
+            h.index_upload(self.targetEncodings)
+            self._index_gen = h.index_gen
+        chunk = max(batch, 32768 // batch * batch)
+        out = []
+        for c0 in range(0, len(self.srcSeq_batch), chunk):
+            ids = np.array(self.srcSeq_batch[c0:c0 + chunk], dtype=np.int32)
+            labels = self.eval_Labels[c0:c0 + chunk]
+            counts = np.array([len(l) for l in labels], dtype=np.int64)
+            pair_q = np.repeat(np.arange(len(ids), dtype=np.int32), counts)
+            pair_id = np.array([t for l in labels for t in l], dtype=np.int64)
+            before, _ = h.score_rank(h.encode(0, ids, True), pair_q, pair_id)
+            out.extend(np.split(before, np.cumsum(counts)[:-1]))
+        return out
+
+    def rank_metrics(self, top_n=(1, 3, 10), batch=600):
+        """{mrr, mean_rank, median_rank, tight_acc} over the evaluation corpus (rank_metrics_from_ranks); tight_acc equals
+        eval(top_n) exactly, the other three do not saturate when the label falls out of the top 10."""
+        self.model.set_forward_only(True)
+        return rank_metrics_from_ranks(self.ranks(batch), top_n, batch)
 
     def eval(self, top_n=(1, 3, 10), batch=600):
         self.model.set_forward_only(True)

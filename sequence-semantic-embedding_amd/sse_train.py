@@ -42,6 +42,8 @@ FLAGS = flags.FlagSet("sse_train", [
                          "operands (~4e-6 relative per product, ~2x faster)"),
     ("eval_loss", int, 0, "1: after each epoch's task evaluation, log the forward-only pair loss and binary accuracy of the held-out "
                           "EvalPairs (each with its first verified target and one sampled negative)"),
+    ("eval_ranks", int, 0, "1: after each epoch's task evaluation, log the mean reciprocal rank and the mean / median rank of the "
+                           "best-ranked verified target of every evaluation source over the whole index"),
 ])
 
 
@@ -152,8 +154,13 @@ def train(f):
             idx_file = os.path.join(f.model_dir, f.encodedIndexFile)
             sse_index.createIndexFile(model, data.encoder, os.path.join(f.model_dir, f.rawfilename), f.max_seq_length,
                                       idx_file, sess, batchsize=1000, row_of=data.target_row)
-            acc1, acc3, acc10 = Evaluator(model, data.rawEvalCorpus, idx_file, sess).eval()
+            evaluator = Evaluator(model, data.rawEvalCorpus, idx_file, sess)
+            acc1, acc3, acc10 = evaluator.eval()
             logging.info("epoc#%d, task specific evaluation: top 1/3/10 accuracies: %f / %f / %f \n\n\n" % (epoch, acc1, acc3, acc10))
+            if f.eval_ranks:
+                rm = evaluator.rank_metrics()
+                logging.info("label ranks over the whole index: MRR %f, mean rank %f, median rank %f (%d sources)"
+                             % (rm["mrr"], rm["mean_rank"], rm["median_rank"], len(evaluator.eval_Labels)))
             if f.eval_loss:
                 if eval_pairs is None:
                     eval_pairs = data.get_eval_pairs(seed=0, target_rows=table_tgt)
