@@ -170,7 +170,8 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value);
  * (gate accumulators from the x-projection table; the others gathered embedding rows).  The pad-prefix table builds a
  * kernel does for itself are not counted.
  * "eval_paired_calls": sse_eval_loss* calls that ran the source encoder once per pair of rows (option train_pair_dedup).
- * "score_rank_band_rows" / "score_rank_bruteforce_pairs": see sse_score_rank. */
+ * "score_rank_band_rows" / "score_rank_bruteforce_pairs": see sse_score_rank.
+ * "score_above_band_rows" / "score_above_bruteforce_pairs" / "score_above_long_segments": see sse_score_above. */
 int sse_get_counter(sse_handle *h, const char *name, int64_t *value);
 
 /* tf.nn.l2_normalize(x, dim=-1) on device rows (sse_model.py:282-283). */
@@ -220,6 +221,37 @@ int sse_score_rank(sse_handle *h, const float *q_host, int32_t Q, const int32_t 
 int sse_score_rank_dev(sse_handle *h, const float *q_dev, int32_t Q, const int32_t *pair_q_dev, const int64_t *pair_id_dev,
                        int64_t L, const double *pair_score_in_dev, int64_t *out_before_dev, double *out_score_dev,
                        void *stream);
+
+/* All rows of the resident index that score at least a threshold: per-query result lengths instead of one global k.
+ * Replaces a full getSortedResults row cut at a confidence (sse_evaluator.py:110-112 ranks every target and keeps nbest,
+ * data_utils.py:263-267 sorts all N float64 scores per query): an answer set with a cut-off instead of nbest, all positives
+ * of a query, a near-duplicate self-join, the predicted-positive set behind precision and recall at a threshold.
+ * Pairs are the unit of work, as in sse_score_rank: pair p is query row pair_q[p] (in [0, Q)) and threshold pair_thr[p]; one
+ * query may carry several thresholds.  Row r matches pair p iff score64(q, r) >= pair_thr[p], score64 being the float64 dot
+ * product sse_score_topk returns for that row, bit for bit; the comparison is IEEE (+inf and NaN match nothing, -inf every row).
+ *   out_offsets [L + 1] is always written: out_offsets[0] = 0, out_offsets[p + 1] - out_offsets[p] = the exact match count
+ *     of pair p (= sse_score_rank with pair_score_in = pair_thr and pair_id = INT64_MAX).
+ *   out_ids / out_scores (both or neither, `cap` entries each) are written iff they are given and out_offsets[L] <= cap:
+ *     segment [out_offsets[p], out_offsets[p + 1]) holds id_base + r and score64 of pair p's rows, score descending, equal
+ *     scores by ascending id -- exactly the first count[p] columns of sse_score_topk(..., k = N) for that query.  When the
+ *     total exceeds cap, or the lists are NULL (count-only, cap ignored), the lists are left untouched and the call still
+ *     succeeds: read out_offsets[L] and come back with enough room.
+ * Counts of row shards add; their lists concatenate and merge in the same order (ids are global through id_base).
+ * One fp32 MFMA sweep per 4096 pairs counts (rows within the certified bound of the threshold are decided in float64: counter
+ * "score_above_band_rows"; a pair with more than 4096 such rows is counted and listed by a float64 sweep: counter
+ * "score_above_bruteforce_pairs"; both counters rise once per call, in its counting pass), a scan of the counts gives the offsets, the same sweep again appends the rows, and the
+ * segments are scored in float64 and sorted (more than 8192 entries: merged through global memory, counter
+ * "score_above_long_segments").  Scratch is O(L + cap), never Q x N.  Results are exact and deterministic.
+ * Rows or queries of norm below 2^-100 and non-finite input are outside the claim (no fault).
+ * A pair_q out of [0, Q) or no index: error with a message, no output written, the handle stays usable.  L == 0 succeeds
+ * and writes out_offsets[0] = 0.  The host form runs on the null stream and synchronises; the _dev form takes device
+ * pointers, enqueues on `stream`, never waits for the device (whether the total fits cap is decided there), and reports a
+ * bad pair through sse_synchronize (like sse_score_rank_dev). */
+int sse_score_above(sse_handle *h, const float *q_host, int32_t Q, const int32_t *pair_q, const double *pair_thr, int64_t L,
+                    int64_t cap, int64_t *out_offsets, int64_t *out_ids, double *out_scores);
+int sse_score_above_dev(sse_handle *h, const float *q_dev, int32_t Q, const int32_t *pair_q_dev, const double *pair_thr_dev,
+                        int64_t L, int64_t cap, int64_t *out_offsets_dev, int64_t *out_ids_dev, double *out_scores_dev,
+                        void *stream);
 
 /* encode + score in one call, the encodings never leaving the device: session.run([src_seq_embedding | norm_...])
  * followed by np.dot + getSortedResults[:k] as sse_demo.py:121-129, webserver.py:144-151 (and the three other routes)

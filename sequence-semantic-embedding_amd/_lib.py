@@ -49,6 +49,8 @@ SYMBOLS = {
     "sse_score_topk_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_score_rank": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P]),
     "sse_score_rank_dev": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "sse_score_above": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P, _P, _P]),
+    "sse_score_above_dev": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
     "sse_encode_score_topk": (C.c_int, [_P, C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_merge_topk_dev": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_merge_topk_strided_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
@@ -310,6 +312,53 @@ class Handle(object):
         is reported by synchronize()."""
         self.check(self.lib.sse_score_rank_dev(self._h, q_ptr, Q, pair_q_ptr, pair_id_ptr, int(L), pair_score_ptr or None,
                                                before_ptr, score_ptr or None, stream))
+
+    def _above_args(self, queries, thr, pair_q):
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError("queries must be [Q,S]")
+        t = np.ascontiguousarray(thr, dtype=np.float64).reshape(-1)
+        pq = np.arange(q.shape[0], dtype=np.int32) if pair_q is None else np.ascontiguousarray(pair_q, dtype=np.int32).reshape(-1)
+        if pq.shape != t.shape:
+            raise ValueError("thr and pair_q must both be [L] (pair_q defaults to arange(Q))")
+        return q, t, pq
+
+    def score_above(self, queries, thr, pair_q=None, cap=None):
+        """All rows of the resident index with float64 score >= thr[p] for query row pair_q[p] (default: pair p is query
+        p).  Returns (offsets int64 [L+1], ids int64 [total], scores float64 [total]): segment offsets[p]:offsets[p+1] holds
+        pair p's rows in score_topk's order (score descending, lower id first) with score_topk's score bits.  Without `cap`
+        a capacity is guessed and, when the total turned out larger, the call repeated with exactly the total.  With `cap`
+        the library's contract is handed through: one call, lists of `cap` entries, and when offsets[-1] > cap the lists
+        come back as (None, None) -- read offsets[-1] and call again."""
+        q, t, pq = self._above_args(queries, thr, pair_q)
+        L = pq.shape[0]
+        offsets = np.zeros(L + 1, np.int64)
+        room = int(cap) if cap is not None else max(1024, 64 * L)
+        while True:
+            ids = np.empty(room, np.int64)
+            scores = np.empty(room, np.float64)
+            self.check(self.lib.sse_score_above(self._h, _ptr(q), q.shape[0], _ptr(pq), _ptr(t), L, room, _ptr(offsets),
+                                                _ptr(ids), _ptr(scores)))
+            total = int(offsets[-1])
+            if total <= room:
+                return offsets, ids[:total], scores[:total]
+            if cap is not None:
+                return offsets, None, None
+            room = total
+
+    def count_above(self, queries, thr, pair_q=None):
+        """The counts alone: int64 [L], rows with float64 score >= thr[p] for query row pair_q[p]."""
+        q, t, pq = self._above_args(queries, thr, pair_q)
+        L = pq.shape[0]
+        offsets = np.zeros(L + 1, np.int64)
+        self.check(self.lib.sse_score_above(self._h, _ptr(q), q.shape[0], _ptr(pq), _ptr(t), L, 0, _ptr(offsets), None, None))
+        return np.diff(offsets)
+
+    def score_above_dev(self, q_ptr, Q, pair_q_ptr, pair_thr_ptr, L, cap, offsets_ptr, ids_ptr, scores_ptr, stream=0):
+        """score_above on device pointers (ids_ptr / scores_ptr both None / 0: counts only), enqueued on `stream`; whether
+        the total fits `cap` is decided on the device; a bad pair is reported by synchronize()."""
+        self.check(self.lib.sse_score_above_dev(self._h, q_ptr, Q, pair_q_ptr, pair_thr_ptr, int(L), int(cap), offsets_ptr,
+                                                ids_ptr or None, scores_ptr or None, stream))
 
     def merge_topk_strided_dev(self, in_s, in_i, shard_stride, P, Q, k, out_s, out_i, stream=0):
         self.check(self.lib.sse_merge_topk_strided_dev(self._h, in_s, in_i, int(shard_stride), P, Q, k, out_s, out_i, stream))

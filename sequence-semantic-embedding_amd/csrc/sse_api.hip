@@ -231,6 +231,11 @@ struct sse_handle {
   // device, staging of the host form.  The band buffers are the collect path's (s_ccnt, s_cbuf).
   DevBuf s_rk, s_rk_cnt, s_rk_in;
   bool rk_cnt_init = false;
+  // rows at or above a threshold (sse_score_above*, score_above.hip): per-pair cursors and overflow marks of a call, merge
+  // scratch of the lists' length, the three "score_above_*" counters, staging of the host form (inputs + offsets | lists).
+  // Per-chunk scratch is the rank count's (s_rk, s_ccnt, s_cbuf).
+  DevBuf s_ab, s_ab_sort, s_ab_cnt, s_ab_in, s_ab_out;
+  bool ab_cnt_init = false;
   // forward-only pair loss (sse_eval_loss*, eval_loss.hip).  Option "eval_chunk_rows": pair rows staged and encoded per chunk (even).
   // Scratch of its own: a gradient result pending between sse_train_grads and sse_train_apply lives in TrainState and the arena.
   int eval_chunk_rows = 65536;
@@ -994,6 +999,8 @@ int check_err_flag(sse_handle *h, hipStream_t st, int32_t *bits = nullptr) {
                                  "out of range in a gathered buffer (sse_train_pack_embedding_grad / sse_train_unpack_embedding_grad)");
     if (flag & 16) return fail(h, "sse_score_rank_dev: a pair_q out of [0, Q) or, without pair scores, a pair_id that is not a row of "
                                   "this index; the call wrote no output");
+    if (flag & 32) return fail(h, "sse_score_above_dev: a pair_q out of [0, Q); the call wrote no output");
+    if (flag & 64) return fail(h, "sse_score_above: the emitting pass found other rows than the counting pass; the lists of the call are not valid");
     if (flag & 4) return fail(h, "LSTM cluster kernel: a workgroup of a cluster did not arrive (device oversubscribed?); the "
                                  "host-buffer entry points fall back to the few-sequences kernel by themselves, for "
                                  "sse_encode_dev set option lstm_persist_rows to 0");
@@ -1236,6 +1243,126 @@ static int score_rank_dev_locked(sse_handle *h, const float *q, int Q, const int
     a.NSPLIT = choose_nsplit(NQ, QB, NT);
     HIPCHECK(h, launch_score_rank(a, st));
   }
+  return 0;
+}
+
+// sse_score_above*, first half: exact counts of all L pairs into offsets[1 .. L], then the scan.  Pairs go in chunks of
+// ABOVE_POOL as score_rank_dev_locked chunks them (same per-chunk scratch); ovf [L] keeps which pairs the float64 sweep took.
+struct AboveCall {
+  AboveArgs a;
+  int64_t *offsets;
+  int32_t *ovf;
+  unsigned long long *cursor;
+};
+static const int ABOVE_POOL = 4096;
+static int score_above_chunks(sse_handle *h, AboveCall &c, const int32_t *pair_q, const double *pair_thr, int64_t L, int emit, hipStream_t st) {
+  const int S = h->idx_S;
+  const int64_t NT = (h->idx_N + 31) / 32;
+  AboveArgs &a = c.a;
+  a.emit = emit;
+  for (int64_t p0 = 0; p0 < L; p0 += ABOVE_POOL) {
+    const int P = (int)std::min<int64_t>(ABOVE_POOL, L - p0);
+    const int NQ = score_pick_nq(P, S, 0);
+    if (NQ == 0) return fail(h, "index dimension %d does not fit the scoring kernel's LDS query block", S);
+    const int QB = (P + NQ * 32 - 1) / (NQ * 32);
+    a.pair_q = pair_q + p0;
+    a.pair_thr = pair_thr + p0;
+    a.counts = c.offsets + 1 + p0;
+    a.offsets = c.offsets + p0;
+    a.ovf = c.ovf + p0;
+    a.cursor = c.cursor + p0;
+    a.P = P;
+    a.NQ = NQ;
+    a.NSPLIT = choose_nsplit(NQ, QB, NT);
+    HIPCHECK(h, launch_score_above(a, st));
+  }
+  return 0;
+}
+
+static int score_above_setup(sse_handle *h, AboveCall &c, const float *q, int64_t L, int64_t *offsets, hipStream_t st) {
+  const int S = h->idx_S, KG = (S + 7) / 8;
+  const int Pmax = (int)std::min<int64_t>(L, ABOVE_POOL);
+  // per-chunk scratch (the rank count's buffers): sure [Pmax] | lo [Pmax] | hi [Pmax] | bad
+  if (reserve(h, h->s_rk, (size_t)Pmax * 24 + 16)) return 1;
+  if (reserve(h, h->s_ccnt, (size_t)(Pmax + 1) * sizeof(int32_t))) return 1;
+  if (reserve(h, h->s_cbuf, (size_t)Pmax * SSE_COLLECT_CAP * sizeof(int32_t))) return 1;
+  if (reserve(h, h->s_ab, (size_t)L * 12 + 16)) return 1;  // cursor [L] | ovf [L]
+  if (reserve(h, h->s_ab_cnt, 3 * sizeof(unsigned long long))) return 1;
+  if (!h->ab_cnt_init) {
+    HIPCHECK(h, hipMemsetAsync(h->s_ab_cnt.p, 0, 3 * sizeof(unsigned long long), st));
+    h->ab_cnt_init = true;
+  }
+  char *base = (char *)h->s_rk.p;
+  AboveArgs &a = c.a;
+  a.q = q;
+  a.idxp = h->idxp;
+  a.idx64 = h->idx64;
+  a.sure = (unsigned long long *)base;
+  a.lo = (float *)(base + (size_t)Pmax * 16);
+  a.hi = (float *)(base + (size_t)Pmax * 20);
+  a.band_cnt = (int32_t *)h->s_ccnt.p;
+  a.band_buf = (int32_t *)h->s_cbuf.p;
+  a.band_cap = SSE_COLLECT_CAP;
+  a.bad = (int32_t *)(base + (size_t)Pmax * 24);
+  a.err_flag = h->err_flag;
+  a.counters = (unsigned long long *)h->s_ab_cnt.p;
+  a.total = offsets + L;
+  a.out_ids = nullptr;
+  a.cap = 0;
+  a.id_base = h->idx_base;
+  a.N = h->idx_N;
+  a.S = S;
+  a.KG = KG;
+  a.NT = (int)((h->idx_N + 31) / 32);
+  a.eps32 = (float)(2.0 * (S + 2) * 5.97e-8 * h->idx_norm_max);
+  c.offsets = offsets;
+  c.cursor = (unsigned long long *)h->s_ab.p;
+  c.ovf = (int32_t *)((char *)h->s_ab.p + (size_t)L * 8);
+  return 0;
+}
+
+static int score_above_count_locked(sse_handle *h, AboveCall &c, const float *q, int Q, const int32_t *pair_q, const double *pair_thr,
+                                    int64_t L, int64_t *offsets, hipStream_t st) {
+  if (score_above_setup(h, c, q, L, offsets, st)) return 1;
+  int32_t *bad = const_cast<int32_t *>(c.a.bad);
+  HIPCHECK(h, hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+  HIPCHECK(h, launch_above_validate(pair_q, L, Q, bad, h->err_flag, st));
+  if (score_above_chunks(h, c, pair_q, pair_thr, L, 0, st)) return 1;
+  HIPCHECK(h, launch_above_scan(offsets, L, bad, st));
+  return 0;
+}
+
+// second half: the lists, queued behind the count; every kernel leaves when the total on the device exceeds cap
+static int score_above_emit_locked(sse_handle *h, AboveCall &c, const int32_t *pair_q, const double *pair_thr, int64_t L, int64_t cap,
+                                   int64_t *ids, double *scores, hipStream_t st) {
+  if (cap <= 0) return 0;  // (only an empty total fits: nothing to write)
+  const bool long_runs = std::min<int64_t>(cap, h->idx_N) > SSE_ABOVE_SORT_CAP;
+  if (long_runs && reserve(h, h->s_ab_sort, (size_t)cap * 16)) return 1;
+  HIPCHECK(h, hipMemsetAsync(c.cursor, 0, (size_t)L * sizeof(unsigned long long), st));
+  c.a.out_ids = ids;
+  c.a.cap = cap;
+  if (score_above_chunks(h, c, pair_q, pair_thr, L, 1, st)) return 1;
+  AboveListArgs l;
+  l.q = c.a.q;
+  l.pair_q = pair_q;
+  l.idxp = h->idxp;
+  l.idx64 = h->idx64;
+  l.offsets = c.offsets;
+  l.cursor = c.cursor;
+  l.ids = ids;
+  l.scores = scores;
+  l.scratch_ids = long_runs ? (int64_t *)h->s_ab_sort.p : nullptr;
+  l.scratch_scores = long_runs ? (double *)((char *)h->s_ab_sort.p + (size_t)cap * 8) : nullptr;
+  l.bad = c.a.bad;
+  l.err_flag = h->err_flag;
+  l.counters = c.a.counters;
+  l.L = L;
+  l.cap = cap;
+  l.id_base = h->idx_base;
+  l.N = h->idx_N;
+  l.S = c.a.S;
+  l.KG = c.a.KG;
+  HIPCHECK(h, launch_above_lists(l, st));
   return 0;
 }
 
@@ -2012,6 +2139,18 @@ int sse_get_counter(sse_handle *h, const char *name, int64_t *value) {
     *value = (int64_t)v[i];
     return 0;
   }
+  static const char *const above_names[3] = {"score_above_band_rows", "score_above_bruteforce_pairs", "score_above_long_segments"};
+  for (int i = 0; i < 3; ++i) {  // sse_score_above*: rows decided in float64, pairs listed by the float64 sweep, segments merged in global memory
+    if (strcmp(name, above_names[i]) != 0) continue;
+    unsigned long long v[3] = {0, 0, 0};
+    if (h->s_ab_cnt.p && h->ab_cnt_init) {
+      HIPCHECK(h, hipSetDevice(h->cfg.device));
+      HIPCHECK(h, hipDeviceSynchronize());
+      HIPCHECK(h, hipMemcpy(v, h->s_ab_cnt.p, sizeof v, hipMemcpyDeviceToHost));
+    }
+    *value = (int64_t)v[i];
+    return 0;
+  }
   static const char *const names[3] = {"score_bf16_second_chance_queries", "score_collect_queries", "score_bruteforce_queries"};
   for (int i = 0; i < 3; ++i) {
     if (strcmp(name, names[i]) != 0) continue;
@@ -2287,6 +2426,73 @@ int sse_score_rank(sse_handle *h, const float *q_host, int32_t Q, const int32_t 
   if (check_err_flag(h, nullptr)) return 1;
   HIPCHECK(h, hipMemcpy(out_before, d_bf, l8, hipMemcpyDeviceToHost));
   if (out_score) HIPCHECK(h, hipMemcpy(out_score, d_sc, l8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int sse_score_above_dev(sse_handle *h, const float *q_dev, int32_t Q, const int32_t *pair_q_dev, const double *pair_thr_dev,
+                        int64_t L, int64_t cap, int64_t *out_offsets_dev, int64_t *out_ids_dev, double *out_scores_dev,
+                        void *stream) {
+  if (!h) return 1;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  hipStream_t st = (hipStream_t)stream;
+  if (!h->idxp) return fail(h, "sse_score_above: no index uploaded");
+  const bool lists = out_ids_dev != nullptr;
+  if (Q < 0 || L < 0 || !out_offsets_dev || (out_ids_dev == nullptr) != (out_scores_dev == nullptr) || (lists && cap < 0))
+    return fail(h, "bad arguments to sse_score_above");
+  if (L == 0) {
+    HIPCHECK(h, hipMemsetAsync(out_offsets_dev, 0, sizeof(int64_t), st));
+    return 0;
+  }
+  if (!q_dev || !pair_q_dev || !pair_thr_dev || Q == 0) return fail(h, "bad arguments to sse_score_above");
+  AboveCall c;
+  if (score_above_count_locked(h, c, q_dev, Q, pair_q_dev, pair_thr_dev, L, out_offsets_dev, st)) return 1;
+  if (lists && score_above_emit_locked(h, c, pair_q_dev, pair_thr_dev, L, cap, out_ids_dev, out_scores_dev, st)) return 1;
+  return 0;
+}
+
+int sse_score_above(sse_handle *h, const float *q_host, int32_t Q, const int32_t *pair_q, const double *pair_thr, int64_t L,
+                    int64_t cap, int64_t *out_offsets, int64_t *out_ids, double *out_scores) {
+  if (!h) return 1;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  if (!h->idxp) return fail(h, "sse_score_above: no index uploaded");
+  const bool lists = out_ids != nullptr;
+  if (Q < 0 || L < 0 || !out_offsets || (out_ids == nullptr) != (out_scores == nullptr) || (lists && cap < 0))
+    return fail(h, "bad arguments to sse_score_above");
+  if (L == 0) {
+    out_offsets[0] = 0;
+    return 0;
+  }
+  if (!q_host || !pair_q || !pair_thr || Q == 0) return fail(h, "bad arguments to sse_score_above");
+  for (int64_t p = 0; p < L; ++p)
+    if (pair_q[p] < 0 || pair_q[p] >= Q) return fail(h, "sse_score_above: pair_q[%lld] = %d is not in [0, Q = %d)", (long long)p, pair_q[p], Q);
+  const size_t S = h->idx_S;
+  // staging: queries | pair_thr | offsets | pair_q (8-byte items first)
+  const size_t qb = ((size_t)Q * S * sizeof(float) + 7) & ~(size_t)7, l8 = (size_t)L * 8, l4 = (size_t)L * 4;
+  if (reserve(h, h->s_ab_in, qb + 2 * l8 + 8 + l4)) return 1;
+  char *b = (char *)h->s_ab_in.p;
+  float *d_q = (float *)b;
+  double *d_thr = (double *)(b + qb);
+  int64_t *d_off = (int64_t *)(b + qb + l8);
+  int32_t *d_pq = (int32_t *)(b + qb + 2 * l8 + 8);
+  HIPCHECK(h, hipMemcpy(d_q, q_host, (size_t)Q * S * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHECK(h, hipMemcpy(d_thr, pair_thr, l8, hipMemcpyHostToDevice));
+  HIPCHECK(h, hipMemcpy(d_pq, pair_q, l4, hipMemcpyHostToDevice));
+  AboveCall c;
+  if (score_above_count_locked(h, c, d_q, Q, d_pq, d_thr, L, d_off, nullptr)) return 1;
+  if (check_err_flag(h, nullptr)) return 1;
+  HIPCHECK(h, hipMemcpy(out_offsets, d_off, l8 + 8, hipMemcpyDeviceToHost));
+  // the host knows the total now: the lists are staged at exactly that length, and skipped when the caller's do not hold it
+  const int64_t total = out_offsets[L];
+  if (!lists || total > cap || total == 0) return 0;
+  if (reserve(h, h->s_ab_out, (size_t)total * 16)) return 1;
+  int64_t *d_ids = (int64_t *)h->s_ab_out.p;
+  double *d_sc = (double *)((char *)h->s_ab_out.p + (size_t)total * 8);
+  if (score_above_emit_locked(h, c, d_pq, d_thr, L, total, d_ids, d_sc, nullptr)) return 1;
+  if (check_err_flag(h, nullptr)) return 1;
+  HIPCHECK(h, hipMemcpy(out_ids, d_ids, (size_t)total * 8, hipMemcpyDeviceToHost));
+  HIPCHECK(h, hipMemcpy(out_scores, d_sc, (size_t)total * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 

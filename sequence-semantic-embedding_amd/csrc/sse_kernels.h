@@ -441,6 +441,62 @@ hipError_t launch_rank_validate(const int32_t *pair_q, const int64_t *pair_id, i
                                 int64_t N, int32_t *bad, int32_t *err_flag, hipStream_t st);
 hipError_t launch_score_rank(const RankArgs &a, hipStream_t st);
 
+// All rows at or above a score threshold (score_above.hip): pair p of a chunk (query pair_q[p], threshold pair_thr[p]) matches
+// row r iff score64(q, r) >= pair_thr[p].  Count pass (emit == 0): counts[p] = the exact number of matching rows, ovf[p] = 1 when
+// the pair's band outgrew band_cap (counted, and later listed, by the float64 sweep).  Emit pass (emit == 1, after
+// launch_above_scan): the same sweep appends id_base + r of every matching row to out_ids[offsets[p] .. offsets[p + 1])
+// through cursor[p], every store guarded by the segment's end.  Per-chunk scratch as RankArgs; counts / offsets / ovf / cursor
+// are per-call arrays already advanced to the chunk.  *bad != 0, or (emit pass) *total > cap: every kernel leaves at once.
+struct AboveArgs {
+  const float *q;            // [Q][S] f32 row-major queries
+  const int32_t *pair_q;     // [P]
+  const double *pair_thr;    // [P]
+  const float *idxp;         // frag32 index [NT][KG][256]
+  const double *idx64;       // [N][S] f64 rows or nullptr
+  float *lo, *hi;            // [P] fp32 interval the bound cannot decide
+  unsigned long long *sure;  // [P] rows with fp32 score > hi (count pass)
+  int32_t *band_cnt, *band_buf;
+  int32_t band_cap;
+  const int32_t *bad;
+  int32_t *err_flag;
+  unsigned long long *counters;  // [0] band rows decided in float64, [1] pairs taken by the float64 sweep, [2] long segments
+  int64_t *counts;               // [P] count pass: out
+  const int64_t *offsets;        // [P + 1] emit pass: the pairs' segments
+  const int64_t *total;          // emit pass: the call's total
+  int32_t *ovf;                  // [P]
+  unsigned long long *cursor;    // [P] emit pass: entries appended so far
+  int64_t *out_ids;
+  int64_t cap;
+  int64_t id_base, N;
+  int32_t S, KG, NT, P, NSPLIT, NQ, emit;
+  float eps32;
+};
+#define SSE_ABOVE_SORT_CAP 8192  // entries one workgroup sorts in LDS (16-byte keys: 128 KiB); a longer segment: global merge passes
+hipError_t launch_above_validate(const int32_t *pair_q, int64_t L, int Q, int32_t *bad, int32_t *err_flag, hipStream_t st);
+hipError_t launch_score_above(const AboveArgs &a, hipStream_t st);  // every stage of one chunk, count or emit pass
+// offsets[0] = 0, offsets[p + 1] = counts of pairs 0 .. p (the counts are offsets[1 .. L] on entry); nothing when *bad
+hipError_t launch_above_scan(int64_t *offsets, int64_t L, const int32_t *bad, hipStream_t st);
+// float64 scores of the appended rows, then every segment sorted by (score descending, id ascending); scratch_*: [cap] each, used
+// when min(cap, N) > SSE_ABOVE_SORT_CAP.  Nothing when *bad or offsets[L] > cap.
+struct AboveListArgs {
+  const float *q;
+  const int32_t *pair_q;
+  const float *idxp;
+  const double *idx64;
+  const int64_t *offsets;  // [L + 1]
+  const unsigned long long *cursor;  // [L]
+  int64_t *ids;
+  double *scores;
+  int64_t *scratch_ids;
+  double *scratch_scores;
+  const int32_t *bad;
+  int32_t *err_flag;
+  unsigned long long *counters;
+  int64_t L, cap, id_base, N;
+  int32_t S, KG;
+};
+hipError_t launch_above_lists(const AboveListArgs &a, hipStream_t st);
+
 // uncertified queries (cert[q] == 0) get collect-buffer slots 0, 1, ... (col_slot[q]; -1 when certified or the pool
 // of `slots` is exhausted); *counter must be zero on entry
 hipError_t launch_assign_slots(const int32_t *cert, int Q, int slots, int32_t *col_slot, int32_t *counter, hipStream_t st);

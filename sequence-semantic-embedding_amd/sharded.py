@@ -53,6 +53,21 @@ def all_gather_topk(local_scores, local_ids, group=None, force=False):
     return gs, gi
 
 
+def merge_above_runs(pair, scores, ids, L):
+    """The per-pair merge of ShardedIndex.score_above on torch tensors of any device: the shards' entries concatenated
+    (pair int64 [M] = the pair of each entry, scores float64 [M], ids int64 [M], in any order) -> (offsets int64 [L+1],
+    ids, scores) with every pair's entries together, score descending, equal scores by ascending id.  Three stable sorts,
+    least significant key first."""
+    import torch
+    o = torch.sort(ids, stable=True).indices
+    o = o[torch.sort(scores[o], descending=True, stable=True).indices]
+    o = o[torch.sort(pair[o], stable=True).indices]
+    offsets = torch.zeros(L + 1, dtype=torch.int64, device=pair.device)
+    if L > 0:
+        offsets[1:] = torch.cumsum(torch.bincount(pair, minlength=L), 0)
+    return offsets, ids[o], scores[o]
+
+
 class ShardedIndex(object):
     """One rank's view of the sharded index.  `handle` is an sse_amd Handle."""
 
@@ -172,6 +187,89 @@ class ShardedIndex(object):
             out[other] = b
         all_reduce_(out, group=self.group)                                # (4)
         return out
+
+    def _above_check(self, queries, pair_q, pair_thr):
+        import torch
+        Q, L = int(queries.shape[0]), int(pair_q.shape[0])
+        if pair_thr.shape[0] != L or pair_q.dtype != torch.int32 or pair_thr.dtype != torch.float64:
+            raise ValueError("pair_q int32 [L] and pair_thr float64 [L] are required")
+        if L > 0 and bool(((pair_q < 0) | (pair_q >= Q)).any().item()):
+            raise ValueError("pair_q must be in [0, Q=%d)" % Q)
+        return Q, L
+
+    def _above_local(self, queries, pair_q, pair_thr, Q, L, lists):
+        """This shard's call: (offsets [L+1], ids, scores) on the device, the lists None when not wanted.  The count-only
+        call sizes the lists (one read-back of the total); an empty shard has no index and contributes nothing."""
+        import torch
+        dev = queries.device
+        stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
+        off = torch.zeros(L + 1, dtype=torch.int64, device=dev)
+        empty = (torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.float64, device=dev))
+        if self.end == self.start or L == 0:
+            return (off,) + (empty if lists else (None, None))
+        self.handle.score_above_dev(queries.data_ptr(), Q, pair_q.data_ptr(), pair_thr.data_ptr(), L, 0, off.data_ptr(), None, None, stream)
+        if not lists:
+            return off, None, None
+        total = int(off[-1].item())
+        if total == 0:
+            return (off,) + empty
+        ids = torch.empty(total, dtype=torch.int64, device=dev)
+        sc = torch.empty(total, dtype=torch.float64, device=dev)
+        self.handle.score_above_dev(queries.data_ptr(), Q, pair_q.data_ptr(), pair_thr.data_ptr(), L, total, off.data_ptr(),
+                                    ids.data_ptr(), sc.data_ptr(), stream)
+        return off, ids, sc
+
+    def count_above(self, queries, pair_q, pair_thr):
+        """Global match counts, int64 [L] on every rank: rows of the whole index with float64 score >= pair_thr[p] for query
+        row pair_q[p].  Every shard counts its own rows; ONE all-reduce adds them."""
+        import torch
+        from .collectives import all_reduce_
+        Q, L = self._above_check(queries, pair_q, pair_thr)
+        queries, pair_q, pair_thr = queries.contiguous(), pair_q.contiguous(), pair_thr.contiguous()
+        off, _, _ = self._above_local(queries, pair_q, pair_thr, Q, L, False)
+        cnt = (off[1:] - off[:-1]).contiguous()
+        if L > 0 and not (self.world == 1 and not self.always_gather):
+            all_reduce_(cnt, group=self.group)
+        return cnt
+
+    def score_above(self, queries, pair_q, pair_thr):
+        """All rows of the whole index at or above a threshold: queries CUDA float32 [Q,S], pair_q int32 [L], pair_thr
+        float64 [L], identical on every rank.  Returns (offsets int64 [L+1], ids int64 [total], scores float64 [total]) --
+        what the unsharded Handle.score_above returns -- on every rank.  (1) every rank lists its shard's matches with
+        global ids, (2) ONE all-gather of the per-pair counts, (3) ONE all-gather of the lists padded to the largest local
+        total, (4) every pair's runs merged in the library's order (torch stable sorts: plumbing).  An empty shard
+        contributes nothing.  Bad input raises ValueError on every rank alike, before any collective."""
+        import torch
+        import torch.distributed as dist
+        from .collectives import all_gather_into
+        Q, L = self._above_check(queries, pair_q, pair_thr)
+        dev = queries.device
+        queries, pair_q, pair_thr = queries.contiguous(), pair_q.contiguous(), pair_thr.contiguous()
+        off, ids, sc = self._above_local(queries, pair_q, pair_thr, Q, L, True)
+        if L == 0 or (self.world == 1 and not self.always_gather):
+            return off, ids, sc
+        world = dist.get_world_size(self.group)
+        cnt = (off[1:] - off[:-1]).contiguous()
+        counts = torch.empty(world * L, dtype=torch.int64, device=dev)
+        all_gather_into(counts, cnt, group=self.group)
+        counts = counts.view(world, L)
+        width = int(counts.sum(1).max().item())
+        if width == 0:
+            return off, ids, sc
+        loc = torch.zeros((2, width), dtype=torch.int64, device=dev)          # [0] = float64 score bits, [1] = ids
+        loc[0, :ids.numel()] = sc.view(torch.int64)
+        loc[1, :ids.numel()] = ids
+        g = torch.empty((world * 2, width), dtype=torch.int64, device=dev)
+        all_gather_into(g, loc, group=self.group)
+        g = g.view(world, 2, width)
+        pair_all, sc_all, id_all = [], [], []
+        pairs = torch.arange(L, dtype=torch.int64, device=dev)
+        for r in range(world):                                                # a shard's list is pair-major: its counts say whose entry is whose
+            n = int(counts[r].sum().item())
+            pair_all.append(torch.repeat_interleave(pairs, counts[r]))
+            sc_all.append(g[r, 0, :n].view(torch.float64))
+            id_all.append(g[r, 1, :n])
+        return merge_above_runs(torch.cat(pair_all), torch.cat(sc_all), torch.cat(id_all), L)
 
 
 class RcclShardedIndex(object):

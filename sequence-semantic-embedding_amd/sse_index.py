@@ -16,6 +16,7 @@ FLAGS = flags.FlagSet("sse_index", [
     ("idx_rawfilename", str, "targetIDs", "raw target sequence file to be indexed"),
     ("idx_encodedIndexFile", str, "targetEncodingIndex.tsv", "target sequece encoding index file."),
     ("device", str, "0", "GPU ordinal"),
+    ("near_dup_threshold", float, 0.0, "when > 0: also write nearDuplicates.tsv, every pair of targets whose encodings score at least this"),
 ])
 
 
@@ -73,7 +74,63 @@ def createIndexFile(model, encoder, rawfile, max_seq_len, encodeIndexFile, sessi
     print("Done of all indexing total count:%d" % cnt)
 
 
-def index(model_dir, rawfile, encodeIndexFile, batchsize=10000, device=0):
+def near_duplicate_pairs(handle, rows, threshold, block=4096):
+    """Near-duplicate self-join of a target space: `rows` float32 [N,S] are the rows of the handle's resident index (uploaded
+    with id_base 0), queried with themselves in blocks of `block` through Handle.score_above.  Returns the list of
+    (i, j, score) with i < j and float64 score >= threshold, each pair once, sorted by (i, j)."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    ii, jj, ss = [], [], []
+    for b0 in range(0, rows.shape[0], int(block)):
+        q = rows[b0:b0 + int(block)]
+        off, ids, sc = handle.score_above(q, np.full(q.shape[0], float(threshold)))
+        qi = np.repeat(np.arange(b0, b0 + q.shape[0], dtype=np.int64), np.diff(off))
+        keep = ids > qi                                   # (i, j) and (j, i) both match, (i, i) matches itself: i < j once
+        ii.append(qi[keep])
+        jj.append(ids[keep])
+        ss.append(sc[keep])
+    if not ii:
+        return []
+    ii, jj, ss = np.concatenate(ii), np.concatenate(jj), np.concatenate(ss)
+    order = np.lexsort((jj, ii))
+    return [(int(ii[o]), int(jj[o]), float(ss[o])) for o in order]
+
+
+def write_near_duplicates(path, tgt_ids, pairs):
+    """nearDuplicates.tsv: tgtid_a \\t tgtid_b \\t repr(float64 score), one pair per line."""
+    with codecs.open(path, "w", "utf-8") as out:
+        for i, j, s in pairs:
+            out.write("%s\t%s\t%r\n" % (tgt_ids[i], tgt_ids[j], s))
+
+
+def read_near_duplicates(path):
+    out = []
+    for line in codecs.open(path, "r", "utf-8"):
+        a, b, s = line.rstrip("\n").split("\t")
+        out.append((a, b, float(s)))
+    return out
+
+
+def near_duplicates_of_index_file(model, encodeIndexFile, threshold, out_path):
+    """reads the index file just written, makes it the model handle's resident index and writes its near-duplicate pairs"""
+    tgt_ids, vecs = [], []
+    for line in codecs.open(encodeIndexFile, "r", "utf-8"):
+        info = line.rstrip("\n").split("\t")
+        if len(info) != 3:
+            continue
+        tgt_ids.append(info[0])
+        vecs.append(info[2])
+    rows = index_io.parse_rows(vecs).astype(np.float32)
+    if rows.shape[0] == 0:
+        write_near_duplicates(out_path, tgt_ids, [])
+        return 0
+    model.handle.index_upload(rows)
+    pairs = near_duplicate_pairs(model.handle, rows, threshold)
+    write_near_duplicates(out_path, tgt_ids, pairs)
+    print("Wrote %d near-duplicate pairs (score >= %r) to %s" % (len(pairs), threshold, out_path))
+    return len(pairs)
+
+
+def index(model_dir, rawfile, encodeIndexFile, batchsize=10000, device=0, near_dup_threshold=0.0):
     if not os.path.exists(model_dir):
         raise FileNotFoundError("Error! Model folder does not exist!! : %s" % model_dir)
     vocab_file = os.path.join(model_dir, "vocabulary.txt")
@@ -89,12 +146,15 @@ def index(model_dir, rawfile, encodeIndexFile, batchsize=10000, device=0):
     print("Reading model parameters from %s" % ckpt)
     model.saver.restore(None, ckpt)
     createIndexFile(model, encoder, rawfile, int(cfg["max_seq_length"]), encodeIndexFile, Session(model), batchsize)
+    if near_dup_threshold > 0:
+        near_duplicates_of_index_file(model, encodeIndexFile, near_dup_threshold,
+                                      os.path.join(os.path.dirname(encodeIndexFile), "nearDuplicates.tsv"))
 
 
 def main(argv=None):
     f = FLAGS.parse(sys.argv[1:] if argv is None else argv)
     index(f.idx_model_dir, os.path.join(f.idx_model_dir, f.idx_rawfilename),
-          os.path.join(f.idx_model_dir, f.idx_encodedIndexFile), device=int(f.device))
+          os.path.join(f.idx_model_dir, f.idx_encodedIndexFile), device=int(f.device), near_dup_threshold=float(f.near_dup_threshold))
 
 
 if __name__ == "__main__":
