@@ -171,7 +171,9 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value);
  * kernel does for itself are not counted.
  * "eval_paired_calls": sse_eval_loss* calls that ran the source encoder once per pair of rows (option train_pair_dedup).
  * "score_rank_band_rows" / "score_rank_bruteforce_pairs": see sse_score_rank.
- * "score_above_band_rows" / "score_above_bruteforce_pairs" / "score_above_long_segments": see sse_score_above. */
+ * "score_above_band_rows" / "score_above_bruteforce_pairs" / "score_above_long_segments": see sse_score_above.
+ * "score_filtered_collected_rows" / "score_filtered_bruteforce_queries" / "score_filtered_tiles_skipped": see
+ * sse_score_topk_filtered. */
 int sse_get_counter(sse_handle *h, const char *name, int64_t *value);
 
 /* tf.nn.l2_normalize(x, dim=-1) on device rows (sse_model.py:282-283). */
@@ -252,6 +254,43 @@ int sse_score_above(sse_handle *h, const float *q_host, int32_t Q, const int32_t
 int sse_score_above_dev(sse_handle *h, const float *q_dev, int32_t Q, const int32_t *pair_q_dev, const double *pair_thr_dev,
                         int64_t L, int64_t cap, int64_t *out_offsets_dev, int64_t *out_ids_dev, double *out_scores_dev,
                         void *stream);
+
+/* Tags of the resident index: one 64-bit word per row, copied and kept on the device (with the OR of every 32-row tile's
+ * words beside them).  N must equal the index's row count, otherwise the call errors with a message and the tags stay as
+ * they were.  tags == NULL clears them; setting, uploading or adopting a new index (sse_index_upload*, sse_index_set_dev)
+ * clears them too.  The _dev form takes a device pointer and enqueues the copy on `stream`. */
+int sse_index_set_tags(sse_handle *h, const uint64_t *tags_host, int64_t N);
+int sse_index_set_tags_dev(sse_handle *h, const uint64_t *tags_dev, int64_t N, void *stream);
+
+/* Exact top-k among the rows a query may return: the best leaves under a known meta-category (sse_model.py:36-41 maps a
+ * title to one of 20,000+ leaf categories, webserver.py:158-159 returns targetCategoryId), the hardest negatives of a
+ * labelled source (data.py:95-115 samples them at random), neighbours other than the row itself.  Row r of the index is
+ * ELIGIBLE for query q iff (q_any[q] == 0 || (tags[r] & q_any[q]) != 0) && (tags[r] & q_none[q]) == 0 and id_base + r is not
+ * among excl_ids[q * n_excl .. (q + 1) * n_excl).  q_any / q_none == NULL mean all-zero words (no requirement); giving either
+ * while no tags are set is an error.  excl_ids may be NULL with n_excl == 0; 0 <= n_excl <= 64; entries outside
+ * [id_base, id_base + N) (a padding value such as -1, ids of another shard) are ignored, duplicates are allowed.
+ *   out_counts [Q]: c = min(k, eligible rows of q).
+ *   out_scores / out_ids [Q][k]: columns 0 .. c of row q are exactly the columns of sse_score_topk(..., k = N) for that query
+ *     with the ineligible rows removed -- the same float64 score bits, score descending, equal scores by ascending id, ids
+ *     including id_base; columns c .. k hold (-inf, INT64_MAX).  1 <= k <= 1024; k may exceed N.
+ * With no masks and n_excl == 0 the columns are sse_score_topk's.  The filter is inside the sweep: an fp32 MFMA sweep keeps
+ * maxima of tag-eligible rows over disjoint row sets, their (k + n_excl)-th largest less twice the certified bound is a
+ * threshold no row of the answer scores below, the same sweep again collects every tag-eligible row at or above it, and
+ * those are re-scored in float64 without the excluded ids and sorted (counter "score_filtered_collected_rows"); a query
+ * with more than 4096 such rows is served by a float64 sweep of the whole index ("score_filtered_bruteforce_queries").
+ * Index tiles none of whose rows carries a bit any query of a workgroup's query block asks for are skipped
+ * ("score_filtered_tiles_skipped", counted in the first sweep; option "score_filtered_skip", default 1, 0 = never skip:
+ * the results are identical).  Scratch is bounded by the chunk of 4096 queries.  Rows or queries of norm below 2^-100 and
+ * non-finite input are outside the claim (no fault).
+ * Q == 0 succeeds.  No index, k or n_excl out of range, masks without tags: error with a message, no output written, the
+ * handle stays usable.  The host form runs on the null stream and synchronises; the _dev form takes device pointers,
+ * enqueues on `stream` and never waits for the device. */
+int sse_score_topk_filtered(sse_handle *h, const float *q_host, int32_t Q, int32_t k, const uint64_t *q_any,
+                            const uint64_t *q_none, const int64_t *excl_ids, int32_t n_excl, double *out_scores,
+                            int64_t *out_ids, int32_t *out_counts);
+int sse_score_topk_filtered_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, const uint64_t *q_any_dev,
+                                const uint64_t *q_none_dev, const int64_t *excl_ids_dev, int32_t n_excl,
+                                double *out_scores_dev, int64_t *out_ids_dev, int32_t *out_counts_dev, void *stream);
 
 /* encode + score in one call, the encodings never leaving the device: session.run([src_seq_embedding | norm_...])
  * followed by np.dot + getSortedResults[:k] as sse_demo.py:121-129, webserver.py:144-151 (and the three other routes)

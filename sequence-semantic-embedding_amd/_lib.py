@@ -51,6 +51,10 @@ SYMBOLS = {
     "sse_score_rank_dev": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P]),
     "sse_score_above": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P, _P, _P]),
     "sse_score_above_dev": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    "sse_index_set_tags": (C.c_int, [_P, _P, C.c_int64]),
+    "sse_index_set_tags_dev": (C.c_int, [_P, _P, C.c_int64, _P]),
+    "sse_score_topk_filtered": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    "sse_score_topk_filtered_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     "sse_encode_score_topk": (C.c_int, [_P, C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_merge_topk_dev": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_merge_topk_strided_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
@@ -359,6 +363,56 @@ class Handle(object):
         the total fits `cap` is decided on the device; a bad pair is reported by synchronize()."""
         self.check(self.lib.sse_score_above_dev(self._h, q_ptr, Q, pair_q_ptr, pair_thr_ptr, int(L), int(cap), offsets_ptr,
                                                 ids_ptr or None, scores_ptr or None, stream))
+
+    def index_set_tags(self, tags):
+        """One uint64 tag word per row of the resident index (tags=None clears them); a new index clears them too."""
+        if tags is None:
+            self.check(self.lib.sse_index_set_tags(self._h, None, 0))
+            return
+        t = np.ascontiguousarray(tags, dtype=np.uint64).reshape(-1)
+        self.check(self.lib.sse_index_set_tags(self._h, _ptr(t), t.shape[0]))
+
+    def index_set_tags_dev(self, tags_ptr, N, stream=0):
+        """index_set_tags from a device pointer of N uint64 words (None / 0 clears), copied on `stream`."""
+        self.check(self.lib.sse_index_set_tags_dev(self._h, tags_ptr or None, int(N), stream))
+
+    def score_topk_filtered(self, queries, k, any_of=None, none_of=None, exclude=None):
+        """Exact top-k among the rows each query may return.  any_of / none_of: uint64 [Q] tag masks (a row is eligible
+        when it carries a bit of any_of -- or any_of is 0 -- and no bit of none_of); exclude: int64 [Q, n] row ids a query
+        must not return (n <= 64; ids outside the index, e.g. -1 padding, are ignored).  Returns (scores float64 [Q,k],
+        ids int64 [Q,k], counts int32 [Q]): the first counts[q] columns are score_topk's columns with the ineligible rows
+        removed, the rest hold (-inf, INT64_MAX)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError("queries must be [Q,S]")
+        Q, k = q.shape[0], int(k)
+        masks = []
+        for m in (any_of, none_of):
+            if m is not None:
+                m = np.ascontiguousarray(m, dtype=np.uint64).reshape(-1)
+                if m.shape[0] != Q:
+                    raise ValueError("any_of / none_of must be uint64 [Q]")
+            masks.append(m)
+        ex, n_excl = None, 0
+        if exclude is not None:
+            ex = np.ascontiguousarray(exclude, dtype=np.int64)
+            if ex.ndim != 2 or ex.shape[0] != Q:
+                raise ValueError("exclude must be int64 [Q, n]")
+            n_excl = ex.shape[1]
+            if n_excl == 0:
+                ex = None
+        scores = np.empty((Q, max(k, 0)), np.float64)
+        ids = np.empty((Q, max(k, 0)), np.int64)
+        counts = np.empty(Q, np.int32)
+        self.check(self.lib.sse_score_topk_filtered(self._h, _ptr(q), Q, k, _ptr(masks[0]) if masks[0] is not None else None,
+                                                    _ptr(masks[1]) if masks[1] is not None else None,
+                                                    _ptr(ex) if ex is not None else None, n_excl, _ptr(scores), _ptr(ids), _ptr(counts)))
+        return scores, ids, counts
+
+    def score_topk_filtered_dev(self, q_ptr, Q, k, any_ptr, none_ptr, excl_ptr, n_excl, scores_ptr, ids_ptr, counts_ptr, stream=0):
+        """score_topk_filtered on device pointers (any_ptr / none_ptr / excl_ptr may be None / 0), enqueued on `stream`."""
+        self.check(self.lib.sse_score_topk_filtered_dev(self._h, q_ptr, int(Q), int(k), any_ptr or None, none_ptr or None,
+                                                        excl_ptr or None, int(n_excl), scores_ptr, ids_ptr, counts_ptr, stream))
 
     def merge_topk_strided_dev(self, in_s, in_i, shard_stride, P, Q, k, out_s, out_i, stream=0):
         self.check(self.lib.sse_merge_topk_strided_dev(self._h, in_s, in_i, int(shard_stride), P, Q, k, out_s, out_i, stream))

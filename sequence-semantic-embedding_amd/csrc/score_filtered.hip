@@ -1,0 +1,490 @@
+// Exact top-k among tag-eligible index rows for gfx950 (MI355X): sse_score_topk_filtered*.
+//
+// The reference ranks every target of a query (sse_evaluator.py:110-112, data_utils.py:263-267) and leaves "only the leaves
+// under this meta-category", "not the labelled positives" or "not the row itself" to a filter of the sorted row on the host.
+// Here the filter is inside the sweep and the threshold comes from eligible rows only (DESIGN K6g):
+//   1. score_filtered_kernel<NQ, false>: the fp32 sweep of score_rank_kernel on v_mfma_f32_32x32x2_f32 (index rows = M, one
+//      query per lane column).  A lane reads the 16 tag words of its rows, turns tag-ineligible rows and the zero padding of
+//      the tail tile into -inf and keeps a running maximum per accumulator register.  The NSPLIT x 8 waves x 2 halves x 16
+//      maxima of a query belong to DISJOINT row sets (folded onto NV = min(NSPLIT, 16) x 256 slots: a slot shared by several
+//      splits holds the maximum of their union).  Exclusion lists play no part here.
+//   2. filtered_threshold_kernel: theta = the (k + n_excl)-th largest maximum (-inf with fewer finite ones).  k + n_excl
+//      distinct tag-eligible rows have an fp32 score >= theta and at most n_excl of them are excluded, so k eligible rows
+//      have score64 >= theta - e, so has the k-th best eligible row, and every row of the exact answer has an fp32 score
+//      >= theta - 2 e (e = eps32 |q| (1 + 2^-20), the bound of score_rank.hip, rounded outward).
+//   3. score_filtered_kernel<NQ, true>: the same template and MFMA chain appends every tag-eligible row at or above that to
+//      the query's buffer.
+//   4. filtered_select_kernel: excluded ids dropped, the rest re-scored with wave_exact_dot, sorted by before(), first k out,
+//      padding (-inf, INT64_MAX), count.  Fewer than k rows is a valid answer (theta = -inf: everything eligible was
+//      collected).  A query whose buffer overflowed is served by a float64 sweep of the whole index in the same workgroup.
+// Tile skip: a tile whose summary word (OR of its 32 tag words) shares no bit with the OR of q_any over the workgroup's
+// query block, none of whose queries is unrestricted, has no eligible row for any of them: the wave moves on.
+#include "sse_kernels.h"
+#include "score_exact.h"
+
+#define FT_THREADS 512       // the sweep: 8 waves = 2 per SIMD, as score_rank_kernel
+#define FT_MAXSPLIT 16       // splits with maxima slots of their own
+#define FT_KEY_NINF 0x007FFFFFu  // key of -inf: finite scores have larger keys, 0 = empty slot
+
+__device__ __forceinline__ uint32_t ft_key(float x) {
+  const uint32_t u = __float_as_uint(x);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ft_unkey(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
+
+__global__ void tag_tile_summary_kernel(const uint64_t *tags, int64_t NT, uint64_t *tile_sum) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= NT) return;
+  uint64_t s = 0;
+  for (int i = 0; i < 32; ++i) s |= tags[t * 32 + i];
+  tile_sum[t] = s;
+}
+hipError_t launch_tag_tile_summary(const uint64_t *tags, int64_t NT, uint64_t *tile_sum, hipStream_t st) {
+  if (NT <= 0) return hipSuccess;
+  hipLaunchKernelGGL(tag_tile_summary_kernel, dim3((int)((NT + 255) / 256)), dim3(256), 0, st, tags, NT, tile_sum);
+  return hipGetLastError();
+}
+
+// The sweep of score_rank_kernel (see there for the layout): workgroup = (block of NQ x 32 queries, index split), a wave walks
+// the split's tiles, a lane owns query column (lane & 31) of every query tile and 16 rows of the index tile.
+template <int NQ, bool COLLECT>
+__global__ __launch_bounds__(FT_THREADS) void score_filtered_kernel(FilteredArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float ft_smem[];  // [KG][NQ][256]
+  __shared__ unsigned long long s_any;
+  __shared__ int s_unres;
+  constexpr int PF = 4;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int KG = a.KG;
+  int split, qb;
+  {
+    const int b = blockIdx.x, xcd = b & 7, j = b >> 3;
+    if (a.NSPLIT <= 8) {
+      const int per = 8 / a.NSPLIT;
+      split = xcd / per;
+      qb = j * per + xcd % per;
+    } else {
+      const int m = a.NSPLIT >> 3;
+      split = xcd + 8 * (j % m);
+      qb = j / m;
+    }
+  }
+  if (qb * NQ * 32 >= a.P) return;
+  if (tid == 0) {
+    s_any = 0ull;
+    s_unres = 0;
+  }
+  __syncthreads();
+  {
+    f32x4 *dst = reinterpret_cast<f32x4 *>(ft_smem);
+    const int Sd = a.S;
+    for (int i = tid; i < NQ * KG * 64; i += FT_THREADS) {
+      const int kg = (i >> 6) / NQ, l = i & 63, pair = (qb * NQ + (i >> 6) % NQ) * 32 + (l & 31);
+      f32x4 v = {0, 0, 0, 0};
+      if (pair < a.P) {
+        const int k0 = kg * 8 + (l >> 5) * 4;
+        const float *src = a.q + (size_t)pair * Sd + k0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (k0 + e < Sd) v[e] = src[e];
+      }
+      dst[i] = v;
+    }
+  }
+  // the block's OR of q_any, and whether one of its queries asks for nothing (the tile skip)
+  if (tid < NQ * 32) {
+    const int pair = qb * NQ * 32 + tid;
+    if (pair < a.P) {
+      const unsigned long long an = a.q_any ? (unsigned long long)a.q_any[pair] : 0ull;
+      if (an == 0ull) atomicOr(&s_unres, 1);
+      else atomicOr(&s_any, an);
+    }
+  }
+  uint64_t qany[NQ], qnone[NQ];
+  float thr[NQ];
+  int pr[NQ];
+  bool live[NQ];
+  f32x16 mx[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    pr[q] = (qb * NQ + q) * 32 + (lane & 31);
+    live[q] = pr[q] < a.P;
+    qany[q] = (live[q] && a.q_any) ? a.q_any[pr[q]] : 0ull;
+    qnone[q] = (live[q] && a.q_none) ? a.q_none[pr[q]] : 0ull;
+    thr[q] = (COLLECT && live[q]) ? a.thr[pr[q]] : __builtin_inff();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) mx[q][r] = -__builtin_inff();
+  }
+  __syncthreads();
+  const bool may_skip = a.skip && a.tags && !s_unres;
+  const unsigned long long blk_any = s_any;
+
+  const int tps = (a.NT + a.NSPLIT - 1) / a.NSPLIT;  // n-tiles per split
+  const int t0 = split * tps, t1 = min(a.NT, t0 + tps);
+  const float *qs = ft_smem + lane * 4;
+  const int tail_tile = (a.N & 31) ? (int)(a.N >> 5) : -1;
+  const int nlim = (int)a.N;
+  int skipped = 0;
+
+  for (int tile = t0 + w; tile < t1; tile += FT_THREADS / 64) {
+    if (may_skip && (a.tile_sum[tile] & blk_any) == 0ull) {  // (wave-uniform)
+      ++skipped;
+      continue;
+    }
+    const f32x4 *ap = reinterpret_cast<const f32x4 *>(a.idxp) + (size_t)tile * KG * 64 + lane;
+    f32x16 acc[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc[q] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const int rem = KG & (PF - 1);
+    f32x4 ar[PF];
+#pragma unroll
+    for (int d = 0; d < PF; ++d) ar[d] = ap[(size_t)min(rem + d, KG - 1) * 64];
+    __builtin_amdgcn_s_setprio(1);
+    for (int kg = 0; kg < rem; ++kg) {
+      const f32x4 av = ap[(size_t)kg * 64];
+      f32x4 bq[NQ];
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) bq[q] = *reinterpret_cast<const f32x4 *>(qs + ((size_t)kg * NQ + q) * 256);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], bq[q][e], acc[q], 0, 0, 0);
+    }
+    f32x4 bq[NQ], bqn[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) bq[q] = *reinterpret_cast<const f32x4 *>(qs + ((size_t)min(rem, KG - 1) * NQ + q) * 256);
+    for (int kg0 = rem; kg0 < KG; kg0 += PF) {
+#pragma unroll
+      for (int d = 0; d < PF; ++d) {
+        const int kg = kg0 + d;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) bqn[q] = *reinterpret_cast<const f32x4 *>(qs + ((size_t)min(kg + 1, KG - 1) * NQ + q) * 256);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int q = 0; q < NQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[d][e], bq[q][e], acc[q], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        ar[d] = ap[(size_t)min(kg + PF, KG - 1) * 64];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) bq[q] = bqn[q];
+      }
+    }
+    __builtin_amdgcn_s_setprio(0);
+
+    const int rbase = tile * 32 + 4 * (lane >> 5);  // row of accumulator register r: rbase + (r & 3) + 8 * (r >> 2)
+    // rows of this tile that exist (the index's last tile is zero padded past N)
+    unsigned rowmask = 0xFFFFu;
+    if (tile == tail_tile) {  // (uniform)
+      rowmask = 0u;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) rowmask |= (rbase + (r & 3) + 8 * (r >> 2) < nlim) ? (1u << r) : 0u;
+    }
+    unsigned em[NQ];  // eligible rows per query tile
+    if (a.tags) {     // (uniform)
+      uint64_t tg[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) tg[r] = a.tags[rbase + (r & 3) + 8 * (r >> 2)];  // (padded to NT * 32 words)
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        unsigned m = 0u;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const bool ok = (qany[q] == 0ull || (tg[r] & qany[q]) != 0ull) && (tg[r] & qnone[q]) == 0ull;
+          m |= ok ? (1u << r) : 0u;
+        }
+        em[q] = live[q] ? (m & rowmask) : 0u;
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) em[q] = live[q] ? rowmask : 0u;
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      if (COLLECT) {
+        unsigned bm = 0u;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) bm |= (acc[q][r] >= thr[q]) ? (1u << r) : 0u;
+        bm &= em[q];
+        while (bm) {
+          const int r = __ffs((int)bm) - 1;
+          bm &= bm - 1;
+          const int row = rbase + (r & 3) + 8 * (r >> 2);
+          const int pos = atomicAdd(a.col_cnt + pr[q], 1);
+          if (pos < a.col_cap && row < nlim) a.col_buf[(size_t)pr[q] * a.col_cap + pos] = row;
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mx[q][r] = fmaxf(mx[q][r], ((em[q] >> r) & 1u) ? acc[q][r] : -__builtin_inff());
+      }
+    }
+  }
+  if (!COLLECT) {
+    // slot of (split, wave, lane half, register); splits past FT_MAXSPLIT fold onto the slots of split % FT_MAXSPLIT
+    const int slot0 = (split & (FT_MAXSPLIT - 1)) * 256 + w * 32 + (lane >> 5) * 16;
+    const bool shared_slots = a.NSPLIT > FT_MAXSPLIT;  // (uniform)
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      if (!live[q]) continue;
+      uint32_t *dst = a.maxima + (size_t)pr[q] * a.NV + slot0;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const uint32_t key = ft_key(mx[q][r]);
+        if (shared_slots) atomicMax(dst + r, key);
+        else dst[r] = key;
+      }
+    }
+    if (skipped && lane == 0) atomicAdd(a.counters + 2, (unsigned long long)skipped);
+  }
+}
+
+// bitonic sort of n2 (power of two) keys in LDS, descending
+__device__ __forceinline__ void ft_sort_u32(uint32_t *key, int n2, int tid, int nthr) {
+  for (int size = 2; size <= n2; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      __syncthreads();
+      for (int i = tid; i < (n2 >> 1); i += nthr) {
+        const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
+        const bool desc = ((lo & size) == 0);
+        const uint32_t x = key[lo], y = key[hi];
+        if ((x < y) == desc) {
+          key[lo] = y;
+          key[hi] = x;
+        }
+      }
+    }
+  __syncthreads();
+}
+
+// one workgroup per query: collect threshold from the (k + n_excl)-th largest of its NV maxima
+__global__ __launch_bounds__(256) void filtered_threshold_kernel(FilteredArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t th_key[];  // [NV]
+  __shared__ double s_qn[4];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  double v = 0.0;
+  for (int d = tid; d < a.S; d += 256) v += (double)a.q[(size_t)p * a.S + d] * a.q[(size_t)p * a.S + d];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if (lane == 0) s_qn[w] = v;
+  for (int c = tid; c < a.NV; c += 256) th_key[c] = a.maxima[(size_t)p * a.NV + c];
+  ft_sort_u32(th_key, a.NV, tid, 256);
+  if (tid == 0) {
+    const int m = a.k + a.n_excl;
+    float thr = -__builtin_inff();
+    if (m <= a.NV && th_key[m - 1] > FT_KEY_NINF) {
+      const double theta = (double)ft_unkey(th_key[m - 1]);
+      const double e = (double)a.eps32 * sqrt(s_qn[0] + s_qn[1] + s_qn[2] + s_qn[3]) * (1.0 + 1.0 / 1048576.0);
+      if (theta == theta) thr = __double2float_rd(theta - 2.0 * e);
+    }
+    a.thr[p] = thr;
+  }
+}
+
+__device__ __forceinline__ unsigned long long ft_key64(double x) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(x);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double ft_unkey64(unsigned long long u) {
+  return __longlong_as_double((long long)((u >> 63) ? (u & 0x7FFFFFFFFFFFFFFFull) : ~u));
+}
+
+// bitonic sort of n2 (power of two) entries in LDS by (key descending, row ascending): the order of before()
+__device__ __forceinline__ void ft_sort_entries(unsigned long long *skey, int *srow, int n2, int tid) {
+  for (int size = 2; size <= n2; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      __syncthreads();
+      for (int i = tid; i < (n2 >> 1); i += 256) {
+        const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
+        const bool desc = ((lo & size) == 0);
+        const unsigned long long x = skey[lo], y = skey[hi];
+        const int rx = srow[lo], ry = srow[hi];
+        const bool x_after_y = (x < y) || (x == y && rx > ry);
+        if (x_after_y == desc) {
+          skey[lo] = y;
+          skey[hi] = x;
+          srow[lo] = ry;
+          srow[hi] = rx;
+        }
+      }
+    }
+  __syncthreads();
+}
+
+#define FT_PAD_ROW 0x7FFFFFFF  // (padding entries: key 0 is below the key of every score, -inf included)
+
+// is id among the query's exclusion list?  One lane per entry (n_excl <= 64); the answer is wave-uniform.
+__device__ __forceinline__ bool ft_excluded(const int64_t *ex, int n_excl, int64_t id, int lane) {
+  if (n_excl == 0) return false;
+  return __ballot(lane < n_excl && ex[lane] == id) != 0ull;
+}
+
+// One workgroup per query.  Buffer held: its rows without the excluded ids, float64 scores, sort, first k.  Buffer
+// overflowed: every eligible row of the index in float64, the best k kept in the same LDS area (filled to col_cap, then cut
+// back to the k best whose last entry becomes the bar later rows have to pass).
+__global__ __launch_bounds__(256) void filtered_select_kernel(FilteredArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long fs_smem[];
+  __shared__ int s_cnt;
+  __shared__ unsigned long long s_bar_key;
+  __shared__ int s_bar_row;
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int cap = a.col_cap;
+  unsigned long long *skey = fs_smem;                  // [cap]
+  int *srow = reinterpret_cast<int *>(fs_smem + cap);  // [cap]
+  const float *qrow = a.q + (size_t)p * a.S;
+  const int64_t *ex = a.excl ? a.excl + (size_t)p * a.n_excl : nullptr;
+  const int n_excl = a.excl ? a.n_excl : 0;
+  const int n = a.col_cnt[p];  // (uniform)
+  if (tid == 0) s_cnt = 0;
+  __syncthreads();
+  int n2 = 1;
+  if (n <= cap) {
+    const int32_t *rows = a.col_buf + (size_t)p * cap;
+    for (int i0 = w * 4; i0 < n; i0 += 16) {
+      int64_t r[4];
+      bool use[4];
+      bool any_use = false;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        r[b] = rows[min(i0 + b, n - 1)];
+        use[b] = (i0 + b < n) && !ft_excluded(ex, n_excl, a.id_base + r[b], lane);
+        any_use |= use[b];
+      }
+      if (!any_use) continue;  // (wave-uniform)
+      double sc[4];
+      wave_exact_dot_n<4>(qrow, a.idxp, a.idx64, r, a.S, a.KG, lane, sc);
+      if (lane == 0) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+          if (use[b]) {
+            const int pos = atomicAdd(&s_cnt, 1);
+            skey[pos] = ft_key64(sc[b]);
+            srow[pos] = (int)r[b];
+          }
+      }
+    }
+    __syncthreads();
+    const int c = s_cnt;
+    while (n2 < c) n2 <<= 1;
+    if (tid == 0 && c) atomicAdd(a.counters, (unsigned long long)c);
+  } else {
+    const uint64_t qa = a.q_any ? a.q_any[p] : 0ull, qn = a.q_none ? a.q_none[p] : 0ull;
+    bool have_bar = false;
+    unsigned long long bar_key = 0ull;
+    int bar_row = 0;
+    for (int64_t n0 = 0; n0 < a.N; n0 += 64) {
+#pragma unroll 1
+      for (int g = 0; g < 4; ++g) {
+        const int64_t base = n0 + g * 16 + w * 4;
+        if (base >= a.N) break;  // (wave-uniform)
+        int64_t r[4];
+        bool use[4];
+        bool any_use = false;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          r[b] = (base + b < a.N) ? base + b : a.N - 1;
+          bool ok = base + b < a.N;
+          if (ok && a.tags) {
+            const uint64_t t = a.tags[r[b]];
+            ok = (qa == 0ull || (t & qa) != 0ull) && (t & qn) == 0ull;
+          }
+          use[b] = ok && !ft_excluded(ex, n_excl, a.id_base + r[b], lane);
+          any_use |= use[b];
+        }
+        if (!any_use) continue;  // (wave-uniform)
+        double sc[4];
+        wave_exact_dot_n<4>(qrow, a.idxp, a.idx64, r, a.S, a.KG, lane, sc);
+        if (lane == 0) {
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            if (!use[b]) continue;
+            const unsigned long long key = ft_key64(sc[b]);
+            if (have_bar && !(key > bar_key || (key == bar_key && (int)r[b] < bar_row))) continue;
+            const int pos = atomicAdd(&s_cnt, 1);  // (at most 64 appends between two cuts: pos < cap)
+            skey[pos] = key;
+            srow[pos] = (int)r[b];
+          }
+        }
+      }
+      __syncthreads();
+      const int c = s_cnt;
+      __syncthreads();
+      if (c > cap - 64) {  // (uniform) cut back to the k best
+        for (int i = c + tid; i < cap; i += 256) {
+          skey[i] = 0ull;
+          srow[i] = FT_PAD_ROW;
+        }
+        ft_sort_entries(skey, srow, cap, tid);
+        if (tid == 0) {
+          s_cnt = a.k;
+          s_bar_key = skey[a.k - 1];
+          s_bar_row = srow[a.k - 1];
+        }
+        __syncthreads();
+        have_bar = true;
+        bar_key = s_bar_key;
+        bar_row = s_bar_row;
+      }
+    }
+    __syncthreads();
+    const int c = s_cnt;
+    while (n2 < c) n2 <<= 1;
+    if (tid == 0) atomicAdd(a.counters + 1, 1ull);
+  }
+  const int c = s_cnt;
+  for (int i = c + tid; i < n2; i += 256) {
+    skey[i] = 0ull;
+    srow[i] = FT_PAD_ROW;
+  }
+  ft_sort_entries(skey, srow, n2, tid);
+  const int cnt = min(c, a.k);
+  for (int j = tid; j < a.k; j += 256) {
+    a.out_scores[(size_t)p * a.k + j] = (j < cnt) ? ft_unkey64(skey[j]) : -(double)__builtin_inff();
+    a.out_ids[(size_t)p * a.k + j] = (j < cnt) ? a.id_base + srow[j] : INT64_MAX;
+  }
+  if (tid == 0) a.out_counts[p] = cnt;
+}
+
+template <int NQ, bool COLLECT>
+static hipError_t launch_filtered_sweep(const FilteredArgs &a, hipStream_t st) {
+  const size_t lds = (size_t)NQ * a.KG * 256 * sizeof(float);
+  if (lds > 159 * 1024) return hipErrorInvalidValue;
+  const int QB = (a.P + NQ * 32 - 1) / (NQ * 32);
+  int grid;
+  if (a.NSPLIT <= 8) {
+    const int per = 8 / a.NSPLIT;
+    grid = (QB + per - 1) / per * 8;
+  } else {
+    grid = QB * a.NSPLIT;
+  }
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(score_filtered_kernel<NQ, COLLECT>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((score_filtered_kernel<NQ, COLLECT>), dim3(grid), dim3(FT_THREADS), lds, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_score_filtered(const FilteredArgs &a, hipStream_t st) {
+  if (a.P <= 0) return hipSuccess;
+  if (a.col_cap != SSE_COLLECT_CAP) return hipErrorInvalidValue;
+  if (a.k < 1 || a.k > SSE_FILTERED_MAX_K || a.n_excl < 0 || a.n_excl > SSE_FILTERED_MAX_EXCL) return hipErrorInvalidValue;
+  if (a.NSPLIT < 1 || (a.NSPLIT & (a.NSPLIT - 1))) return hipErrorInvalidValue;  // a power of two: 1, 2, 4, 8, then multiples of 8
+  if (a.NV != (a.NSPLIT < FT_MAXSPLIT ? a.NSPLIT : FT_MAXSPLIT) * 256) return hipErrorInvalidValue;
+  hipError_t e;
+  if (a.NQ == 4) e = launch_filtered_sweep<4, false>(a, st);
+  else if (a.NQ == 2) e = launch_filtered_sweep<2, false>(a, st);
+  else if (a.NQ == 1) e = launch_filtered_sweep<1, false>(a, st);
+  else e = hipErrorInvalidValue;
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(filtered_threshold_kernel, dim3(a.P), dim3(256), (size_t)a.NV * sizeof(uint32_t), st, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (a.NQ == 4) e = launch_filtered_sweep<4, true>(a, st);
+  else if (a.NQ == 2) e = launch_filtered_sweep<2, true>(a, st);
+  else e = launch_filtered_sweep<1, true>(a, st);
+  if (e != hipSuccess) return e;
+  const size_t lds = (size_t)a.col_cap * (sizeof(unsigned long long) + sizeof(int));
+  e = hipFuncSetAttribute(reinterpret_cast<const void *>(filtered_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(filtered_select_kernel, dim3(a.P), dim3(256), lds, st, a);
+  return hipGetLastError();
+}

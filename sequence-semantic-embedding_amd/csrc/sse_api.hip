@@ -236,6 +236,12 @@ struct sse_handle {
   // Per-chunk scratch is the rank count's (s_rk, s_ccnt, s_cbuf).
   DevBuf s_ab, s_ab_sort, s_ab_cnt, s_ab_in, s_ab_out;
   bool ab_cnt_init = false;
+  // top-k among tag-eligible rows (sse_score_topk_filtered*, score_filtered.hip): the tags of the resident index (one word per
+  // row, zero padded to whole tiles) and their per-tile OR, valid while tags_set; the maxima of a chunk, the three
+  // "score_filtered_*" counters, staging of the host form.  Thresholds and row buffers are the collect path's (s_cthr, s_ccnt, s_cbuf).
+  DevBuf idx_tags, idx_tag_sum, s_ft_max, s_ft_cnt, s_ft_in;
+  bool tags_set = false, ft_cnt_init = false;
+  bool score_filtered_skip = true;  // option "score_filtered_skip": the sweeps skip index tiles no query of a block can use
   // forward-only pair loss (sse_eval_loss*, eval_loss.hip).  Option "eval_chunk_rows": pair rows staged and encoded per chunk (even).
   // Scratch of its own: a gradient result pending between sse_train_grads and sse_train_apply lives in TrainState and the arena.
   int eval_chunk_rows = 65536;
@@ -1015,6 +1021,7 @@ int index_from_dev_rows(sse_handle *h, const float *rows_dev, int64_t N, int S, 
   if (N > (int64_t)2147483000) return fail(h, "index shard too large for int32 row ids");
   const int KG = (S + 7) / 8;
   const int64_t NT = (N + 31) / 32;
+  h->tags_set = false;  // (tags belong to the rows they were set for)
   // fragment-order copy of the index: grow-only (re-indexing with the same or a smaller shard reuses the allocation)
   const size_t need = (size_t)NT * KG * 256 * sizeof(float);
   if (need > h->idxp_cap) {
@@ -1363,6 +1370,103 @@ static int score_above_emit_locked(sse_handle *h, AboveCall &c, const int32_t *p
   l.S = c.a.S;
   l.KG = c.a.KG;
   HIPCHECK(h, launch_above_lists(l, st));
+  return 0;
+}
+
+// sse_index_set_tags*: the words copied behind the index (device to device on `st`, or from the host), zero padded to whole
+// tiles, and the per-tile OR.  Nothing changes before every check and allocation has passed.
+static int index_set_tags_locked(sse_handle *h, const uint64_t *tags, int64_t N, bool from_host, hipStream_t st) {
+  if (!tags) {
+    h->tags_set = false;
+    return 0;
+  }
+  if (!h->idxp) return fail(h, "sse_index_set_tags: no index uploaded");
+  if (N != h->idx_N) return fail(h, "sse_index_set_tags: %lld tags for an index of %lld rows; the tags are unchanged", (long long)N, (long long)h->idx_N);
+  const int64_t NT = (N + 31) / 32;
+  if (!h->tags_set) {  // (live tags are never reallocated: the sizes are the index's)
+    if (reserve(h, h->idx_tags, (size_t)NT * 32 * sizeof(uint64_t))) return 1;
+    if (reserve(h, h->idx_tag_sum, (size_t)NT * sizeof(uint64_t))) return 1;
+  }
+  uint64_t *d = (uint64_t *)h->idx_tags.p;
+  if (NT * 32 > N) HIPCHECK(h, hipMemsetAsync(d + N, 0, (size_t)(NT * 32 - N) * sizeof(uint64_t), st));
+  if (from_host) HIPCHECK(h, hipMemcpy(d, tags, (size_t)N * sizeof(uint64_t), hipMemcpyHostToDevice));
+  else HIPCHECK(h, hipMemcpyAsync(d, tags, (size_t)N * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  HIPCHECK(h, launch_tag_tile_summary(d, NT, (uint64_t *)h->idx_tag_sum.p, st));
+  h->tags_set = true;
+  return 0;
+}
+
+// argument errors of sse_score_topk_filtered*, all decidable on the host
+static int score_filtered_check(sse_handle *h, int Q, int k, const void *q_any, const void *q_none, const void *excl, int n_excl) {
+  if (!h->idxp) return fail(h, "sse_score_topk_filtered: no index uploaded");
+  if (Q < 0) return fail(h, "bad arguments to sse_score_topk_filtered");
+  if (k < 1 || k > SSE_FILTERED_MAX_K) return fail(h, "sse_score_topk_filtered: k = %d is not in [1, %d]", k, SSE_FILTERED_MAX_K);
+  if (n_excl < 0 || n_excl > SSE_FILTERED_MAX_EXCL) return fail(h, "sse_score_topk_filtered: n_excl = %d is not in [0, %d]", n_excl, SSE_FILTERED_MAX_EXCL);
+  if (n_excl > 0 && !excl) return fail(h, "sse_score_topk_filtered: n_excl = %d without excl_ids", n_excl);
+  if ((q_any || q_none) && !h->tags_set) return fail(h, "sse_score_topk_filtered: tag masks given but the index has no tags (sse_index_set_tags)");
+  return 0;
+}
+
+// sse_score_topk_filtered*: every stage queued on `st` (device pointers throughout), queries in chunks of 4096 with the chunk
+// scratch of the rank count (DESIGN K6e): maxima [P][NV], thresholds, row buffers [P][SSE_COLLECT_CAP].
+static int score_filtered_dev_locked(sse_handle *h, const float *q, int Q, int k, const uint64_t *q_any, const uint64_t *q_none,
+                                     const int64_t *excl, int n_excl, double *out_s, int64_t *out_i, int32_t *out_c, hipStream_t st) {
+  const int POOL = 4096;
+  const int S = h->idx_S, KG = (S + 7) / 8;
+  const int64_t NT = (h->idx_N + 31) / 32;
+  if (reserve(h, h->s_ft_cnt, 3 * sizeof(unsigned long long))) return 1;
+  if (!h->ft_cnt_init) {
+    HIPCHECK(h, hipMemsetAsync(h->s_ft_cnt.p, 0, 3 * sizeof(unsigned long long), st));
+    h->ft_cnt_init = true;
+  }
+  FilteredArgs a;
+  a.idxp = h->idxp;
+  a.idx64 = h->idx64;
+  a.tags = h->tags_set ? (const uint64_t *)h->idx_tags.p : nullptr;
+  a.tile_sum = h->tags_set ? (const uint64_t *)h->idx_tag_sum.p : nullptr;
+  a.col_cap = SSE_COLLECT_CAP;
+  a.counters = (unsigned long long *)h->s_ft_cnt.p;
+  a.id_base = h->idx_base;
+  a.N = h->idx_N;
+  a.S = S;
+  a.KG = KG;
+  a.NT = (int)NT;
+  a.k = k;
+  a.n_excl = excl ? n_excl : 0;
+  a.skip = h->score_filtered_skip ? 1 : 0;
+  a.eps32 = (float)(2.0 * (S + 2) * 5.97e-8 * h->idx_norm_max);
+  for (int q0 = 0; q0 < Q; q0 += POOL) {
+    const int P = std::min(POOL, Q - q0);
+    const int NQ = score_pick_nq(P, S, 0);
+    if (NQ == 0) return fail(h, "index dimension %d does not fit the scoring kernel's LDS query block", S);
+    const int QB = (P + NQ * 32 - 1) / (NQ * 32);
+    int nsplit = choose_nsplit(NQ, QB, NT);
+    // at least 2 (k + n_excl) maxima per query where every wave of a split still has a tile of its own
+    while (nsplit < 128 && nsplit * 256 < 2 * (k + a.n_excl) && NT / (nsplit * 2) >= 8) nsplit *= 2;
+    const int NV = std::min(nsplit, 16) * 256;
+    if (reserve(h, h->s_ft_max, (size_t)P * NV * sizeof(uint32_t))) return 1;
+    if (reserve(h, h->s_cthr, (size_t)P * sizeof(float))) return 1;
+    if (reserve(h, h->s_ccnt, (size_t)(P + 1) * sizeof(int32_t))) return 1;
+    if (reserve(h, h->s_cbuf, (size_t)P * SSE_COLLECT_CAP * sizeof(int32_t))) return 1;
+    HIPCHECK(h, hipMemsetAsync(h->s_ft_max.p, 0, (size_t)P * NV * sizeof(uint32_t), st));
+    HIPCHECK(h, hipMemsetAsync(h->s_ccnt.p, 0, (size_t)P * sizeof(int32_t), st));
+    a.q = q + (size_t)q0 * S;
+    a.q_any = q_any ? q_any + q0 : nullptr;
+    a.q_none = q_none ? q_none + q0 : nullptr;
+    a.excl = excl ? excl + (size_t)q0 * n_excl : nullptr;
+    a.maxima = (uint32_t *)h->s_ft_max.p;
+    a.thr = (float *)h->s_cthr.p;
+    a.col_cnt = (int32_t *)h->s_ccnt.p;
+    a.col_buf = (int32_t *)h->s_cbuf.p;
+    a.out_scores = out_s + (size_t)q0 * k;
+    a.out_ids = out_i + (size_t)q0 * k;
+    a.out_counts = out_c + q0;
+    a.P = P;
+    a.NQ = NQ;
+    a.NSPLIT = nsplit;
+    a.NV = NV;
+    HIPCHECK(h, launch_score_filtered(a, st));
+  }
   return 0;
 }
 
@@ -2151,6 +2255,18 @@ int sse_get_counter(sse_handle *h, const char *name, int64_t *value) {
     *value = (int64_t)v[i];
     return 0;
   }
+  static const char *const filtered_names[3] = {"score_filtered_collected_rows", "score_filtered_bruteforce_queries", "score_filtered_tiles_skipped"};
+  for (int i = 0; i < 3; ++i) {  // sse_score_topk_filtered*: rows re-scored by the select stage, queries of the float64 sweep, tiles skipped
+    if (strcmp(name, filtered_names[i]) != 0) continue;
+    unsigned long long v[3] = {0, 0, 0};
+    if (h->s_ft_cnt.p && h->ft_cnt_init) {
+      HIPCHECK(h, hipSetDevice(h->cfg.device));
+      HIPCHECK(h, hipDeviceSynchronize());
+      HIPCHECK(h, hipMemcpy(v, h->s_ft_cnt.p, sizeof v, hipMemcpyDeviceToHost));
+    }
+    *value = (int64_t)v[i];
+    return 0;
+  }
   static const char *const names[3] = {"score_bf16_second_chance_queries", "score_collect_queries", "score_bruteforce_queries"};
   for (int i = 0; i < 3; ++i) {
     if (strcmp(name, names[i]) != 0) continue;
@@ -2175,6 +2291,10 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value) {
   }
   if (strcmp(name, "score_small_x3") == 0) {
     h->score_small_x3 = value != 0;
+    return 0;
+  }
+  if (strcmp(name, "score_filtered_skip") == 0) {
+    h->score_filtered_skip = value != 0;
     return 0;
   }
   if (strcmp(name, "score_bf16") == 0) {
@@ -2493,6 +2613,70 @@ int sse_score_above(sse_handle *h, const float *q_host, int32_t Q, const int32_t
   if (check_err_flag(h, nullptr)) return 1;
   HIPCHECK(h, hipMemcpy(out_ids, d_ids, (size_t)total * 8, hipMemcpyDeviceToHost));
   HIPCHECK(h, hipMemcpy(out_scores, d_sc, (size_t)total * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int sse_index_set_tags(sse_handle *h, const uint64_t *tags_host, int64_t N) {
+  if (!h) return 1;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  if (index_set_tags_locked(h, tags_host, N, true, nullptr)) return 1;
+  HIPCHECK(h, hipStreamSynchronize(nullptr));
+  return 0;
+}
+
+int sse_index_set_tags_dev(sse_handle *h, const uint64_t *tags_dev, int64_t N, void *stream) {
+  if (!h) return 1;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  return index_set_tags_locked(h, tags_dev, N, false, (hipStream_t)stream);
+}
+
+int sse_score_topk_filtered_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, const uint64_t *q_any_dev,
+                                const uint64_t *q_none_dev, const int64_t *excl_ids_dev, int32_t n_excl,
+                                double *out_scores_dev, int64_t *out_ids_dev, int32_t *out_counts_dev, void *stream) {
+  if (!h) return 1;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  if (score_filtered_check(h, Q, k, q_any_dev, q_none_dev, excl_ids_dev, n_excl)) return 1;
+  if (Q == 0) return 0;
+  if (!q_dev || !out_scores_dev || !out_ids_dev || !out_counts_dev) return fail(h, "bad arguments to sse_score_topk_filtered");
+  return score_filtered_dev_locked(h, q_dev, Q, k, q_any_dev, q_none_dev, excl_ids_dev, n_excl, out_scores_dev, out_ids_dev,
+                                   out_counts_dev, (hipStream_t)stream);
+}
+
+int sse_score_topk_filtered(sse_handle *h, const float *q_host, int32_t Q, int32_t k, const uint64_t *q_any,
+                            const uint64_t *q_none, const int64_t *excl_ids, int32_t n_excl, double *out_scores,
+                            int64_t *out_ids, int32_t *out_counts) {
+  if (!h) return 1;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  if (score_filtered_check(h, Q, k, q_any, q_none, excl_ids, n_excl)) return 1;
+  if (Q == 0) return 0;
+  if (!q_host || !out_scores || !out_ids || !out_counts) return fail(h, "bad arguments to sse_score_topk_filtered");
+  const size_t S = h->idx_S;
+  // staging (8-byte items first): scores | ids | any | none | excl | queries | counts
+  const size_t o8 = (size_t)Q * k * 8, m8 = (size_t)Q * 8, e8 = (size_t)Q * n_excl * 8;
+  const size_t qb = ((size_t)Q * S * sizeof(float) + 7) & ~(size_t)7;
+  if (reserve(h, h->s_ft_in, 2 * o8 + 2 * m8 + e8 + qb + (size_t)Q * 4)) return 1;
+  char *b = (char *)h->s_ft_in.p;
+  double *d_s = (double *)b;
+  int64_t *d_i = (int64_t *)(b + o8);
+  uint64_t *d_any = (uint64_t *)(b + 2 * o8), *d_none = (uint64_t *)(b + 2 * o8 + m8);
+  int64_t *d_ex = (int64_t *)(b + 2 * o8 + 2 * m8);
+  float *d_q = (float *)(b + 2 * o8 + 2 * m8 + e8);
+  int32_t *d_c = (int32_t *)(b + 2 * o8 + 2 * m8 + e8 + qb);
+  HIPCHECK(h, hipMemcpy(d_q, q_host, (size_t)Q * S * sizeof(float), hipMemcpyHostToDevice));
+  if (q_any) HIPCHECK(h, hipMemcpy(d_any, q_any, m8, hipMemcpyHostToDevice));
+  if (q_none) HIPCHECK(h, hipMemcpy(d_none, q_none, m8, hipMemcpyHostToDevice));
+  if (n_excl > 0) HIPCHECK(h, hipMemcpy(d_ex, excl_ids, e8, hipMemcpyHostToDevice));
+  if (score_filtered_dev_locked(h, d_q, Q, k, q_any ? d_any : nullptr, q_none ? d_none : nullptr, n_excl > 0 ? d_ex : nullptr, n_excl,
+                                d_s, d_i, d_c, nullptr))
+    return 1;
+  HIPCHECK(h, sync_stream(nullptr));
+  HIPCHECK(h, hipMemcpy(out_scores, d_s, o8, hipMemcpyDeviceToHost));
+  HIPCHECK(h, hipMemcpy(out_ids, d_i, o8, hipMemcpyDeviceToHost));
+  HIPCHECK(h, hipMemcpy(out_counts, d_c, (size_t)Q * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -497,6 +497,37 @@ struct AboveListArgs {
 };
 hipError_t launch_above_lists(const AboveListArgs &a, hipStream_t st);
 
+// Exact top-k among tag-eligible rows (score_filtered.hip, DESIGN K6g).  Row r is eligible for query p of a chunk iff
+// (q_any[p] == 0 || (tags[r] & q_any[p]) != 0) && (tags[r] & q_none[p]) == 0 and id_base + r is not among excl[p][0 .. n_excl).
+// Stages: eligible-max sweep (per query NV = min(NSPLIT, 16) * 256 maxima of disjoint row sets, as order-preserving keys, 0 =
+// empty: the caller zeroes them), threshold from the (k + n_excl)-th largest, collect sweep of every tag-eligible row at or above
+// it (col_cnt zeroed by the caller), select (float64, before()) or -- buffer overflow -- a float64 sweep of the whole index.
+struct FilteredArgs {
+  const float *q;             // [P][S] f32 row-major queries of the chunk
+  const float *idxp;          // frag32 index [NT][KG][256]
+  const double *idx64;        // [N][S] f64 rows or nullptr
+  const uint64_t *tags;       // [NT * 32] (zero past N) or nullptr: no tags set
+  const uint64_t *tile_sum;   // [NT] OR of a tile's 32 tag words
+  const uint64_t *q_any, *q_none;  // [P] or nullptr
+  const int64_t *excl;        // [P][n_excl] or nullptr
+  uint32_t *maxima;           // [P][NV]
+  float *thr;                 // [P] collect thresholds
+  int32_t *col_cnt, *col_buf; // [P], [P][col_cap]
+  int32_t col_cap;
+  double *out_scores;         // [P][k]
+  int64_t *out_ids;           // [P][k]
+  int32_t *out_counts;        // [P]
+  unsigned long long *counters;  // [0] rows re-scored by the select stage, [1] queries of the float64 sweep, [2] tiles skipped
+  int64_t id_base, N;
+  int32_t S, KG, NT, P, NSPLIT, NQ, NV, k, n_excl, skip;
+  float eps32;
+};
+#define SSE_FILTERED_MAX_K 1024
+#define SSE_FILTERED_MAX_EXCL 64
+hipError_t launch_score_filtered(const FilteredArgs &a, hipStream_t st);  // every stage of one chunk
+// tile_sum[t] = OR of tags[32 t .. 32 t + 32) (tags padded with zero words to NT * 32)
+hipError_t launch_tag_tile_summary(const uint64_t *tags, int64_t NT, uint64_t *tile_sum, hipStream_t st);
+
 // uncertified queries (cert[q] == 0) get collect-buffer slots 0, 1, ... (col_slot[q]; -1 when certified or the pool
 // of `slots` is exhausted); *counter must be zero on entry
 hipError_t launch_assign_slots(const int32_t *cert, int Q, int slots, int32_t *col_slot, int32_t *counter, hipStream_t st);

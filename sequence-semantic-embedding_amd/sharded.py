@@ -137,6 +137,69 @@ class ShardedIndex(object):
             pending = nxt
         return fs, fi
 
+    def set_local_tags(self, tags):
+        """tags: CUDA uint64 (or int64 holding the same bits) tensor [end-start] -- the tag words of this rank's rows, set
+        after set_local_rows.  None clears them; a rank without rows has nothing to tag."""
+        if tags is not None and tags.shape[0] != self.end - self.start:
+            raise ValueError("rank %d holds %d rows, got %d tags" % (self.rank, self.end - self.start, tags.shape[0]))
+        if self.end == self.start:
+            return
+        if tags is None:
+            self.handle.index_set_tags_dev(None, 0)
+            return
+        import torch
+        tags = tags.contiguous()
+        stream = torch.cuda.current_stream(tags.device).cuda_stream if tags.is_cuda else 0
+        self.handle.index_set_tags_dev(tags.data_ptr(), tags.shape[0], stream)
+
+    def score_topk_filtered(self, queries, k, any_of=None, none_of=None, exclude=None):
+        """Handle.score_topk_filtered over the whole sharded index: queries CUDA float32 [Q,S], any_of / none_of int64 [Q]
+        tensors holding the uint64 mask bits (or None), exclude int64 [Q, n] GLOBAL row ids (or None), identical on every
+        rank.  Returns (scores float64 [Q,k], ids int64 [Q,k], counts int32 [Q]) on every rank: what the unsharded call
+        returns.  Every rank makes the local call with the full k (its padding makes short shards uniform; a rank
+        without rows contributes all padding), ONE all-gather exchanges the lists, the k-way merge ranks padding behind
+        every real entry and fills the slots past the real entries with it, ONE all-reduce adds the counts."""
+        import torch
+        import torch.distributed as dist
+        from .collectives import all_gather_into, all_reduce_
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise ValueError("k=%d must be in [1, 1024]" % k)
+        Q = int(queries.shape[0])
+        dev = queries.device
+        n_excl = 0
+        if exclude is not None:
+            if exclude.dim() != 2 or exclude.shape[0] != Q or exclude.dtype != torch.int64 or exclude.shape[1] > 64:
+                raise ValueError("exclude must be int64 [Q, n <= 64]")
+            n_excl = int(exclude.shape[1])
+            exclude = exclude.contiguous() if n_excl else None
+        for m in (any_of, none_of):
+            if m is not None and (m.shape[0] != Q or m.dtype != torch.int64):
+                raise ValueError("any_of / none_of must be int64 [Q] tensors of mask bits")
+        queries = queries.contiguous()
+        any_of = any_of.contiguous() if any_of is not None else None
+        none_of = none_of.contiguous() if none_of is not None else None
+        stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
+        loc = torch.empty((2, Q, k), dtype=torch.int64, device=dev)        # [0] = float64 score bits, [1] = row ids
+        cnt = torch.zeros(Q, dtype=torch.int32, device=dev)
+        if self.end > self.start and Q > 0:
+            self.handle.score_topk_filtered_dev(queries.data_ptr(), Q, k, any_of.data_ptr() if any_of is not None else None,
+                                                none_of.data_ptr() if none_of is not None else None,
+                                                exclude.data_ptr() if exclude is not None else None, n_excl,
+                                                loc[0].data_ptr(), loc[1].data_ptr(), cnt.data_ptr(), stream)
+        else:
+            loc[0].view(torch.float64).fill_(float("-inf"))
+            loc[1].fill_(torch.iinfo(torch.int64).max)
+        if Q == 0 or (self.world == 1 and not self.always_gather):
+            return loc[0].view(torch.float64), loc[1], cnt
+        world = dist.get_world_size(self.group)
+        g = torch.empty((world * 2, Q, k), dtype=torch.int64, device=dev)
+        all_gather_into(g, loc, group=self.group)
+        out = torch.empty((2, Q, k), dtype=torch.int64, device=dev)
+        self.handle.merge_topk_strided_dev(g.data_ptr(), g[1].data_ptr(), 2 * Q * k, world, Q, k, out[0].data_ptr(), out[1].data_ptr(), stream)
+        total = cnt.to(torch.int64)
+        all_reduce_(total, group=self.group)
+        return out[0].view(torch.float64), out[1], torch.clamp(total, max=k).to(torch.int32)
 
     def rank_of(self, queries, pair_q, pair_id):
         """Exact global rank of labelled rows: queries CUDA float32 [Q,S], pair_q int32 [L] (query row of pair p), pair_id

@@ -95,6 +95,35 @@ def near_duplicate_pairs(handle, rows, threshold, block=4096):
     return [(int(ii[o]), int(jj[o]), float(ss[o])) for o in order]
 
 
+def tag_words(groups):
+    """Tag words for Handle.index_set_tags from one group label per row (a meta-category, a language, a shop): `groups` is a
+    sequence of N labels with at most 64 distinct ones.  Returns (uint64 [N] one-hot words, {label: bit}); bits are handed out
+    in order of first appearance, so `1 << bits[label]` is the `any_of` / `none_of` mask that asks for / rules out a group."""
+    bits = {}
+    words = np.zeros(len(groups), np.uint64)
+    for r, g in enumerate(groups):
+        if g not in bits:
+            if len(bits) == 64:
+                raise ValueError("more than 64 distinct group labels: a tag word has 64 bits")
+            bits[g] = len(bits)
+        words[r] = np.uint64(1) << np.uint64(bits[g])
+    return words, bits
+
+
+def hard_negatives(handle, queries, positives, n):
+    """The n best rows of the handle's resident index per query that are NOT among its labelled positives (the reference
+    samples negatives at random, data.py:95-115): `positives` is a sequence of Q sequences of row ids (at most 64 each).
+    Returns (ids int64 [Q,n], scores float64 [Q,n]); a query with fewer than n other rows is padded with (INT64_MAX, -inf)."""
+    width = max([len(p) for p in positives] + [1])
+    if width > 64:
+        raise ValueError("at most 64 positives per query can be excluded, got %d" % width)
+    ex = np.full((len(positives), width), -1, np.int64)      # -1: no row has this id
+    for i, p in enumerate(positives):
+        ex[i, :len(p)] = np.asarray(p, np.int64)
+    scores, ids, _ = handle.score_topk_filtered(queries, n, exclude=ex)
+    return ids, scores
+
+
 def write_near_duplicates(path, tgt_ids, pairs):
     """nearDuplicates.tsv: tgtid_a \\t tgtid_b \\t repr(float64 score), one pair per line."""
     with codecs.open(path, "w", "utf-8") as out:
