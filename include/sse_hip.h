@@ -173,7 +173,8 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value);
  * "score_rank_band_rows" / "score_rank_bruteforce_pairs": see sse_score_rank.
  * "score_above_band_rows" / "score_above_bruteforce_pairs" / "score_above_long_segments": see sse_score_above.
  * "score_filtered_collected_rows" / "score_filtered_bruteforce_queries" / "score_filtered_tiles_skipped": see
- * sse_score_topk_filtered. */
+ * sse_score_topk_filtered.
+ * "score_grouped_collected_rows" / "score_grouped_bruteforce_queries": see sse_score_topk_grouped. */
 int sse_get_counter(sse_handle *h, const char *name, int64_t *value);
 
 /* tf.nn.l2_normalize(x, dim=-1) on device rows (sse_model.py:282-283). */
@@ -291,6 +292,45 @@ int sse_score_topk_filtered(sse_handle *h, const float *q_host, int32_t Q, int32
 int sse_score_topk_filtered_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, const uint64_t *q_any_dev,
                                 const uint64_t *q_none_dev, const int64_t *excl_ids_dev, int32_t n_excl,
                                 double *out_scores_dev, int64_t *out_ids_dev, int32_t *out_counts_dev, void *stream);
+
+/* Group keys of the resident index: one int64 key per row, copied and kept on the device.  Any value is a key (negative
+ * ones, keys above 2^32, INT64_MAX); rows with equal keys form a group.  N must equal the index's row count, otherwise the
+ * call errors with a message and the keys stay as they were.  groups == NULL clears them; setting, uploading or adopting a
+ * new index (sse_index_upload*, sse_index_set_dev) clears them too.  Tags and group keys are independent of each other.  The
+ * _dev form takes a device pointer and enqueues the copy on `stream`. */
+int sse_index_set_groups(sse_handle *h, const int64_t *groups_host, int64_t N);
+int sse_index_set_groups_dev(sse_handle *h, const int64_t *groups_dev, int64_t N, void *stream);
+
+/* Exact top-k DISTINCT groups, when several index rows stand for the same thing: the leaf categories of a title, each
+ * represented by many labelled example titles rather than by its one name (README: "one or multiples of the 20,000+ leaf
+ * categories"), result pages that collapse the listings of one product or near-duplicate cluster.  Row eligibility is the
+ * tag rule of sse_score_topk_filtered (q_any / q_none may be NULL; giving either while no tags are set is an error); there
+ * are no exclusion lists.  For query q take the columns of sse_score_topk(..., k = N) -- the float64 score bits, score
+ * descending, equal scores by ascending id -- remove the ineligible rows, then every row whose group already appeared to its
+ * left.  Of what remains:
+ *   out_counts [Q]: c = min(k, groups with an eligible row).
+ *   out_scores / out_ids / out_groups [Q][k]: columns 0 .. c are the first c entries: each group once, represented by its
+ *     best row (the lowest id among equal bests), ids including id_base, out_groups that row's key; columns c .. k hold
+ *     (-inf, INT64_MAX, INT64_MAX) -- out_counts is authoritative, a real group may carry that key.
+ * 1 <= k <= 1024; k may exceed the number of groups or N.  With every row in a group of its own and no masks the score and id
+ * columns are sse_score_topk's.  The stages are sse_score_topk_filtered's with a threshold from distinct groups: an fp32
+ * MFMA sweep keeps the maxima of tag-eligible rows over disjoint row sets together with their rows, the k-th largest of
+ * the per-group bests among them less twice the certified bound is a threshold the representative of no answer group
+ * scores below, the collect sweep takes every tag-eligible row at or above it, those are re-scored in float64, reduced to
+ * one entry per group and sorted (counter "score_grouped_collected_rows"); a query with more than 4096 such rows -- one
+ * that sits deep inside a large group whose rows all outscore the k-th group -- is served by a float64 sweep of the whole
+ * index with the same reduction ("score_grouped_bruteforce_queries"); the result is exact either way.  Option
+ * "score_filtered_skip" governs the tile skip here too and changes no result.  Scratch is bounded by the chunk of 4096
+ * queries.  Rows or queries of norm below 2^-100 and non-finite input are outside the claim (no fault).
+ * Q == 0 succeeds.  No index, no group keys, k out of range, masks without tags: error with a message, decided on the host
+ * before anything is queued, no output written, the handle stays usable.  The host form runs on the null stream and
+ * synchronises; the _dev form takes device pointers, enqueues on `stream` and never waits for the device. */
+int sse_score_topk_grouped(sse_handle *h, const float *q_host, int32_t Q, int32_t k, const uint64_t *q_any,
+                           const uint64_t *q_none, double *out_scores, int64_t *out_ids, int64_t *out_groups,
+                           int32_t *out_counts);
+int sse_score_topk_grouped_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, const uint64_t *q_any_dev,
+                               const uint64_t *q_none_dev, double *out_scores_dev, int64_t *out_ids_dev,
+                               int64_t *out_groups_dev, int32_t *out_counts_dev, void *stream);
 
 /* encode + score in one call, the encodings never leaving the device: session.run([src_seq_embedding | norm_...])
  * followed by np.dot + getSortedResults[:k] as sse_demo.py:121-129, webserver.py:144-151 (and the three other routes)

@@ -55,6 +55,10 @@ SYMBOLS = {
     "sse_index_set_tags_dev": (C.c_int, [_P, _P, C.c_int64, _P]),
     "sse_score_topk_filtered": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),
     "sse_score_topk_filtered_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    "sse_index_set_groups": (C.c_int, [_P, _P, C.c_int64]),
+    "sse_index_set_groups_dev": (C.c_int, [_P, _P, C.c_int64, _P]),
+    "sse_score_topk_grouped": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "sse_score_topk_grouped_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "sse_encode_score_topk": (C.c_int, [_P, C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_merge_topk_dev": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_merge_topk_strided_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
@@ -413,6 +417,48 @@ class Handle(object):
         """score_topk_filtered on device pointers (any_ptr / none_ptr / excl_ptr may be None / 0), enqueued on `stream`."""
         self.check(self.lib.sse_score_topk_filtered_dev(self._h, q_ptr, int(Q), int(k), any_ptr or None, none_ptr or None,
                                                         excl_ptr or None, int(n_excl), scores_ptr, ids_ptr, counts_ptr, stream))
+
+    def index_set_groups(self, groups):
+        """One int64 group key per row of the resident index (groups=None clears them); a new index clears them too."""
+        if groups is None:
+            self.check(self.lib.sse_index_set_groups(self._h, None, 0))
+            return
+        g = np.ascontiguousarray(groups, dtype=np.int64).reshape(-1)
+        self.check(self.lib.sse_index_set_groups(self._h, _ptr(g), g.shape[0]))
+
+    def index_set_groups_dev(self, groups_ptr, N, stream=0):
+        """index_set_groups from a device pointer of N int64 keys (None / 0 clears), copied on `stream`."""
+        self.check(self.lib.sse_index_set_groups_dev(self._h, groups_ptr or None, int(N), stream))
+
+    def score_topk_grouped(self, queries, k, any_of=None, none_of=None):
+        """Exact top-k distinct groups of index rows (keys: index_set_groups).  any_of / none_of: uint64 [Q] tag masks, the
+        eligibility rule of score_topk_filtered.  Returns (scores float64 [Q,k], ids int64 [Q,k], groups int64 [Q,k], counts
+        int32 [Q]): the first counts[q] columns hold each group once, represented by its best eligible row (the lowest id
+        among equal bests), best group first; the rest hold (-inf, INT64_MAX, INT64_MAX)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError("queries must be [Q,S]")
+        Q, k = q.shape[0], int(k)
+        masks = []
+        for m in (any_of, none_of):
+            if m is not None:
+                m = np.ascontiguousarray(m, dtype=np.uint64).reshape(-1)
+                if m.shape[0] != Q:
+                    raise ValueError("any_of / none_of must be uint64 [Q]")
+            masks.append(m)
+        scores = np.empty((Q, max(k, 0)), np.float64)
+        ids = np.empty((Q, max(k, 0)), np.int64)
+        groups = np.empty((Q, max(k, 0)), np.int64)
+        counts = np.empty(Q, np.int32)
+        self.check(self.lib.sse_score_topk_grouped(self._h, _ptr(q), Q, k, _ptr(masks[0]) if masks[0] is not None else None,
+                                                   _ptr(masks[1]) if masks[1] is not None else None,
+                                                   _ptr(scores), _ptr(ids), _ptr(groups), _ptr(counts)))
+        return scores, ids, groups, counts
+
+    def score_topk_grouped_dev(self, q_ptr, Q, k, any_ptr, none_ptr, scores_ptr, ids_ptr, groups_ptr, counts_ptr, stream=0):
+        """score_topk_grouped on device pointers (any_ptr / none_ptr may be None / 0), enqueued on `stream`."""
+        self.check(self.lib.sse_score_topk_grouped_dev(self._h, q_ptr, int(Q), int(k), any_ptr or None, none_ptr or None,
+                                                       scores_ptr, ids_ptr, groups_ptr, counts_ptr, stream))
 
     def merge_topk_strided_dev(self, in_s, in_i, shard_stride, P, Q, k, out_s, out_i, stream=0):
         self.check(self.lib.sse_merge_topk_strided_dev(self._h, in_s, in_i, int(shard_stride), P, Q, k, out_s, out_i, stream))

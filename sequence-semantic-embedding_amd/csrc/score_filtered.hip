@@ -21,16 +21,7 @@
 // query block, none of whose queries is unrestricted, has no eligible row for any of them: the wave moves on.
 #include "sse_kernels.h"
 #include "score_exact.h"
-
-#define FT_THREADS 512       // the sweep: 8 waves = 2 per SIMD, as score_rank_kernel
-#define FT_MAXSPLIT 16       // splits with maxima slots of their own
-#define FT_KEY_NINF 0x007FFFFFu  // key of -inf: finite scores have larger keys, 0 = empty slot
-
-__device__ __forceinline__ uint32_t ft_key(float x) {
-  const uint32_t u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ft_unkey(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
+#include "score_filtered_common.h"
 
 __global__ void tag_tile_summary_kernel(const uint64_t *tags, int64_t NT, uint64_t *tile_sum) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -238,24 +229,6 @@ __global__ __launch_bounds__(FT_THREADS) void score_filtered_kernel(FilteredArgs
   }
 }
 
-// bitonic sort of n2 (power of two) keys in LDS, descending
-__device__ __forceinline__ void ft_sort_u32(uint32_t *key, int n2, int tid, int nthr) {
-  for (int size = 2; size <= n2; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int i = tid; i < (n2 >> 1); i += nthr) {
-        const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
-        const bool desc = ((lo & size) == 0);
-        const uint32_t x = key[lo], y = key[hi];
-        if ((x < y) == desc) {
-          key[lo] = y;
-          key[hi] = x;
-        }
-      }
-    }
-  __syncthreads();
-}
-
 // one workgroup per query: collect threshold from the (k + n_excl)-th largest of its NV maxima
 __global__ __launch_bounds__(256) void filtered_threshold_kernel(FilteredArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t th_key[];  // [NV]
@@ -280,14 +253,6 @@ __global__ __launch_bounds__(256) void filtered_threshold_kernel(FilteredArgs a)
   }
 }
 
-__device__ __forceinline__ unsigned long long ft_key64(double x) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(x);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double ft_unkey64(unsigned long long u) {
-  return __longlong_as_double((long long)((u >> 63) ? (u & 0x7FFFFFFFFFFFFFFFull) : ~u));
-}
-
 // bitonic sort of n2 (power of two) entries in LDS by (key descending, row ascending): the order of before()
 __device__ __forceinline__ void ft_sort_entries(unsigned long long *skey, int *srow, int n2, int tid) {
   for (int size = 2; size <= n2; size <<= 1)
@@ -309,8 +274,6 @@ __device__ __forceinline__ void ft_sort_entries(unsigned long long *skey, int *s
     }
   __syncthreads();
 }
-
-#define FT_PAD_ROW 0x7FFFFFFF  // (padding entries: key 0 is below the key of every score, -inf included)
 
 // is id among the query's exclusion list?  One lane per entry (n_excl <= 64); the answer is wave-uniform.
 __device__ __forceinline__ bool ft_excluded(const int64_t *ex, int n_excl, int64_t id, int lane) {
@@ -487,4 +450,14 @@ hipError_t launch_score_filtered(const FilteredArgs &a, hipStream_t st) {
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(filtered_select_kernel, dim3(a.P), dim3(256), lds, st, a);
   return hipGetLastError();
+}
+
+// the collect sweep alone (stage 3), for callers with a threshold of their own: sse_score_topk_grouped (score_grouped.hip)
+hipError_t launch_filtered_collect(const FilteredArgs &a, hipStream_t st) {
+  if (a.P <= 0) return hipSuccess;
+  if (a.col_cap != SSE_COLLECT_CAP || a.NSPLIT < 1 || (a.NSPLIT & (a.NSPLIT - 1))) return hipErrorInvalidValue;
+  if (a.NQ == 4) return launch_filtered_sweep<4, true>(a, st);
+  if (a.NQ == 2) return launch_filtered_sweep<2, true>(a, st);
+  if (a.NQ == 1) return launch_filtered_sweep<1, true>(a, st);
+  return hipErrorInvalidValue;
 }

@@ -242,6 +242,10 @@ struct sse_handle {
   DevBuf idx_tags, idx_tag_sum, s_ft_max, s_ft_cnt, s_ft_in;
   bool tags_set = false, ft_cnt_init = false;
   bool score_filtered_skip = true;  // option "score_filtered_skip": the sweeps skip index tiles no query of a block can use
+  // top-k distinct groups (sse_score_topk_grouped*, score_grouped.hip): one int64 key per row of the resident index, valid
+  // while groups_set; the (key, row) maxima of a chunk, the two "score_grouped_*" counters, staging of the host form
+  DevBuf idx_groups, s_gp_max, s_gp_cnt, s_gp_in;
+  bool groups_set = false, gp_cnt_init = false;
   // forward-only pair loss (sse_eval_loss*, eval_loss.hip).  Option "eval_chunk_rows": pair rows staged and encoded per chunk (even).
   // Scratch of its own: a gradient result pending between sse_train_grads and sse_train_apply lives in TrainState and the arena.
   int eval_chunk_rows = 65536;
@@ -1022,6 +1026,7 @@ int index_from_dev_rows(sse_handle *h, const float *rows_dev, int64_t N, int S, 
   const int KG = (S + 7) / 8;
   const int64_t NT = (N + 31) / 32;
   h->tags_set = false;  // (tags belong to the rows they were set for)
+  h->groups_set = false;  // (and so do group keys)
   // fragment-order copy of the index: grow-only (re-indexing with the same or a smaller shard reuses the allocation)
   const size_t need = (size_t)NT * KG * 256 * sizeof(float);
   if (need > h->idxp_cap) {
@@ -1466,6 +1471,108 @@ static int score_filtered_dev_locked(sse_handle *h, const float *q, int Q, int k
     a.NSPLIT = nsplit;
     a.NV = NV;
     HIPCHECK(h, launch_score_filtered(a, st));
+  }
+  return 0;
+}
+
+// sse_index_set_groups*: the keys copied behind the index (device to device on `st`, or from the host).  Nothing changes
+// before every check and allocation has passed.
+static int index_set_groups_locked(sse_handle *h, const int64_t *groups, int64_t N, bool from_host, hipStream_t st) {
+  if (!groups) {
+    h->groups_set = false;
+    return 0;
+  }
+  if (!h->idxp) return fail(h, "sse_index_set_groups: no index uploaded");
+  if (N != h->idx_N) return fail(h, "sse_index_set_groups: %lld keys for an index of %lld rows; the keys are unchanged", (long long)N, (long long)h->idx_N);
+  if (!h->groups_set) {  // (live keys are never reallocated: the size is the index's)
+    if (reserve(h, h->idx_groups, (size_t)N * sizeof(int64_t))) return 1;
+  }
+  if (from_host) HIPCHECK(h, hipMemcpy(h->idx_groups.p, groups, (size_t)N * sizeof(int64_t), hipMemcpyHostToDevice));
+  else HIPCHECK(h, hipMemcpyAsync(h->idx_groups.p, groups, (size_t)N * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+  h->groups_set = true;
+  return 0;
+}
+
+// argument errors of sse_score_topk_grouped*, all decidable on the host
+static int score_grouped_check(sse_handle *h, int Q, int k, const void *q_any, const void *q_none) {
+  if (!h->idxp) return fail(h, "sse_score_topk_grouped: no index uploaded");
+  if (!h->groups_set) return fail(h, "sse_score_topk_grouped: the index has no group keys (sse_index_set_groups)");
+  if (Q < 0) return fail(h, "bad arguments to sse_score_topk_grouped");
+  if (k < 1 || k > SSE_GROUPED_MAX_K) return fail(h, "sse_score_topk_grouped: k = %d is not in [1, %d]", k, SSE_GROUPED_MAX_K);
+  if ((q_any || q_none) && !h->tags_set) return fail(h, "sse_score_topk_grouped: tag masks given but the index has no tags (sse_index_set_tags)");
+  return 0;
+}
+
+// sse_score_topk_grouped*: every stage queued on `st` (device pointers throughout), queries in chunks of 4096 with the chunk
+// scratch of the filtered call (thresholds, row buffers) and (key, row) maxima [P][NV] of its own (DESIGN K6h).
+static int score_grouped_dev_locked(sse_handle *h, const float *q, int Q, int k, const uint64_t *q_any, const uint64_t *q_none,
+                                    double *out_s, int64_t *out_i, int64_t *out_g, int32_t *out_c, hipStream_t st) {
+  const int POOL = 4096;
+  const int S = h->idx_S, KG = (S + 7) / 8;
+  const int64_t NT = (h->idx_N + 31) / 32;
+  if (reserve(h, h->s_gp_cnt, 3 * sizeof(unsigned long long))) return 1;
+  if (!h->gp_cnt_init) {
+    HIPCHECK(h, hipMemsetAsync(h->s_gp_cnt.p, 0, 3 * sizeof(unsigned long long), st));
+    h->gp_cnt_init = true;
+  }
+  GroupedArgs g;
+  FilteredArgs &a = g.rest;
+  a.idxp = h->idxp;
+  a.idx64 = h->idx64;
+  a.tags = h->tags_set ? (const uint64_t *)h->idx_tags.p : nullptr;
+  a.tile_sum = h->tags_set ? (const uint64_t *)h->idx_tag_sum.p : nullptr;
+  a.excl = nullptr;
+  a.maxima = nullptr;
+  a.col_cap = SSE_COLLECT_CAP;
+  a.counters = (unsigned long long *)h->s_gp_cnt.p;
+  a.id_base = h->idx_base;
+  a.N = h->idx_N;
+  a.S = S;
+  a.KG = KG;
+  a.NT = (int)NT;
+  a.k = k;
+  a.n_excl = 0;
+  a.skip = h->score_filtered_skip ? 1 : 0;
+  a.eps32 = (float)(2.0 * (S + 2) * 5.97e-8 * h->idx_norm_max);
+  g.groups = (const int64_t *)h->idx_groups.p;
+  for (int q0 = 0; q0 < Q; q0 += POOL) {
+    const int P = std::min(POOL, Q - q0);
+    const int NQ = score_pick_nq(P, S, 0);
+    if (NQ == 0) return fail(h, "index dimension %d does not fit the scoring kernel's LDS query block", S);
+    const int nsplit = choose_nsplit(NQ, (P + NQ * 32 - 1) / (NQ * 32), NT);
+    // the eligible-max sweep: at most 2 query tiles per workgroup (the tile of every maximum costs 16 registers per query
+    // tile) and at least 4 k maxima per query where every wave of a split still has a tile of its own: the maxima of several
+    // row sets share groups, and theta needs k DISTINCT groups among them (DESIGN K6h)
+    const int NQM = std::min(NQ, 2);
+    int msplit = choose_nsplit(NQM, (P + NQM * 32 - 1) / (NQM * 32), NT);
+    while (msplit < 128 && msplit * 256 < 4 * k && NT / (msplit * 2) >= 8) msplit *= 2;
+    const int NV = std::min(msplit, 16) * 256;
+    if (reserve(h, h->s_gp_max, (size_t)P * NV * sizeof(unsigned long long))) return 1;
+    if (reserve(h, h->s_cthr, (size_t)P * sizeof(float))) return 1;
+    if (reserve(h, h->s_ccnt, (size_t)(P + 1) * sizeof(int32_t))) return 1;
+    if (reserve(h, h->s_cbuf, (size_t)P * SSE_COLLECT_CAP * sizeof(int32_t))) return 1;
+    HIPCHECK(h, hipMemsetAsync(h->s_gp_max.p, 0, (size_t)P * NV * sizeof(unsigned long long), st));
+    HIPCHECK(h, hipMemsetAsync(h->s_ccnt.p, 0, (size_t)P * sizeof(int32_t), st));
+    a.q = q + (size_t)q0 * S;
+    a.q_any = q_any ? q_any + q0 : nullptr;
+    a.q_none = q_none ? q_none + q0 : nullptr;
+    a.thr = (float *)h->s_cthr.p;
+    a.col_cnt = (int32_t *)h->s_ccnt.p;
+    a.col_buf = (int32_t *)h->s_cbuf.p;
+    a.out_scores = out_s + (size_t)q0 * k;
+    a.out_ids = out_i + (size_t)q0 * k;
+    a.out_counts = out_c + q0;
+    a.P = P;
+    a.NQ = NQ;
+    a.NSPLIT = nsplit;
+    a.NV = std::min(nsplit, 16) * 256;
+    g.max = a;
+    g.max.NQ = NQM;
+    g.max.NSPLIT = msplit;
+    g.max.NV = NV;
+    g.maxima64 = (unsigned long long *)h->s_gp_max.p;
+    g.out_groups = out_g + (size_t)q0 * k;
+    HIPCHECK(h, launch_score_grouped(g, st));
   }
   return 0;
 }
@@ -2267,6 +2374,18 @@ int sse_get_counter(sse_handle *h, const char *name, int64_t *value) {
     *value = (int64_t)v[i];
     return 0;
   }
+  static const char *const grouped_names[2] = {"score_grouped_collected_rows", "score_grouped_bruteforce_queries"};
+  for (int i = 0; i < 2; ++i) {  // sse_score_topk_grouped*: rows re-scored by the select stage, queries of the float64 sweep
+    if (strcmp(name, grouped_names[i]) != 0) continue;
+    unsigned long long v[3] = {0, 0, 0};
+    if (h->s_gp_cnt.p && h->gp_cnt_init) {
+      HIPCHECK(h, hipSetDevice(h->cfg.device));
+      HIPCHECK(h, hipDeviceSynchronize());
+      HIPCHECK(h, hipMemcpy(v, h->s_gp_cnt.p, sizeof v, hipMemcpyDeviceToHost));
+    }
+    *value = (int64_t)v[i];
+    return 0;
+  }
   static const char *const names[3] = {"score_bf16_second_chance_queries", "score_collect_queries", "score_bruteforce_queries"};
   for (int i = 0; i < 3; ++i) {
     if (strcmp(name, names[i]) != 0) continue;
@@ -2676,6 +2795,67 @@ int sse_score_topk_filtered(sse_handle *h, const float *q_host, int32_t Q, int32
   HIPCHECK(h, sync_stream(nullptr));
   HIPCHECK(h, hipMemcpy(out_scores, d_s, o8, hipMemcpyDeviceToHost));
   HIPCHECK(h, hipMemcpy(out_ids, d_i, o8, hipMemcpyDeviceToHost));
+  HIPCHECK(h, hipMemcpy(out_counts, d_c, (size_t)Q * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int sse_index_set_groups(sse_handle *h, const int64_t *groups_host, int64_t N) {
+  if (!h) return 1;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  if (index_set_groups_locked(h, groups_host, N, true, nullptr)) return 1;
+  HIPCHECK(h, hipStreamSynchronize(nullptr));
+  return 0;
+}
+
+int sse_index_set_groups_dev(sse_handle *h, const int64_t *groups_dev, int64_t N, void *stream) {
+  if (!h) return 1;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  return index_set_groups_locked(h, groups_dev, N, false, (hipStream_t)stream);
+}
+
+int sse_score_topk_grouped_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, const uint64_t *q_any_dev,
+                               const uint64_t *q_none_dev, double *out_scores_dev, int64_t *out_ids_dev,
+                               int64_t *out_groups_dev, int32_t *out_counts_dev, void *stream) {
+  if (!h) return 1;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  if (score_grouped_check(h, Q, k, q_any_dev, q_none_dev)) return 1;
+  if (Q == 0) return 0;
+  if (!q_dev || !out_scores_dev || !out_ids_dev || !out_groups_dev || !out_counts_dev) return fail(h, "bad arguments to sse_score_topk_grouped");
+  return score_grouped_dev_locked(h, q_dev, Q, k, q_any_dev, q_none_dev, out_scores_dev, out_ids_dev, out_groups_dev,
+                                  out_counts_dev, (hipStream_t)stream);
+}
+
+int sse_score_topk_grouped(sse_handle *h, const float *q_host, int32_t Q, int32_t k, const uint64_t *q_any,
+                           const uint64_t *q_none, double *out_scores, int64_t *out_ids, int64_t *out_groups,
+                           int32_t *out_counts) {
+  if (!h) return 1;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  if (score_grouped_check(h, Q, k, q_any, q_none)) return 1;
+  if (Q == 0) return 0;
+  if (!q_host || !out_scores || !out_ids || !out_groups || !out_counts) return fail(h, "bad arguments to sse_score_topk_grouped");
+  const size_t S = h->idx_S;
+  // staging (8-byte items first): scores | ids | groups | any | none | queries | counts
+  const size_t o8 = (size_t)Q * k * 8, m8 = (size_t)Q * 8;
+  const size_t qb = ((size_t)Q * S * sizeof(float) + 7) & ~(size_t)7;
+  if (reserve(h, h->s_gp_in, 3 * o8 + 2 * m8 + qb + (size_t)Q * 4)) return 1;
+  char *b = (char *)h->s_gp_in.p;
+  double *d_s = (double *)b;
+  int64_t *d_i = (int64_t *)(b + o8), *d_g = (int64_t *)(b + 2 * o8);
+  uint64_t *d_any = (uint64_t *)(b + 3 * o8), *d_none = (uint64_t *)(b + 3 * o8 + m8);
+  float *d_q = (float *)(b + 3 * o8 + 2 * m8);
+  int32_t *d_c = (int32_t *)(b + 3 * o8 + 2 * m8 + qb);
+  HIPCHECK(h, hipMemcpy(d_q, q_host, (size_t)Q * S * sizeof(float), hipMemcpyHostToDevice));
+  if (q_any) HIPCHECK(h, hipMemcpy(d_any, q_any, m8, hipMemcpyHostToDevice));
+  if (q_none) HIPCHECK(h, hipMemcpy(d_none, q_none, m8, hipMemcpyHostToDevice));
+  if (score_grouped_dev_locked(h, d_q, Q, k, q_any ? d_any : nullptr, q_none ? d_none : nullptr, d_s, d_i, d_g, d_c, nullptr)) return 1;
+  HIPCHECK(h, sync_stream(nullptr));
+  HIPCHECK(h, hipMemcpy(out_scores, d_s, o8, hipMemcpyDeviceToHost));
+  HIPCHECK(h, hipMemcpy(out_ids, d_i, o8, hipMemcpyDeviceToHost));
+  HIPCHECK(h, hipMemcpy(out_groups, d_g, o8, hipMemcpyDeviceToHost));
   HIPCHECK(h, hipMemcpy(out_counts, d_c, (size_t)Q * 4, hipMemcpyDeviceToHost));
   return 0;
 }

@@ -525,6 +525,21 @@ struct FilteredArgs {
 #define SSE_FILTERED_MAX_K 1024
 #define SSE_FILTERED_MAX_EXCL 64
 hipError_t launch_score_filtered(const FilteredArgs &a, hipStream_t st);  // every stage of one chunk
+hipError_t launch_filtered_collect(const FilteredArgs &a, hipStream_t st);  // the collect sweep alone: a.thr given, col_cnt zeroed
+
+// Exact top-k distinct groups among tag-eligible rows (score_grouped.hip, DESIGN K6h): the stages of FilteredArgs with a
+// threshold from distinct groups and a group reduction in the select stage; no exclusion lists (excl = nullptr, n_excl = 0).
+// `max` describes the eligible-max sweep and the threshold (NQ <= 2, its own NSPLIT and NV; its slots are maxima64 [P][NV]:
+// key << 32 | shard-local row, 0 = empty, zeroed by the caller), `rest` the collect sweep and the select.  counters of `rest`:
+// [0] rows re-scored by the select stage, [1] queries of the float64 sweep.
+struct GroupedArgs {
+  FilteredArgs max, rest;
+  const int64_t *groups;            // [N] group key per row
+  unsigned long long *maxima64;     // [P][max.NV]
+  int64_t *out_groups;              // [P][k]
+};
+#define SSE_GROUPED_MAX_K 1024
+hipError_t launch_score_grouped(const GroupedArgs &g, hipStream_t st);  // every stage of one chunk
 // tile_sum[t] = OR of tags[32 t .. 32 t + 32) (tags padded with zero words to NT * 32)
 hipError_t launch_tag_tile_summary(const uint64_t *tags, int64_t NT, uint64_t *tile_sum, hipStream_t st);
 

@@ -68,6 +68,40 @@ def merge_above_runs(pair, scores, ids, L):
     return offsets, ids[o], scores[o]
 
 
+def merge_grouped_lists(scores, ids, groups, k):
+    """The merge of ShardedIndex.score_topk_grouped on torch tensors of any device: the shards' lists side by side (scores
+    float64 [Q,M], ids int64 [Q,M], groups int64 [Q,M]; padding entries carry id INT64_MAX) -> (scores [Q,k], ids [Q,k],
+    groups [Q,k], counts int32 [Q]).  A group may live on several shards, so the lists are collapsed again: entries ordered by
+    (score descending, id ascending), the first entry of each group kept, cut to k, padded with (-inf, INT64_MAX, INT64_MAX);
+    the count is the number of distinct groups kept."""
+    import torch
+    Q, M = scores.shape
+    pad = torch.iinfo(torch.int64).max
+    out_s = torch.full((Q, k), float("-inf"), dtype=torch.float64, device=scores.device)
+    out_i = torch.full((Q, k), pad, dtype=torch.int64, device=scores.device)
+    out_g = torch.full((Q, k), pad, dtype=torch.int64, device=scores.device)
+    if Q == 0 or M == 0:
+        return out_s, out_i, out_g, torch.zeros(Q, dtype=torch.int32, device=scores.device)
+    # rank of every entry in (score descending, id ascending): two stable sorts, least significant key first
+    o = torch.sort(ids, dim=1, stable=True).indices
+    o = torch.gather(o, 1, torch.sort(torch.gather(scores, 1, o), dim=1, descending=True, stable=True).indices)
+    s, i, g = torch.gather(scores, 1, o), torch.gather(ids, 1, o), torch.gather(groups, 1, o)
+    # an entry is its group's first iff its position is the least of its group: stable sort by group, heads of the runs
+    og = torch.sort(g, dim=1, stable=True).indices
+    gs = torch.gather(g, 1, og)
+    head = torch.ones((Q, M), dtype=torch.bool, device=scores.device)
+    head[:, 1:] = gs[:, 1:] != gs[:, :-1]
+    keep = torch.zeros((Q, M), dtype=torch.bool, device=scores.device)
+    keep.scatter_(1, og, head)
+    keep &= i != pad                                            # padding stands for no group
+    rank = torch.cumsum(keep.to(torch.int64), 1) - 1           # column of a kept entry
+    take = keep & (rank < k)
+    rows = torch.arange(Q, device=scores.device).unsqueeze(1).expand(Q, M)[take]
+    cols = rank[take]
+    out_s[rows, cols], out_i[rows, cols], out_g[rows, cols] = s[take], i[take], g[take]
+    return out_s, out_i, out_g, take.sum(1).to(torch.int32)
+
+
 class ShardedIndex(object):
     """One rank's view of the sharded index.  `handle` is an sse_amd Handle."""
 
@@ -200,6 +234,62 @@ class ShardedIndex(object):
         total = cnt.to(torch.int64)
         all_reduce_(total, group=self.group)
         return out[0].view(torch.float64), out[1], torch.clamp(total, max=k).to(torch.int32)
+
+    def set_local_groups(self, groups):
+        """groups: CUDA int64 tensor [end-start] -- the group keys of this rank's rows, set after set_local_rows.  None
+        clears them; a rank without rows has nothing to group."""
+        if groups is not None and groups.shape[0] != self.end - self.start:
+            raise ValueError("rank %d holds %d rows, got %d group keys" % (self.rank, self.end - self.start, groups.shape[0]))
+        if self.end == self.start:
+            return
+        if groups is None:
+            self.handle.index_set_groups_dev(None, 0)
+            return
+        import torch
+        if groups.dtype != torch.int64:
+            raise ValueError("group keys must be an int64 tensor")
+        groups = groups.contiguous()
+        stream = torch.cuda.current_stream(groups.device).cuda_stream if groups.is_cuda else 0
+        self.handle.index_set_groups_dev(groups.data_ptr(), groups.shape[0], stream)
+
+    def score_topk_grouped(self, queries, k, any_of=None, none_of=None):
+        """Handle.score_topk_grouped over the whole sharded index: queries CUDA float32 [Q,S], any_of / none_of int64 [Q]
+        tensors holding the uint64 mask bits (or None), identical on every rank.  Returns (scores float64 [Q,k], ids int64
+        [Q,k], groups int64 [Q,k], counts int32 [Q]) on every rank: what the unsharded call returns.  Every rank makes the
+        local call with the full k (a rank without rows contributes all padding), ONE all-gather carries scores, ids and
+        groups, merge_grouped_lists collapses the groups again.  Exact: were the representative of an answer group missing
+        from its rank's local top-k, k other groups would beat it on that rank alone."""
+        import torch
+        import torch.distributed as dist
+        from .collectives import all_gather_into
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise ValueError("k=%d must be in [1, 1024]" % k)
+        Q = int(queries.shape[0])
+        dev = queries.device
+        for m in (any_of, none_of):
+            if m is not None and (m.shape[0] != Q or m.dtype != torch.int64):
+                raise ValueError("any_of / none_of must be int64 [Q] tensors of mask bits")
+        queries = queries.contiguous()
+        any_of = any_of.contiguous() if any_of is not None else None
+        none_of = none_of.contiguous() if none_of is not None else None
+        stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
+        loc = torch.empty((3, Q, k), dtype=torch.int64, device=dev)        # float64 score bits | row ids | group keys
+        cnt = torch.zeros(Q, dtype=torch.int32, device=dev)
+        if self.end > self.start and Q > 0:
+            self.handle.score_topk_grouped_dev(queries.data_ptr(), Q, k, any_of.data_ptr() if any_of is not None else None,
+                                               none_of.data_ptr() if none_of is not None else None,
+                                               loc[0].data_ptr(), loc[1].data_ptr(), loc[2].data_ptr(), cnt.data_ptr(), stream)
+        else:
+            loc[0].view(torch.float64).fill_(float("-inf"))
+            loc[1:].fill_(torch.iinfo(torch.int64).max)
+        if Q == 0 or (self.world == 1 and not self.always_gather):
+            return loc[0].view(torch.float64), loc[1], loc[2], cnt
+        world = dist.get_world_size(self.group)
+        g = torch.empty((world * 3, Q, k), dtype=torch.int64, device=dev)
+        all_gather_into(g, loc, group=self.group)
+        g = g.view(world, 3, Q, k).permute(1, 2, 0, 3).reshape(3, Q, world * k)   # the shards' lists side by side
+        return merge_grouped_lists(g[0].view(torch.float64), g[1], g[2], k)
 
     def rank_of(self, queries, pair_q, pair_id):
         """Exact global rank of labelled rows: queries CUDA float32 [Q,S], pair_q int32 [L] (query row of pair p), pair_id

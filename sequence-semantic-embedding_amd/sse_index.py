@@ -110,6 +110,32 @@ def tag_words(groups):
     return words, bits
 
 
+def group_keys(labels):
+    """Group keys for Handle.index_set_groups from one label per row (a leaf category, a product, a cluster number): `labels`
+    is a sequence of N hashable labels.  Returns (int64 [N] keys, {label: key}).  An integer that fits int64 is its own key;
+    every other label gets, in order of first appearance, the smallest key >= 0 that no integer label uses."""
+    lo, hi = -(1 << 63), (1 << 63) - 1
+
+    def own(g):
+        return isinstance(g, (int, np.integer)) and lo <= int(g) <= hi
+
+    table = {}
+    taken = {int(g) for g in labels if own(g)}
+    nxt = 0
+    keys = np.zeros(len(labels), np.int64)
+    for r, g in enumerate(labels):
+        if g not in table:
+            if own(g):
+                table[g] = int(g)
+            else:
+                while nxt in taken:
+                    nxt += 1
+                table[g] = nxt
+                nxt += 1
+        keys[r] = table[g]
+    return keys, table
+
+
 def hard_negatives(handle, queries, positives, n):
     """The n best rows of the handle's resident index per query that are NOT among its labelled positives (the reference
     samples negatives at random, data.py:95-115): `positives` is a sequence of Q sequences of row ids (at most 64 each).
