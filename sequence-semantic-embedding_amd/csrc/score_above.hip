@@ -6,7 +6,7 @@
 // pair_thr[p]) gets exactly the rows r with score64(q, r) >= pair_thr[p] -- the float64 dot product sse_score_topk returns for
 // that row -- as a segment of per-pair length, sorted the way sse_score_topk ranks (DESIGN K6f):
 //   1. above_prepare_kernel: the threshold narrowed outward to an fp32 interval [lo, hi] (the bound of score_rank.hip).
-//   2. score_above_kernel<NQ, false>: the count sweep of score_rank_kernel on v_mfma_f32_32x32x2_f32: x > hi adds 1 to the
+//   2. score_above_kernel<NQ, false>: the shared sweep (score_sweep.h) on v_mfma_f32_32x32x2_f32: x > hi adds 1 to the
 //      pair's sure count, lo <= x <= hi appends the row to the pair's band buffer.
 //   3. above_resolve_kernel / above_bruteforce_kernel: band rows decided in float64; a band that outgrew its buffer makes the
 //      pair an "overflowed" one, counted (and later listed) by a float64 sweep of the whole index.  Counts are exact.
@@ -23,8 +23,8 @@
 //      the total order makes the result deterministic.
 #include "sse_kernels.h"
 #include "score_exact.h"
+#include "score_sweep.h"
 
-#define AB_THREADS 512     // the sweep: 8 waves = 2 per SIMD, as score_rank_kernel
 #define AB_SORT_THREADS 1024
 #define AB_ERR_PAIR 32     // device error word: a pair_q out of range
 #define AB_ERR_PASSES 64   // device error word: the emitting pass found other rows than the counting pass
@@ -76,48 +76,20 @@ __global__ __launch_bounds__(256) void above_prepare_kernel(AboveArgs a) {
   }
 }
 
-// The sweep of score_rank_kernel (see there for the layout): workgroup = (block of NQ x 32 pairs, index split), a wave walks
-// the split's tiles, a lane owns pair column (lane & 31) of every pair tile and 16 rows of the index tile.  EMIT: rows above
-// hi are appended to the pair's segment instead of counted.
+// The shared sweep (score_sweep.h), one (query, threshold) pair per column.  EMIT: rows above hi are appended to the pair's
+// segment instead of counted.
 template <int NQ, bool EMIT>
-__global__ __launch_bounds__(AB_THREADS) void score_above_kernel(AboveArgs a) {
+__global__ __launch_bounds__(SWEEP_THREADS) void score_above_kernel(AboveArgs a) {
   extern __shared__ __attribute__((aligned(16))) float ab_smem[];  // [KG][NQ][256]
-  constexpr int PF = 4;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int KG = a.KG;
   if (above_skip(a)) return;  // (uniform)
   int split, qb;
-  {
-    const int b = blockIdx.x, xcd = b & 7, j = b >> 3;
-    if (a.NSPLIT <= 8) {
-      const int per = 8 / a.NSPLIT;
-      split = xcd / per;
-      qb = j * per + xcd % per;
-    } else {
-      const int m = a.NSPLIT >> 3;
-      split = xcd + 8 * (j % m);
-      qb = j / m;
-    }
-  }
+  sweep_decode(a.NSPLIT, split, qb);
   if (qb * NQ * 32 >= a.P) return;
 
-  {
-    f32x4 *dst = reinterpret_cast<f32x4 *>(ab_smem);
-    const int Sd = a.S;
-    for (int i = tid; i < NQ * KG * 64; i += AB_THREADS) {
-      const int kg = (i >> 6) / NQ, l = i & 63, pair = (qb * NQ + (i >> 6) % NQ) * 32 + (l & 31);
-      f32x4 v = {0, 0, 0, 0};
-      if (pair < a.P) {
-        const int k0 = kg * 8 + (l >> 5) * 4;
-        const float *src = a.q + (size_t)a.pair_q[pair] * Sd + k0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (k0 + e < Sd) v[e] = src[e];
-      }
-      dst[i] = v;
-    }
-  }
+  sweep_stage_queries<NQ, true>(ab_smem, a.q, a.pair_q, qb, a.P, a.S, KG, tid);
   float lo[NQ], hi[NQ];
   int pr[NQ], cnt[NQ];
 #pragma unroll
@@ -130,61 +102,22 @@ __global__ __launch_bounds__(AB_THREADS) void score_above_kernel(AboveArgs a) {
   }
   __syncthreads();
 
-  const int tps = (a.NT + a.NSPLIT - 1) / a.NSPLIT;  // n-tiles per split
-  const int t0 = split * tps, t1 = min(a.NT, t0 + tps);
+  int t0, t1;
+  sweep_tile_range(a.NT, a.NSPLIT, split, t0, t1);
   const float *qs = ab_smem + lane * 4;
-  const int tail_tile = (a.N & 31) ? (int)(a.N >> 5) : -1;
+  const int tail_tile = sweep_tail_tile(a.N);
   const int nlim = (int)a.N;
 
-  for (int tile = t0 + w; tile < t1; tile += AB_THREADS / 64) {
-    const f32x4 *ap = reinterpret_cast<const f32x4 *>(a.idxp) + (size_t)tile * KG * 64 + lane;
-    f32x16 acc[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) acc[q] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const int rem = KG & (PF - 1);
-    f32x4 ar[PF];
-#pragma unroll
-    for (int d = 0; d < PF; ++d) ar[d] = ap[(size_t)min(rem + d, KG - 1) * 64];
-    __builtin_amdgcn_s_setprio(1);
-    for (int kg = 0; kg < rem; ++kg) {
-      const f32x4 av = ap[(size_t)kg * 64];
-      f32x4 bq[NQ];
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) bq[q] = *reinterpret_cast<const f32x4 *>(qs + ((size_t)kg * NQ + q) * 256);
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], bq[q][e], acc[q], 0, 0, 0);
-    }
-    f32x4 bq[NQ], bqn[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) bq[q] = *reinterpret_cast<const f32x4 *>(qs + ((size_t)min(rem, KG - 1) * NQ + q) * 256);
-    for (int kg0 = rem; kg0 < KG; kg0 += PF) {
-#pragma unroll
-      for (int d = 0; d < PF; ++d) {
-        const int kg = kg0 + d;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) bqn[q] = *reinterpret_cast<const f32x4 *>(qs + ((size_t)min(kg + 1, KG - 1) * NQ + q) * 256);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int q = 0; q < NQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[d][e], bq[q][e], acc[q], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        ar[d] = ap[(size_t)min(kg + PF, KG - 1) * 64];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) bq[q] = bqn[q];
-      }
-    }
-    __builtin_amdgcn_s_setprio(0);
+  for (int tile = t0 + w; tile < t1; tile += SWEEP_THREADS / 64) {
+    SWEEP_TILE_MFMA(NQ, a.idxp, tile, KG, qs, lane, acc);
 
-    const int rbase = tile * 32 + 4 * (lane >> 5);  // row of accumulator register r: rbase + (r & 3) + 8 * (r >> 2)
-    const bool tail = (tile == tail_tile);          // only the index's last tile has rows >= N (zero padding): uniform
+    const int rbase = sweep_rbase(tile, lane);
+    const bool tail = (tile == tail_tile);  // (uniform)
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
       if (tail) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = (rbase + (r & 3) + 8 * (r >> 2) >= nlim) ? -__builtin_inff() : acc[q][r];
+        for (int r = 0; r < 16; ++r) acc[q][r] = (sweep_row(rbase, r) >= nlim) ? -__builtin_inff() : acc[q][r];
       }
       int cgt = 0, cge = 0;
 #pragma unroll
@@ -202,7 +135,7 @@ __global__ __launch_bounds__(AB_THREADS) void score_above_kernel(AboveArgs a) {
           while (sm) {
             const int r = __ffs((int)sm) - 1;
             sm &= sm - 1;
-            const int row = rbase + (r & 3) + 8 * (r >> 2);
+            const int row = sweep_row(rbase, r);
             if (pos < s1 && row < nlim) a.out_ids[pos] = a.id_base + row;
             else atomicOr(a.err_flag, AB_ERR_PASSES);
             ++pos;
@@ -218,11 +151,8 @@ __global__ __launch_bounds__(AB_THREADS) void score_above_kernel(AboveArgs a) {
         while (bm) {
           const int r = __ffs((int)bm) - 1;
           bm &= bm - 1;
-          const int row = rbase + (r & 3) + 8 * (r >> 2);
-          if (row < nlim && pr[q] < a.P) {
-            const int pos = atomicAdd(a.band_cnt + pr[q], 1);
-            if (pos < a.band_cap) a.band_buf[(size_t)pr[q] * a.band_cap + pos] = row;
-          }
+          const int row = sweep_row(rbase, r);
+          if (row < nlim && pr[q] < a.P) sweep_append(a.band_cnt, a.band_buf, a.band_cap, pr[q], row);
         }
       }
     }
@@ -473,28 +403,13 @@ hipError_t launch_above_validate(const int32_t *pair_q, int64_t L, int Q, int32_
 
 template <int NQ, bool EMIT>
 static hipError_t launch_above_sweep(const AboveArgs &a, hipStream_t st) {
-  const size_t lds = (size_t)NQ * a.KG * 256 * sizeof(float);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  const int QB = (a.P + NQ * 32 - 1) / (NQ * 32);
-  int grid;
-  if (a.NSPLIT <= 8) {
-    const int per = 8 / a.NSPLIT;
-    grid = (QB + per - 1) / per * 8;
-  } else {
-    grid = QB * a.NSPLIT;
-  }
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(score_above_kernel<NQ, EMIT>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((score_above_kernel<NQ, EMIT>), dim3(grid), dim3(AB_THREADS), lds, st, a);
-  return hipGetLastError();
+  return launch_sweep(score_above_kernel<NQ, EMIT>, a.P, NQ, a.KG, a.NSPLIT, SWEEP_LDS_MAX, st, a);
 }
 
 hipError_t launch_score_above(const AboveArgs &a, hipStream_t st) {
   if (a.P <= 0) return hipSuccess;
   if (a.band_cap > SSE_COLLECT_CAP || a.band_cap < 1) return hipErrorInvalidValue;
-  if (a.NSPLIT > 8 && (a.NSPLIT & 7)) return hipErrorInvalidValue;
-  if (a.NSPLIT < 8 && (a.NSPLIT < 1 || 8 % a.NSPLIT)) return hipErrorInvalidValue;
+  if (!sweep_nsplit_ok(a.NSPLIT)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(above_prepare_kernel, dim3((a.P + 3) / 4), dim3(256), 0, st, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;

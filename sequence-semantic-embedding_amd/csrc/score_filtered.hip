@@ -3,7 +3,7 @@
 // The reference ranks every target of a query (sse_evaluator.py:110-112, data_utils.py:263-267) and leaves "only the leaves
 // under this meta-category", "not the labelled positives" or "not the row itself" to a filter of the sorted row on the host.
 // Here the filter is inside the sweep and the threshold comes from eligible rows only (DESIGN K6g):
-//   1. score_filtered_kernel<NQ, false>: the fp32 sweep of score_rank_kernel on v_mfma_f32_32x32x2_f32 (index rows = M, one
+//   1. score_filtered_kernel<NQ, false>: the shared fp32 sweep (score_sweep.h) on v_mfma_f32_32x32x2_f32 (index rows = M, one
 //      query per lane column).  A lane reads the 16 tag words of its rows, turns tag-ineligible rows and the zero padding of
 //      the tail tile into -inf and keeps a running maximum per accumulator register.  The NSPLIT x 8 waves x 2 halves x 16
 //      maxima of a query belong to DISJOINT row sets (folded onto NV = min(NSPLIT, 16) x 256 slots: a slot shared by several
@@ -22,6 +22,7 @@
 #include "sse_kernels.h"
 #include "score_exact.h"
 #include "score_filtered_common.h"
+#include "score_sweep.h"
 
 __global__ void tag_tile_summary_kernel(const uint64_t *tags, int64_t NT, uint64_t *tile_sum) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -36,52 +37,25 @@ hipError_t launch_tag_tile_summary(const uint64_t *tags, int64_t NT, uint64_t *t
   return hipGetLastError();
 }
 
-// The sweep of score_rank_kernel (see there for the layout): workgroup = (block of NQ x 32 queries, index split), a wave walks
-// the split's tiles, a lane owns query column (lane & 31) of every query tile and 16 rows of the index tile.
+// The shared sweep (score_sweep.h), one query per column.  COLLECT: eligible rows at or above thr are appended to the query's
+// buffer; otherwise a running maximum per accumulator register.
 template <int NQ, bool COLLECT>
-__global__ __launch_bounds__(FT_THREADS) void score_filtered_kernel(FilteredArgs a) {
+__global__ __launch_bounds__(SWEEP_THREADS) void score_filtered_kernel(FilteredArgs a) {
   extern __shared__ __attribute__((aligned(16))) float ft_smem[];  // [KG][NQ][256]
   __shared__ unsigned long long s_any;
   __shared__ int s_unres;
-  constexpr int PF = 4;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int KG = a.KG;
   int split, qb;
-  {
-    const int b = blockIdx.x, xcd = b & 7, j = b >> 3;
-    if (a.NSPLIT <= 8) {
-      const int per = 8 / a.NSPLIT;
-      split = xcd / per;
-      qb = j * per + xcd % per;
-    } else {
-      const int m = a.NSPLIT >> 3;
-      split = xcd + 8 * (j % m);
-      qb = j / m;
-    }
-  }
+  sweep_decode(a.NSPLIT, split, qb);
   if (qb * NQ * 32 >= a.P) return;
   if (tid == 0) {
     s_any = 0ull;
     s_unres = 0;
   }
   __syncthreads();
-  {
-    f32x4 *dst = reinterpret_cast<f32x4 *>(ft_smem);
-    const int Sd = a.S;
-    for (int i = tid; i < NQ * KG * 64; i += FT_THREADS) {
-      const int kg = (i >> 6) / NQ, l = i & 63, pair = (qb * NQ + (i >> 6) % NQ) * 32 + (l & 31);
-      f32x4 v = {0, 0, 0, 0};
-      if (pair < a.P) {
-        const int k0 = kg * 8 + (l >> 5) * 4;
-        const float *src = a.q + (size_t)pair * Sd + k0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (k0 + e < Sd) v[e] = src[e];
-      }
-      dst[i] = v;
-    }
-  }
+  sweep_stage_queries<NQ, false>(ft_smem, a.q, nullptr, qb, a.P, a.S, KG, tid);
   // the block's OR of q_any, and whether one of its queries asks for nothing (the tile skip)
   if (tid < NQ * 32) {
     const int pair = qb * NQ * 32 + tid;
@@ -110,72 +84,28 @@ __global__ __launch_bounds__(FT_THREADS) void score_filtered_kernel(FilteredArgs
   const bool may_skip = a.skip && a.tags && !s_unres;
   const unsigned long long blk_any = s_any;
 
-  const int tps = (a.NT + a.NSPLIT - 1) / a.NSPLIT;  // n-tiles per split
-  const int t0 = split * tps, t1 = min(a.NT, t0 + tps);
+  int t0, t1;
+  sweep_tile_range(a.NT, a.NSPLIT, split, t0, t1);
   const float *qs = ft_smem + lane * 4;
-  const int tail_tile = (a.N & 31) ? (int)(a.N >> 5) : -1;
+  const int tail_tile = sweep_tail_tile(a.N);
   const int nlim = (int)a.N;
   int skipped = 0;
 
-  for (int tile = t0 + w; tile < t1; tile += FT_THREADS / 64) {
+  for (int tile = t0 + w; tile < t1; tile += SWEEP_THREADS / 64) {
     if (may_skip && (a.tile_sum[tile] & blk_any) == 0ull) {  // (wave-uniform)
       ++skipped;
       continue;
     }
-    const f32x4 *ap = reinterpret_cast<const f32x4 *>(a.idxp) + (size_t)tile * KG * 64 + lane;
-    f32x16 acc[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) acc[q] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const int rem = KG & (PF - 1);
-    f32x4 ar[PF];
-#pragma unroll
-    for (int d = 0; d < PF; ++d) ar[d] = ap[(size_t)min(rem + d, KG - 1) * 64];
-    __builtin_amdgcn_s_setprio(1);
-    for (int kg = 0; kg < rem; ++kg) {
-      const f32x4 av = ap[(size_t)kg * 64];
-      f32x4 bq[NQ];
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) bq[q] = *reinterpret_cast<const f32x4 *>(qs + ((size_t)kg * NQ + q) * 256);
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], bq[q][e], acc[q], 0, 0, 0);
-    }
-    f32x4 bq[NQ], bqn[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) bq[q] = *reinterpret_cast<const f32x4 *>(qs + ((size_t)min(rem, KG - 1) * NQ + q) * 256);
-    for (int kg0 = rem; kg0 < KG; kg0 += PF) {
-#pragma unroll
-      for (int d = 0; d < PF; ++d) {
-        const int kg = kg0 + d;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) bqn[q] = *reinterpret_cast<const f32x4 *>(qs + ((size_t)min(kg + 1, KG - 1) * NQ + q) * 256);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int q = 0; q < NQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[d][e], bq[q][e], acc[q], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        ar[d] = ap[(size_t)min(kg + PF, KG - 1) * 64];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) bq[q] = bqn[q];
-      }
-    }
-    __builtin_amdgcn_s_setprio(0);
+    SWEEP_TILE_MFMA(NQ, a.idxp, tile, KG, qs, lane, acc);
 
-    const int rbase = tile * 32 + 4 * (lane >> 5);  // row of accumulator register r: rbase + (r & 3) + 8 * (r >> 2)
+    const int rbase = sweep_rbase(tile, lane);
     // rows of this tile that exist (the index's last tile is zero padded past N)
-    unsigned rowmask = 0xFFFFu;
-    if (tile == tail_tile) {  // (uniform)
-      rowmask = 0u;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) rowmask |= (rbase + (r & 3) + 8 * (r >> 2) < nlim) ? (1u << r) : 0u;
-    }
+    const unsigned rowmask = (tile == tail_tile) ? sweep_tail_rowmask(rbase, nlim) : 0xFFFFu;  // (uniform condition)
     unsigned em[NQ];  // eligible rows per query tile
     if (a.tags) {     // (uniform)
       uint64_t tg[16];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) tg[r] = a.tags[rbase + (r & 3) + 8 * (r >> 2)];  // (padded to NT * 32 words)
+      for (int r = 0; r < 16; ++r) tg[r] = a.tags[sweep_row(rbase, r)];  // (padded to NT * 32 words)
 #pragma unroll
       for (int q = 0; q < NQ; ++q) {
         unsigned m = 0u;
@@ -200,9 +130,8 @@ __global__ __launch_bounds__(FT_THREADS) void score_filtered_kernel(FilteredArgs
         while (bm) {
           const int r = __ffs((int)bm) - 1;
           bm &= bm - 1;
-          const int row = rbase + (r & 3) + 8 * (r >> 2);
-          const int pos = atomicAdd(a.col_cnt + pr[q], 1);
-          if (pos < a.col_cap && row < nlim) a.col_buf[(size_t)pr[q] * a.col_cap + pos] = row;
+          const int row = sweep_row(rbase, r);
+          sweep_append(a.col_cnt, a.col_buf, a.col_cap, pr[q], row, row < nlim);
         }
       } else {
 #pragma unroll
@@ -407,23 +336,10 @@ __global__ __launch_bounds__(256) void filtered_select_kernel(FilteredArgs a) {
   if (tid == 0) a.out_counts[p] = cnt;
 }
 
+// (1 KiB of the workgroup's LDS left to s_any / s_unres)
 template <int NQ, bool COLLECT>
 static hipError_t launch_filtered_sweep(const FilteredArgs &a, hipStream_t st) {
-  const size_t lds = (size_t)NQ * a.KG * 256 * sizeof(float);
-  if (lds > 159 * 1024) return hipErrorInvalidValue;
-  const int QB = (a.P + NQ * 32 - 1) / (NQ * 32);
-  int grid;
-  if (a.NSPLIT <= 8) {
-    const int per = 8 / a.NSPLIT;
-    grid = (QB + per - 1) / per * 8;
-  } else {
-    grid = QB * a.NSPLIT;
-  }
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(score_filtered_kernel<NQ, COLLECT>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((score_filtered_kernel<NQ, COLLECT>), dim3(grid), dim3(FT_THREADS), lds, st, a);
-  return hipGetLastError();
+  return launch_sweep(score_filtered_kernel<NQ, COLLECT>, a.P, NQ, a.KG, a.NSPLIT, SWEEP_LDS_MAX - 1024, st, a);
 }
 
 hipError_t launch_score_filtered(const FilteredArgs &a, hipStream_t st) {

@@ -3,7 +3,6 @@
 #pragma once
 #include <stdint.h>
 
-#define FT_THREADS 512       // the sweep: 8 waves = 2 per SIMD, as score_rank_kernel
 #define FT_MAXSPLIT 16       // splits with maxima slots of their own
 #define FT_KEY_NINF 0x007FFFFFu  // key of -inf: finite scores have larger keys, 0 = empty slot
 

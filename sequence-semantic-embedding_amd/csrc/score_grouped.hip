@@ -4,7 +4,7 @@
 // multiples of the 20,000+ leaf categories"), the listings of one product.  Every row carries an int64 group key
 // (sse_index_set_groups); the answer of a query is the k best groups, each represented by its best tag-eligible row (the
 // lowest id among equal bests).  The stages are those of score_filtered.hip with a threshold from distinct groups (DESIGN K6h):
-//   1. score_grouped_max_kernel<NQ>: the eligible-max sweep of score_filtered_kernel<NQ, false>; beside each of its 16 running
+//   1. score_grouped_max_kernel<NQ>: the shared sweep (score_sweep.h), eligible maxima as score_filtered_kernel<NQ, false>; beside each of its 16 running
 //      maxima a lane keeps the TILE the maximum came from (register and lane fix the row inside the tile).  A slot holds
 //      (order-preserving key of the fp32 score) << 32 | shard-local row: plain stores where a split owns its slots, 64-bit
 //      atomicMax where splits fold.  NQ <= 2: the sixteen tile numbers per query tile do not fit beside NQ = 4's accumulators.
@@ -22,52 +22,26 @@
 #include "sse_kernels.h"
 #include "score_exact.h"
 #include "score_filtered_common.h"
+#include "score_sweep.h"
 
-// The sweep of score_filtered_kernel<NQ, false> (see there and score_rank_kernel for the layout) with the tile of every maximum.
+// The shared sweep (score_sweep.h) with the eligible-max epilogue of score_filtered_kernel<NQ, false> and the tile of every maximum.
 template <int NQ>
-__global__ __launch_bounds__(FT_THREADS) void score_grouped_max_kernel(FilteredArgs a, unsigned long long *maxima64) {
+__global__ __launch_bounds__(SWEEP_THREADS) void score_grouped_max_kernel(FilteredArgs a, unsigned long long *maxima64) {
   extern __shared__ __attribute__((aligned(16))) float gp_smem[];  // [KG][NQ][256]
   __shared__ unsigned long long s_any;
   __shared__ int s_unres;
-  constexpr int PF = 4;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int KG = a.KG;
   int split, qb;
-  {
-    const int b = blockIdx.x, xcd = b & 7, j = b >> 3;
-    if (a.NSPLIT <= 8) {
-      const int per = 8 / a.NSPLIT;
-      split = xcd / per;
-      qb = j * per + xcd % per;
-    } else {
-      const int m = a.NSPLIT >> 3;
-      split = xcd + 8 * (j % m);
-      qb = j / m;
-    }
-  }
+  sweep_decode(a.NSPLIT, split, qb);
   if (qb * NQ * 32 >= a.P) return;
   if (tid == 0) {
     s_any = 0ull;
     s_unres = 0;
   }
   __syncthreads();
-  {
-    f32x4 *dst = reinterpret_cast<f32x4 *>(gp_smem);
-    const int Sd = a.S;
-    for (int i = tid; i < NQ * KG * 64; i += FT_THREADS) {
-      const int kg = (i >> 6) / NQ, l = i & 63, pair = (qb * NQ + (i >> 6) % NQ) * 32 + (l & 31);
-      f32x4 v = {0, 0, 0, 0};
-      if (pair < a.P) {
-        const int k0 = kg * 8 + (l >> 5) * 4;
-        const float *src = a.q + (size_t)pair * Sd + k0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (k0 + e < Sd) v[e] = src[e];
-      }
-      dst[i] = v;
-    }
-  }
+  sweep_stage_queries<NQ, false>(gp_smem, a.q, nullptr, qb, a.P, a.S, KG, tid);
   if (tid < NQ * 32) {
     const int pair = qb * NQ * 32 + tid;
     if (pair < a.P) {
@@ -97,67 +71,24 @@ __global__ __launch_bounds__(FT_THREADS) void score_grouped_max_kernel(FilteredA
   const bool may_skip = a.skip && a.tags && !s_unres;
   const unsigned long long blk_any = s_any;
 
-  const int tps = (a.NT + a.NSPLIT - 1) / a.NSPLIT;  // n-tiles per split
-  const int t0 = split * tps, t1 = min(a.NT, t0 + tps);
+  int t0, t1;
+  sweep_tile_range(a.NT, a.NSPLIT, split, t0, t1);
   const float *qs = gp_smem + lane * 4;
-  const int tail_tile = (a.N & 31) ? (int)(a.N >> 5) : -1;
+  const int tail_tile = sweep_tail_tile(a.N);
   const int nlim = (int)a.N;
 
-  for (int tile = t0 + w; tile < t1; tile += FT_THREADS / 64) {
+  for (int tile = t0 + w; tile < t1; tile += SWEEP_THREADS / 64) {
     if (may_skip && (a.tile_sum[tile] & blk_any) == 0ull) continue;  // (wave-uniform) no eligible row for any query of the block
-    const f32x4 *ap = reinterpret_cast<const f32x4 *>(a.idxp) + (size_t)tile * KG * 64 + lane;
-    f32x16 acc[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) acc[q] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const int rem = KG & (PF - 1);
-    f32x4 ar[PF];
-#pragma unroll
-    for (int d = 0; d < PF; ++d) ar[d] = ap[(size_t)min(rem + d, KG - 1) * 64];
-    __builtin_amdgcn_s_setprio(1);
-    for (int kg = 0; kg < rem; ++kg) {
-      const f32x4 av = ap[(size_t)kg * 64];
-      f32x4 bq[NQ];
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) bq[q] = *reinterpret_cast<const f32x4 *>(qs + ((size_t)kg * NQ + q) * 256);
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], bq[q][e], acc[q], 0, 0, 0);
-    }
-    f32x4 bq[NQ], bqn[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) bq[q] = *reinterpret_cast<const f32x4 *>(qs + ((size_t)min(rem, KG - 1) * NQ + q) * 256);
-    for (int kg0 = rem; kg0 < KG; kg0 += PF) {
-#pragma unroll
-      for (int d = 0; d < PF; ++d) {
-        const int kg = kg0 + d;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) bqn[q] = *reinterpret_cast<const f32x4 *>(qs + ((size_t)min(kg + 1, KG - 1) * NQ + q) * 256);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int q = 0; q < NQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[d][e], bq[q][e], acc[q], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        ar[d] = ap[(size_t)min(kg + PF, KG - 1) * 64];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) bq[q] = bqn[q];
-      }
-    }
-    __builtin_amdgcn_s_setprio(0);
+    SWEEP_TILE_MFMA(NQ, a.idxp, tile, KG, qs, lane, acc);
 
-    const int rbase = tile * 32 + 4 * (lane >> 5);  // row of accumulator register r: rbase + (r & 3) + 8 * (r >> 2)
-    unsigned rowmask = 0xFFFFu;                     // rows of this tile that exist (the last tile is zero padded past N)
-    if (tile == tail_tile) {                        // (uniform)
-      rowmask = 0u;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) rowmask |= (rbase + (r & 3) + 8 * (r >> 2) < nlim) ? (1u << r) : 0u;
-    }
+    const int rbase = sweep_rbase(tile, lane);
+    // rows of this tile that exist (the index's last tile is zero padded past N)
+    const unsigned rowmask = (tile == tail_tile) ? sweep_tail_rowmask(rbase, nlim) : 0xFFFFu;  // (uniform condition)
     unsigned em[NQ];  // eligible rows per query tile
     if (a.tags) {     // (uniform)
       uint64_t tg[16];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) tg[r] = a.tags[rbase + (r & 3) + 8 * (r >> 2)];  // (padded to NT * 32 words)
+      for (int r = 0; r < 16; ++r) tg[r] = a.tags[sweep_row(rbase, r)];  // (padded to NT * 32 words)
 #pragma unroll
       for (int q = 0; q < NQ; ++q) {
         unsigned m = 0u;
@@ -190,7 +121,7 @@ __global__ __launch_bounds__(FT_THREADS) void score_grouped_max_kernel(FilteredA
     unsigned long long *dst = maxima64 + (size_t)pr[q] * a.NV + slot0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const uint32_t row = (uint32_t)(mt[q][r] * 32 + 4 * (lane >> 5) + (r & 3) + 8 * (r >> 2));
+      const uint32_t row = (uint32_t)sweep_row(sweep_rbase(mt[q][r], lane), r);
       const unsigned long long v = ((unsigned long long)ft_key(mx[q][r]) << 32) | row;  // (-inf: FT_KEY_NINF, the row unused)
       if (shared_slots) atomicMax(dst + r, v);
       else dst[r] = v;
@@ -423,23 +354,10 @@ __global__ __launch_bounds__(256) void grouped_select_kernel(FilteredArgs a, con
   if (tid == 0) a.out_counts[p] = cnt;
 }
 
+// (1 KiB of the workgroup's LDS left to s_any / s_unres)
 template <int NQ>
 static hipError_t launch_grouped_max(const FilteredArgs &a, unsigned long long *maxima64, hipStream_t st) {
-  const size_t lds = (size_t)NQ * a.KG * 256 * sizeof(float);
-  if (lds > 159 * 1024) return hipErrorInvalidValue;
-  const int QB = (a.P + NQ * 32 - 1) / (NQ * 32);
-  int grid;
-  if (a.NSPLIT <= 8) {
-    const int per = 8 / a.NSPLIT;
-    grid = (QB + per - 1) / per * 8;
-  } else {
-    grid = QB * a.NSPLIT;
-  }
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(score_grouped_max_kernel<NQ>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((score_grouped_max_kernel<NQ>), dim3(grid), dim3(FT_THREADS), lds, st, a, maxima64);
-  return hipGetLastError();
+  return launch_sweep(score_grouped_max_kernel<NQ>, a.P, NQ, a.KG, a.NSPLIT, SWEEP_LDS_MAX - 1024, st, a, maxima64);
 }
 
 hipError_t launch_score_grouped(const GroupedArgs &g, hipStream_t st) {

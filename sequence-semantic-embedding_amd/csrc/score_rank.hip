@@ -7,8 +7,8 @@
 //   1. rank_prepare_kernel: the float64 threshold score of every (query, row) pair with the re-scorer's own dot product
 //      (wave_exact_dot: the bits sse_score_topk returns for that row), narrowed outward to an fp32 interval [lo, hi] that
 //      holds every fp32 score the bound eps32 |q| cannot decide.
-//   2. score_rank_kernel: [N,S] x [S,P] on v_mfma_f32_32x32x2_f32 from the fragment-order index, the sweep of
-//      score_topk_kernel's COLLECT variant (index rows = MFMA M, one pair per lane column) with a compare-and-count in place
+//   2. score_rank_kernel: [N,S] x [S,P] on v_mfma_f32_32x32x2_f32 from the fragment-order index, the shared sweep of
+//      score_sweep.h (index rows = MFMA M, one pair per lane column) with a compare-and-count in place
 //      of lists: x > hi adds 1 to the pair's sure count, lo <= x <= hi appends the row to the pair's band buffer, anything
 //      else is dropped.  Integer adds: any grid shape gives the same counts.
 //   3. rank_resolve_kernel: the band rows re-scored in float64 and counted when before() holds (strict: the label row, which
@@ -21,8 +21,7 @@
 // score64 < s (after it), and every row that ties or nearly ties with s sits in [lo, hi].
 #include "sse_kernels.h"
 #include "score_exact.h"
-
-#define RK_THREADS 512  // the sweep: 8 waves = 2 per SIMD, as score_topk_kernel
+#include "score_sweep.h"
 
 // pair_q in [0, Q); first form: the label is a row of this index.  One bad pair cancels the whole call: every later kernel
 // reads *bad first and writes nothing.
@@ -63,50 +62,19 @@ __global__ __launch_bounds__(256) void rank_prepare_kernel(RankArgs a) {
   }
 }
 
-// Count sweep.  Workgroup = (block of NQ x 32 pairs, index split); a wave walks the split's tiles w, w + 8, ...: one index tile
-// (32 rows, M) x NQ pair tiles (N), the pair's query rows staged into LDS as MFMA B fragments [k-group][pair tile][1 KiB]
-// straight from the row-major queries (the values launch_pack_rows produces).  Index fragments come from global memory PF
-// k-groups ahead (a ring in registers).  A lane owns pair column (lane & 31) of every pair tile and 16 rows of the index tile.
+// Count sweep: the shared sweep (score_sweep.h), one (query, label) pair per column.
 template <int NQ>
-__global__ __launch_bounds__(RK_THREADS) void score_rank_kernel(RankArgs a) {
+__global__ __launch_bounds__(SWEEP_THREADS) void score_rank_kernel(RankArgs a) {
   extern __shared__ __attribute__((aligned(16))) float rk_smem[];  // [KG][NQ][256]
-  constexpr int PF = 4;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int KG = a.KG;
   if (*a.bad) return;  // (uniform)
-  // XCD-aware decode, as score_topk_kernel: the workgroups of one XCD (blockIdx % 8) sweep the same index range
   int split, qb;
-  {
-    const int b = blockIdx.x, xcd = b & 7, j = b >> 3;
-    if (a.NSPLIT <= 8) {
-      const int per = 8 / a.NSPLIT;
-      split = xcd / per;
-      qb = j * per + xcd % per;
-    } else {
-      const int m = a.NSPLIT >> 3;
-      split = xcd + 8 * (j % m);
-      qb = j / m;
-    }
-  }
+  sweep_decode(a.NSPLIT, split, qb);
   if (qb * NQ * 32 >= a.P) return;
 
-  {
-    f32x4 *dst = reinterpret_cast<f32x4 *>(rk_smem);
-    const int Sd = a.S;
-    for (int i = tid; i < NQ * KG * 64; i += RK_THREADS) {
-      const int kg = (i >> 6) / NQ, l = i & 63, pair = (qb * NQ + (i >> 6) % NQ) * 32 + (l & 31);
-      f32x4 v = {0, 0, 0, 0};
-      if (pair < a.P) {
-        const int k0 = kg * 8 + (l >> 5) * 4;
-        const float *src = a.q + (size_t)a.pair_q[pair] * Sd + k0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (k0 + e < Sd) v[e] = src[e];
-      }
-      dst[i] = v;
-    }
-  }
+  sweep_stage_queries<NQ, true>(rk_smem, a.q, a.pair_q, qb, a.P, a.S, KG, tid);
   // this lane's interval per pair tile (pairs past the chunk: nothing is above +inf, nothing inside an empty interval)
   float lo[NQ], hi[NQ];
   int pr[NQ], cnt[NQ];
@@ -120,65 +88,22 @@ __global__ __launch_bounds__(RK_THREADS) void score_rank_kernel(RankArgs a) {
   }
   __syncthreads();
 
-  const int tps = (a.NT + a.NSPLIT - 1) / a.NSPLIT;  // n-tiles per split
-  const int t0 = split * tps, t1 = min(a.NT, t0 + tps);
+  int t0, t1;
+  sweep_tile_range(a.NT, a.NSPLIT, split, t0, t1);
   const float *qs = rk_smem + lane * 4;
-  const int tail_tile = (a.N & 31) ? (int)(a.N >> 5) : -1;
+  const int tail_tile = sweep_tail_tile(a.N);
   const int nlim = (int)a.N;
 
-  for (int tile = t0 + w; tile < t1; tile += RK_THREADS / 64) {
-    const f32x4 *ap = reinterpret_cast<const f32x4 *>(a.idxp) + (size_t)tile * KG * 64 + lane;
-    f32x16 acc[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) acc[q] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    // the first KG % PF k-groups one by one, then a ring of PF index fragments in flight over the rest (no branch in
-    // the unrolled body: a refill past the tile's end re-reads its last k-group and is never used)
-    const int rem = KG & (PF - 1);
-    f32x4 ar[PF];
-#pragma unroll
-    for (int d = 0; d < PF; ++d) ar[d] = ap[(size_t)min(rem + d, KG - 1) * 64];
-    __builtin_amdgcn_s_setprio(1);
-    for (int kg = 0; kg < rem; ++kg) {
-      const f32x4 av = ap[(size_t)kg * 64];
-      f32x4 bq[NQ];
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) bq[q] = *reinterpret_cast<const f32x4 *>(qs + ((size_t)kg * NQ + q) * 256);
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], bq[q][e], acc[q], 0, 0, 0);
-    }
-    // (pair fragments of the next k-group are read from LDS in front of this k-group's MFMAs; the order is pinned, as in
-    // score_small_index_kernel: the compiler otherwise sinks the refills behind the block and waits for them at once)
-    f32x4 bq[NQ], bqn[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) bq[q] = *reinterpret_cast<const f32x4 *>(qs + ((size_t)min(rem, KG - 1) * NQ + q) * 256);
-    for (int kg0 = rem; kg0 < KG; kg0 += PF) {
-#pragma unroll
-      for (int d = 0; d < PF; ++d) {
-        const int kg = kg0 + d;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) bqn[q] = *reinterpret_cast<const f32x4 *>(qs + ((size_t)min(kg + 1, KG - 1) * NQ + q) * 256);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int q = 0; q < NQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[d][e], bq[q][e], acc[q], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        ar[d] = ap[(size_t)min(kg + PF, KG - 1) * 64];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) bq[q] = bqn[q];
-      }
-    }
-    __builtin_amdgcn_s_setprio(0);
+  for (int tile = t0 + w; tile < t1; tile += SWEEP_THREADS / 64) {
+    SWEEP_TILE_MFMA(NQ, a.idxp, tile, KG, qs, lane, acc);
 
-    const int rbase = tile * 32 + 4 * (lane >> 5);  // row of accumulator register r: rbase + (r & 3) + 8 * (r >> 2)
-    const bool tail = (tile == tail_tile);          // only the index's last tile has rows >= N (zero padding): uniform
+    const int rbase = sweep_rbase(tile, lane);
+    const bool tail = (tile == tail_tile);  // (uniform)
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
       if (tail) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = (rbase + (r & 3) + 8 * (r >> 2) >= nlim) ? -__builtin_inff() : acc[q][r];
+        for (int r = 0; r < 16; ++r) acc[q][r] = (sweep_row(rbase, r) >= nlim) ? -__builtin_inff() : acc[q][r];
       }
       // rows above hi and rows at or above lo: they differ exactly when a row sits in the band (lo <= hi)
       int cgt = 0, cge = 0;
@@ -195,11 +120,8 @@ __global__ __launch_bounds__(RK_THREADS) void score_rank_kernel(RankArgs a) {
         while (bm) {
           const int r = __ffs((int)bm) - 1;
           bm &= bm - 1;
-          const int row = rbase + (r & 3) + 8 * (r >> 2);
-          if (row < nlim && pr[q] < a.P) {
-            const int pos = atomicAdd(a.band_cnt + pr[q], 1);
-            if (pos < a.band_cap) a.band_buf[(size_t)pr[q] * a.band_cap + pos] = row;
-          }
+          const int row = sweep_row(rbase, r);
+          if (row < nlim && pr[q] < a.P) sweep_append(a.band_cnt, a.band_buf, a.band_cap, pr[q], row);
         }
       }
     }
@@ -281,28 +203,14 @@ hipError_t launch_rank_validate(const int32_t *pair_q, const int64_t *pair_id, i
 
 template <int NQ>
 static hipError_t launch_rank_sweep(const RankArgs &a, hipStream_t st) {
-  const size_t lds = (size_t)NQ * a.KG * 256 * sizeof(float);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  const int QB = (a.P + NQ * 32 - 1) / (NQ * 32);
-  int grid;
-  if (a.NSPLIT <= 8) {
-    const int per = 8 / a.NSPLIT;
-    grid = (QB + per - 1) / per * 8;
-  } else {
-    grid = QB * a.NSPLIT;
-  }
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(score_rank_kernel<NQ>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((score_rank_kernel<NQ>), dim3(grid), dim3(RK_THREADS), lds, st, a);
-  return hipGetLastError();
+  return launch_sweep(score_rank_kernel<NQ>, a.P, NQ, a.KG, a.NSPLIT, SWEEP_LDS_MAX, st, a);
 }
 
 // all four stages of one chunk of a.P pairs
 hipError_t launch_score_rank(const RankArgs &a, hipStream_t st) {
   if (a.P <= 0) return hipSuccess;
   if (a.band_cap > SSE_COLLECT_CAP || a.band_cap < 1) return hipErrorInvalidValue;
-  if (a.NSPLIT > 8 && (a.NSPLIT & 7)) return hipErrorInvalidValue;
-  if (a.NSPLIT < 8 && (a.NSPLIT < 1 || 8 % a.NSPLIT)) return hipErrorInvalidValue;
+  if (!sweep_nsplit_ok(a.NSPLIT)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(rank_prepare_kernel, dim3((a.P + 3) / 4), dim3(256), 0, st, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;

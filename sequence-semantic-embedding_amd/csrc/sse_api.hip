@@ -228,24 +228,27 @@ struct sse_handle {
   DevBuf s_pb, s_cthr, s_cslot, s_ccnt, s_cbuf;  // per-split bounds; collect path: thresholds, slots, counters, row buffers
   // exact rank of labelled rows (sse_score_rank*, score_rank.hip): per-pair scratch of a chunk (thresholds, fp32 intervals, sure
   // counts, the call's "bad pair" word), the two counters "score_rank_band_rows" / "score_rank_bruteforce_pairs" on the
-  // device, staging of the host form.  The band buffers are the collect path's (s_ccnt, s_cbuf).
-  DevBuf s_rk, s_rk_cnt, s_rk_in;
+  // device.  The band buffers are the collect path's (s_ccnt, s_cbuf).
+  DevBuf s_rk, s_rk_cnt;
   bool rk_cnt_init = false;
   // rows at or above a threshold (sse_score_above*, score_above.hip): per-pair cursors and overflow marks of a call, merge
-  // scratch of the lists' length, the three "score_above_*" counters, staging of the host form (inputs + offsets | lists).
+  // scratch of the lists' length, the three "score_above_*" counters, the lists of the host form.
   // Per-chunk scratch is the rank count's (s_rk, s_ccnt, s_cbuf).
-  DevBuf s_ab, s_ab_sort, s_ab_cnt, s_ab_in, s_ab_out;
+  DevBuf s_ab, s_ab_sort, s_ab_cnt, s_ab_out;
   bool ab_cnt_init = false;
   // top-k among tag-eligible rows (sse_score_topk_filtered*, score_filtered.hip): the tags of the resident index (one word per
   // row, zero padded to whole tiles) and their per-tile OR, valid while tags_set; the maxima of a chunk, the three
-  // "score_filtered_*" counters, staging of the host form.  Thresholds and row buffers are the collect path's (s_cthr, s_ccnt, s_cbuf).
-  DevBuf idx_tags, idx_tag_sum, s_ft_max, s_ft_cnt, s_ft_in;
+  // "score_filtered_*" counters.  Thresholds and row buffers are the collect path's (s_cthr, s_ccnt, s_cbuf).
+  DevBuf idx_tags, idx_tag_sum, s_ft_max, s_ft_cnt;
   bool tags_set = false, ft_cnt_init = false;
   bool score_filtered_skip = true;  // option "score_filtered_skip": the sweeps skip index tiles no query of a block can use
   // top-k distinct groups (sse_score_topk_grouped*, score_grouped.hip): one int64 key per row of the resident index, valid
-  // while groups_set; the (key, row) maxima of a chunk, the two "score_grouped_*" counters, staging of the host form
-  DevBuf idx_groups, s_gp_max, s_gp_cnt, s_gp_in;
+  // while groups_set; the (key, row) maxima of a chunk, the two "score_grouped_*" counters
+  DevBuf idx_groups, s_gp_max, s_gp_cnt;
   bool groups_set = false, gp_cnt_init = false;
+  // staging of the host forms of the four calls above (stage_pieces): they hold the handle's mutex and finish all device work
+  // before they return, so one buffer serves them all
+  DevBuf s_stage;
   // forward-only pair loss (sse_eval_loss*, eval_loss.hip).  Option "eval_chunk_rows": pair rows staged and encoded per chunk (even).
   // Scratch of its own: a gradient result pending between sse_train_grads and sse_train_apply lives in TrainState and the arena.
   int eval_chunk_rows = 65536;
@@ -1105,15 +1108,49 @@ static int choose_nsplit(int NQ, int QB, int64_t NT) {
   return nsplit;
 }
 
+// NQ, query blocks and base split count of one sweep over P columns (queries or pairs) of the resident index
+struct SweepChunk {
+  int NQ, QB, nsplit;
+};
+static int sweep_chunk(sse_handle *h, int P, SweepChunk &c) {
+  c.NQ = score_pick_nq(P, h->idx_S, 0);
+  if (c.NQ == 0) return fail(h, "index dimension %d does not fit the scoring kernel's LDS query block", h->idx_S);
+  c.QB = (P + c.NQ * 32 - 1) / (c.NQ * 32);
+  c.nsplit = choose_nsplit(c.NQ, c.QB, (h->idx_N + 31) / 32);
+  return 0;
+}
+
+// |fp32 MFMA score - float64 score| <= score_eps32 |q| for every row of the resident index (DESIGN K6/K7)
+static float score_eps32(const sse_handle *h) { return (float)(2.0 * (h->idx_S + 2) * 5.97e-8 * h->idx_norm_max); }
+
+// n_words device counters in b, zeroed when they are first reserved (they accumulate over the handle's life)
+static int ensure_zeroed_once(sse_handle *h, DevBuf &b, bool &init, int n_words, hipStream_t st) {
+  if (reserve(h, b, n_words * sizeof(unsigned long long))) return 1;
+  if (!init) {
+    HIPCHECK(h, hipMemsetAsync(b.p, 0, n_words * sizeof(unsigned long long), st));
+    init = true;
+  }
+  return 0;
+}
+
 // diagnostic counters on the device: [0] queries whose bf16-candidate result missed its certificate, [1] queries served
 // by the collect path, [2] queries that fell through to the float64 brute force
 static int ensure_counters(sse_handle *h, hipStream_t st) {
   // four diagnostic counters, then the pair of "queries left uncertified" words (RescoreArgs::uncert)
-  if (reserve(h, h->s_fb_cnt, 6 * sizeof(unsigned long long))) return 1;
-  if (!h->fb_cnt_init) {
-    HIPCHECK(h, hipMemsetAsync(h->s_fb_cnt.p, 0, 6 * sizeof(unsigned long long), st));
-    h->fb_cnt_init = true;
+  return ensure_zeroed_once(h, h->s_fb_cnt, h->fb_cnt_init, 6, st);
+}
+
+// Staging of a host-buffer entry point: N pieces of bytes[i] bytes in h->s_stage, reserved once; p[i] = the 8-byte-aligned
+// start of piece i.
+template <size_t N>
+static int stage_pieces(sse_handle *h, const size_t (&bytes)[N], char *(&p)[N]) {
+  size_t off[N], total = 0;
+  for (size_t i = 0; i < N; ++i) {
+    off[i] = total;
+    total += (bytes[i] + 7) & ~(size_t)7;
   }
+  if (reserve(h, h->s_stage, total)) return 1;
+  for (size_t i = 0; i < N; ++i) p[i] = (char *)h->s_stage.p + off[i];
   return 0;
 }
 
@@ -1135,7 +1172,7 @@ static int score_select_locked(sse_handle *h, const float *q, int Q, int k, doub
   const int S = h->idx_S, KG = (S + 7) / 8;
   const int64_t NT = (h->idx_N + 31) / 32;
   const int POOL = 2048;
-  const float eps32 = (float)(2.0 * (S + 2) * 5.97e-8 * h->idx_norm_max);
+  const float eps32 = score_eps32(h);
   if (ensure_counters(h, st)) return 1;
   unsigned long long *counters = (unsigned long long *)h->s_fb_cnt.p;
   for (int q0 = 0; q0 < Q; q0 += POOL) {
@@ -1212,11 +1249,7 @@ static int score_rank_dev_locked(sse_handle *h, const float *q, int Q, const int
   if (reserve(h, h->s_rk, (size_t)Pmax * 24 + 16)) return 1;
   if (reserve(h, h->s_ccnt, (size_t)(Pmax + 1) * sizeof(int32_t))) return 1;
   if (reserve(h, h->s_cbuf, (size_t)Pmax * SSE_COLLECT_CAP * sizeof(int32_t))) return 1;
-  if (reserve(h, h->s_rk_cnt, 2 * sizeof(unsigned long long))) return 1;
-  if (!h->rk_cnt_init) {
-    HIPCHECK(h, hipMemsetAsync(h->s_rk_cnt.p, 0, 2 * sizeof(unsigned long long), st));
-    h->rk_cnt_init = true;
-  }
+  if (ensure_zeroed_once(h, h->s_rk_cnt, h->rk_cnt_init, 2, st)) return 1;
   char *base = (char *)h->s_rk.p;
   int32_t *bad = (int32_t *)(base + (size_t)Pmax * 24);
   HIPCHECK(h, hipMemsetAsync(bad, 0, sizeof(int32_t), st));
@@ -1239,20 +1272,19 @@ static int score_rank_dev_locked(sse_handle *h, const float *q, int Q, const int
   a.S = S;
   a.KG = KG;
   a.NT = (int)NT;
-  a.eps32 = (float)(2.0 * (S + 2) * 5.97e-8 * h->idx_norm_max);
+  a.eps32 = score_eps32(h);
   for (int64_t p0 = 0; p0 < L; p0 += RANK_POOL) {
     const int P = (int)std::min<int64_t>(RANK_POOL, L - p0);
-    const int NQ = score_pick_nq(P, S, 0);
-    if (NQ == 0) return fail(h, "index dimension %d does not fit the scoring kernel's LDS query block", S);
-    const int QB = (P + NQ * 32 - 1) / (NQ * 32);
+    SweepChunk ck;
+    if (sweep_chunk(h, P, ck)) return 1;
     a.pair_q = pair_q + p0;
     a.pair_id = pair_id + p0;
     a.pair_score_in = pair_score_in ? pair_score_in + p0 : nullptr;
     a.out_before = out_before + p0;
     a.out_score = out_score ? out_score + p0 : nullptr;
     a.P = P;
-    a.NQ = NQ;
-    a.NSPLIT = choose_nsplit(NQ, QB, NT);
+    a.NQ = ck.NQ;
+    a.NSPLIT = ck.nsplit;
     HIPCHECK(h, launch_score_rank(a, st));
   }
   return 0;
@@ -1268,15 +1300,12 @@ struct AboveCall {
 };
 static const int ABOVE_POOL = 4096;
 static int score_above_chunks(sse_handle *h, AboveCall &c, const int32_t *pair_q, const double *pair_thr, int64_t L, int emit, hipStream_t st) {
-  const int S = h->idx_S;
-  const int64_t NT = (h->idx_N + 31) / 32;
   AboveArgs &a = c.a;
   a.emit = emit;
   for (int64_t p0 = 0; p0 < L; p0 += ABOVE_POOL) {
     const int P = (int)std::min<int64_t>(ABOVE_POOL, L - p0);
-    const int NQ = score_pick_nq(P, S, 0);
-    if (NQ == 0) return fail(h, "index dimension %d does not fit the scoring kernel's LDS query block", S);
-    const int QB = (P + NQ * 32 - 1) / (NQ * 32);
+    SweepChunk ck;
+    if (sweep_chunk(h, P, ck)) return 1;
     a.pair_q = pair_q + p0;
     a.pair_thr = pair_thr + p0;
     a.counts = c.offsets + 1 + p0;
@@ -1284,8 +1313,8 @@ static int score_above_chunks(sse_handle *h, AboveCall &c, const int32_t *pair_q
     a.ovf = c.ovf + p0;
     a.cursor = c.cursor + p0;
     a.P = P;
-    a.NQ = NQ;
-    a.NSPLIT = choose_nsplit(NQ, QB, NT);
+    a.NQ = ck.NQ;
+    a.NSPLIT = ck.nsplit;
     HIPCHECK(h, launch_score_above(a, st));
   }
   return 0;
@@ -1299,11 +1328,7 @@ static int score_above_setup(sse_handle *h, AboveCall &c, const float *q, int64_
   if (reserve(h, h->s_ccnt, (size_t)(Pmax + 1) * sizeof(int32_t))) return 1;
   if (reserve(h, h->s_cbuf, (size_t)Pmax * SSE_COLLECT_CAP * sizeof(int32_t))) return 1;
   if (reserve(h, h->s_ab, (size_t)L * 12 + 16)) return 1;  // cursor [L] | ovf [L]
-  if (reserve(h, h->s_ab_cnt, 3 * sizeof(unsigned long long))) return 1;
-  if (!h->ab_cnt_init) {
-    HIPCHECK(h, hipMemsetAsync(h->s_ab_cnt.p, 0, 3 * sizeof(unsigned long long), st));
-    h->ab_cnt_init = true;
-  }
+  if (ensure_zeroed_once(h, h->s_ab_cnt, h->ab_cnt_init, 3, st)) return 1;
   char *base = (char *)h->s_rk.p;
   AboveArgs &a = c.a;
   a.q = q;
@@ -1326,7 +1351,7 @@ static int score_above_setup(sse_handle *h, AboveCall &c, const float *q, int64_
   a.S = S;
   a.KG = KG;
   a.NT = (int)((h->idx_N + 31) / 32);
-  a.eps32 = (float)(2.0 * (S + 2) * 5.97e-8 * h->idx_norm_max);
+  a.eps32 = score_eps32(h);
   c.offsets = offsets;
   c.cursor = (unsigned long long *)h->s_ab.p;
   c.ovf = (int32_t *)((char *)h->s_ab.p + (size_t)L * 8);
@@ -1412,40 +1437,40 @@ static int score_filtered_check(sse_handle *h, int Q, int k, const void *q_any, 
   return 0;
 }
 
-// sse_score_topk_filtered*: every stage queued on `st` (device pointers throughout), queries in chunks of 4096 with the chunk
-// scratch of the rank count (DESIGN K6e): maxima [P][NV], thresholds, row buffers [P][SSE_COLLECT_CAP].
-static int score_filtered_dev_locked(sse_handle *h, const float *q, int Q, int k, const uint64_t *q_any, const uint64_t *q_none,
-                                     const int64_t *excl, int n_excl, double *out_s, int64_t *out_i, int32_t *out_c, hipStream_t st) {
-  const int POOL = 4096;
-  const int S = h->idx_S, KG = (S + 7) / 8;
-  const int64_t NT = (h->idx_N + 31) / 32;
-  if (reserve(h, h->s_ft_cnt, 3 * sizeof(unsigned long long))) return 1;
-  if (!h->ft_cnt_init) {
-    HIPCHECK(h, hipMemsetAsync(h->s_ft_cnt.p, 0, 3 * sizeof(unsigned long long), st));
-    h->ft_cnt_init = true;
-  }
-  FilteredArgs a;
+// the fields of FilteredArgs that sse_score_topk_filtered* and sse_score_topk_grouped* fill alike, for every chunk of a call
+static void fill_filtered_common(sse_handle *h, FilteredArgs &a, int k, int n_excl, const DevBuf &counters) {
   a.idxp = h->idxp;
   a.idx64 = h->idx64;
   a.tags = h->tags_set ? (const uint64_t *)h->idx_tags.p : nullptr;
   a.tile_sum = h->tags_set ? (const uint64_t *)h->idx_tag_sum.p : nullptr;
   a.col_cap = SSE_COLLECT_CAP;
-  a.counters = (unsigned long long *)h->s_ft_cnt.p;
+  a.counters = (unsigned long long *)counters.p;
   a.id_base = h->idx_base;
   a.N = h->idx_N;
-  a.S = S;
-  a.KG = KG;
-  a.NT = (int)NT;
+  a.S = h->idx_S;
+  a.KG = (h->idx_S + 7) / 8;
+  a.NT = (int)((h->idx_N + 31) / 32);
   a.k = k;
-  a.n_excl = excl ? n_excl : 0;
+  a.n_excl = n_excl;
   a.skip = h->score_filtered_skip ? 1 : 0;
-  a.eps32 = (float)(2.0 * (S + 2) * 5.97e-8 * h->idx_norm_max);
+  a.eps32 = score_eps32(h);
+}
+
+// sse_score_topk_filtered*: every stage queued on `st` (device pointers throughout), queries in chunks of 4096 with the chunk
+// scratch of the rank count (DESIGN K6e): maxima [P][NV], thresholds, row buffers [P][SSE_COLLECT_CAP].
+static int score_filtered_dev_locked(sse_handle *h, const float *q, int Q, int k, const uint64_t *q_any, const uint64_t *q_none,
+                                     const int64_t *excl, int n_excl, double *out_s, int64_t *out_i, int32_t *out_c, hipStream_t st) {
+  const int POOL = 4096;
+  const int S = h->idx_S;
+  const int64_t NT = (h->idx_N + 31) / 32;
+  if (ensure_zeroed_once(h, h->s_ft_cnt, h->ft_cnt_init, 3, st)) return 1;
+  FilteredArgs a;
+  fill_filtered_common(h, a, k, excl ? n_excl : 0, h->s_ft_cnt);
   for (int q0 = 0; q0 < Q; q0 += POOL) {
     const int P = std::min(POOL, Q - q0);
-    const int NQ = score_pick_nq(P, S, 0);
-    if (NQ == 0) return fail(h, "index dimension %d does not fit the scoring kernel's LDS query block", S);
-    const int QB = (P + NQ * 32 - 1) / (NQ * 32);
-    int nsplit = choose_nsplit(NQ, QB, NT);
+    SweepChunk ck;
+    if (sweep_chunk(h, P, ck)) return 1;
+    int nsplit = ck.nsplit;
     // at least 2 (k + n_excl) maxima per query where every wave of a split still has a tile of its own
     while (nsplit < 128 && nsplit * 256 < 2 * (k + a.n_excl) && NT / (nsplit * 2) >= 8) nsplit *= 2;
     const int NV = std::min(nsplit, 16) * 256;
@@ -1467,7 +1492,7 @@ static int score_filtered_dev_locked(sse_handle *h, const float *q, int Q, int k
     a.out_ids = out_i + (size_t)q0 * k;
     a.out_counts = out_c + q0;
     a.P = P;
-    a.NQ = NQ;
+    a.NQ = ck.NQ;
     a.NSPLIT = nsplit;
     a.NV = NV;
     HIPCHECK(h, launch_score_filtered(a, st));
@@ -1508,38 +1533,20 @@ static int score_grouped_check(sse_handle *h, int Q, int k, const void *q_any, c
 static int score_grouped_dev_locked(sse_handle *h, const float *q, int Q, int k, const uint64_t *q_any, const uint64_t *q_none,
                                     double *out_s, int64_t *out_i, int64_t *out_g, int32_t *out_c, hipStream_t st) {
   const int POOL = 4096;
-  const int S = h->idx_S, KG = (S + 7) / 8;
+  const int S = h->idx_S;
   const int64_t NT = (h->idx_N + 31) / 32;
-  if (reserve(h, h->s_gp_cnt, 3 * sizeof(unsigned long long))) return 1;
-  if (!h->gp_cnt_init) {
-    HIPCHECK(h, hipMemsetAsync(h->s_gp_cnt.p, 0, 3 * sizeof(unsigned long long), st));
-    h->gp_cnt_init = true;
-  }
+  if (ensure_zeroed_once(h, h->s_gp_cnt, h->gp_cnt_init, 3, st)) return 1;
   GroupedArgs g;
   FilteredArgs &a = g.rest;
-  a.idxp = h->idxp;
-  a.idx64 = h->idx64;
-  a.tags = h->tags_set ? (const uint64_t *)h->idx_tags.p : nullptr;
-  a.tile_sum = h->tags_set ? (const uint64_t *)h->idx_tag_sum.p : nullptr;
+  fill_filtered_common(h, a, k, 0, h->s_gp_cnt);
   a.excl = nullptr;
   a.maxima = nullptr;
-  a.col_cap = SSE_COLLECT_CAP;
-  a.counters = (unsigned long long *)h->s_gp_cnt.p;
-  a.id_base = h->idx_base;
-  a.N = h->idx_N;
-  a.S = S;
-  a.KG = KG;
-  a.NT = (int)NT;
-  a.k = k;
-  a.n_excl = 0;
-  a.skip = h->score_filtered_skip ? 1 : 0;
-  a.eps32 = (float)(2.0 * (S + 2) * 5.97e-8 * h->idx_norm_max);
   g.groups = (const int64_t *)h->idx_groups.p;
   for (int q0 = 0; q0 < Q; q0 += POOL) {
     const int P = std::min(POOL, Q - q0);
-    const int NQ = score_pick_nq(P, S, 0);
-    if (NQ == 0) return fail(h, "index dimension %d does not fit the scoring kernel's LDS query block", S);
-    const int nsplit = choose_nsplit(NQ, (P + NQ * 32 - 1) / (NQ * 32), NT);
+    SweepChunk ck;
+    if (sweep_chunk(h, P, ck)) return 1;
+    const int NQ = ck.NQ, nsplit = ck.nsplit;
     // the eligible-max sweep: at most 2 query tiles per workgroup (the tile of every maximum costs 16 registers per query
     // tile) and at least 4 k maxima per query where every wave of a split still has a tile of its own: the maxima of several
     // row sets share groups, and theta needs k DISTINCT groups among them (DESIGN K6h)
@@ -1674,7 +1681,7 @@ int score_dev_locked(sse_handle *h, const float *q, int Q, int k, double *out_s,
     if (phase == SCORE_REST) return 0;
     h->two_pass_calls += 1;
     constexpr int MID_CAP = 512;  // rows one query may collect (typically 20 - 30); more: float64 brute force for that query
-    const float eps32 = (float)(2.0 * (S + 2) * 5.97e-8 * h->idx_norm_max);
+    const float eps32 = score_eps32(h);
     const float eps_bf = eps32 + (float)(1.02 * (1.0 / 256.0 + 1.0 / 262144.0) * h->idx_norm_max);
     if (reserve(h, h->s_qp, (size_t)QB * NQ * KG * 256 * sizeof(float))) return 1;
     if (reserve(h, h->s_lmax, (size_t)Q * ns2 * 16 * sizeof(float))) return 1;
@@ -1780,7 +1787,7 @@ int score_dev_locked(sse_handle *h, const float *q, int Q, int k, double *out_s,
   r.NC = NC;
   r.k = k;
   // |fp32 fma-chain dot - exact| <= S * 2^-24 * |q||t| (+ the f32 rounding of f64 rows); use 2x margin
-  const float eps32 = (float)(2.0 * (S + 2) * 5.97e-8 * h->idx_norm_max);
+  const float eps32 = score_eps32(h);
   r.eps = eps32;
   r.eps32 = eps32;
   r.col_thr = (float *)h->s_cthr.p;
@@ -2647,17 +2654,15 @@ int sse_score_rank(sse_handle *h, const float *q_host, int32_t Q, const int32_t 
       return fail(h, "sse_score_rank: pair_id[%lld] = %lld is not a row of this index [%lld, %lld)", (long long)p, (long long)pair_id[p],
                   (long long)h->idx_base, (long long)(h->idx_base + h->idx_N));
   }
-  const size_t S = h->idx_S;
-  // staging: queries | pair_id | pair_score_in | out_score | out_before | pair_q (8-byte items first)
-  const size_t qb = ((size_t)Q * S * sizeof(float) + 7) & ~(size_t)7, l8 = (size_t)L * 8, l4 = (size_t)L * 4;
-  if (reserve(h, h->s_rk_in, qb + 4 * l8 + l4)) return 1;
-  char *b = (char *)h->s_rk_in.p;
-  float *d_q = (float *)b;
-  int64_t *d_id = (int64_t *)(b + qb);
-  double *d_in = (double *)(b + qb + l8), *d_sc = (double *)(b + qb + 2 * l8);
-  int64_t *d_bf = (int64_t *)(b + qb + 3 * l8);
-  int32_t *d_pq = (int32_t *)(b + qb + 4 * l8);
-  HIPCHECK(h, hipMemcpy(d_q, q_host, (size_t)Q * S * sizeof(float), hipMemcpyHostToDevice));
+  const size_t qb = (size_t)Q * h->idx_S * sizeof(float), l8 = (size_t)L * 8, l4 = (size_t)L * 4;
+  char *piece[6];  // queries | pair_id | pair_score_in | out_score | out_before | pair_q
+  if (stage_pieces(h, {qb, l8, l8, l8, l8, l4}, piece)) return 1;
+  float *d_q = (float *)piece[0];
+  int64_t *d_id = (int64_t *)piece[1];
+  double *d_in = (double *)piece[2], *d_sc = (double *)piece[3];
+  int64_t *d_bf = (int64_t *)piece[4];
+  int32_t *d_pq = (int32_t *)piece[5];
+  HIPCHECK(h, hipMemcpy(d_q, q_host, qb, hipMemcpyHostToDevice));
   HIPCHECK(h, hipMemcpy(d_id, pair_id, l8, hipMemcpyHostToDevice));
   HIPCHECK(h, hipMemcpy(d_pq, pair_q, l4, hipMemcpyHostToDevice));
   if (pair_score_in) HIPCHECK(h, hipMemcpy(d_in, pair_score_in, l8, hipMemcpyHostToDevice));
@@ -2706,16 +2711,14 @@ int sse_score_above(sse_handle *h, const float *q_host, int32_t Q, const int32_t
   if (!q_host || !pair_q || !pair_thr || Q == 0) return fail(h, "bad arguments to sse_score_above");
   for (int64_t p = 0; p < L; ++p)
     if (pair_q[p] < 0 || pair_q[p] >= Q) return fail(h, "sse_score_above: pair_q[%lld] = %d is not in [0, Q = %d)", (long long)p, pair_q[p], Q);
-  const size_t S = h->idx_S;
-  // staging: queries | pair_thr | offsets | pair_q (8-byte items first)
-  const size_t qb = ((size_t)Q * S * sizeof(float) + 7) & ~(size_t)7, l8 = (size_t)L * 8, l4 = (size_t)L * 4;
-  if (reserve(h, h->s_ab_in, qb + 2 * l8 + 8 + l4)) return 1;
-  char *b = (char *)h->s_ab_in.p;
-  float *d_q = (float *)b;
-  double *d_thr = (double *)(b + qb);
-  int64_t *d_off = (int64_t *)(b + qb + l8);
-  int32_t *d_pq = (int32_t *)(b + qb + 2 * l8 + 8);
-  HIPCHECK(h, hipMemcpy(d_q, q_host, (size_t)Q * S * sizeof(float), hipMemcpyHostToDevice));
+  const size_t qb = (size_t)Q * h->idx_S * sizeof(float), l8 = (size_t)L * 8, l4 = (size_t)L * 4;
+  char *piece[4];  // queries | pair_thr | offsets [L + 1] | pair_q
+  if (stage_pieces(h, {qb, l8, l8 + 8, l4}, piece)) return 1;
+  float *d_q = (float *)piece[0];
+  double *d_thr = (double *)piece[1];
+  int64_t *d_off = (int64_t *)piece[2];
+  int32_t *d_pq = (int32_t *)piece[3];
+  HIPCHECK(h, hipMemcpy(d_q, q_host, qb, hipMemcpyHostToDevice));
   HIPCHECK(h, hipMemcpy(d_thr, pair_thr, l8, hipMemcpyHostToDevice));
   HIPCHECK(h, hipMemcpy(d_pq, pair_q, l4, hipMemcpyHostToDevice));
   AboveCall c;
@@ -2773,19 +2776,17 @@ int sse_score_topk_filtered(sse_handle *h, const float *q_host, int32_t Q, int32
   if (score_filtered_check(h, Q, k, q_any, q_none, excl_ids, n_excl)) return 1;
   if (Q == 0) return 0;
   if (!q_host || !out_scores || !out_ids || !out_counts) return fail(h, "bad arguments to sse_score_topk_filtered");
-  const size_t S = h->idx_S;
-  // staging (8-byte items first): scores | ids | any | none | excl | queries | counts
   const size_t o8 = (size_t)Q * k * 8, m8 = (size_t)Q * 8, e8 = (size_t)Q * n_excl * 8;
-  const size_t qb = ((size_t)Q * S * sizeof(float) + 7) & ~(size_t)7;
-  if (reserve(h, h->s_ft_in, 2 * o8 + 2 * m8 + e8 + qb + (size_t)Q * 4)) return 1;
-  char *b = (char *)h->s_ft_in.p;
-  double *d_s = (double *)b;
-  int64_t *d_i = (int64_t *)(b + o8);
-  uint64_t *d_any = (uint64_t *)(b + 2 * o8), *d_none = (uint64_t *)(b + 2 * o8 + m8);
-  int64_t *d_ex = (int64_t *)(b + 2 * o8 + 2 * m8);
-  float *d_q = (float *)(b + 2 * o8 + 2 * m8 + e8);
-  int32_t *d_c = (int32_t *)(b + 2 * o8 + 2 * m8 + e8 + qb);
-  HIPCHECK(h, hipMemcpy(d_q, q_host, (size_t)Q * S * sizeof(float), hipMemcpyHostToDevice));
+  const size_t qb = (size_t)Q * h->idx_S * sizeof(float);
+  char *piece[7];  // scores | ids | any | none | excl | queries | counts
+  if (stage_pieces(h, {o8, o8, m8, m8, e8, qb, (size_t)Q * 4}, piece)) return 1;
+  double *d_s = (double *)piece[0];
+  int64_t *d_i = (int64_t *)piece[1];
+  uint64_t *d_any = (uint64_t *)piece[2], *d_none = (uint64_t *)piece[3];
+  int64_t *d_ex = (int64_t *)piece[4];
+  float *d_q = (float *)piece[5];
+  int32_t *d_c = (int32_t *)piece[6];
+  HIPCHECK(h, hipMemcpy(d_q, q_host, qb, hipMemcpyHostToDevice));
   if (q_any) HIPCHECK(h, hipMemcpy(d_any, q_any, m8, hipMemcpyHostToDevice));
   if (q_none) HIPCHECK(h, hipMemcpy(d_none, q_none, m8, hipMemcpyHostToDevice));
   if (n_excl > 0) HIPCHECK(h, hipMemcpy(d_ex, excl_ids, e8, hipMemcpyHostToDevice));
@@ -2837,18 +2838,15 @@ int sse_score_topk_grouped(sse_handle *h, const float *q_host, int32_t Q, int32_
   if (score_grouped_check(h, Q, k, q_any, q_none)) return 1;
   if (Q == 0) return 0;
   if (!q_host || !out_scores || !out_ids || !out_groups || !out_counts) return fail(h, "bad arguments to sse_score_topk_grouped");
-  const size_t S = h->idx_S;
-  // staging (8-byte items first): scores | ids | groups | any | none | queries | counts
-  const size_t o8 = (size_t)Q * k * 8, m8 = (size_t)Q * 8;
-  const size_t qb = ((size_t)Q * S * sizeof(float) + 7) & ~(size_t)7;
-  if (reserve(h, h->s_gp_in, 3 * o8 + 2 * m8 + qb + (size_t)Q * 4)) return 1;
-  char *b = (char *)h->s_gp_in.p;
-  double *d_s = (double *)b;
-  int64_t *d_i = (int64_t *)(b + o8), *d_g = (int64_t *)(b + 2 * o8);
-  uint64_t *d_any = (uint64_t *)(b + 3 * o8), *d_none = (uint64_t *)(b + 3 * o8 + m8);
-  float *d_q = (float *)(b + 3 * o8 + 2 * m8);
-  int32_t *d_c = (int32_t *)(b + 3 * o8 + 2 * m8 + qb);
-  HIPCHECK(h, hipMemcpy(d_q, q_host, (size_t)Q * S * sizeof(float), hipMemcpyHostToDevice));
+  const size_t o8 = (size_t)Q * k * 8, m8 = (size_t)Q * 8, qb = (size_t)Q * h->idx_S * sizeof(float);
+  char *piece[7];  // scores | ids | groups | any | none | queries | counts
+  if (stage_pieces(h, {o8, o8, o8, m8, m8, qb, (size_t)Q * 4}, piece)) return 1;
+  double *d_s = (double *)piece[0];
+  int64_t *d_i = (int64_t *)piece[1], *d_g = (int64_t *)piece[2];
+  uint64_t *d_any = (uint64_t *)piece[3], *d_none = (uint64_t *)piece[4];
+  float *d_q = (float *)piece[5];
+  int32_t *d_c = (int32_t *)piece[6];
+  HIPCHECK(h, hipMemcpy(d_q, q_host, qb, hipMemcpyHostToDevice));
   if (q_any) HIPCHECK(h, hipMemcpy(d_any, q_any, m8, hipMemcpyHostToDevice));
   if (q_none) HIPCHECK(h, hipMemcpy(d_none, q_none, m8, hipMemcpyHostToDevice));
   if (score_grouped_dev_locked(h, d_q, Q, k, q_any ? d_any : nullptr, q_none ? d_none : nullptr, d_s, d_i, d_g, d_c, nullptr)) return 1;

@@ -26,10 +26,17 @@ def _scorer(S=8):
 
 
 @pytest.mark.parametrize("Q,N,S,how", [(65, 4099, 256, "f32"), (65, 4099, 256, "f64"), (65, 4099, 256, "dev"),
-                                       (65, 31, 50, "f32"), (9, 1, 50, "f32")])
+                                       (65, 31, 50, "f32"), (9, 1, 50, "f32"),
+                                       (40, 700, 300, "f32"), (40, 700, 620, "f32"), (8, 8227, 20, "f32")])
 def test_segment_is_a_prefix_of_the_certified_ranking(Q, N, S, how):
     """N = 4099: a partial last tile and 8 index splits; S = 50: not a multiple of 8; N = 1.  Threshold = the score of column
-    j of score_topk: the segment is columns 0 .. j, ids and bits."""
+    j of score_topk: the segment is columns 0 .. j, ids and bits.
+    The sweep's other instantiations and its other decode (csrc/score_sweep.h): S = 300 (296 < S <= 616) is two pair tiles
+    per workgroup, S = 620 one, with 78 k-groups (78 % 4 = 2: the head of the k-loop and its ring); the 200 pairs leave the
+    last pair block partial.  N = 8227 = 257 * 32 + 3 is 258 tiles with a partial last one, and choose_nsplit gives 16 splits
+    for any number of pairs: doubling goes on while 258 / (2 splits) >= 16, so it stops at 16, and evening out the rounds
+    needs 200 tiles per split.  More than 8 splits is the second branch of the workgroup decode and of the grid size;
+    S = 20 is 3 k-groups: all head, no ring body."""
     rng = np.random.RandomState(Q + N + S)
     q, t = RC.unit(rng, Q, S), RC.unit(rng, N, S)
     h = _scorer()

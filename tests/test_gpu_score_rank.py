@@ -39,10 +39,17 @@ def _check_against_topk(h, q, N, k):
 
 @pytest.mark.parametrize("Q,N,S,how", [(257, 4099, 256, "f32"), (257, 4099, 256, "f64"), (257, 4099, 256, "dev"),
                                        (257, 31, 50, "f32"), (257, 31, 50, "f64"), (257, 31, 50, "dev"),
-                                       (33, 1, 50, "f32"), (33, 1, 256, "f64"), (33, 1, 256, "dev")])
+                                       (33, 1, 50, "f32"), (33, 1, 256, "f64"), (33, 1, 256, "dev"),
+                                       (40, 700, 300, "f32"), (40, 700, 620, "f32"), (8, 8227, 20, "f32")])
 def test_rank_agrees_with_certified_topk(Q, N, S, how):
     """N = 4099: a partial last tile and 8 index splits; S = 50: not a multiple of 8; N = 1.  Index uploaded as float32, as
-    float64 (the re-scorer then reads the float64 rows) and adopted from device memory."""
+    float64 (the re-scorer then reads the float64 rows) and adopted from device memory.
+    The sweep's other instantiations and its other decode (csrc/score_sweep.h): S = 300 (296 < S <= 616) is two pair tiles
+    per workgroup, S = 620 one, with 78 k-groups (78 % 4 = 2: the head of the k-loop and its ring); the 2560 pairs leave the
+    last pair block partial.  N = 8227 = 257 * 32 + 3 is 258 tiles with a partial last one, and choose_nsplit gives 16 splits
+    for any number of pairs: doubling goes on while 258 / (2 splits) >= 16, so it stops at 16, and evening out the rounds
+    needs 200 tiles per split.  More than 8 splits is the second branch of the workgroup decode and of the grid size;
+    S = 20 is 3 k-groups: all head, no ring body."""
     rng = np.random.RandomState(Q + N + S)
     q, t = RC.unit(rng, Q, S), RC.unit(rng, N, S)
     h = _scorer()
