@@ -332,6 +332,43 @@ int sse_score_topk_grouped_dev(sse_handle *h, const float *q_dev, int32_t Q, int
                                const uint64_t *q_none_dev, double *out_scores_dev, int64_t *out_ids_dev,
                                int64_t *out_groups_dev, int32_t *out_counts_dev, void *stream);
 
+/* Exact next page of the ranked list: the k best rows AFTER a (score, id) cursor, in the order sse_score_topk ranks by.  The
+ * reference cuts the sorted row of every target at nbest (webserver.py:144-151); what follows the rows a caller already holds
+ * is asked for here by handing back the last (score, id) it saw.  The cursor is stateless, and the same cursor is valid on
+ * every row shard because ids are global through id_base.
+ *   Row r is AFTER the cursor of query q iff score64(q, r) < after_score[q], or score64(q, r) == after_score[q] and
+ *   id_base + r > after_id[q], where score64 is the float64 dot product sse_score_topk returns for that row, bit for bit,
+ *   and the comparisons are IEEE: a cursor score of +inf puts every row after it (the first page), NaN and -inf none.  The
+ *   cursor need not be a row of this index: any (double, int64) is valid -- what a shard gets for a cursor row that lives
+ *   elsewhere.
+ * after_score and after_id are both given or both NULL; both NULL means no cursor (every row is after it).  Row eligibility is
+ * the tag rule of sse_score_topk_filtered (q_any / q_none may be NULL; giving either while no tags are set is an error); there
+ * are no exclusion lists.
+ *   out_counts [Q]: c = min(k, eligible rows after the cursor).
+ *   out_scores / out_ids [Q][k]: columns 0 .. c of row q are exactly the columns of sse_score_topk(..., k = N) for that query
+ *     with the ineligible rows and the rows not after the cursor removed -- the same float64 score bits, score descending,
+ *     equal scores by ascending id, ids including id_base; columns c .. k hold (-inf, INT64_MAX).  1 <= k <= 1024; k may
+ *     exceed N.
+ * Feeding the last (score, id) of a page back as the cursor yields the following rows: pages concatenated are
+ * sse_score_topk(k = N).  With e the certified fp32 bound of the query, a first kernel brackets the cursor score by
+ * lo = (after_score - e) rounded down and hi = (after_score + e) rounded up to fp32; the fp32 MFMA sweep keeps maxima over
+ * disjoint row sets of the tag-eligible rows below lo (certainly after the cursor), their k-th largest less 2 e is a threshold
+ * no row of the answer scores below, the same sweep again collects every tag-eligible row from there up to hi, and those are
+ * re-scored in float64, the rows not after the cursor dropped on (score64, id), the rest sorted (counter
+ * "score_after_collected_rows": rows re-scored); a query with more than 4096 such rows is served by a float64 sweep of the
+ * whole index with the same predicate ("score_after_bruteforce_queries").  Option "score_filtered_skip" governs the tile skip
+ * here too and changes no result.  Scratch is bounded by the chunk of 4096 queries.  Rows or queries of norm below 2^-100 and
+ * non-finite rows or queries are outside the claim (no fault); non-finite cursors are inside it, as stated above.
+ * Q == 0 succeeds.  No index, k out of range, one cursor array without the other, masks without tags: error with a message,
+ * decided on the host before anything is queued, no output written, the handle stays usable.  The host form runs on the null
+ * stream and synchronises; the _dev form takes device pointers, enqueues on `stream` and never waits for the device. */
+int sse_score_topk_after(sse_handle *h, const float *q_host, int32_t Q, int32_t k, const double *after_score,
+                         const int64_t *after_id, const uint64_t *q_any, const uint64_t *q_none, double *out_scores,
+                         int64_t *out_ids, int32_t *out_counts);
+int sse_score_topk_after_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, const double *after_score_dev,
+                             const int64_t *after_id_dev, const uint64_t *q_any_dev, const uint64_t *q_none_dev,
+                             double *out_scores_dev, int64_t *out_ids_dev, int32_t *out_counts_dev, void *stream);
+
 /* encode + score in one call, the encodings never leaving the device: session.run([src_seq_embedding | norm_...])
  * followed by np.dot + getSortedResults[:k] as sse_demo.py:121-129, webserver.py:144-151 (and the three other routes)
  * and sse_evaluator.py:107-111 do per query / batch.  enc_out_host (may be NULL) also receives the [B,S] encodings. */

@@ -59,6 +59,8 @@ SYMBOLS = {
     "sse_index_set_groups_dev": (C.c_int, [_P, _P, C.c_int64, _P]),
     "sse_score_topk_grouped": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "sse_score_topk_grouped_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "sse_score_topk_after": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "sse_score_topk_after_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sse_encode_score_topk": (C.c_int, [_P, C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_merge_topk_dev": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_merge_topk_strided_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
@@ -459,6 +461,47 @@ class Handle(object):
         """score_topk_grouped on device pointers (any_ptr / none_ptr may be None / 0), enqueued on `stream`."""
         self.check(self.lib.sse_score_topk_grouped_dev(self._h, q_ptr, int(Q), int(k), any_ptr or None, none_ptr or None,
                                                        scores_ptr, ids_ptr, groups_ptr, counts_ptr, stream))
+
+    def score_topk_after(self, queries, k, after=None, any_of=None, none_of=None):
+        """The next k rows of score_topk's ranked list after a cursor.  after: None (no cursor: the first page) or (scores
+        float64 [Q], ids int64 [Q]), the last (score, id) each query has seen -- a row is after it when its float64 score is
+        lower, or equal with a higher id; +inf starts at the top, NaN / -inf leave nothing.  any_of / none_of: uint64 [Q] tag
+        masks, the eligibility rule of score_topk_filtered.  Returns (scores float64 [Q,k], ids int64 [Q,k], counts int32
+        [Q]): the first counts[q] columns are score_topk's columns with the ineligible rows and the rows not after the cursor
+        removed, the rest hold (-inf, INT64_MAX)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError("queries must be [Q,S]")
+        Q, k = q.shape[0], int(k)
+        cs = ci = None
+        if after is not None:
+            cs = np.ascontiguousarray(after[0], dtype=np.float64).reshape(-1)
+            ci = np.ascontiguousarray(after[1], dtype=np.int64).reshape(-1)
+            if cs.shape[0] != Q or ci.shape[0] != Q:
+                raise ValueError("after must be (scores float64 [Q], ids int64 [Q])")
+        masks = []
+        for m in (any_of, none_of):
+            if m is not None:
+                m = np.ascontiguousarray(m, dtype=np.uint64).reshape(-1)
+                if m.shape[0] != Q:
+                    raise ValueError("any_of / none_of must be uint64 [Q]")
+            masks.append(m)
+        scores = np.empty((Q, max(k, 0)), np.float64)
+        ids = np.empty((Q, max(k, 0)), np.int64)
+        counts = np.empty(Q, np.int32)
+        self.check(self.lib.sse_score_topk_after(self._h, _ptr(q), Q, k, _ptr(cs) if cs is not None else None,
+                                                 _ptr(ci) if ci is not None else None,
+                                                 _ptr(masks[0]) if masks[0] is not None else None,
+                                                 _ptr(masks[1]) if masks[1] is not None else None,
+                                                 _ptr(scores), _ptr(ids), _ptr(counts)))
+        return scores, ids, counts
+
+    def score_topk_after_dev(self, q_ptr, Q, k, after_score_ptr, after_id_ptr, any_ptr, none_ptr, scores_ptr, ids_ptr, counts_ptr,
+                             stream=0):
+        """score_topk_after on device pointers (the cursor pointers both None / 0: no cursor; any_ptr / none_ptr may be
+        None / 0), enqueued on `stream`."""
+        self.check(self.lib.sse_score_topk_after_dev(self._h, q_ptr, int(Q), int(k), after_score_ptr or None, after_id_ptr or None,
+                                                     any_ptr or None, none_ptr or None, scores_ptr, ids_ptr, counts_ptr, stream))
 
     def merge_topk_strided_dev(self, in_s, in_i, shard_stride, P, Q, k, out_s, out_i, stream=0):
         self.check(self.lib.sse_merge_topk_strided_dev(self._h, in_s, in_i, int(shard_stride), P, Q, k, out_s, out_i, stream))

@@ -182,28 +182,6 @@ __global__ __launch_bounds__(256) void filtered_threshold_kernel(FilteredArgs a)
   }
 }
 
-// bitonic sort of n2 (power of two) entries in LDS by (key descending, row ascending): the order of before()
-__device__ __forceinline__ void ft_sort_entries(unsigned long long *skey, int *srow, int n2, int tid) {
-  for (int size = 2; size <= n2; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int i = tid; i < (n2 >> 1); i += 256) {
-        const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
-        const bool desc = ((lo & size) == 0);
-        const unsigned long long x = skey[lo], y = skey[hi];
-        const int rx = srow[lo], ry = srow[hi];
-        const bool x_after_y = (x < y) || (x == y && rx > ry);
-        if (x_after_y == desc) {
-          skey[lo] = y;
-          skey[hi] = x;
-          srow[lo] = ry;
-          srow[hi] = rx;
-        }
-      }
-    }
-  __syncthreads();
-}
-
 // is id among the query's exclusion list?  One lane per entry (n_excl <= 64); the answer is wave-uniform.
 __device__ __forceinline__ bool ft_excluded(const int64_t *ex, int n_excl, int64_t id, int lane) {
   if (n_excl == 0) return false;

@@ -1,5 +1,5 @@
-// Helpers shared by the eligible-row selections (score_filtered.hip, score_grouped.hip): order-preserving keys of fp32 and
-// float64 scores, the bitonic sort of maxima keys, the padding row of the select stages.
+// Helpers shared by the eligible-row selections (score_filtered.hip, score_grouped.hip, score_after.hip): order-preserving keys
+// of fp32 and float64 scores, the bitonic sorts of maxima keys and of (key, row) entries, the padding row of the select stages.
 #pragma once
 #include <stdint.h>
 
@@ -40,3 +40,24 @@ __device__ __forceinline__ double ft_unkey64(unsigned long long u) {
 
 #define FT_PAD_ROW 0x7FFFFFFF  // (padding entries: key 0 is below the key of every score, -inf included)
 
+// bitonic sort of n2 (power of two) entries in LDS by (key descending, row ascending): the order of before()
+__device__ __forceinline__ void ft_sort_entries(unsigned long long *skey, int *srow, int n2, int tid) {
+  for (int size = 2; size <= n2; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      __syncthreads();
+      for (int i = tid; i < (n2 >> 1); i += 256) {
+        const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
+        const bool desc = ((lo & size) == 0);
+        const unsigned long long x = skey[lo], y = skey[hi];
+        const int rx = srow[lo], ry = srow[hi];
+        const bool x_after_y = (x < y) || (x == y && rx > ry);
+        if (x_after_y == desc) {
+          skey[lo] = y;
+          skey[hi] = x;
+          srow[lo] = ry;
+          srow[hi] = rx;
+        }
+      }
+    }
+  __syncthreads();
+}

@@ -1,7 +1,7 @@
-// The fp32 index sweep shared by sse_score_rank, sse_score_above, sse_score_topk_filtered and sse_score_topk_grouped
-// (score_rank.hip, score_above.hip, score_filtered.hip, score_grouped.hip; DESIGN K6i): [N,S] x [S,P] on
-// v_mfma_f32_32x32x2_f32 from the fragment-order index, the sweep of score_topk_kernel's COLLECT variant with the queries
-// taken row-major.  Each of the four kernels keeps its own prologue (what a lane holds per column) and epilogue (what it
+// The fp32 index sweep shared by sse_score_rank, sse_score_above, sse_score_topk_filtered, sse_score_topk_grouped and
+// sse_score_topk_after (score_rank.hip, score_above.hip, score_filtered.hip, score_grouped.hip, score_after.hip; DESIGN K6i):
+// [N,S] x [S,P] on v_mfma_f32_32x32x2_f32 from the fragment-order index, the sweep of score_topk_kernel's COLLECT variant with
+// the queries taken row-major.  Each of the kernels keeps its own prologue (what a lane holds per column) and epilogue (what it
 // does with a tile's 16 scores per column) and calls the pieces below in this order:
 //   sweep_decode         workgroup = (block of NQ x 32 columns, index split)
 //   sweep_stage_queries  the block's query rows into LDS as MFMA B fragments [k-group][column tile][1 KiB]
@@ -9,7 +9,7 @@
 //   SWEEP_TILE_MFMA      one index tile (32 rows, M) x NQ column tiles (N): index fragments from global memory PF k-groups
 //                        ahead (a ring in registers), query fragments from LDS
 //   sweep_row ...        a lane owns column (lane & 31) of every column tile and 16 rows of the index tile
-// A column is a (query, label) or (query, threshold) pair for rank and above, a query for filtered and grouped.
+// A column is a (query, label) or (query, threshold) pair for rank and above, a query for filtered, grouped and after.
 #pragma once
 #include "sse_kernels.h"
 

@@ -246,7 +246,11 @@ struct sse_handle {
   // while groups_set; the (key, row) maxima of a chunk, the two "score_grouped_*" counters
   DevBuf idx_groups, s_gp_max, s_gp_cnt;
   bool groups_set = false, gp_cnt_init = false;
-  // staging of the host forms of the four calls above (stage_pieces): they hold the handle's mutex and finish all device work
+  // next page after a cursor (sse_score_topk_after*, score_after.hip): the bracket of a chunk's cursor scores ([P] e as double,
+  // [P] lo, [P] hi), the two "score_after_*" counters.  Maxima, thresholds and row buffers are the filtered call's.
+  DevBuf s_af_bnd, s_af_cnt;
+  bool af_cnt_init = false;
+  // staging of the host forms of the five calls above (stage_pieces): they hold the handle's mutex and finish all device work
   // before they return, so one buffer serves them all
   DevBuf s_stage;
   // forward-only pair loss (sse_eval_loss*, eval_loss.hip).  Option "eval_chunk_rows": pair rows staged and encoded per chunk (even).
@@ -1500,6 +1504,69 @@ static int score_filtered_dev_locked(sse_handle *h, const float *q, int Q, int k
   return 0;
 }
 
+// argument errors of sse_score_topk_after*, all decidable on the host
+static int score_after_check(sse_handle *h, int Q, int k, const void *after_score, const void *after_id, const void *q_any, const void *q_none) {
+  if (!h->idxp) return fail(h, "sse_score_topk_after: no index uploaded");
+  if (Q < 0) return fail(h, "bad arguments to sse_score_topk_after");
+  if (k < 1 || k > SSE_AFTER_MAX_K) return fail(h, "sse_score_topk_after: k = %d is not in [1, %d]", k, SSE_AFTER_MAX_K);
+  if ((after_score == nullptr) != (after_id == nullptr))
+    return fail(h, "sse_score_topk_after: after_score and after_id are both given or both NULL (%s is missing)", after_score ? "after_id" : "after_score");
+  if ((q_any || q_none) && !h->tags_set) return fail(h, "sse_score_topk_after: tag masks given but the index has no tags (sse_index_set_tags)");
+  return 0;
+}
+
+// sse_score_topk_after*: every stage queued on `st` (device pointers throughout), queries in chunks of 4096 with the chunk
+// scratch of the filtered call and the cursor brackets beside it (DESIGN K6j).
+static int score_after_dev_locked(sse_handle *h, const float *q, int Q, int k, const double *after_s, const int64_t *after_i,
+                                  const uint64_t *q_any, const uint64_t *q_none, double *out_s, int64_t *out_i, int32_t *out_c,
+                                  hipStream_t st) {
+  const int POOL = 4096;
+  const int S = h->idx_S;
+  const int64_t NT = (h->idx_N + 31) / 32;
+  if (ensure_zeroed_once(h, h->s_af_cnt, h->af_cnt_init, 3, st)) return 1;
+  AfterArgs g;
+  FilteredArgs &a = g.f;
+  fill_filtered_common(h, a, k, 0, h->s_af_cnt);
+  a.excl = nullptr;
+  for (int q0 = 0; q0 < Q; q0 += POOL) {
+    const int P = std::min(POOL, Q - q0);
+    SweepChunk ck;
+    if (sweep_chunk(h, P, ck)) return 1;
+    int nsplit = ck.nsplit;
+    // at least 2 k maxima per query where every wave of a split still has a tile of its own
+    while (nsplit < 128 && nsplit * 256 < 2 * k && NT / (nsplit * 2) >= 8) nsplit *= 2;
+    const int NV = std::min(nsplit, 16) * 256;
+    if (reserve(h, h->s_ft_max, (size_t)P * NV * sizeof(uint32_t))) return 1;
+    if (reserve(h, h->s_cthr, (size_t)P * sizeof(float))) return 1;
+    if (reserve(h, h->s_ccnt, (size_t)(P + 1) * sizeof(int32_t))) return 1;
+    if (reserve(h, h->s_cbuf, (size_t)P * SSE_COLLECT_CAP * sizeof(int32_t))) return 1;
+    if (reserve(h, h->s_af_bnd, (size_t)P * (sizeof(double) + 2 * sizeof(float)))) return 1;
+    HIPCHECK(h, hipMemsetAsync(h->s_ft_max.p, 0, (size_t)P * NV * sizeof(uint32_t), st));
+    HIPCHECK(h, hipMemsetAsync(h->s_ccnt.p, 0, (size_t)P * sizeof(int32_t), st));
+    a.q = q + (size_t)q0 * S;
+    a.q_any = q_any ? q_any + q0 : nullptr;
+    a.q_none = q_none ? q_none + q0 : nullptr;
+    a.maxima = (uint32_t *)h->s_ft_max.p;
+    a.thr = (float *)h->s_cthr.p;
+    a.col_cnt = (int32_t *)h->s_ccnt.p;
+    a.col_buf = (int32_t *)h->s_cbuf.p;
+    a.out_scores = out_s + (size_t)q0 * k;
+    a.out_ids = out_i + (size_t)q0 * k;
+    a.out_counts = out_c + q0;
+    a.P = P;
+    a.NQ = ck.NQ;
+    a.NSPLIT = nsplit;
+    a.NV = NV;
+    g.after_score = after_s ? after_s + q0 : nullptr;
+    g.after_id = after_i ? after_i + q0 : nullptr;
+    g.eb = (double *)h->s_af_bnd.p;
+    g.lo = (float *)(g.eb + P);
+    g.hi = g.lo + P;
+    HIPCHECK(h, launch_score_after(g, st));
+  }
+  return 0;
+}
+
 // sse_index_set_groups*: the keys copied behind the index (device to device on `st`, or from the host).  Nothing changes
 // before every check and allocation has passed.
 static int index_set_groups_locked(sse_handle *h, const int64_t *groups, int64_t N, bool from_host, hipStream_t st) {
@@ -2393,6 +2460,18 @@ int sse_get_counter(sse_handle *h, const char *name, int64_t *value) {
     *value = (int64_t)v[i];
     return 0;
   }
+  static const char *const after_names[2] = {"score_after_collected_rows", "score_after_bruteforce_queries"};
+  for (int i = 0; i < 2; ++i) {  // sse_score_topk_after*: rows re-scored by the select stage, queries of the float64 sweep
+    if (strcmp(name, after_names[i]) != 0) continue;
+    unsigned long long v[3] = {0, 0, 0};
+    if (h->s_af_cnt.p && h->af_cnt_init) {
+      HIPCHECK(h, hipSetDevice(h->cfg.device));
+      HIPCHECK(h, hipDeviceSynchronize());
+      HIPCHECK(h, hipMemcpy(v, h->s_af_cnt.p, sizeof v, hipMemcpyDeviceToHost));
+    }
+    *value = (int64_t)v[i];
+    return 0;
+  }
   static const char *const names[3] = {"score_bf16_second_chance_queries", "score_collect_queries", "score_bruteforce_queries"};
   for (int i = 0; i < 3; ++i) {
     if (strcmp(name, names[i]) != 0) continue;
@@ -2854,6 +2933,55 @@ int sse_score_topk_grouped(sse_handle *h, const float *q_host, int32_t Q, int32_
   HIPCHECK(h, hipMemcpy(out_scores, d_s, o8, hipMemcpyDeviceToHost));
   HIPCHECK(h, hipMemcpy(out_ids, d_i, o8, hipMemcpyDeviceToHost));
   HIPCHECK(h, hipMemcpy(out_groups, d_g, o8, hipMemcpyDeviceToHost));
+  HIPCHECK(h, hipMemcpy(out_counts, d_c, (size_t)Q * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int sse_score_topk_after_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, const double *after_score_dev,
+                             const int64_t *after_id_dev, const uint64_t *q_any_dev, const uint64_t *q_none_dev,
+                             double *out_scores_dev, int64_t *out_ids_dev, int32_t *out_counts_dev, void *stream) {
+  if (!h) return 1;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  if (score_after_check(h, Q, k, after_score_dev, after_id_dev, q_any_dev, q_none_dev)) return 1;
+  if (Q == 0) return 0;
+  if (!q_dev || !out_scores_dev || !out_ids_dev || !out_counts_dev) return fail(h, "bad arguments to sse_score_topk_after");
+  return score_after_dev_locked(h, q_dev, Q, k, after_score_dev, after_id_dev, q_any_dev, q_none_dev, out_scores_dev, out_ids_dev,
+                                out_counts_dev, (hipStream_t)stream);
+}
+
+int sse_score_topk_after(sse_handle *h, const float *q_host, int32_t Q, int32_t k, const double *after_score,
+                         const int64_t *after_id, const uint64_t *q_any, const uint64_t *q_none, double *out_scores,
+                         int64_t *out_ids, int32_t *out_counts) {
+  if (!h) return 1;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  if (score_after_check(h, Q, k, after_score, after_id, q_any, q_none)) return 1;
+  if (Q == 0) return 0;
+  if (!q_host || !out_scores || !out_ids || !out_counts) return fail(h, "bad arguments to sse_score_topk_after");
+  const size_t o8 = (size_t)Q * k * 8, m8 = (size_t)Q * 8, qb = (size_t)Q * h->idx_S * sizeof(float);
+  char *piece[8];  // scores | ids | cursor scores | cursor ids | any | none | queries | counts
+  if (stage_pieces(h, {o8, o8, m8, m8, m8, m8, qb, (size_t)Q * 4}, piece)) return 1;
+  double *d_s = (double *)piece[0];
+  int64_t *d_i = (int64_t *)piece[1];
+  double *d_as = (double *)piece[2];
+  int64_t *d_ai = (int64_t *)piece[3];
+  uint64_t *d_any = (uint64_t *)piece[4], *d_none = (uint64_t *)piece[5];
+  float *d_q = (float *)piece[6];
+  int32_t *d_c = (int32_t *)piece[7];
+  HIPCHECK(h, hipMemcpy(d_q, q_host, qb, hipMemcpyHostToDevice));
+  if (after_score) {
+    HIPCHECK(h, hipMemcpy(d_as, after_score, m8, hipMemcpyHostToDevice));
+    HIPCHECK(h, hipMemcpy(d_ai, after_id, m8, hipMemcpyHostToDevice));
+  }
+  if (q_any) HIPCHECK(h, hipMemcpy(d_any, q_any, m8, hipMemcpyHostToDevice));
+  if (q_none) HIPCHECK(h, hipMemcpy(d_none, q_none, m8, hipMemcpyHostToDevice));
+  if (score_after_dev_locked(h, d_q, Q, k, after_score ? d_as : nullptr, after_score ? d_ai : nullptr, q_any ? d_any : nullptr,
+                             q_none ? d_none : nullptr, d_s, d_i, d_c, nullptr))
+    return 1;
+  HIPCHECK(h, sync_stream(nullptr));
+  HIPCHECK(h, hipMemcpy(out_scores, d_s, o8, hipMemcpyDeviceToHost));
+  HIPCHECK(h, hipMemcpy(out_ids, d_i, o8, hipMemcpyDeviceToHost));
   HIPCHECK(h, hipMemcpy(out_counts, d_c, (size_t)Q * 4, hipMemcpyDeviceToHost));
   return 0;
 }

@@ -540,6 +540,19 @@ struct GroupedArgs {
 };
 #define SSE_GROUPED_MAX_K 1024
 hipError_t launch_score_grouped(const GroupedArgs &g, hipStream_t st);  // every stage of one chunk
+// Exact next k tag-eligible rows after a (score, id) cursor (score_after.hip, DESIGN K6j): the stages of FilteredArgs (no
+// exclusion lists: excl = nullptr, n_excl = 0) with an fp32 bracket [lo, hi] of the cursor score in front of them.  The max
+// sweep takes rows below lo only, the collect sweep rows in [thr, hi], the select stage drops what is not after the cursor in
+// float64.  counters of `f`: [0] rows re-scored by the select stage, [1] queries of the float64 sweep.
+struct AfterArgs {
+  FilteredArgs f;
+  const double *after_score;  // [P] cursor scores, or nullptr together with after_id: no cursor
+  const int64_t *after_id;    // [P] cursor ids (global: id_base included)
+  float *lo, *hi;             // [P] scratch: rd(cs - e), ru(cs + e)
+  double *eb;                 // [P] scratch: e = eps32 |q| (1 + 2^-20)
+};
+#define SSE_AFTER_MAX_K 1024
+hipError_t launch_score_after(const AfterArgs &g, hipStream_t st);  // every stage of one chunk
 // tile_sum[t] = OR of tags[32 t .. 32 t + 32) (tags padded with zero words to NT * 32)
 hipError_t launch_tag_tile_summary(const uint64_t *tags, int64_t NT, uint64_t *tile_sum, hipStream_t st);
 

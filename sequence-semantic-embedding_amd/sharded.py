@@ -235,6 +235,57 @@ class ShardedIndex(object):
         all_reduce_(total, group=self.group)
         return out[0].view(torch.float64), out[1], torch.clamp(total, max=k).to(torch.int32)
 
+    def score_topk_after(self, queries, k, after=None, any_of=None, none_of=None):
+        """Handle.score_topk_after over the whole sharded index: queries CUDA float32 [Q,S], after = None or (scores float64
+        [Q], ids int64 [Q]) tensors -- GLOBAL cursors, the same on every rank, whichever rank holds the cursor's row --
+        any_of / none_of int64 [Q] tensors holding the uint64 mask bits (or None).  Returns (scores float64 [Q,k], ids int64
+        [Q,k], counts int32 [Q]) on every rank: what the unsharded call returns.  An offset could not be sharded (a shard
+        cannot know how many of the rows before it are its own); a cursor can: every rank returns its own k rows after it,
+        padded to k, ONE all-gather exchanges the lists, the k-way merge ranks padding behind every real entry, ONE
+        all-reduce adds the counts."""
+        import torch
+        import torch.distributed as dist
+        from .collectives import all_gather_into, all_reduce_
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise ValueError("k=%d must be in [1, 1024]" % k)
+        Q = int(queries.shape[0])
+        dev = queries.device
+        cs = ci = None
+        if after is not None:
+            cs, ci = after
+            if cs.shape[0] != Q or ci.shape[0] != Q or cs.dtype != torch.float64 or ci.dtype != torch.int64:
+                raise ValueError("after must be (float64 [Q], int64 [Q]) tensors")
+            cs, ci = cs.contiguous(), ci.contiguous()
+        for m in (any_of, none_of):
+            if m is not None and (m.shape[0] != Q or m.dtype != torch.int64):
+                raise ValueError("any_of / none_of must be int64 [Q] tensors of mask bits")
+        queries = queries.contiguous()
+        any_of = any_of.contiguous() if any_of is not None else None
+        none_of = none_of.contiguous() if none_of is not None else None
+        stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
+        loc = torch.empty((2, Q, k), dtype=torch.int64, device=dev)        # [0] = float64 score bits, [1] = row ids
+        cnt = torch.zeros(Q, dtype=torch.int32, device=dev)
+        if self.end > self.start and Q > 0:
+            self.handle.score_topk_after_dev(queries.data_ptr(), Q, k, cs.data_ptr() if cs is not None else None,
+                                             ci.data_ptr() if ci is not None else None,
+                                             any_of.data_ptr() if any_of is not None else None,
+                                             none_of.data_ptr() if none_of is not None else None,
+                                             loc[0].data_ptr(), loc[1].data_ptr(), cnt.data_ptr(), stream)
+        else:
+            loc[0].view(torch.float64).fill_(float("-inf"))
+            loc[1].fill_(torch.iinfo(torch.int64).max)
+        if Q == 0 or (self.world == 1 and not self.always_gather):
+            return loc[0].view(torch.float64), loc[1], cnt
+        world = dist.get_world_size(self.group)
+        g = torch.empty((world * 2, Q, k), dtype=torch.int64, device=dev)
+        all_gather_into(g, loc, group=self.group)
+        out = torch.empty((2, Q, k), dtype=torch.int64, device=dev)
+        self.handle.merge_topk_strided_dev(g.data_ptr(), g[1].data_ptr(), 2 * Q * k, world, Q, k, out[0].data_ptr(), out[1].data_ptr(), stream)
+        total = cnt.to(torch.int64)
+        all_reduce_(total, group=self.group)
+        return out[0].view(torch.float64), out[1], torch.clamp(total, max=k).to(torch.int32)
+
     def set_local_groups(self, groups):
         """groups: CUDA int64 tensor [end-start] -- the group keys of this rank's rows, set after set_local_rows.  None
         clears them; a rank without rows has nothing to group."""

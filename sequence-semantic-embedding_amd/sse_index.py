@@ -150,6 +150,47 @@ def hard_negatives(handle, queries, positives, n):
     return ids, scores
 
 
+def ranked_pages(handle, queries, page, any_of=None, none_of=None):
+    """The whole ranked list of every query, page after page (the reference sorts all targets and cuts once, webserver.py:
+    144-151): a generator of (scores float64 [Q,page], ids int64 [Q,page], counts int32 [Q]) from Handle.score_topk_after, each
+    call fed with every query's last real entry of the call before.  The pages of a query concatenated over their counts are
+    Handle.score_topk(k = N) with the ineligible rows removed; a query that has run out keeps returning count 0.  Stops
+    when every count is 0 (that page is not yielded) -- known without a call once every count fell short of `page`."""
+    q = np.ascontiguousarray(queries, dtype=np.float32)
+    Q, page = q.shape[0], int(page)
+    cs = np.full(Q, np.inf)                                  # +inf: every row is after it
+    ci = np.zeros(Q, np.int64)
+    while Q > 0:
+        scores, ids, counts = handle.score_topk_after(q, page, after=(cs, ci), any_of=any_of, none_of=none_of)
+        if not counts.any():
+            return
+        yield scores, ids, counts
+        if (counts < page).all():
+            return
+        rows = np.flatnonzero(counts > 0)
+        cs[rows], ci[rows] = scores[rows, counts[rows] - 1], ids[rows, counts[rows] - 1]
+        # (a query whose count is 0 keeps the cursor that already has nothing after it)
+
+
+def ranked_rows(handle, queries, k_total, page=1024):
+    """The first k_total rows of every query's ranked list for ANY k_total, built from ranked_pages in pages of at most 1024:
+    (scores, ids), two lists of Q float64 / int64 arrays of min(k_total, N) entries each, score_topk's columns bit for bit."""
+    q = np.ascontiguousarray(queries, dtype=np.float32)
+    Q, k_total = q.shape[0], int(k_total)
+    out_s, out_i = [[] for _ in range(Q)], [[] for _ in range(Q)]
+    have = 0
+    if k_total > 0:
+        for scores, ids, counts in ranked_pages(handle, q, min(int(page), 1024)):
+            for r in range(Q):
+                out_s[r].append(scores[r, :counts[r]])
+                out_i[r].append(ids[r, :counts[r]])
+            have += scores.shape[1]
+            if have >= k_total:
+                break
+    return ([np.concatenate(s)[:k_total] if s else np.zeros(0, np.float64) for s in out_s],
+            [np.concatenate(i)[:k_total] if i else np.zeros(0, np.int64) for i in out_i])
+
+
 def write_near_duplicates(path, tgt_ids, pairs):
     """nearDuplicates.tsv: tgtid_a \\t tgtid_b \\t repr(float64 score), one pair per line."""
     with codecs.open(path, "w", "utf-8") as out:

@@ -74,13 +74,21 @@ class Ranker(object):
         """webserver.py:135-142: encode(lower-cased text), left-pad / truncate to max_seq_length."""
         return sse_text.pad_tokens(self.encoder.encode(text.lower()), self.max_seq_length)
 
-    def rank(self, token_rows, nbest, normalize):
-        """Top-`nbest` (score, target id, target name) per token row; one encode + one sweep for all rows."""
+    def rank(self, token_rows, nbest, normalize, after=None):
+        """Top-`nbest` (score, target id, target name) per token row; one encode + one sweep for all rows.
+        after = (scores [B], row ids [B]): the next `nbest` (at most 1024) after each row's (score, row id) cursor instead, in
+        the same order (Handle.score_topk_after), as (score, target id, target name, row id) -- a list may be shorter than
+        `nbest`, or empty, when the ranked list ends."""
         h = self.model.handle
         if h.index_gen != self._index_gen:                  # somebody scored another index on this handle
             h.index_upload(self._encodings)
             self._index_gen = h.index_gen
         k = max(1, min(int(nbest), len(self.targetIDs)))
+        if after is not None:
+            enc = h.encode(0, np.asarray(token_rows, np.int32), normalize)
+            scores, rows, counts = h.score_topk_after(enc, min(k, 1024), after=after)
+            return [[(float(scores[i, j]), self.targetIDs[rows[i, j]], self.targetNames[rows[i, j]], int(rows[i, j]))
+                     for j in range(int(counts[i]))] for i in range(len(token_rows))]
         scores, rows = h.encode_score_topk(0, np.asarray(token_rows, np.int32), normalize, k)
         return [[(float(scores[i, j]), self.targetIDs[rows[i, j]], self.targetNames[rows[i, j]]) for j in range(k)]
                 for i in range(len(token_rows))]
@@ -146,9 +154,23 @@ class MicroBatcher(object):
                         it["done"].set()
 
 
+def parse_cursor(args):
+    """The optional GET arguments after_score / after_id of a paged request -> (float, int) or None; ValueError when one
+    comes without the other or does not parse.  The score is what a response's next_after_score said: Python's float()
+    reads back the repr that json.dumps wrote, bit for bit ('inf' / 'Infinity' start at the top)."""
+    if "after_score" not in args and "after_id" not in args:
+        return None
+    if "after_score" not in args or "after_id" not in args:
+        raise ValueError("after_score and after_id go together")
+    return float(args["after_score"]), int(args["after_id"])
+
+
 def handle_request(path, args, rank_fn, tokens_fn):
     """Route logic shared by the WSGI app and the tests: returns (status, body dict | str).
-    `args`: {name: value}; `rank_fn(tokens, nbest, normalize)` -> [(score, id, name)]."""
+    `args`: {name: value}; `rank_fn(tokens, nbest, normalize)` -> [(score, id, name)].  With after_score and after_id among
+    the arguments the list is the next nbest after that cursor -- `rank_fn(tokens, nbest, normalize, after=(score, row id))`
+    -> [(score, id, name, row id)] -- and the response carries next_after_score / next_after_id, the cursor of the page
+    after this one (the request's own when the list came back empty)."""
     if path == "/":
         return 200, BANNER
     route = ROUTES.get(path)
@@ -161,6 +183,15 @@ def handle_request(path, args, rank_fn, tokens_fn):
     # (the URLs documented in webserver.py:126,166 say '&?nbest=': that argument is named '?nbest', which the
     # reference does not look at -- it answers with the default count; same here)
     nbest = int(args["nbest"]) if "nbest" in args else default_nbest
+    try:
+        cursor = parse_cursor(args)
+    except ValueError as e:
+        return 400, "bad cursor: %s" % e
+    if cursor is not None:
+        ranked = rank_fn(tokens_fn(text), nbest, normalize, after=cursor)
+        results = [{idk: tid, namek: name, scorek: float(score)} for score, tid, name, _row in ranked]
+        nxt = (float(ranked[-1][0]), int(ranked[-1][3])) if ranked else cursor
+        return 200, {qkey: text, rkey: results, "next_after_score": nxt[0], "next_after_id": nxt[1]}
     ranked = rank_fn(tokens_fn(text), nbest, normalize)
     results = []
     for i, (score, tid, name) in enumerate(ranked):
@@ -178,7 +209,9 @@ def create_app(model_dir=None, index_file=None, device=0, ranker=None, batch=Tru
         ranker = Ranker(model_dir, index_file, device)
     batcher = MicroBatcher(ranker) if batch else None
 
-    def rank_fn(tokens, nbest, normalize):
+    def rank_fn(tokens, nbest, normalize, after=None):
+        if after is not None:                                # paged requests go past the micro-batcher
+            return ranker.rank([tokens], nbest, normalize, after=([after[0]], [after[1]]))[0]
         if batcher is not None:
             return batcher.submit(tokens, nbest, normalize)
         return ranker.rank([tokens], nbest, normalize)[0]
