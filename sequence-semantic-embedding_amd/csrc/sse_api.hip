@@ -115,9 +115,6 @@ struct TrainState {
 // sse_handle::lstm_path_calls: one entry per kernel an encode can be sent to, then what the matrix kernel's launcher picked
 enum { PATH_PERSIST, PATH_CLUSTER, PATH_SMALL, PATH_X3, PATH_GENERIC, PATH_FWD, PATH_FWD_ROWS32, PATH_FWD_ROWS64, PATH_FWD_GS, PATH_FWD_XT,
        PATH_COUNT };
-static const char *const LSTM_PATH_NAMES[PATH_COUNT] = {"lstm_path_persist", "lstm_path_cluster", "lstm_path_small", "lstm_path_x3",
-                                                "lstm_path_generic", "lstm_path_fwd", "lstm_fwd_rows32", "lstm_fwd_rows64",
-                                                "lstm_fwd_gate_split", "lstm_fwd_x_table"};
 
 struct sse_handle {
   sse_config cfg;
@@ -128,7 +125,7 @@ struct sse_handle {
   bool packed_dirty = true;
   uint64_t weights_version = 1;  // bumped with every change of a variable: the any-shape path's packs (lstm_generic.hip) are cached against it
   bool mp_fresh = false;     // the packed projections match the variables although packed_dirty is set (ensure_proj_packed)
-  bool pad_skip = true;      // option "pad_skip": exact left-pad prefix skip in inference encodes
+  int pad_skip = 1;      // option "pad_skip": exact left-pad prefix skip in inference encodes
   // option "pad_sort_dev": PAD-prefix bucketing of device-resident id matrices (sse_encode_dev) by two small kernels (pack.hip):
   // 0 off | 1 adaptive: every eligible call measures its batch; rows are bucketed while the latest completed call of that side
   // saw any padding, 32-row tiles while it saw a mean prefix >= T / 4 (no host round trip: an index build's batches look alike)
@@ -139,23 +136,23 @@ struct sse_handle {
   // Window measured on well-spread unit vectors, S = 256 (tools/bench_c3.py, tools/bench_score.py, profiles/r06_notes.txt), two-pass /
   // list sweep in ms: 16,491 queries x 32 k rows 1.19 / 1.03, 64 k 1.58 / 1.72, 128 k 2.39 / 3.07, 256 k 4.13 / 5.51, 512 k 7.61 / 10.17;
   // 1024 x 300 k 0.44 / 0.57; but 8192 x 1.25 M 7.83 / 4.91 (a list-free sweep runs at 0.54 of the bf16 peak there, the list sweep at 0.43)
-  int64_t score_two_pass_min_rows = 49152, score_two_pass_rows = 524288;
+  int score_two_pass_min_rows = 49152, score_two_pass_rows = 524288;
   int64_t two_pass_calls = 0;  // counter "score_two_pass_calls"
   DevBuf s_lmax;
-  bool lstm_gate_split = true;  // option "lstm_gate_split": small cells (H <= 128) at 64-row tiles on lstm_fwd_gs.hip (bit-identical)
+  int lstm_gate_split = 1;  // option "lstm_gate_split": small cells (H <= 128) at 64-row tiles on lstm_fwd_gs.hip (bit-identical)
   DevBuf s_padzero, s_padwork, s_padorder;
   int32_t *pad_stat = nullptr;  // pinned host words the device stores to: [side] {call number, class 0 / 1 / 2}
   int32_t pad_seq = 0;
   int64_t pad_sorted_calls = 0;  // counter "pad_sorted_calls"
-  // counters "lstm_path_*" / "lstm_fwd_*": LSTM inference encodes by the kernel they were sent to (LSTM_PATH_NAMES, same order)
-  int64_t lstm_path_calls[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  bool lstm_x3 = false;       // option "lstm_x3": large inference encodes (Hp = 256) on the bf16 matrix pipe with split operands
+  // counters "lstm_path_*" / "lstm_fwd_*": LSTM inference encodes by the kernel they were sent to (PATH_* order)
+  int64_t lstm_path_calls[PATH_COUNT] = {};
+  int lstm_x3 = 0;       // option "lstm_x3": large inference encodes (Hp = 256) on the bf16 matrix pipe with split operands
   unsigned short *emb16 = nullptr;  // split embedding table of that path
   bool emb16_valid = false;
   int lstm_persist_rows = 32; // option "lstm_persist_rows": batches up to this many rows (<= 32) take the weights-in-LDS cluster kernel
   uint32_t persist_epoch = 0; // tag epoch of the cluster kernel's exchange buffers
   hipStream_t stream = nullptr;  // sse_set_stream: the stream the train-step entry points enqueue on (default: the null stream)
-  bool persist_inject = false;   // testing aid (option lstm_persist_inject_miss): report a missing cluster workgroup after every cluster launch
+  int persist_inject = 0;   // testing aid (option lstm_persist_inject_miss): report a missing cluster workgroup after every cluster launch
   int64_t persist_fallbacks = 0; // host-buffer encodes re-run on lstm_small because a cluster workgroup did not arrive
   int cu_count = 0;           // compute units of the device (co-residency check of the cluster kernel)
   int lstm_cluster_rows = 1024; // option "lstm_cluster_rows": batches above lstm_persist_rows up to this many rows (<= 1024) take the MFMA cluster kernel
@@ -175,9 +172,9 @@ struct sse_handle {
   int lstm_x_table = 1;
   int lstm_x_table_mb = 256;
   int64_t x_table_builds = 0;
-  bool score_small_index = true;  // option "score_small_index": many queries against <= 1024 rows skip the list sweep (launch_score_small_index)
-  bool score_small_x3 = true;     // option "score_small_x3": the small-index scorer forms its candidates from split-bf16 operands (idx_x3; wider r.eps)
-  bool score_bf16 = true;    // option "score_bf16" (default on): candidate pass on the bf16 matrix pipe; results stay exact
+  int score_small_index = 1;  // option "score_small_index": many queries against <= 1024 rows skip the list sweep (launch_score_small_index)
+  int score_small_x3 = 1;     // option "score_small_x3": the small-index scorer forms its candidates from split-bf16 operands (idx_x3; wider r.eps)
+  int score_bf16 = 1;    // option "score_bf16" (default on): candidate pass on the bf16 matrix pipe; results stay exact
   void *idxp16 = nullptr;    // bf16 fragment copy of the index (built on demand)
   size_t idxp16_cap = 0;
   bool idxp16_valid = false;
@@ -188,13 +185,13 @@ struct sse_handle {
   int lstm_train_rows = 0;   // option "lstm_train_rows": 0 = automatic, 32 / 64 = rows per workgroup of the training forward (Hp = 256)
   // The train step computes in fp32 like the reference (tf.float32 graph, sse_model.py:355-364): the three split-operand
   // options below are OPT-IN (a default narrower than the reference's arithmetic earns no credit).
-  bool train_bwd_x3 = false;  // option "train_bwd_x3": recurrent GEMM of BPTT on the bf16 matrix pipe with split operands (needs train_dk_x3)
-  bool train_fwd_x3 = false;  // option "train_fwd_x3": forward of the LSTM train step on the bf16 matrix pipe with split operands
-  bool train_dk_x3 = false;   // option "train_dk_x3": weight-gradient GEMM of the LSTM train step on the bf16 matrix pipe with split operands
-  bool train_generic = false;  // option "train_generic": the LSTM train step on the any-shape path (lstm_generic.hip) whatever the shape (tests, A/B)
-  bool train_gen1 = false;    // option "train_gen1": the fp32 train step on the first-generation kernels (lstm_bwd_kernel + dx_kernel + db partials; A/B timing and tests)
-  bool train_pair_dedup = true; // option "train_pair_dedup": run the source encoder once per (pos, neg) pair of rows that share it
-  bool train_serial = false; // option "train_serial": both encoders on one stream (profiling: isolated kernel times)
+  int train_bwd_x3 = 0;  // option "train_bwd_x3": recurrent GEMM of BPTT on the bf16 matrix pipe with split operands (needs train_dk_x3)
+  int train_fwd_x3 = 0;  // option "train_fwd_x3": forward of the LSTM train step on the bf16 matrix pipe with split operands
+  int train_dk_x3 = 0;   // option "train_dk_x3": weight-gradient GEMM of the LSTM train step on the bf16 matrix pipe with split operands
+  int train_generic = 0;  // option "train_generic": the LSTM train step on the any-shape path (lstm_generic.hip) whatever the shape (tests, A/B)
+  int train_gen1 = 0;    // option "train_gen1": the fp32 train step on the first-generation kernels (lstm_bwd_kernel + dx_kernel + db partials; A/B timing and tests)
+  int train_pair_dedup = 1; // option "train_pair_dedup": run the source encoder once per (pos, neg) pair of rows that share it
+  int train_serial = 0; // option "train_serial": both encoders on one stream (profiling: isolated kernel times)
   float *emb_pad = nullptr;  // [V][Ep]
   // source_only_cnn
   int cnn_W[4] = {-1, -1, -1, -1}, cnn_b[4] = {-1, -1, -1, -1}, cnn_M = -1, tgt_table = -1;
@@ -241,7 +238,7 @@ struct sse_handle {
   // "score_filtered_*" counters.  Thresholds and row buffers are the collect path's (s_cthr, s_ccnt, s_cbuf).
   DevBuf idx_tags, idx_tag_sum, s_ft_max, s_ft_cnt;
   bool tags_set = false, ft_cnt_init = false;
-  bool score_filtered_skip = true;  // option "score_filtered_skip": the sweeps skip index tiles no query of a block can use
+  int score_filtered_skip = 1;  // option "score_filtered_skip": the sweeps skip index tiles no query of a block can use
   // top-k distinct groups (sse_score_topk_grouped*, score_grouped.hip): one int64 key per row of the resident index, valid
   // while groups_set; the (key, row) maxima of a chunk, the two "score_grouped_*" counters
   DevBuf idx_groups, s_gp_max, s_gp_cnt;
@@ -250,7 +247,7 @@ struct sse_handle {
   // [P] lo, [P] hi), the two "score_after_*" counters.  Maxima, thresholds and row buffers are the filtered call's.
   DevBuf s_af_bnd, s_af_cnt;
   bool af_cnt_init = false;
-  // staging of the host forms of the five calls above (stage_pieces): they hold the handle's mutex and finish all device work
+  // staging of the host forms of the five calls above (stage_in): they hold the handle's mutex and finish all device work
   // before they return, so one buffer serves them all
   DevBuf s_stage;
   // forward-only pair loss (sse_eval_loss*, eval_loss.hip).  Option "eval_chunk_rows": pair rows staged and encoded per chunk (even).
@@ -282,6 +279,12 @@ int fail(sse_handle *h, const char *fmt, ...) {
     hipError_t e_ = (expr);                                                                       \
     if (e_ != hipSuccess) return fail(h, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
+
+// how most entry points open: null handle, the handle's mutex for the rest of the call, its device current
+#define SSE_ENTER(h)                       \
+  if (!(h)) return 1;                      \
+  std::lock_guard<std::mutex> lk((h)->mu); \
+  HIPCHECK(h, hipSetDevice((h)->cfg.device))
 
 // Wait for a stream: poll for up to ~3 ms (the latency-critical calls finish in 0.1 - 0.5 ms; the runtime's blocking wait
 // was seen to add 1 - 2 ms to some of them: an 8-token query against a 1.25 M-row index took 2.0 ms end to end with 0.3 ms
@@ -1144,17 +1147,34 @@ static int ensure_counters(sse_handle *h, hipStream_t st) {
   return ensure_zeroed_once(h, h->s_fb_cnt, h->fb_cnt_init, 6, st);
 }
 
-// Staging of a host-buffer entry point: N pieces of bytes[i] bytes in h->s_stage, reserved once; p[i] = the 8-byte-aligned
-// start of piece i.
+// Staging of a host-buffer entry point in h->s_stage, reserved once.  A piece is `bytes` of device memory with the host data
+// that goes in before the call (src) and the host buffer its content comes back to after it (dst), either may be null.
+struct StagePiece {
+  size_t bytes;
+  const void *src;
+  void *dst;
+  char *dev;  // set by stage_in: the 8-byte-aligned start of the piece
+  // the piece as a kernel argument; null for an optional input the caller left out
+  template <class T>
+  T *as() const { return src || dst ? (T *)dev : nullptr; }
+};
 template <size_t N>
-static int stage_pieces(sse_handle *h, const size_t (&bytes)[N], char *(&p)[N]) {
-  size_t off[N], total = 0;
-  for (size_t i = 0; i < N; ++i) {
-    off[i] = total;
-    total += (bytes[i] + 7) & ~(size_t)7;
-  }
+static int stage_in(sse_handle *h, StagePiece (&p)[N]) {
+  size_t total = 0;
+  for (const StagePiece &x : p) total += (x.bytes + 7) & ~(size_t)7;
   if (reserve(h, h->s_stage, total)) return 1;
-  for (size_t i = 0; i < N; ++i) p[i] = (char *)h->s_stage.p + off[i];
+  total = 0;
+  for (StagePiece &x : p) {
+    x.dev = (char *)h->s_stage.p + total;
+    total += (x.bytes + 7) & ~(size_t)7;
+    if (x.src) HIPCHECK(h, hipMemcpy(x.dev, x.src, x.bytes, hipMemcpyHostToDevice));
+  }
+  return 0;
+}
+template <size_t N>
+static int stage_out(sse_handle *h, const StagePiece (&p)[N]) {
+  for (const StagePiece &x : p)
+    if (x.dst) HIPCHECK(h, hipMemcpy(x.dst, x.dev, x.bytes, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1430,18 +1450,43 @@ static int index_set_tags_locked(sse_handle *h, const uint64_t *tags, int64_t N,
   return 0;
 }
 
-// argument errors of sse_score_topk_filtered*, all decidable on the host
-static int score_filtered_check(sse_handle *h, int Q, int k, const void *q_any, const void *q_none, const void *excl, int n_excl) {
-  if (!h->idxp) return fail(h, "sse_score_topk_filtered: no index uploaded");
-  if (Q < 0) return fail(h, "bad arguments to sse_score_topk_filtered");
-  if (k < 1 || k > SSE_FILTERED_MAX_K) return fail(h, "sse_score_topk_filtered: k = %d is not in [1, %d]", k, SSE_FILTERED_MAX_K);
-  if (n_excl < 0 || n_excl > SSE_FILTERED_MAX_EXCL) return fail(h, "sse_score_topk_filtered: n_excl = %d is not in [0, %d]", n_excl, SSE_FILTERED_MAX_EXCL);
-  if (n_excl > 0 && !excl) return fail(h, "sse_score_topk_filtered: n_excl = %d without excl_ids", n_excl);
-  if ((q_any || q_none) && !h->tags_set) return fail(h, "sse_score_topk_filtered: tag masks given but the index has no tags (sse_index_set_tags)");
+// The three top-k calls that sweep the index with the filtered call's machinery: the name their messages carry, the largest k,
+// whether they need group keys
+struct TopkCall {
+  const char *name;
+  int max_k;
+  bool grouped;
+};
+static const TopkCall CALL_FILTERED = {"sse_score_topk_filtered", SSE_FILTERED_MAX_K, false};
+static const TopkCall CALL_GROUPED = {"sse_score_topk_grouped", SSE_GROUPED_MAX_K, true};
+static const TopkCall CALL_AFTER = {"sse_score_topk_after", SSE_AFTER_MAX_K, false};
+
+// what a call reads and writes per query (device pointers), beyond what only one of the three takes
+struct TopkIo {
+  const float *q;
+  const uint64_t *q_any, *q_none;
+  double *out_s;
+  int64_t *out_i;
+  int32_t *out_c;
+};
+
+// argument errors of the three calls, all decidable on the host.  excl / n_excl: the filtered call's; after_score / after_id:
+// the after call's cursor.
+static int score_topk_check(sse_handle *h, const TopkCall &c, int Q, int k, const void *q_any, const void *q_none, const void *excl = nullptr,
+                            int n_excl = 0, const void *after_score = nullptr, const void *after_id = nullptr) {
+  if (!h->idxp) return fail(h, "%s: no index uploaded", c.name);
+  if (c.grouped && !h->groups_set) return fail(h, "%s: the index has no group keys (sse_index_set_groups)", c.name);
+  if (Q < 0) return fail(h, "bad arguments to %s", c.name);
+  if (k < 1 || k > c.max_k) return fail(h, "%s: k = %d is not in [1, %d]", c.name, k, c.max_k);
+  if (n_excl < 0 || n_excl > SSE_FILTERED_MAX_EXCL) return fail(h, "%s: n_excl = %d is not in [0, %d]", c.name, n_excl, SSE_FILTERED_MAX_EXCL);
+  if (n_excl > 0 && !excl) return fail(h, "%s: n_excl = %d without excl_ids", c.name, n_excl);
+  if ((after_score == nullptr) != (after_id == nullptr))
+    return fail(h, "%s: after_score and after_id are both given or both NULL (%s is missing)", c.name, after_score ? "after_id" : "after_score");
+  if ((q_any || q_none) && !h->tags_set) return fail(h, "%s: tag masks given but the index has no tags (sse_index_set_tags)", c.name);
   return 0;
 }
 
-// the fields of FilteredArgs that sse_score_topk_filtered* and sse_score_topk_grouped* fill alike, for every chunk of a call
+// the fields of FilteredArgs that the three calls fill alike, for every chunk of a call
 static void fill_filtered_common(sse_handle *h, FilteredArgs &a, int k, int n_excl, const DevBuf &counters) {
   a.idxp = h->idxp;
   a.idx64 = h->idx64;
@@ -1460,103 +1505,79 @@ static void fill_filtered_common(sse_handle *h, FilteredArgs &a, int k, int n_ex
   a.eps32 = score_eps32(h);
 }
 
-// sse_score_topk_filtered*: every stage queued on `st` (device pointers throughout), queries in chunks of 4096 with the chunk
-// scratch of the rank count (DESIGN K6e): maxima [P][NV], thresholds, row buffers [P][SSE_COLLECT_CAP].
-static int score_filtered_dev_locked(sse_handle *h, const float *q, int Q, int k, const uint64_t *q_any, const uint64_t *q_none,
-                                     const int64_t *excl, int n_excl, double *out_s, int64_t *out_i, int32_t *out_c, hipStream_t st) {
-  const int POOL = 4096;
-  const int S = h->idx_S;
+// queries per chunk of the three calls
+static const int TOPK_POOL = 4096;
+
+// nsplit doubled until a query gets at least `need` maxima (256 per split) where every wave of a split still has a tile of its own
+static int split_for_maxima(int nsplit, int need, int64_t NT) {
+  while (nsplit < 128 && nsplit * 256 < need && NT / (nsplit * 2) >= 8) nsplit *= 2;
+  return nsplit;
+}
+
+// One chunk, P queries from q0, of any of the three calls: reserves the chunk scratch -- the maxima (in `maxima`, max_bytes:
+// each call's own shape), then the rank count's thresholds and row buffers [P][SSE_COLLECT_CAP] (DESIGN K6e), then `extra` --
+// clears the maxima and the row counts on `st`, and points `a` at the chunk's queries, scratch and outputs.
+static int topk_chunk(sse_handle *h, FilteredArgs &a, const TopkIo &io, int q0, int P, int NQ, int nsplit, DevBuf &maxima, size_t max_bytes,
+                      hipStream_t st, DevBuf *extra = nullptr, size_t extra_bytes = 0) {
+  if (reserve(h, maxima, max_bytes)) return 1;
+  if (reserve(h, h->s_cthr, (size_t)P * sizeof(float))) return 1;
+  if (reserve(h, h->s_ccnt, (size_t)(P + 1) * sizeof(int32_t))) return 1;
+  if (reserve(h, h->s_cbuf, (size_t)P * SSE_COLLECT_CAP * sizeof(int32_t))) return 1;
+  if (extra && reserve(h, *extra, extra_bytes)) return 1;
+  HIPCHECK(h, hipMemsetAsync(maxima.p, 0, max_bytes, st));
+  HIPCHECK(h, hipMemsetAsync(h->s_ccnt.p, 0, (size_t)P * sizeof(int32_t), st));
+  a.q = io.q + (size_t)q0 * h->idx_S;
+  a.q_any = io.q_any ? io.q_any + q0 : nullptr;
+  a.q_none = io.q_none ? io.q_none + q0 : nullptr;
+  a.thr = (float *)h->s_cthr.p;
+  a.col_cnt = (int32_t *)h->s_ccnt.p;
+  a.col_buf = (int32_t *)h->s_cbuf.p;
+  a.out_scores = io.out_s + (size_t)q0 * a.k;
+  a.out_ids = io.out_i + (size_t)q0 * a.k;
+  a.out_counts = io.out_c + q0;
+  a.P = P;
+  a.NQ = NQ;
+  a.NSPLIT = nsplit;
+  a.NV = std::min(nsplit, 16) * 256;
+  return 0;
+}
+
+// sse_score_topk_filtered*: every stage queued on `st` (device pointers throughout), queries in chunks of 4096; maxima [P][NV]
+static int score_filtered_dev_locked(sse_handle *h, const TopkIo &io, int Q, int k, const int64_t *excl, int n_excl, hipStream_t st) {
   const int64_t NT = (h->idx_N + 31) / 32;
   if (ensure_zeroed_once(h, h->s_ft_cnt, h->ft_cnt_init, 3, st)) return 1;
   FilteredArgs a;
   fill_filtered_common(h, a, k, excl ? n_excl : 0, h->s_ft_cnt);
-  for (int q0 = 0; q0 < Q; q0 += POOL) {
-    const int P = std::min(POOL, Q - q0);
+  for (int q0 = 0; q0 < Q; q0 += TOPK_POOL) {
+    const int P = std::min(TOPK_POOL, Q - q0);
     SweepChunk ck;
     if (sweep_chunk(h, P, ck)) return 1;
-    int nsplit = ck.nsplit;
-    // at least 2 (k + n_excl) maxima per query where every wave of a split still has a tile of its own
-    while (nsplit < 128 && nsplit * 256 < 2 * (k + a.n_excl) && NT / (nsplit * 2) >= 8) nsplit *= 2;
-    const int NV = std::min(nsplit, 16) * 256;
-    if (reserve(h, h->s_ft_max, (size_t)P * NV * sizeof(uint32_t))) return 1;
-    if (reserve(h, h->s_cthr, (size_t)P * sizeof(float))) return 1;
-    if (reserve(h, h->s_ccnt, (size_t)(P + 1) * sizeof(int32_t))) return 1;
-    if (reserve(h, h->s_cbuf, (size_t)P * SSE_COLLECT_CAP * sizeof(int32_t))) return 1;
-    HIPCHECK(h, hipMemsetAsync(h->s_ft_max.p, 0, (size_t)P * NV * sizeof(uint32_t), st));
-    HIPCHECK(h, hipMemsetAsync(h->s_ccnt.p, 0, (size_t)P * sizeof(int32_t), st));
-    a.q = q + (size_t)q0 * S;
-    a.q_any = q_any ? q_any + q0 : nullptr;
-    a.q_none = q_none ? q_none + q0 : nullptr;
+    const int nsplit = split_for_maxima(ck.nsplit, 2 * (k + a.n_excl), NT);
+    if (topk_chunk(h, a, io, q0, P, ck.NQ, nsplit, h->s_ft_max, (size_t)P * std::min(nsplit, 16) * 256 * sizeof(uint32_t), st)) return 1;
     a.excl = excl ? excl + (size_t)q0 * n_excl : nullptr;
     a.maxima = (uint32_t *)h->s_ft_max.p;
-    a.thr = (float *)h->s_cthr.p;
-    a.col_cnt = (int32_t *)h->s_ccnt.p;
-    a.col_buf = (int32_t *)h->s_cbuf.p;
-    a.out_scores = out_s + (size_t)q0 * k;
-    a.out_ids = out_i + (size_t)q0 * k;
-    a.out_counts = out_c + q0;
-    a.P = P;
-    a.NQ = ck.NQ;
-    a.NSPLIT = nsplit;
-    a.NV = NV;
     HIPCHECK(h, launch_score_filtered(a, st));
   }
   return 0;
 }
 
-// argument errors of sse_score_topk_after*, all decidable on the host
-static int score_after_check(sse_handle *h, int Q, int k, const void *after_score, const void *after_id, const void *q_any, const void *q_none) {
-  if (!h->idxp) return fail(h, "sse_score_topk_after: no index uploaded");
-  if (Q < 0) return fail(h, "bad arguments to sse_score_topk_after");
-  if (k < 1 || k > SSE_AFTER_MAX_K) return fail(h, "sse_score_topk_after: k = %d is not in [1, %d]", k, SSE_AFTER_MAX_K);
-  if ((after_score == nullptr) != (after_id == nullptr))
-    return fail(h, "sse_score_topk_after: after_score and after_id are both given or both NULL (%s is missing)", after_score ? "after_id" : "after_score");
-  if ((q_any || q_none) && !h->tags_set) return fail(h, "sse_score_topk_after: tag masks given but the index has no tags (sse_index_set_tags)");
-  return 0;
-}
-
-// sse_score_topk_after*: every stage queued on `st` (device pointers throughout), queries in chunks of 4096 with the chunk
-// scratch of the filtered call and the cursor brackets beside it (DESIGN K6j).
-static int score_after_dev_locked(sse_handle *h, const float *q, int Q, int k, const double *after_s, const int64_t *after_i,
-                                  const uint64_t *q_any, const uint64_t *q_none, double *out_s, int64_t *out_i, int32_t *out_c,
-                                  hipStream_t st) {
-  const int POOL = 4096;
-  const int S = h->idx_S;
+// sse_score_topk_after*: the filtered call's chunks with the cursor brackets beside them (DESIGN K6j): [P] e as double, [P] lo, [P] hi
+static int score_after_dev_locked(sse_handle *h, const TopkIo &io, int Q, int k, const double *after_s, const int64_t *after_i, hipStream_t st) {
   const int64_t NT = (h->idx_N + 31) / 32;
   if (ensure_zeroed_once(h, h->s_af_cnt, h->af_cnt_init, 3, st)) return 1;
   AfterArgs g;
   FilteredArgs &a = g.f;
   fill_filtered_common(h, a, k, 0, h->s_af_cnt);
   a.excl = nullptr;
-  for (int q0 = 0; q0 < Q; q0 += POOL) {
-    const int P = std::min(POOL, Q - q0);
+  for (int q0 = 0; q0 < Q; q0 += TOPK_POOL) {
+    const int P = std::min(TOPK_POOL, Q - q0);
     SweepChunk ck;
     if (sweep_chunk(h, P, ck)) return 1;
-    int nsplit = ck.nsplit;
-    // at least 2 k maxima per query where every wave of a split still has a tile of its own
-    while (nsplit < 128 && nsplit * 256 < 2 * k && NT / (nsplit * 2) >= 8) nsplit *= 2;
-    const int NV = std::min(nsplit, 16) * 256;
-    if (reserve(h, h->s_ft_max, (size_t)P * NV * sizeof(uint32_t))) return 1;
-    if (reserve(h, h->s_cthr, (size_t)P * sizeof(float))) return 1;
-    if (reserve(h, h->s_ccnt, (size_t)(P + 1) * sizeof(int32_t))) return 1;
-    if (reserve(h, h->s_cbuf, (size_t)P * SSE_COLLECT_CAP * sizeof(int32_t))) return 1;
-    if (reserve(h, h->s_af_bnd, (size_t)P * (sizeof(double) + 2 * sizeof(float)))) return 1;
-    HIPCHECK(h, hipMemsetAsync(h->s_ft_max.p, 0, (size_t)P * NV * sizeof(uint32_t), st));
-    HIPCHECK(h, hipMemsetAsync(h->s_ccnt.p, 0, (size_t)P * sizeof(int32_t), st));
-    a.q = q + (size_t)q0 * S;
-    a.q_any = q_any ? q_any + q0 : nullptr;
-    a.q_none = q_none ? q_none + q0 : nullptr;
+    const int nsplit = split_for_maxima(ck.nsplit, 2 * k, NT);
+    if (topk_chunk(h, a, io, q0, P, ck.NQ, nsplit, h->s_ft_max, (size_t)P * std::min(nsplit, 16) * 256 * sizeof(uint32_t), st, &h->s_af_bnd,
+                   (size_t)P * (sizeof(double) + 2 * sizeof(float))))
+      return 1;
     a.maxima = (uint32_t *)h->s_ft_max.p;
-    a.thr = (float *)h->s_cthr.p;
-    a.col_cnt = (int32_t *)h->s_ccnt.p;
-    a.col_buf = (int32_t *)h->s_cbuf.p;
-    a.out_scores = out_s + (size_t)q0 * k;
-    a.out_ids = out_i + (size_t)q0 * k;
-    a.out_counts = out_c + q0;
-    a.P = P;
-    a.NQ = ck.NQ;
-    a.NSPLIT = nsplit;
-    a.NV = NV;
     g.after_score = after_s ? after_s + q0 : nullptr;
     g.after_id = after_i ? after_i + q0 : nullptr;
     g.eb = (double *)h->s_af_bnd.p;
@@ -1585,22 +1606,9 @@ static int index_set_groups_locked(sse_handle *h, const int64_t *groups, int64_t
   return 0;
 }
 
-// argument errors of sse_score_topk_grouped*, all decidable on the host
-static int score_grouped_check(sse_handle *h, int Q, int k, const void *q_any, const void *q_none) {
-  if (!h->idxp) return fail(h, "sse_score_topk_grouped: no index uploaded");
-  if (!h->groups_set) return fail(h, "sse_score_topk_grouped: the index has no group keys (sse_index_set_groups)");
-  if (Q < 0) return fail(h, "bad arguments to sse_score_topk_grouped");
-  if (k < 1 || k > SSE_GROUPED_MAX_K) return fail(h, "sse_score_topk_grouped: k = %d is not in [1, %d]", k, SSE_GROUPED_MAX_K);
-  if ((q_any || q_none) && !h->tags_set) return fail(h, "sse_score_topk_grouped: tag masks given but the index has no tags (sse_index_set_tags)");
-  return 0;
-}
-
-// sse_score_topk_grouped*: every stage queued on `st` (device pointers throughout), queries in chunks of 4096 with the chunk
-// scratch of the filtered call (thresholds, row buffers) and (key, row) maxima [P][NV] of its own (DESIGN K6h).
-static int score_grouped_dev_locked(sse_handle *h, const float *q, int Q, int k, const uint64_t *q_any, const uint64_t *q_none,
-                                    double *out_s, int64_t *out_i, int64_t *out_g, int32_t *out_c, hipStream_t st) {
-  const int POOL = 4096;
-  const int S = h->idx_S;
+// sse_score_topk_grouped*: the filtered call's chunks with (key, row) maxima [P][NV] of its own (DESIGN K6h), found by a sweep
+// of its own shape
+static int score_grouped_dev_locked(sse_handle *h, const TopkIo &io, int Q, int k, int64_t *out_g, hipStream_t st) {
   const int64_t NT = (h->idx_N + 31) / 32;
   if (ensure_zeroed_once(h, h->s_gp_cnt, h->gp_cnt_init, 3, st)) return 1;
   GroupedArgs g;
@@ -1609,37 +1617,17 @@ static int score_grouped_dev_locked(sse_handle *h, const float *q, int Q, int k,
   a.excl = nullptr;
   a.maxima = nullptr;
   g.groups = (const int64_t *)h->idx_groups.p;
-  for (int q0 = 0; q0 < Q; q0 += POOL) {
-    const int P = std::min(POOL, Q - q0);
+  for (int q0 = 0; q0 < Q; q0 += TOPK_POOL) {
+    const int P = std::min(TOPK_POOL, Q - q0);
     SweepChunk ck;
     if (sweep_chunk(h, P, ck)) return 1;
-    const int NQ = ck.NQ, nsplit = ck.nsplit;
     // the eligible-max sweep: at most 2 query tiles per workgroup (the tile of every maximum costs 16 registers per query
-    // tile) and at least 4 k maxima per query where every wave of a split still has a tile of its own: the maxima of several
-    // row sets share groups, and theta needs k DISTINCT groups among them (DESIGN K6h)
-    const int NQM = std::min(NQ, 2);
-    int msplit = choose_nsplit(NQM, (P + NQM * 32 - 1) / (NQM * 32), NT);
-    while (msplit < 128 && msplit * 256 < 4 * k && NT / (msplit * 2) >= 8) msplit *= 2;
+    // tile) and at least 4 k maxima per query: the maxima of several row sets share groups, and theta needs k DISTINCT groups
+    // among them (DESIGN K6h)
+    const int NQM = std::min(ck.NQ, 2);
+    const int msplit = split_for_maxima(choose_nsplit(NQM, (P + NQM * 32 - 1) / (NQM * 32), NT), 4 * k, NT);
     const int NV = std::min(msplit, 16) * 256;
-    if (reserve(h, h->s_gp_max, (size_t)P * NV * sizeof(unsigned long long))) return 1;
-    if (reserve(h, h->s_cthr, (size_t)P * sizeof(float))) return 1;
-    if (reserve(h, h->s_ccnt, (size_t)(P + 1) * sizeof(int32_t))) return 1;
-    if (reserve(h, h->s_cbuf, (size_t)P * SSE_COLLECT_CAP * sizeof(int32_t))) return 1;
-    HIPCHECK(h, hipMemsetAsync(h->s_gp_max.p, 0, (size_t)P * NV * sizeof(unsigned long long), st));
-    HIPCHECK(h, hipMemsetAsync(h->s_ccnt.p, 0, (size_t)P * sizeof(int32_t), st));
-    a.q = q + (size_t)q0 * S;
-    a.q_any = q_any ? q_any + q0 : nullptr;
-    a.q_none = q_none ? q_none + q0 : nullptr;
-    a.thr = (float *)h->s_cthr.p;
-    a.col_cnt = (int32_t *)h->s_ccnt.p;
-    a.col_buf = (int32_t *)h->s_cbuf.p;
-    a.out_scores = out_s + (size_t)q0 * k;
-    a.out_ids = out_i + (size_t)q0 * k;
-    a.out_counts = out_c + q0;
-    a.P = P;
-    a.NQ = NQ;
-    a.NSPLIT = nsplit;
-    a.NV = std::min(nsplit, 16) * 256;
+    if (topk_chunk(h, a, io, q0, P, ck.NQ, ck.nsplit, h->s_gp_max, (size_t)P * NV * sizeof(unsigned long long), st)) return 1;
     g.max = a;
     g.max.NQ = NQM;
     g.max.NSPLIT = msplit;
@@ -2158,9 +2146,7 @@ int sse_get_variable(sse_handle *h, const char *name, float *host, int64_t count
 
 int sse_encode_dev(sse_handle *h, int side, const int32_t *ids_dev, int32_t B, int32_t T, int32_t normalize,
                    float *out_dev, void *stream) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   return encode_dev_locked(h, side, ids_dev, B, T, normalize, out_dev, (hipStream_t)stream);
 }
 
@@ -2238,9 +2224,7 @@ static int encode_host_ids_locked(sse_handle *h, int side, const int32_t *ids_ho
 
 int sse_encode(sse_handle *h, int side, const int32_t *ids_host, int32_t B, int32_t T, int32_t normalize,
                float *out_host) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if (B == 0) return 0;
   if (B < 0 || T < 1 || !ids_host || !out_host) return fail(h, "bad arguments to sse_encode");
   const size_t nbytes = (size_t)B * h->cfg.encoding_size * sizeof(float);
@@ -2354,9 +2338,7 @@ static int score_to_host_locked(sse_handle *h, const float *q_dev, int Q, int k,
 
 int sse_encode_score_topk(sse_handle *h, int side, const int32_t *ids_host, int32_t B, int32_t T, int32_t normalize,
                           int32_t k, double *out_scores, int64_t *out_ids, float *enc_out_host) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if (B == 0) return 0;
   if (B < 0 || T < 1 || !ids_host || !out_scores || !out_ids) return fail(h, "bad arguments to sse_encode_score_topk");
   if (!h->idxp) return fail(h, "no index uploaded");
@@ -2380,108 +2362,127 @@ int sse_encode_score_topk(sse_handle *h, int side, const int32_t *ids_host, int3
   return 0;
 }
 
+namespace {
+
+// Counters whose words live on the device, one group per family of scoring calls: the words accumulate over the handle's life
+// (ensure_zeroed_once) and read as 0 until the first call of the family has reserved and cleared them.
+struct DevCounters {
+  DevBuf sse_handle::*buf;
+  bool sse_handle::*init;
+  int words;  // read back together
+};
+enum { CG_RANK, CG_ABOVE, CG_FILTERED, CG_GROUPED, CG_AFTER, CG_TOPK, CG_DEV_COUNT, CG_HOST = CG_DEV_COUNT, CG_PATH, CG_COOP };
+const DevCounters DEV_COUNTERS[CG_DEV_COUNT] = {
+    {&sse_handle::s_rk_cnt, &sse_handle::rk_cnt_init, 2}, {&sse_handle::s_ab_cnt, &sse_handle::ab_cnt_init, 3},
+    {&sse_handle::s_ft_cnt, &sse_handle::ft_cnt_init, 3}, {&sse_handle::s_gp_cnt, &sse_handle::gp_cnt_init, 3},
+    {&sse_handle::s_af_cnt, &sse_handle::af_cnt_init, 3}, {&sse_handle::s_fb_cnt, &sse_handle::fb_cnt_init, 4}};
+int64_t sse_handle::*const HOST_COUNTERS[] = {&sse_handle::persist_fallbacks, &sse_handle::two_pass_calls, &sse_handle::pad_sorted_calls,
+                                              &sse_handle::eval_paired_calls, &sse_handle::x_table_builds};
+
+// every name sse_get_counter answers: its group and its word there (CG_HOST: entry of HOST_COUNTERS; CG_PATH: entry of
+// sse_handle::lstm_path_calls; a device group: the word the kernels of that family count in)
+const struct {
+  const char *name;
+  int group, word;
+} COUNTERS[] = {
+    {"lstm_persist_fallbacks", CG_HOST, 0},
+    {"score_two_pass_calls", CG_HOST, 1},  // sse_score_topk* calls ranked by the two-pass path for mid-size indexes
+    {"pad_sorted_calls", CG_HOST, 2},      // encodes of device-resident ids whose rows were bucketed by PAD prefix on the device
+    {"eval_paired_calls", CG_HOST, 3},     // sse_eval_loss* calls whose source encoder ran once per (positive, negative) pair
+    {"lstm_x_table_builds", CG_HOST, 4},   // x-projection tables built (option lstm_x_table)
+    // LSTM inference encodes by kernel
+    {"lstm_path_persist", CG_PATH, PATH_PERSIST},
+    {"lstm_path_cluster", CG_PATH, PATH_CLUSTER},
+    {"lstm_path_small", CG_PATH, PATH_SMALL},
+    {"lstm_path_x3", CG_PATH, PATH_X3},
+    {"lstm_path_generic", CG_PATH, PATH_GENERIC},
+    {"lstm_path_fwd", CG_PATH, PATH_FWD},
+    {"lstm_fwd_rows32", CG_PATH, PATH_FWD_ROWS32},
+    {"lstm_fwd_rows64", CG_PATH, PATH_FWD_ROWS64},
+    {"lstm_fwd_gate_split", CG_PATH, PATH_FWD_GS},
+    {"lstm_fwd_x_table", CG_PATH, PATH_FWD_XT},
+    {"lstm_coop_refused", CG_COOP, 0},  // process-wide: cooperative launches refused by the runtime (plain launch taken)
+    // sse_score_rank* (score_rank.hip): rows that needed float64, pairs whose band outgrew its buffer
+    {"score_rank_band_rows", CG_RANK, 0},
+    {"score_rank_bruteforce_pairs", CG_RANK, 1},
+    // sse_score_above* (score_above.hip): rows decided in float64, pairs listed by the float64 sweep, segments merged in global memory
+    {"score_above_band_rows", CG_ABOVE, 0},
+    {"score_above_bruteforce_pairs", CG_ABOVE, 1},
+    {"score_above_long_segments", CG_ABOVE, 2},
+    // sse_score_topk_filtered* (score_filtered.hip): rows re-scored by the select stage, queries of the float64 sweep, tiles skipped
+    {"score_filtered_collected_rows", CG_FILTERED, 0},
+    {"score_filtered_bruteforce_queries", CG_FILTERED, 1},
+    {"score_filtered_tiles_skipped", CG_FILTERED, 2},
+    // sse_score_topk_grouped* (score_grouped.hip) and sse_score_topk_after* (score_after.hip): rows re-scored by the select
+    // stage, queries of the float64 sweep
+    {"score_grouped_collected_rows", CG_GROUPED, 0},
+    {"score_grouped_bruteforce_queries", CG_GROUPED, 1},
+    {"score_after_collected_rows", CG_AFTER, 0},
+    {"score_after_bruteforce_queries", CG_AFTER, 1},
+    // sse_score_topk* (score_topk.hip): queries whose bf16-candidate result missed its certificate, queries served by the
+    // collect path, queries that fell through to the float64 brute force
+    {"score_bf16_second_chance_queries", CG_TOPK, 0},
+    {"score_collect_queries", CG_TOPK, 1},
+    {"score_bruteforce_queries", CG_TOPK, 2},
+};
+
+static int read_dev_counter(sse_handle *h, const DevCounters &g, int word, int64_t *value) {
+  unsigned long long v[4] = {0, 0, 0, 0};
+  if ((h->*g.buf).p && h->*g.init) {
+    HIPCHECK(h, hipSetDevice(h->cfg.device));
+    HIPCHECK(h, hipDeviceSynchronize());
+    HIPCHECK(h, hipMemcpy(v, (h->*g.buf).p, g.words * sizeof v[0], hipMemcpyDeviceToHost));
+  }
+  *value = (int64_t)v[word];
+  return 0;
+}
+
+// The options that are one int of the handle: a switch (message null; stored as value != 0) or a value in [min, max], refused
+// with `message` outside.  What each one does stands beside its member in sse_handle.h.
+const struct {
+  const char *name;
+  int sse_handle::*member;
+  int min, max;
+  const char *message;
+} OPTIONS[] = {
+    {"score_small_index", &sse_handle::score_small_index},
+    {"score_small_x3", &sse_handle::score_small_x3},
+    {"score_filtered_skip", &sse_handle::score_filtered_skip},
+    {"score_bf16", &sse_handle::score_bf16},
+    {"train_bwd_x3", &sse_handle::train_bwd_x3},
+    {"train_fwd_x3", &sse_handle::train_fwd_x3},
+    {"train_dk_x3", &sse_handle::train_dk_x3},
+    {"train_generic", &sse_handle::train_generic},
+    {"train_gen1", &sse_handle::train_gen1},
+    {"train_pair_dedup", &sse_handle::train_pair_dedup},
+    {"train_serial", &sse_handle::train_serial},
+    {"pad_skip", &sse_handle::pad_skip},
+    {"lstm_gate_split", &sse_handle::lstm_gate_split},
+    {"lstm_x3", &sse_handle::lstm_x3},
+    {"lstm_persist_inject_miss", &sse_handle::persist_inject},  // testing aid for the fallback path of the host-buffer encodes
+    {"lstm_cluster_drop_wg", &sse_handle::lstm_cluster_drop},
+    {"lstm_cluster_coop", &sse_handle::lstm_cluster_coop},
+    {"lstm_cluster_write_through", &sse_handle::lstm_cluster_wt},
+    {"score_two_pass_min_rows", &sse_handle::score_two_pass_min_rows, 0, INT32_MAX, "score_two_pass_min_rows must be >= 0"},
+    {"score_two_pass_rows", &sse_handle::score_two_pass_rows, 0, INT32_MAX, "score_two_pass_rows must be >= 0"},
+    {"pad_sort_dev", &sse_handle::pad_sort_dev, 0, 2, "pad_sort_dev must be 0 (off), 1 (adaptive) or 2 (always)"},
+    {"lstm_persist_rows", &sse_handle::lstm_persist_rows, 0, INT32_MAX, "lstm_persist_rows must be >= 0"},
+    {"lstm_cluster_chunks", &sse_handle::lstm_cluster_chunks, 1, INT32_MAX, "lstm_cluster_chunks must be >= 1"},
+    {"lstm_cluster_rows", &sse_handle::lstm_cluster_rows, 0, INT32_MAX, "lstm_cluster_rows must be >= 0"},
+    {"lstm_small_rows", &sse_handle::lstm_small_rows, 0, INT32_MAX, "lstm_small_rows must be >= 0"},
+    {"lstm_x_table", &sse_handle::lstm_x_table, 0, 2, "lstm_x_table must be 0 (off), 1 (batches with B * T >= vocab_size) or 2 (always)"},
+    {"lstm_x_table_mb", &sse_handle::lstm_x_table_mb, 0, INT32_MAX, "lstm_x_table_mb must be >= 0"},
+};
+
+}  // namespace
+
 int sse_get_counter(sse_handle *h, const char *name, int64_t *value) {
   if (!h || !name || !value) return 1;
   std::lock_guard<std::mutex> lk(h->mu);
-  if (strcmp(name, "lstm_persist_fallbacks") == 0) {
-    *value = h->persist_fallbacks;
-    return 0;
-  }
-  if (strcmp(name, "score_two_pass_calls") == 0) {  // sse_score_topk* calls ranked by the two-pass path for mid-size indexes
-    *value = h->two_pass_calls;
-    return 0;
-  }
-  if (strcmp(name, "pad_sorted_calls") == 0) {  // encodes of device-resident ids whose rows were bucketed by PAD prefix on the device
-    *value = h->pad_sorted_calls;
-    return 0;
-  }
-  if (strcmp(name, "eval_paired_calls") == 0) {  // sse_eval_loss* calls whose source encoder ran once per (positive, negative) pair
-    *value = h->eval_paired_calls;
-    return 0;
-  }
-  if (strcmp(name, "lstm_x_table_builds") == 0) {  // x-projection tables built (option lstm_x_table)
-    *value = h->x_table_builds;
-    return 0;
-  }
-  for (int i = 0; i < PATH_COUNT; ++i) {  // LSTM inference encodes by kernel
-    if (strcmp(name, LSTM_PATH_NAMES[i]) != 0) continue;
-    *value = h->lstm_path_calls[i];
-    return 0;
-  }
-  if (strcmp(name, "lstm_coop_refused") == 0) {  // process-wide: cooperative launches refused by the runtime (plain launch taken)
-    *value = (int64_t)lstm_coop_refused();
-    return 0;
-  }
-  static const char *const rank_names[2] = {"score_rank_band_rows", "score_rank_bruteforce_pairs"};
-  for (int i = 0; i < 2; ++i) {  // sse_score_rank*: rows that needed float64, pairs whose band outgrew its buffer
-    if (strcmp(name, rank_names[i]) != 0) continue;
-    unsigned long long v[2] = {0, 0};
-    if (h->s_rk_cnt.p && h->rk_cnt_init) {
-      HIPCHECK(h, hipSetDevice(h->cfg.device));
-      HIPCHECK(h, hipDeviceSynchronize());
-      HIPCHECK(h, hipMemcpy(v, h->s_rk_cnt.p, sizeof v, hipMemcpyDeviceToHost));
-    }
-    *value = (int64_t)v[i];
-    return 0;
-  }
-  static const char *const above_names[3] = {"score_above_band_rows", "score_above_bruteforce_pairs", "score_above_long_segments"};
-  for (int i = 0; i < 3; ++i) {  // sse_score_above*: rows decided in float64, pairs listed by the float64 sweep, segments merged in global memory
-    if (strcmp(name, above_names[i]) != 0) continue;
-    unsigned long long v[3] = {0, 0, 0};
-    if (h->s_ab_cnt.p && h->ab_cnt_init) {
-      HIPCHECK(h, hipSetDevice(h->cfg.device));
-      HIPCHECK(h, hipDeviceSynchronize());
-      HIPCHECK(h, hipMemcpy(v, h->s_ab_cnt.p, sizeof v, hipMemcpyDeviceToHost));
-    }
-    *value = (int64_t)v[i];
-    return 0;
-  }
-  static const char *const filtered_names[3] = {"score_filtered_collected_rows", "score_filtered_bruteforce_queries", "score_filtered_tiles_skipped"};
-  for (int i = 0; i < 3; ++i) {  // sse_score_topk_filtered*: rows re-scored by the select stage, queries of the float64 sweep, tiles skipped
-    if (strcmp(name, filtered_names[i]) != 0) continue;
-    unsigned long long v[3] = {0, 0, 0};
-    if (h->s_ft_cnt.p && h->ft_cnt_init) {
-      HIPCHECK(h, hipSetDevice(h->cfg.device));
-      HIPCHECK(h, hipDeviceSynchronize());
-      HIPCHECK(h, hipMemcpy(v, h->s_ft_cnt.p, sizeof v, hipMemcpyDeviceToHost));
-    }
-    *value = (int64_t)v[i];
-    return 0;
-  }
-  static const char *const grouped_names[2] = {"score_grouped_collected_rows", "score_grouped_bruteforce_queries"};
-  for (int i = 0; i < 2; ++i) {  // sse_score_topk_grouped*: rows re-scored by the select stage, queries of the float64 sweep
-    if (strcmp(name, grouped_names[i]) != 0) continue;
-    unsigned long long v[3] = {0, 0, 0};
-    if (h->s_gp_cnt.p && h->gp_cnt_init) {
-      HIPCHECK(h, hipSetDevice(h->cfg.device));
-      HIPCHECK(h, hipDeviceSynchronize());
-      HIPCHECK(h, hipMemcpy(v, h->s_gp_cnt.p, sizeof v, hipMemcpyDeviceToHost));
-    }
-    *value = (int64_t)v[i];
-    return 0;
-  }
-  static const char *const after_names[2] = {"score_after_collected_rows", "score_after_bruteforce_queries"};
-  for (int i = 0; i < 2; ++i) {  // sse_score_topk_after*: rows re-scored by the select stage, queries of the float64 sweep
-    if (strcmp(name, after_names[i]) != 0) continue;
-    unsigned long long v[3] = {0, 0, 0};
-    if (h->s_af_cnt.p && h->af_cnt_init) {
-      HIPCHECK(h, hipSetDevice(h->cfg.device));
-      HIPCHECK(h, hipDeviceSynchronize());
-      HIPCHECK(h, hipMemcpy(v, h->s_af_cnt.p, sizeof v, hipMemcpyDeviceToHost));
-    }
-    *value = (int64_t)v[i];
-    return 0;
-  }
-  static const char *const names[3] = {"score_bf16_second_chance_queries", "score_collect_queries", "score_bruteforce_queries"};
-  for (int i = 0; i < 3; ++i) {
-    if (strcmp(name, names[i]) != 0) continue;
-    unsigned long long v[4] = {0, 0, 0, 0};
-    if (h->s_fb_cnt.p && h->fb_cnt_init) {
-      HIPCHECK(h, hipSetDevice(h->cfg.device));
-      HIPCHECK(h, hipDeviceSynchronize());
-      HIPCHECK(h, hipMemcpy(v, h->s_fb_cnt.p, sizeof v, hipMemcpyDeviceToHost));
-    }
-    *value = (int64_t)v[i];
+  for (const auto &c : COUNTERS) {
+    if (strcmp(name, c.name) != 0) continue;
+    if (c.group < CG_DEV_COUNT) return read_dev_counter(h, DEV_COUNTERS[c.group], c.word, value);
+    *value = c.group == CG_HOST ? h->*HOST_COUNTERS[c.word] : c.group == CG_PATH ? h->lstm_path_calls[c.word] : (int64_t)lstm_coop_refused();
     return 0;
   }
   return fail(h, "unknown counter '%s'", name);
@@ -2490,22 +2491,13 @@ int sse_get_counter(sse_handle *h, const char *name, int64_t *value) {
 int sse_set_option(sse_handle *h, const char *name, int32_t value) {
   if (!h || !name) return 1;
   std::lock_guard<std::mutex> lk(h->mu);
-  if (strcmp(name, "score_small_index") == 0) {
-    h->score_small_index = value != 0;
+  for (const auto &o : OPTIONS) {
+    if (strcmp(name, o.name) != 0) continue;
+    if (o.message && (value < o.min || value > o.max)) return fail(h, "%s", o.message);
+    h->*o.member = o.message ? value : value != 0;
     return 0;
   }
-  if (strcmp(name, "score_small_x3") == 0) {
-    h->score_small_x3 = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "score_filtered_skip") == 0) {
-    h->score_filtered_skip = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "score_bf16") == 0) {
-    h->score_bf16 = value != 0;
-    return 0;
-  }
+  // the options that do more than store one int
   if (strcmp(name, "cnn_bf16") == 0) {
     if (h->cfg.network_mode != SSE_MODE_SOURCE_ONLY_CNN) return fail(h, "option cnn_bf16 needs network_mode source_only_cnn");
     h->cnn_bf16 = value != 0;
@@ -2518,78 +2510,14 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value) {
     h->lstm_train_rows = (int)value;
     return 0;
   }
-  if (strcmp(name, "train_bwd_x3") == 0) {
-    h->train_bwd_x3 = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "train_fwd_x3") == 0) {
-    h->train_fwd_x3 = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "train_dk_x3") == 0) {
-    h->train_dk_x3 = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "train_generic") == 0) {
-    h->train_generic = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "train_gen1") == 0) {
-    h->train_gen1 = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "train_pair_dedup") == 0) {
-    h->train_pair_dedup = value != 0;
-    return 0;
-  }
   if (strcmp(name, "eval_chunk_rows") == 0) {
     if (value < 2) return fail(h, "eval_chunk_rows must be >= 2");
     h->eval_chunk_rows = (int)(value & ~1);  // even: a chunk never splits a (positive, negative) pair of rows
     return 0;
   }
-  if (strcmp(name, "train_serial") == 0) {
-    h->train_serial = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "pad_skip") == 0) {
-    h->pad_skip = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "score_two_pass_min_rows") == 0) {
-    if (value < 0) return fail(h, "score_two_pass_min_rows must be >= 0");
-    h->score_two_pass_min_rows = value;
-    return 0;
-  }
-  if (strcmp(name, "score_two_pass_rows") == 0) {
-    if (value < 0) return fail(h, "score_two_pass_rows must be >= 0");
-    h->score_two_pass_rows = value;
-    return 0;
-  }
-  if (strcmp(name, "lstm_gate_split") == 0) {
-    h->lstm_gate_split = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "pad_sort_dev") == 0) {
-    if (value < 0 || value > 2) return fail(h, "pad_sort_dev must be 0 (off), 1 (adaptive) or 2 (always)");
-    h->pad_sort_dev = (int)value;
-    return 0;
-  }
-  if (strcmp(name, "lstm_x3") == 0) {
-    h->lstm_x3 = value != 0;
-    return 0;
-  }
   if (strcmp(name, "lstm_persist_epoch") == 0) {  // testing aid: move the cluster kernel's 20-bit tag epoch (wrap-around path)
     if (value < 0 || value >= (1 << 20)) return fail(h, "lstm_persist_epoch must be in [0, 2^20)");
     h->persist_epoch = (uint32_t)value;
-    return 0;
-  }
-  if (strcmp(name, "lstm_persist_inject_miss") == 0) {  // testing aid for the fallback path of the host-buffer encodes
-    h->persist_inject = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "lstm_persist_rows") == 0) {
-    if (value < 0) return fail(h, "lstm_persist_rows must be >= 0");
-    h->lstm_persist_rows = (int)value;
     return 0;
   }
   if (strcmp(name, "lstm_cluster_backoff") == 0) {
@@ -2598,58 +2526,17 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value) {
     h->cluster_skip[0] = h->cluster_skip[1] = 0;
     return 0;
   }
-  if (strcmp(name, "lstm_cluster_chunks") == 0) {
-    if (value < 1) return fail(h, "lstm_cluster_chunks must be >= 1");
-    h->lstm_cluster_chunks = (int)value;
-    return 0;
-  }
-  if (strcmp(name, "lstm_cluster_drop_wg") == 0) {
-    h->lstm_cluster_drop = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "lstm_cluster_coop") == 0) {
-    h->lstm_cluster_coop = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "lstm_cluster_write_through") == 0) {
-    h->lstm_cluster_wt = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "lstm_cluster_rows") == 0) {
-    if (value < 0) return fail(h, "lstm_cluster_rows must be >= 0");
-    h->lstm_cluster_rows = value;
-    return 0;
-  }
-  if (strcmp(name, "lstm_small_rows") == 0) {
-    if (value < 0) return fail(h, "lstm_small_rows must be >= 0");
-    h->lstm_small_rows = value;
-    return 0;
-  }
-  if (strcmp(name, "lstm_x_table") == 0) {
-    if (value < 0 || value > 2) return fail(h, "lstm_x_table must be 0 (off), 1 (batches with B * T >= vocab_size) or 2 (always)");
-    h->lstm_x_table = value;
-    return 0;
-  }
-  if (strcmp(name, "lstm_x_table_mb") == 0) {
-    if (value < 0) return fail(h, "lstm_x_table_mb must be >= 0");
-    h->lstm_x_table_mb = value;
-    return 0;
-  }
   return fail(h, "unknown option '%s'", name);
 }
 
 int sse_l2_normalize_dev(sse_handle *h, const float *x_dev, float *out_dev, int64_t rows, int32_t cols, void *stream) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   HIPCHECK(h, launch_l2_normalize(x_dev, out_dev, rows, cols, (hipStream_t)stream));
   return 0;
 }
 
 int sse_index_set_dev(sse_handle *h, const float *rows_dev, int64_t N, int32_t S, int64_t id_base, void *stream) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if (h->idx64) {
     HIPCHECK(h, hipFree(h->idx64));
     h->idx64 = nullptr;
@@ -2689,16 +2576,12 @@ int sse_index_upload_f64(sse_handle *h, const double *rows_host, int64_t N, int3
 
 int sse_score_topk_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, double *out_scores_dev,
                        int64_t *out_ids_dev, void *stream) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   return score_dev_locked(h, q_dev, Q, k, out_scores_dev, out_ids_dev, (hipStream_t)stream);
 }
 
 int sse_score_topk(sse_handle *h, const float *q_host, int32_t Q, int32_t k, double *out_scores, int64_t *out_ids) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if (Q == 0) return 0;
   if (Q < 0 || !q_host || !out_scores || !out_ids) return fail(h, "bad arguments to sse_score_topk");
   if (!h->idxp) return fail(h, "no index uploaded");
@@ -2710,18 +2593,14 @@ int sse_score_topk(sse_handle *h, const float *q_host, int32_t Q, int32_t k, dou
 
 int sse_score_rank_dev(sse_handle *h, const float *q_dev, int32_t Q, const int32_t *pair_q_dev, const int64_t *pair_id_dev, int64_t L,
                        const double *pair_score_in_dev, int64_t *out_before_dev, double *out_score_dev, void *stream) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   return score_rank_dev_locked(h, q_dev, Q, pair_q_dev, pair_id_dev, L, pair_score_in_dev, out_before_dev, out_score_dev,
                                (hipStream_t)stream);
 }
 
 int sse_score_rank(sse_handle *h, const float *q_host, int32_t Q, const int32_t *pair_q, const int64_t *pair_id, int64_t L,
                    const double *pair_score_in, int64_t *out_before, double *out_score) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if (!h->idxp) return fail(h, "no index uploaded");
   if (Q < 0 || L < 0) return fail(h, "bad arguments to sse_score_rank");
   if (L == 0) return 0;
@@ -2733,31 +2612,22 @@ int sse_score_rank(sse_handle *h, const float *q_host, int32_t Q, const int32_t 
       return fail(h, "sse_score_rank: pair_id[%lld] = %lld is not a row of this index [%lld, %lld)", (long long)p, (long long)pair_id[p],
                   (long long)h->idx_base, (long long)(h->idx_base + h->idx_N));
   }
-  const size_t qb = (size_t)Q * h->idx_S * sizeof(float), l8 = (size_t)L * 8, l4 = (size_t)L * 4;
-  char *piece[6];  // queries | pair_id | pair_score_in | out_score | out_before | pair_q
-  if (stage_pieces(h, {qb, l8, l8, l8, l8, l4}, piece)) return 1;
-  float *d_q = (float *)piece[0];
-  int64_t *d_id = (int64_t *)piece[1];
-  double *d_in = (double *)piece[2], *d_sc = (double *)piece[3];
-  int64_t *d_bf = (int64_t *)piece[4];
-  int32_t *d_pq = (int32_t *)piece[5];
-  HIPCHECK(h, hipMemcpy(d_q, q_host, qb, hipMemcpyHostToDevice));
-  HIPCHECK(h, hipMemcpy(d_id, pair_id, l8, hipMemcpyHostToDevice));
-  HIPCHECK(h, hipMemcpy(d_pq, pair_q, l4, hipMemcpyHostToDevice));
-  if (pair_score_in) HIPCHECK(h, hipMemcpy(d_in, pair_score_in, l8, hipMemcpyHostToDevice));
-  if (score_rank_dev_locked(h, d_q, Q, d_pq, d_id, L, pair_score_in ? d_in : nullptr, d_bf, d_sc, nullptr)) return 1;
+  const size_t l8 = (size_t)L * 8;
+  StagePiece p[] = {{(size_t)Q * h->idx_S * sizeof(float), q_host}, {l8, pair_id}, {l8, pair_score_in}, {l8, nullptr, out_score},
+                    {l8, nullptr, out_before}, {(size_t)L * 4, pair_q}};
+  if (stage_in(h, p)) return 1;
+  // (the scores are always computed: out_score only decides whether they come back)
+  if (score_rank_dev_locked(h, p[0].as<float>(), Q, p[5].as<int32_t>(), p[1].as<int64_t>(), L, p[2].as<double>(), p[4].as<int64_t>(),
+                            (double *)p[3].dev, nullptr))
+    return 1;
   if (check_err_flag(h, nullptr)) return 1;
-  HIPCHECK(h, hipMemcpy(out_before, d_bf, l8, hipMemcpyDeviceToHost));
-  if (out_score) HIPCHECK(h, hipMemcpy(out_score, d_sc, l8, hipMemcpyDeviceToHost));
-  return 0;
+  return stage_out(h, p);
 }
 
 int sse_score_above_dev(sse_handle *h, const float *q_dev, int32_t Q, const int32_t *pair_q_dev, const double *pair_thr_dev,
                         int64_t L, int64_t cap, int64_t *out_offsets_dev, int64_t *out_ids_dev, double *out_scores_dev,
                         void *stream) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   hipStream_t st = (hipStream_t)stream;
   if (!h->idxp) return fail(h, "sse_score_above: no index uploaded");
   const bool lists = out_ids_dev != nullptr;
@@ -2776,9 +2646,7 @@ int sse_score_above_dev(sse_handle *h, const float *q_dev, int32_t Q, const int3
 
 int sse_score_above(sse_handle *h, const float *q_host, int32_t Q, const int32_t *pair_q, const double *pair_thr, int64_t L,
                     int64_t cap, int64_t *out_offsets, int64_t *out_ids, double *out_scores) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if (!h->idxp) return fail(h, "sse_score_above: no index uploaded");
   const bool lists = out_ids != nullptr;
   if (Q < 0 || L < 0 || !out_offsets || (out_ids == nullptr) != (out_scores == nullptr) || (lists && cap < 0))
@@ -2790,20 +2658,15 @@ int sse_score_above(sse_handle *h, const float *q_host, int32_t Q, const int32_t
   if (!q_host || !pair_q || !pair_thr || Q == 0) return fail(h, "bad arguments to sse_score_above");
   for (int64_t p = 0; p < L; ++p)
     if (pair_q[p] < 0 || pair_q[p] >= Q) return fail(h, "sse_score_above: pair_q[%lld] = %d is not in [0, Q = %d)", (long long)p, pair_q[p], Q);
-  const size_t qb = (size_t)Q * h->idx_S * sizeof(float), l8 = (size_t)L * 8, l4 = (size_t)L * 4;
-  char *piece[4];  // queries | pair_thr | offsets [L + 1] | pair_q
-  if (stage_pieces(h, {qb, l8, l8 + 8, l4}, piece)) return 1;
-  float *d_q = (float *)piece[0];
-  double *d_thr = (double *)piece[1];
-  int64_t *d_off = (int64_t *)piece[2];
-  int32_t *d_pq = (int32_t *)piece[3];
-  HIPCHECK(h, hipMemcpy(d_q, q_host, qb, hipMemcpyHostToDevice));
-  HIPCHECK(h, hipMemcpy(d_thr, pair_thr, l8, hipMemcpyHostToDevice));
-  HIPCHECK(h, hipMemcpy(d_pq, pair_q, l4, hipMemcpyHostToDevice));
+  StagePiece p[] = {{(size_t)Q * h->idx_S * sizeof(float), q_host}, {(size_t)L * 8, pair_thr}, {(size_t)L * 8 + 8, nullptr, out_offsets},
+                    {(size_t)L * 4, pair_q}};
+  if (stage_in(h, p)) return 1;
+  const double *d_thr = p[1].as<double>();
+  const int32_t *d_pq = p[3].as<int32_t>();
   AboveCall c;
-  if (score_above_count_locked(h, c, d_q, Q, d_pq, d_thr, L, d_off, nullptr)) return 1;
+  if (score_above_count_locked(h, c, p[0].as<float>(), Q, d_pq, d_thr, L, p[2].as<int64_t>(), nullptr)) return 1;
   if (check_err_flag(h, nullptr)) return 1;
-  HIPCHECK(h, hipMemcpy(out_offsets, d_off, l8 + 8, hipMemcpyDeviceToHost));
+  if (stage_out(h, p)) return 1;
   // the host knows the total now: the lists are staged at exactly that length, and skipped when the caller's do not hold it
   const int64_t total = out_offsets[L];
   if (!lists || total > cap || total == 0) return 0;
@@ -2818,179 +2681,116 @@ int sse_score_above(sse_handle *h, const float *q_host, int32_t Q, const int32_t
 }
 
 int sse_index_set_tags(sse_handle *h, const uint64_t *tags_host, int64_t N) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if (index_set_tags_locked(h, tags_host, N, true, nullptr)) return 1;
   HIPCHECK(h, hipStreamSynchronize(nullptr));
   return 0;
 }
 
 int sse_index_set_tags_dev(sse_handle *h, const uint64_t *tags_dev, int64_t N, void *stream) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   return index_set_tags_locked(h, tags_dev, N, false, (hipStream_t)stream);
 }
 
 int sse_score_topk_filtered_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, const uint64_t *q_any_dev,
                                 const uint64_t *q_none_dev, const int64_t *excl_ids_dev, int32_t n_excl,
                                 double *out_scores_dev, int64_t *out_ids_dev, int32_t *out_counts_dev, void *stream) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
-  if (score_filtered_check(h, Q, k, q_any_dev, q_none_dev, excl_ids_dev, n_excl)) return 1;
+  SSE_ENTER(h);
+  if (score_topk_check(h, CALL_FILTERED, Q, k, q_any_dev, q_none_dev, excl_ids_dev, n_excl)) return 1;
   if (Q == 0) return 0;
   if (!q_dev || !out_scores_dev || !out_ids_dev || !out_counts_dev) return fail(h, "bad arguments to sse_score_topk_filtered");
-  return score_filtered_dev_locked(h, q_dev, Q, k, q_any_dev, q_none_dev, excl_ids_dev, n_excl, out_scores_dev, out_ids_dev,
-                                   out_counts_dev, (hipStream_t)stream);
+  const TopkIo io{q_dev, q_any_dev, q_none_dev, out_scores_dev, out_ids_dev, out_counts_dev};
+  return score_filtered_dev_locked(h, io, Q, k, excl_ids_dev, n_excl, (hipStream_t)stream);
 }
 
 int sse_score_topk_filtered(sse_handle *h, const float *q_host, int32_t Q, int32_t k, const uint64_t *q_any,
                             const uint64_t *q_none, const int64_t *excl_ids, int32_t n_excl, double *out_scores,
                             int64_t *out_ids, int32_t *out_counts) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
-  if (score_filtered_check(h, Q, k, q_any, q_none, excl_ids, n_excl)) return 1;
+  SSE_ENTER(h);
+  if (score_topk_check(h, CALL_FILTERED, Q, k, q_any, q_none, excl_ids, n_excl)) return 1;
   if (Q == 0) return 0;
   if (!q_host || !out_scores || !out_ids || !out_counts) return fail(h, "bad arguments to sse_score_topk_filtered");
-  const size_t o8 = (size_t)Q * k * 8, m8 = (size_t)Q * 8, e8 = (size_t)Q * n_excl * 8;
-  const size_t qb = (size_t)Q * h->idx_S * sizeof(float);
-  char *piece[7];  // scores | ids | any | none | excl | queries | counts
-  if (stage_pieces(h, {o8, o8, m8, m8, e8, qb, (size_t)Q * 4}, piece)) return 1;
-  double *d_s = (double *)piece[0];
-  int64_t *d_i = (int64_t *)piece[1];
-  uint64_t *d_any = (uint64_t *)piece[2], *d_none = (uint64_t *)piece[3];
-  int64_t *d_ex = (int64_t *)piece[4];
-  float *d_q = (float *)piece[5];
-  int32_t *d_c = (int32_t *)piece[6];
-  HIPCHECK(h, hipMemcpy(d_q, q_host, qb, hipMemcpyHostToDevice));
-  if (q_any) HIPCHECK(h, hipMemcpy(d_any, q_any, m8, hipMemcpyHostToDevice));
-  if (q_none) HIPCHECK(h, hipMemcpy(d_none, q_none, m8, hipMemcpyHostToDevice));
-  if (n_excl > 0) HIPCHECK(h, hipMemcpy(d_ex, excl_ids, e8, hipMemcpyHostToDevice));
-  if (score_filtered_dev_locked(h, d_q, Q, k, q_any ? d_any : nullptr, q_none ? d_none : nullptr, n_excl > 0 ? d_ex : nullptr, n_excl,
-                                d_s, d_i, d_c, nullptr))
-    return 1;
+  const size_t o8 = (size_t)Q * k * 8, m8 = (size_t)Q * 8;
+  StagePiece p[] = {{o8, nullptr, out_scores}, {o8, nullptr, out_ids}, {m8, q_any}, {m8, q_none}, {m8 * n_excl, n_excl > 0 ? excl_ids : nullptr},
+                    {(size_t)Q * h->idx_S * sizeof(float), q_host}, {(size_t)Q * 4, nullptr, out_counts}};
+  if (stage_in(h, p)) return 1;
+  const TopkIo io{p[5].as<float>(), p[2].as<uint64_t>(), p[3].as<uint64_t>(), p[0].as<double>(), p[1].as<int64_t>(), p[6].as<int32_t>()};
+  if (score_filtered_dev_locked(h, io, Q, k, p[4].as<int64_t>(), n_excl, nullptr)) return 1;
   HIPCHECK(h, sync_stream(nullptr));
-  HIPCHECK(h, hipMemcpy(out_scores, d_s, o8, hipMemcpyDeviceToHost));
-  HIPCHECK(h, hipMemcpy(out_ids, d_i, o8, hipMemcpyDeviceToHost));
-  HIPCHECK(h, hipMemcpy(out_counts, d_c, (size_t)Q * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return stage_out(h, p);
 }
 
 int sse_index_set_groups(sse_handle *h, const int64_t *groups_host, int64_t N) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if (index_set_groups_locked(h, groups_host, N, true, nullptr)) return 1;
   HIPCHECK(h, hipStreamSynchronize(nullptr));
   return 0;
 }
 
 int sse_index_set_groups_dev(sse_handle *h, const int64_t *groups_dev, int64_t N, void *stream) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   return index_set_groups_locked(h, groups_dev, N, false, (hipStream_t)stream);
 }
 
 int sse_score_topk_grouped_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, const uint64_t *q_any_dev,
                                const uint64_t *q_none_dev, double *out_scores_dev, int64_t *out_ids_dev,
                                int64_t *out_groups_dev, int32_t *out_counts_dev, void *stream) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
-  if (score_grouped_check(h, Q, k, q_any_dev, q_none_dev)) return 1;
+  SSE_ENTER(h);
+  if (score_topk_check(h, CALL_GROUPED, Q, k, q_any_dev, q_none_dev)) return 1;
   if (Q == 0) return 0;
   if (!q_dev || !out_scores_dev || !out_ids_dev || !out_groups_dev || !out_counts_dev) return fail(h, "bad arguments to sse_score_topk_grouped");
-  return score_grouped_dev_locked(h, q_dev, Q, k, q_any_dev, q_none_dev, out_scores_dev, out_ids_dev, out_groups_dev,
-                                  out_counts_dev, (hipStream_t)stream);
+  const TopkIo io{q_dev, q_any_dev, q_none_dev, out_scores_dev, out_ids_dev, out_counts_dev};
+  return score_grouped_dev_locked(h, io, Q, k, out_groups_dev, (hipStream_t)stream);
 }
 
 int sse_score_topk_grouped(sse_handle *h, const float *q_host, int32_t Q, int32_t k, const uint64_t *q_any,
                            const uint64_t *q_none, double *out_scores, int64_t *out_ids, int64_t *out_groups,
                            int32_t *out_counts) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
-  if (score_grouped_check(h, Q, k, q_any, q_none)) return 1;
+  SSE_ENTER(h);
+  if (score_topk_check(h, CALL_GROUPED, Q, k, q_any, q_none)) return 1;
   if (Q == 0) return 0;
   if (!q_host || !out_scores || !out_ids || !out_groups || !out_counts) return fail(h, "bad arguments to sse_score_topk_grouped");
-  const size_t o8 = (size_t)Q * k * 8, m8 = (size_t)Q * 8, qb = (size_t)Q * h->idx_S * sizeof(float);
-  char *piece[7];  // scores | ids | groups | any | none | queries | counts
-  if (stage_pieces(h, {o8, o8, o8, m8, m8, qb, (size_t)Q * 4}, piece)) return 1;
-  double *d_s = (double *)piece[0];
-  int64_t *d_i = (int64_t *)piece[1], *d_g = (int64_t *)piece[2];
-  uint64_t *d_any = (uint64_t *)piece[3], *d_none = (uint64_t *)piece[4];
-  float *d_q = (float *)piece[5];
-  int32_t *d_c = (int32_t *)piece[6];
-  HIPCHECK(h, hipMemcpy(d_q, q_host, qb, hipMemcpyHostToDevice));
-  if (q_any) HIPCHECK(h, hipMemcpy(d_any, q_any, m8, hipMemcpyHostToDevice));
-  if (q_none) HIPCHECK(h, hipMemcpy(d_none, q_none, m8, hipMemcpyHostToDevice));
-  if (score_grouped_dev_locked(h, d_q, Q, k, q_any ? d_any : nullptr, q_none ? d_none : nullptr, d_s, d_i, d_g, d_c, nullptr)) return 1;
+  const size_t o8 = (size_t)Q * k * 8, m8 = (size_t)Q * 8;
+  StagePiece p[] = {{o8, nullptr, out_scores}, {o8, nullptr, out_ids}, {o8, nullptr, out_groups}, {m8, q_any}, {m8, q_none},
+                    {(size_t)Q * h->idx_S * sizeof(float), q_host}, {(size_t)Q * 4, nullptr, out_counts}};
+  if (stage_in(h, p)) return 1;
+  const TopkIo io{p[5].as<float>(), p[3].as<uint64_t>(), p[4].as<uint64_t>(), p[0].as<double>(), p[1].as<int64_t>(), p[6].as<int32_t>()};
+  if (score_grouped_dev_locked(h, io, Q, k, p[2].as<int64_t>(), nullptr)) return 1;
   HIPCHECK(h, sync_stream(nullptr));
-  HIPCHECK(h, hipMemcpy(out_scores, d_s, o8, hipMemcpyDeviceToHost));
-  HIPCHECK(h, hipMemcpy(out_ids, d_i, o8, hipMemcpyDeviceToHost));
-  HIPCHECK(h, hipMemcpy(out_groups, d_g, o8, hipMemcpyDeviceToHost));
-  HIPCHECK(h, hipMemcpy(out_counts, d_c, (size_t)Q * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return stage_out(h, p);
 }
 
 int sse_score_topk_after_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, const double *after_score_dev,
                              const int64_t *after_id_dev, const uint64_t *q_any_dev, const uint64_t *q_none_dev,
                              double *out_scores_dev, int64_t *out_ids_dev, int32_t *out_counts_dev, void *stream) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
-  if (score_after_check(h, Q, k, after_score_dev, after_id_dev, q_any_dev, q_none_dev)) return 1;
+  SSE_ENTER(h);
+  if (score_topk_check(h, CALL_AFTER, Q, k, q_any_dev, q_none_dev, nullptr, 0, after_score_dev, after_id_dev)) return 1;
   if (Q == 0) return 0;
   if (!q_dev || !out_scores_dev || !out_ids_dev || !out_counts_dev) return fail(h, "bad arguments to sse_score_topk_after");
-  return score_after_dev_locked(h, q_dev, Q, k, after_score_dev, after_id_dev, q_any_dev, q_none_dev, out_scores_dev, out_ids_dev,
-                                out_counts_dev, (hipStream_t)stream);
+  const TopkIo io{q_dev, q_any_dev, q_none_dev, out_scores_dev, out_ids_dev, out_counts_dev};
+  return score_after_dev_locked(h, io, Q, k, after_score_dev, after_id_dev, (hipStream_t)stream);
 }
 
 int sse_score_topk_after(sse_handle *h, const float *q_host, int32_t Q, int32_t k, const double *after_score,
                          const int64_t *after_id, const uint64_t *q_any, const uint64_t *q_none, double *out_scores,
                          int64_t *out_ids, int32_t *out_counts) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
-  if (score_after_check(h, Q, k, after_score, after_id, q_any, q_none)) return 1;
+  SSE_ENTER(h);
+  if (score_topk_check(h, CALL_AFTER, Q, k, q_any, q_none, nullptr, 0, after_score, after_id)) return 1;
   if (Q == 0) return 0;
   if (!q_host || !out_scores || !out_ids || !out_counts) return fail(h, "bad arguments to sse_score_topk_after");
-  const size_t o8 = (size_t)Q * k * 8, m8 = (size_t)Q * 8, qb = (size_t)Q * h->idx_S * sizeof(float);
-  char *piece[8];  // scores | ids | cursor scores | cursor ids | any | none | queries | counts
-  if (stage_pieces(h, {o8, o8, m8, m8, m8, m8, qb, (size_t)Q * 4}, piece)) return 1;
-  double *d_s = (double *)piece[0];
-  int64_t *d_i = (int64_t *)piece[1];
-  double *d_as = (double *)piece[2];
-  int64_t *d_ai = (int64_t *)piece[3];
-  uint64_t *d_any = (uint64_t *)piece[4], *d_none = (uint64_t *)piece[5];
-  float *d_q = (float *)piece[6];
-  int32_t *d_c = (int32_t *)piece[7];
-  HIPCHECK(h, hipMemcpy(d_q, q_host, qb, hipMemcpyHostToDevice));
-  if (after_score) {
-    HIPCHECK(h, hipMemcpy(d_as, after_score, m8, hipMemcpyHostToDevice));
-    HIPCHECK(h, hipMemcpy(d_ai, after_id, m8, hipMemcpyHostToDevice));
-  }
-  if (q_any) HIPCHECK(h, hipMemcpy(d_any, q_any, m8, hipMemcpyHostToDevice));
-  if (q_none) HIPCHECK(h, hipMemcpy(d_none, q_none, m8, hipMemcpyHostToDevice));
-  if (score_after_dev_locked(h, d_q, Q, k, after_score ? d_as : nullptr, after_score ? d_ai : nullptr, q_any ? d_any : nullptr,
-                             q_none ? d_none : nullptr, d_s, d_i, d_c, nullptr))
-    return 1;
+  const size_t o8 = (size_t)Q * k * 8, m8 = (size_t)Q * 8;
+  StagePiece p[] = {{o8, nullptr, out_scores}, {o8, nullptr, out_ids}, {m8, after_score}, {m8, after_id}, {m8, q_any}, {m8, q_none},
+                    {(size_t)Q * h->idx_S * sizeof(float), q_host}, {(size_t)Q * 4, nullptr, out_counts}};
+  if (stage_in(h, p)) return 1;
+  const TopkIo io{p[6].as<float>(), p[4].as<uint64_t>(), p[5].as<uint64_t>(), p[0].as<double>(), p[1].as<int64_t>(), p[7].as<int32_t>()};
+  if (score_after_dev_locked(h, io, Q, k, p[2].as<double>(), p[3].as<int64_t>(), nullptr)) return 1;
   HIPCHECK(h, sync_stream(nullptr));
-  HIPCHECK(h, hipMemcpy(out_scores, d_s, o8, hipMemcpyDeviceToHost));
-  HIPCHECK(h, hipMemcpy(out_ids, d_i, o8, hipMemcpyDeviceToHost));
-  HIPCHECK(h, hipMemcpy(out_counts, d_c, (size_t)Q * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return stage_out(h, p);
 }
 
 int sse_merge_topk_strided_dev(sse_handle *h, const double *in_scores_dev, const int64_t *in_ids_dev, int64_t shard_stride,
                                int32_t P, int32_t Q, int32_t k, double *out_scores_dev, int64_t *out_ids_dev, void *stream) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if (P < 1 || Q < 0 || k < 1 || shard_stride < (int64_t)Q * k) return fail(h, "bad arguments to sse_merge_topk_dev");
   if (Q == 0) return 0;
   HIPCHECK(h, launch_merge_topk(in_scores_dev, in_ids_dev, shard_stride, P, Q, k, out_scores_dev, out_ids_dev, (hipStream_t)stream));
@@ -3150,9 +2950,7 @@ static int allgather_merge_locked(sse_handle *h, void *comm, int world, const do
 int sse_allgather_merge_topk_dev(sse_handle *h, void *nccl_comm, int32_t world, const double *local_scores_dev,
                                  const int64_t *local_ids_dev, int32_t Q, int32_t k, double *out_scores_dev, int64_t *out_ids_dev,
                                  void *stream) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if (!nccl_comm || world < 1 || Q < 0 || k < 1 || !local_scores_dev || !local_ids_dev || !out_scores_dev || !out_ids_dev)
     return fail(h, "bad arguments to sse_allgather_merge_topk_dev");
   if (Q == 0) return 0;
@@ -3161,9 +2959,7 @@ int sse_allgather_merge_topk_dev(sse_handle *h, void *nccl_comm, int32_t world, 
 
 int sse_score_topk_sharded_dev(sse_handle *h, void *nccl_comm, int32_t world, const float *q_dev, int32_t Q, int32_t k,
                                double *out_scores_dev, int64_t *out_ids_dev, void *stream) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if (!nccl_comm || world < 1 || Q < 0 || k < 1 || !q_dev || !out_scores_dev || !out_ids_dev)
     return fail(h, "bad arguments to sse_score_topk_sharded_dev");
   if (Q == 0) return 0;
@@ -3198,9 +2994,7 @@ int sse_train_grad_count(sse_handle *h, int64_t *count) {
 }
 
 int sse_train_set_grad_arena(sse_handle *h, float *arena_dev, int64_t count) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if (!h->train) h->train = new TrainState();
   TrainState &ts = *h->train;
   if (arena_dev && count != grad_arena_count(h))
@@ -3866,16 +3660,12 @@ static int train_apply_locked(sse_handle *h, float *loss, float *train_acc) {
 
 int sse_train_grads(sse_handle *h, const int32_t *src_ids_host, const int32_t *tgt_ids_host, const float *labels_host,
                     int32_t B, int32_t T, int64_t rows_global) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   return train_grads_locked(h, src_ids_host, tgt_ids_host, labels_host, B, T, rows_global);
 }
 
 int sse_corpus_upload(sse_handle *h, int side, const int32_t *ids_host, int64_t N, int32_t T) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if ((side != 0 && side != 1) || !ids_host || N < 1 || T < 1 || N > 2147483000) return fail(h, "bad arguments to sse_corpus_upload");
   if (!h->train) h->train = new TrainState();
   TrainState &ts = *h->train;
@@ -3889,9 +3679,7 @@ int sse_corpus_upload(sse_handle *h, int side, const int32_t *ids_host, int64_t 
 
 int sse_train_grads_rows(sse_handle *h, const int32_t *src_rows_host, const int32_t *tgt_rows_host, const float *labels_host,
                          int32_t B, int64_t rows_global) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if (!h->train || !h->train->corpus[0].p) return fail(h, "train step by rows: no source corpus on the device (sse_corpus_upload)");
   h->train->rows_mode = true;
   const int rc = train_grads_locked(h, src_rows_host, tgt_rows_host, labels_host, B, h->train->corpus_T[0], rows_global);
@@ -3901,9 +3689,7 @@ int sse_train_grads_rows(sse_handle *h, const int32_t *src_rows_host, const int3
 
 int sse_train_step_rows(sse_handle *h, const int32_t *src_rows_host, const int32_t *tgt_rows_host, const float *labels_host,
                         int32_t B, float *loss, float *train_acc) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if (!h->train || !h->train->corpus[0].p) return fail(h, "train step by rows: no source corpus on the device (sse_corpus_upload)");
   h->train->rows_mode = true;
   h->train->defer_err = true;
@@ -3920,9 +3706,7 @@ int64_t sse_train_packed_embedding_floats(sse_handle *h, int32_t cap) {
 }
 
 int sse_train_pack_embedding_grad(sse_handle *h, int32_t cap, float *packed_dev) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if (!h->train || !h->train->grads_ready) return fail(h, "pack embedding gradient: no gradients pending (call sse_train_grads first)");
   if (cap < 1 || !packed_dev) return fail(h, "bad arguments to sse_train_pack_embedding_grad");
   HIPCHECK(h, launch_emb_grad_pack(h->vars[0].grad, h->cfg.vocab_size, h->cfg.embedding_size, cap, packed_dev, h->err_flag, h->stream));
@@ -3930,9 +3714,7 @@ int sse_train_pack_embedding_grad(sse_handle *h, int32_t cap, float *packed_dev)
 }
 
 int sse_train_unpack_embedding_grad(sse_handle *h, const float *gathered_dev, int32_t world, int32_t cap) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if (!h->train || !h->train->grads_ready) return fail(h, "unpack embedding gradient: no gradients pending (call sse_train_grads first)");
   if (cap < 1 || world < 1 || !gathered_dev) return fail(h, "bad arguments to sse_train_unpack_embedding_grad");
   HIPCHECK(h, launch_emb_grad_unpack(gathered_dev, world, h->cfg.vocab_size, h->cfg.embedding_size, cap, h->vars[0].grad, h->err_flag,
@@ -3941,9 +3723,7 @@ int sse_train_unpack_embedding_grad(sse_handle *h, const float *gathered_dev, in
 }
 
 int sse_train_apply(sse_handle *h, float *loss, float *train_acc) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   return train_apply_locked(h, loss, train_acc);
 }
 
@@ -4061,17 +3841,13 @@ static int eval_loss_locked(sse_handle *h, const int32_t *src_host, const int32_
 
 int sse_eval_loss(sse_handle *h, const int32_t *src_ids_host, const int32_t *tgt_ids_host, const float *labels_host, int32_t B,
                   int32_t T, double *sums, float *row_cos_host) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   return eval_loss_locked(h, src_ids_host, tgt_ids_host, labels_host, B, T, false, sums, row_cos_host);
 }
 
 int sse_eval_loss_rows(sse_handle *h, const int32_t *src_rows_host, const int32_t *tgt_rows_host, const float *labels_host,
                        int32_t B, double *sums, float *row_cos_host) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   if (!h->train || !h->train->corpus[0].p) return fail(h, "loss evaluation by rows: no source corpus on the device (sse_corpus_upload)");
   return eval_loss_locked(h, src_rows_host, tgt_rows_host, labels_host, B, h->train->corpus_T[0], true, sums, row_cos_host);
 }
@@ -4104,9 +3880,7 @@ int sse_set_global_step(sse_handle *h, int64_t step) {
 }
 
 int sse_set_stream(sse_handle *h, void *stream) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   HIPCHECK(h, hipStreamSynchronize(h->stream));  // nothing of an earlier step may still be in flight on the old stream
   h->stream = (hipStream_t)stream;
   return 0;
@@ -4131,9 +3905,7 @@ int sse_timer_elapsed_ms(sse_handle *h, int32_t a, int32_t b, float *ms) {
   return 0;
 }
 int sse_synchronize(sse_handle *h) {
-  if (!h) return 1;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SSE_ENTER(h);
   HIPCHECK(h, hipDeviceSynchronize());
   return check_err_flag(h, nullptr);
 }
