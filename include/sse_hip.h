@@ -186,7 +186,9 @@ int sse_l2_normalize_dev(sse_handle *h, const float *x_dev, float *out_dev, int6
  * resident.  *_f64 keeps the float64 values the reference parses from text for
  * the exact re-scoring pass; id_base is added to row numbers in results (row
  * shards of one index).  sse_index_set_dev adopts rows already on
- * the device (copied). */
+ * the device (copied).  A shape the scorer cannot hold (N <= 0, S <= 0,
+ * S > 1024, N > 2147483000) is refused with a message before anything is
+ * touched: the resident index, its float64 rows, tags and group keys stay. */
 int sse_index_upload(sse_handle *h, const float *rows_host, int64_t N, int32_t S, int64_t id_base);
 int sse_index_upload_f64(sse_handle *h, const double *rows_host, int64_t N, int32_t S, int64_t id_base);
 int sse_index_set_dev(sse_handle *h, const float *rows_dev, int64_t N, int32_t S, int64_t id_base,

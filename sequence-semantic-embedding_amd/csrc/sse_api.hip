@@ -1029,10 +1029,17 @@ int check_err_flag(sse_handle *h, hipStream_t st, int32_t *bits = nullptr) {
   return 0;
 }
 
-int index_from_dev_rows(sse_handle *h, const float *rows_dev, int64_t N, int S, int64_t id_base, hipStream_t st) {
+// The shapes an index can have.  The upload entry points ask this BEFORE they free, allocate or invalidate anything: a refused
+// upload leaves the resident index, its float64 rows, tags and group keys as they were.
+int index_shape_check(sse_handle *h, int64_t N, int64_t S) {
   if (N <= 0 || S <= 0) return fail(h, "empty index");
-  if (S > SSE_MAX_INDEX_DIM) return fail(h, "index dimension %d > %d not supported by the scoring kernel", S, SSE_MAX_INDEX_DIM);
+  if (S > SSE_MAX_INDEX_DIM) return fail(h, "index dimension %lld > %d not supported by the scoring kernel", (long long)S, SSE_MAX_INDEX_DIM);
   if (N > (int64_t)2147483000) return fail(h, "index shard too large for int32 row ids");
+  return 0;
+}
+
+int index_from_dev_rows(sse_handle *h, const float *rows_dev, int64_t N, int S, int64_t id_base, hipStream_t st) {
+  if (index_shape_check(h, N, S)) return 1;
   const int KG = (S + 7) / 8;
   const int64_t NT = (N + 31) / 32;
   h->tags_set = false;  // (tags belong to the rows they were set for)
@@ -2537,6 +2544,7 @@ int sse_l2_normalize_dev(sse_handle *h, const float *x_dev, float *out_dev, int6
 
 int sse_index_set_dev(sse_handle *h, const float *rows_dev, int64_t N, int32_t S, int64_t id_base, void *stream) {
   SSE_ENTER(h);
+  if (index_shape_check(h, N, S)) return 1;
   if (h->idx64) {
     HIPCHECK(h, hipFree(h->idx64));
     h->idx64 = nullptr;
@@ -2548,7 +2556,7 @@ int sse_index_upload(sse_handle *h, const float *rows_host, int64_t N, int32_t S
   if (!h || !rows_host) return 1;
   std::lock_guard<std::mutex> lk(h->mu);
   HIPCHECK(h, hipSetDevice(h->cfg.device));
-  if (N <= 0 || S <= 0) return fail(h, "empty index");
+  if (index_shape_check(h, N, S)) return 1;
   if (reserve(h, h->s_tmp, (size_t)N * S * sizeof(float))) return 1;
   HIPCHECK(h, hipMemcpy(h->s_tmp.p, rows_host, (size_t)N * S * sizeof(float), hipMemcpyHostToDevice));
   if (h->idx64) {
@@ -2562,7 +2570,7 @@ int sse_index_upload_f64(sse_handle *h, const double *rows_host, int64_t N, int3
   if (!h || !rows_host) return 1;
   std::lock_guard<std::mutex> lk(h->mu);
   HIPCHECK(h, hipSetDevice(h->cfg.device));
-  if (N <= 0 || S <= 0) return fail(h, "empty index");
+  if (index_shape_check(h, N, S)) return 1;
   if (h->idx64) {
     HIPCHECK(h, hipFree(h->idx64));
     h->idx64 = nullptr;
