@@ -1,8 +1,9 @@
 // The fp32 index sweep shared by sse_score_rank, sse_score_above, sse_score_topk_filtered, sse_score_topk_grouped and
-// sse_score_topk_after (score_rank.hip, score_above.hip, score_filtered.hip, score_grouped.hip, score_after.hip; DESIGN K6i):
+// sse_score_topk_after (score_rank.hip, score_above.hip and -- the last three calls -- score_eligible.h; DESIGN K6i):
 // [N,S] x [S,P] on v_mfma_f32_32x32x2_f32 from the fragment-order index, the sweep of score_topk_kernel's COLLECT variant with
-// the queries taken row-major.  Each of the kernels keeps its own prologue (what a lane holds per column) and epilogue (what it
-// does with a tile's 16 scores per column) and calls the pieces below in this order:
+// the queries taken row-major.  score_rank_kernel, score_above_kernel and eligible_sweep_kernel each keep their own prologue
+// (what a lane holds per column) and epilogue (what it does with a tile's 16 scores per column) and call the pieces below in
+// this order:
 //   sweep_decode         workgroup = (block of NQ x 32 columns, index split)
 //   sweep_stage_queries  the block's query rows into LDS as MFMA B fragments [k-group][column tile][1 KiB]
 //   sweep_tile_range     a wave walks its split's tiles w, w + 8, ...

@@ -372,6 +372,8 @@ CASES = [
     Case("k1024", _base("k1", 3, 5000, 64), _b_none, _s_k1024, why="largest k: rows 1025 .. 2048"),
     Case("overflow", TC.Case("ao", 8, 6000, 64, 50, kind="dup", seed=14, copies=4500, planted=(3,), ordinary_below=True), _b_none,
          _s_overflow, why="the cursor inside 4500 copies > 4096: the float64 sweep serves the planted query alone"),
+    Case("folded_splits", _base("fs", 5, 16400, 16), FC._b_sixteen_blocks, _s_pages(10),
+         why="513 tiles, 5 queries: 32 index splits share 16 x 256 maxima slots (atomicMax), eligible rows on both sides of a fold"),
 ]
 BY_NAME = {c.name: c for c in CASES}
 

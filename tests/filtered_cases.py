@@ -143,6 +143,12 @@ def _b_sorted(case, q, t, group, s, rng):
     return dict(tags=tags, any=any_)
 
 
+def _b_sixteen_blocks(case, q, t, group, s, rng):
+    per = (case.N + 15) // 16                                # 16 runs of rows, a tag each; a query takes runs b and b + 8
+    tags = (U1 << (np.arange(case.N) // per).astype(np.uint64)).astype(np.uint64)
+    return dict(tags=tags, any=np.array([bit(qi % 8) | bit(qi % 8 + 8) for qi in range(case.Q)], np.uint64))
+
+
 CASES = [
     Case("no_filter_k10", _base("nf", 5, 3000, 32, 10, seed=7101), 10, _b_none, same_as_topk=True, why="score_topk's bits, k <= 16"),
     Case("no_filter_k40", _base("nf", 5, 3000, 32, 40, seed=7101), 40, _b_none, same_as_topk=True, why="score_topk's bits, k > 16"),
@@ -169,6 +175,8 @@ CASES = [
     Case("sorted_tags", _base("st", 64, 4096, 32, 10), 10, _b_sorted,
          variants=(("skip_on", 1, "any", "pos"), ("skip_off", 0, "any", 0), ("any_null", 1, "none", 0)),
          why="rows grouped by tag: tiles of tags 2 .. 7 skipped; results equal with the option off and with none_of in place of any_of"),
+    Case("folded_splits", _base("fs", 5, 16400, 16, 10), 10, _b_sixteen_blocks, variants=(("skip_on", 1, "any", "pos"),),
+         why="513 tiles, 5 queries: 32 index splits share 16 x 256 maxima slots (atomicMax), eligible rows on both sides of a fold"),
 ]
 BY_NAME = {c.name: c for c in CASES}
 

@@ -24,7 +24,7 @@ import numpy as np
 
 from oracle import sse_oracle as O
 from tests import topk_cases as TC
-from tests.filtered_cases import U1, bit
+from tests.filtered_cases import U1, _b_sixteen_blocks, bit
 from tests.topk_cases import BASE, unit  # noqa: F401
 
 COLLECT_CAP = TC.COLLECT_CAP
@@ -165,6 +165,12 @@ def _b_shard(case, q, t, copies, s, rng):
     return d
 
 
+def _b_folded(case, q, t, copies, s, rng):
+    d = _b_random(8)(case, q, t, copies, s, rng)
+    d.update(_b_sixteen_blocks(case, q, t, copies, s, rng))    # rows in 16 runs by tag: whole tiles without an eligible row
+    return d
+
+
 CASES = [
     Case("own_group_k10", _base("og", 5, 3000, 32, 10, seed=8101), 10, _b_own, same_as_topk=True, why="score_topk's bits, k <= 16"),
     Case("own_group_k40", _base("og", 5, 3000, 32, 40, seed=8101), 40, _b_own, same_as_topk=True, why="score_topk's bits, k > 16"),
@@ -193,6 +199,8 @@ CASES = [
          why="index_set_dev + index_set_groups_dev + index_set_tags_dev: ids global"),
     Case("shard_base_f64", _base("sb", 9, 1200, 40, 33, seed=8111, upload="f64", id_base=BASE), 33, _b_shard,
          why="float64 index: idx64 branch of wave_exact_dot"),
+    Case("folded_splits_skipped_tiles", _base("fs", 5, 16400, 16, 10), 10, _b_folded,
+         why="513 tiles, 5 queries: 32 index splits share 16 x 256 (key, row) slots (64-bit atomicMax); tiles skipped in the max sweep"),
 ]
 BY_NAME = {c.name: c for c in CASES}
 

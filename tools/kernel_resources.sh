@@ -9,13 +9,13 @@ src="$1"
 import re, sys, subprocess
 rows, cur = [], None
 for line in sys.stdin:
-    m = re.search(r"remark: (?:\s*)(Function Name|VGPRs|AGPRs|SGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
+    m = re.search(r"remark: (?:\s*)(Function Name|VGPRs|AGPRs|(?:Total)?SGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
     if not m: continue
     k, v = m.groups()
     if k == "Function Name":
         cur = {"name": v}; rows.append(cur)
     elif cur is not None:
-        cur[k.split(" ")[0]] = v
+        cur[k.split(" ")[0].replace("Total", "")] = v   # (TotalSGPRs with newer compilers)
 names = subprocess.run(["c++filt"] + [r["name"] for r in rows], capture_output=True, text=True).stdout.split("\n")
 print("%-78s %5s %5s %5s %7s %4s %7s" % ("kernel", "VGPR", "AGPR", "SGPR", "scratch", "occ", "LDS"))
 for r, n in zip(rows, names):
