@@ -16,6 +16,7 @@
 #include "../../include/sse_hip.h"
 #include "sse_kernels.h"
 #include "train.h"
+#include "train_step.h"
 
 namespace {
 
@@ -63,51 +64,6 @@ struct Encoder {
   // lstm_fwd_kernel's table path (Hp = 256 / 512 inference)
   float *xtab = nullptr;
   bool xtab_valid = false;
-};
-
-struct DevBuf {  // grow-only device scratch; freed with its owner (handle / TrainState)
-  void *p = nullptr;
-  size_t cap = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-// device buffers of the training path, grown on demand
-struct TrainState {
-  DevBuf ids[2], labels, raw[2], draw[2], tape_g[2], tape_a[2], h_last[2], dh_last[2], dg_a[2], dg_b[2], db_part[2],
-      dk_part[2], dm_part[2], sq_part, norm_part, row_loss, row_acc, scal;
-  DevBuf feat_rm, pos, dfeat, dw_part, dbias_part, wt, wct;  // text-CNN training
-  uint64_t gen_ver[2] = {0, 0};  // weights_version the any-shape packs gen_KT / gen_Kq / gen_MT were built from
-  DevBuf gen_A[2], gen_tape[2], gen_dG[2], gen_hl[2], gen_KT[2], gen_Kq[2], gen_MT[2], gen_G, gen_c, gen_dA, gen_dc, gen_dkp;  // any-shape LSTM path
-  hipStream_t side[2] = {nullptr, nullptr};  // the two encoders run concurrently (forward and backward)
-  hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
-  float *KhT[2] = {nullptr, nullptr}, *KxT[2] = {nullptr, nullptr};
-  unsigned short *KhT16[2] = {nullptr, nullptr};  // option train_bwd_x3: Kh^T as split frag16 blocks
-  unsigned short *KxT16[2] = {nullptr, nullptr};  // ... and Kx^T as 16x16x32 B fragments (dX inside the BPTT kernel)
-  bool packed_dirty = true;
-  bool fp32_dirty = true;  // the fp32 Kh^T / Kx^T fragment copies are stale (rebuilt only by steps that run fp32 BPTT kernels)
-  // gradient arena: [grad of variable 0 | ... | grad of variable n-1 | tail[4]]; tail = {sum of squares of the
-  // un-deduplicated embedding-gradient slices, loss, train_acc, rows}, every entry a plain sum over the
-  // ranks of a data-parallel job (one flat all-reduce)
-  float *arena = nullptr;
-  bool arena_external = false, grads_ready = false;
-  // corpus resident on the device (sse_corpus_upload): the *_rows train entry points ship row numbers, not token ids
-  DevBuf corpus[2], rows[2];
-  int64_t corpus_N[2] = {0, 0};
-  int32_t corpus_T[2] = {0, 0};
-  bool rows_mode = false;  // set by the *_rows entry points around train_grads_locked
-  bool defer_err = false;  // set by the fused step entry points: the device error flag is read once, with the loss, after the
-                           // whole step has been queued (a flagged step cancels its own update on the device)
-  // paired batches (data.py:95-115: every source row appears twice, once with its positive and once with a negative
-  // target): internal row order = [rows 0,2,4,.. | rows 1,3,5,..], the source encoder runs on the first half only
-  DevBuf ids_raw[2], perm, hot_part[2];
-  int perm_B = 0;
-  std::vector<int32_t> h_perm, h_rows[2], h_tgt;
-  std::vector<float> h_labels;
 };
 
 }  // namespace
@@ -3031,13 +2987,13 @@ static int ensure_arena(sse_handle *h) {
   return 0;
 }
 
-// token ids of one side of the batch into ts.ids[side] ([B][T] on the device): copied from the host, or -- rows mode --
+// token ids of one side of the batch into ts.ids[side] ([B][T] on the device): copied from the host, or -- by_rows --
 // gathered on the device from the resident corpus by B row numbers (B ints cross PCIe instead of B*T)
 // perm (host, [B], or nullptr): internal row r holds the caller's row perm[r].
-static int stage_ids(sse_handle *h, TrainState &ts, int side, const int32_t *host, int B, int T, const int32_t *perm,
+static int stage_ids(sse_handle *h, TrainState &ts, int side, const int32_t *host, int B, int T, bool by_rows, const int32_t *perm,
                      hipStream_t st) {
   if (reserve(h, ts.ids[side], (size_t)B * T * sizeof(int32_t))) return 1;
-  if (!ts.rows_mode) {
+  if (!by_rows) {
     if (!perm) {
       HIPCHECK(h, hipMemcpyAsync(ts.ids[side].p, host, (size_t)B * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
       return 0;
@@ -3063,81 +3019,133 @@ static int stage_ids(sse_handle *h, TrainState &ts, int side, const int32_t *hos
   return 0;
 }
 
-// source_only_cnn (BUILDER-DEFINED, see cnn_bwd.hip): row b pairs source sequence b with row tgt_rows[b]
-// of the free target matrix; same loss kernel, CNN forward with arg-max tape, gather/scatter backward.
-static int cnn_train_grads_locked(sse_handle *h, const int32_t *src_ids_host, const int32_t *tgt_rows_host,
-                                  const float *labels_host, int32_t B, int32_t T, int64_t rows_global) {
-  const sse_config &c = h->cfg;
-  hipStream_t st = h->stream;
-  TrainState &ts = *h->train;
-  const int E = c.embedding_size, S = c.encoding_size, V = c.vocab_size, Ep = emb_cols(c);
-  const int Bp = round_up(B, 64);
-  if (T < 5) return fail(h, "source_only_cnn needs max_seq_length >= 5 (widest filter)");
-  if (E > 64) return fail(h, "train step: embedding_size %d > 64 not supported yet", E);
-  const int Ep8 = round_up(E, 8);
-  if ((h->cnn_bf16 ? cnn_bf16_lds_bytes(T, Ep8, 1) : cnn_lds_bytes(T, Ep, 1)) > 160 * 1024)
-    return fail(h, "source_only_cnn training: T*E = %d*%d does not fit the LDS tile of the gfx950 kernel", T, E);
-  // the weight-gradient kernel stages two [T][E] fp32 tiles + 384 floats (cnn_bwd.hip): its own limit, named here
-  if (((size_t)2 * T * E + 384) * sizeof(float) > (size_t)160 * 1024)
-    return fail(h, "source_only_cnn training: T*E = %d*%d needs %zu bytes of LDS in the weight-gradient kernel (limit 160 KiB: T*E <= 20288)",
-                T, E, ((size_t)2 * T * E + 384) * sizeof(float));
-  if (ensure_arena(h)) return 1;
-  if (ensure_packed(h, st)) return 1;
-  float *tail = ts.arena + grad_arena_count(h) - 4;
-  const float inv_rows = 1.0f / (float)rows_global;
-  Variable &emb = h->vars[0], &table = h->vars[h->tgt_table], &M = h->vars[h->cnn_M];
+// ---- the step frame.  Every path reads: begin -> stage inputs -> its forward -> loss -> its backward -> finish, with the
+// free target matrix's gather / scatter where the path has always queued them.
 
-  if (reserve(h, ts.ids[1], (size_t)B * sizeof(int32_t))) return 1;
-  if (reserve(h, ts.labels, (size_t)B * sizeof(float))) return 1;
-  if (stage_ids(h, ts, 0, src_ids_host, B, T, nullptr, st)) return 1;
-  HIPCHECK(h, hipMemcpyAsync(ts.ids[1].p, tgt_rows_host, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIPCHECK(h, hipMemcpyAsync(ts.labels.p, labels_host, (size_t)B * sizeof(float), hipMemcpyHostToDevice, st));
-  for (int s = 0; s < 2; ++s) {
-    if (reserve(h, ts.raw[s], (size_t)Bp * S * sizeof(float))) return 1;
-    if (reserve(h, ts.draw[s], (size_t)Bp * S * sizeof(float))) return 1;
+// arena, tail, shapes.  row_tile: 64 (text-CNN, fused LSTM) or 32 (any-shape LSTM).  The caller has checked the arguments.
+static int step_begin(sse_handle *h, const TrainCall &call, int row_tile, StepFrame &f) {
+  if (ensure_arena(h)) return 1;
+  f.h = h;  f.call = &call;  f.ts = h->train;  f.st = h->stream;
+  f.B = call.B;  f.T = call.T;  f.S = h->cfg.encoding_size;  f.Bp = round_up(call.B, row_tile);
+  // source-encoder-only (BUILDER-DEFINED like the CNN mode: the reference's loss is ill-shaped there,
+  // sse_model.py:233,290): LSTM source encoder, target side = embedding_lookup(tgt_seq_embedding, rows);
+  // call.tgt is int32 [B] rows of the free target matrix.
+  f.table_tgt = h->cfg.network_mode == SSE_MODE_SOURCE_ENCODER_ONLY || h->cfg.network_mode == SSE_MODE_SOURCE_ONLY_CNN;
+  f.nside = f.table_tgt ? 1 : 2;
+  f.emb = &h->vars[0];
+  f.table = f.table_tgt ? &h->vars[h->tgt_table] : nullptr;
+  f.tail = f.ts->arena + grad_arena_count(h) - 4;
+  f.inv_rows = 1.0f / (float)call.rows_global;
+  f.n_sq = 0;
+  return 0;
+}
+
+// both id sides and the labels onto the device, in the internal row order (perm: see pair_permutation; nullptr = the
+// caller's), and the buffers every path fills: raw[] / draw[] encodings, per-row loss / accuracy, the n_sq partial sums
+static int step_stage_inputs(StepFrame &f, const int32_t *perm, int n_sq) {
+  sse_handle *h = f.h;
+  TrainState &ts = *f.ts;
+  const TrainCall &call = *f.call;
+  const int B = f.B;
+  f.n_sq = n_sq;
+  if (stage_ids(h, ts, 0, call.src, B, f.T, call.by_rows, perm, f.st)) return 1;
+  if (f.table_tgt) {  // rows of the free target matrix
+    if (reserve(h, ts.ids[1], (size_t)B * sizeof(int32_t))) return 1;
+    const int32_t *rows = call.tgt;
+    if (perm) {
+      ts.h_tgt.resize(B);
+      for (int r = 0; r < B; ++r) ts.h_tgt[r] = rows[perm[r]];
+      rows = ts.h_tgt.data();
+    }
+    HIPCHECK(h, hipMemcpyAsync(ts.ids[1].p, rows, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, f.st));
+  } else if (stage_ids(h, ts, 1, call.tgt, B, f.T, call.by_rows, perm, f.st)) {
+    return 1;
   }
-  if (reserve(h, h->s_feat, (size_t)((B + 31) / 32) * 72 * 256 * sizeof(float))) return 1;
-  if (reserve(h, ts.feat_rm, (size_t)Bp * 576 * sizeof(float))) return 1;
-  if (reserve(h, ts.pos, (size_t)Bp * 576 * sizeof(int32_t))) return 1;
-  if (reserve(h, ts.dfeat, (size_t)Bp * 576 * sizeof(float))) return 1;
-  if (reserve(h, ts.dw_part, cnn_dw_part_floats(E, B) * sizeof(float))) return 1;
-  if (reserve(h, ts.dbias_part, (size_t)cnn_bwd_chunks(B) * 576 * sizeof(float))) return 1;
-  if (reserve(h, ts.wt, (size_t)E * 1728 * sizeof(float))) return 1;
-  if (reserve(h, ts.wct, cnn_wct_elems(E) * sizeof(unsigned short))) return 1;
-  if (reserve(h, ts.hot_part[0], (size_t)std::max(B, cnn_dx_mfma_blocks(B)) * 2 * 64 * sizeof(float))) return 1;
-  if (reserve(h, ts.dm_part[0], (size_t)proj_bwd_chunks(Bp) * 576 * S * sizeof(float))) return 1;
-  if (reserve(h, ts.sq_part, (size_t)2 * B * sizeof(float))) return 1;
+  const float *labels = call.labels;
+  if (perm) {
+    ts.h_labels.resize(B);
+    for (int r = 0; r < B; ++r) ts.h_labels[r] = labels[perm[r]];
+    labels = ts.h_labels.data();
+  }
+  if (reserve(h, ts.labels, (size_t)B * sizeof(float))) return 1;
+  HIPCHECK(h, hipMemcpyAsync(ts.labels.p, labels, (size_t)B * sizeof(float), hipMemcpyHostToDevice, f.st));
+  for (int s = 0; s < 2; ++s) {
+    if (reserve(h, ts.raw[s], (size_t)f.Bp * f.S * sizeof(float))) return 1;
+    if (reserve(h, ts.draw[s], (size_t)f.Bp * f.S * sizeof(float))) return 1;
+  }
   if (reserve(h, ts.row_loss, (size_t)B * sizeof(float))) return 1;
   if (reserve(h, ts.row_acc, (size_t)B * sizeof(float))) return 1;
+  return reserve(h, ts.sq_part, (size_t)n_sq * sizeof(float));
+}
 
-  // ---- forward with the arg-max tape; target rows looked up from the free matrix
-  HIPCHECK(h, hipMemsetAsync(ts.feat_rm.p, 0, (size_t)Bp * 576 * sizeof(float), st));  // padding rows feed the dM GEMM
+// table target: raw[1] = the batch's rows of the free matrix
+static int step_table_forward(StepFrame &f) {
+  if (!f.table_tgt) return 0;
+  HIPCHECK(f.h, launch_rows_gather(f.table->dev, f.ids(1), f.B, f.Bp, f.table->rows, f.S, f.raw(1), f.h->err_flag, f.st));
+  return 0;
+}
+
+// loss, train accuracy, d(raw encodings); then the two lookup tables' gradients zeroed for the scatters of the backward
+static int step_loss(StepFrame &f) {
+  sse_handle *h = f.h;
+  TrainState &ts = *f.ts;
+  // token ids / corpus rows / target rows out of range: every backward kernel validates the ids it scatters by itself
+  // (the sequence-encoder BPTT kernels, gen_dx_scatter_kernel, cnn_dx_kernel; rows_scatter_kernel validates the target
+  // rows itself since round 5), so the fused step (sse_train_step) reads the flag once at its end -- train_apply_locked; a
+  // flagged step cancels its own update on the device -- instead of stalling the queue here.  sse_train_grads reads it now,
+  // on every path, so that a rank with a bad id fails here instead of only in its own sse_train_apply.
+  if (!f.call->defer_err && check_err_flag(h, f.st)) return 1;
+  HIPCHECK(h, launch_loss(f.raw(0), f.raw(1), (const float *)ts.labels.p, f.draw(0), f.draw(1), (float *)ts.row_loss.p,
+                          (float *)ts.row_acc.p, f.tail + 1, f.B, f.Bp, f.S, f.inv_rows, f.st));
+  HIPCHECK(h, hipMemsetAsync(f.emb->grad, 0, f.emb->count * sizeof(float), f.st));
+  if (f.table_tgt) HIPCHECK(h, hipMemsetAsync(f.table->grad, 0, f.table->count * sizeof(float), f.st));
+  return 0;
+}
+
+// table target: d(raw[1]) scattered onto the free matrix's gradient, its slice norms into the last B partial sums
+static int step_table_backward(StepFrame &f) {
+  if (!f.table_tgt) return 0;
+  HIPCHECK(f.h, launch_rows_scatter(f.draw(1), f.ids(1), f.B, f.S, f.table->rows, f.table->grad, f.sq() + (f.n_sq - f.B), f.st));
+  return 0;
+}
+
+// tail[0] = sum of squares of the raw (un-deduplicated) embedding-gradient slices (both lookups are IndexedSlices),
+// tail[3] = rows
+static int step_finish(StepFrame &f) {
+  HIPCHECK(f.h, launch_sum(f.sq(), f.n_sq, (float)f.B, f.tail, f.st));
+  f.ts->grads_ready = true;
+  return 0;
+}
+
+// ---- source_only_cnn (BUILDER-DEFINED, see cnn_bwd.hip): row b pairs source sequence b with row tgt_rows[b]
+// of the free target matrix; same loss kernel, CNN forward with arg-max tape, gather/scatter backward.
+
+// forward with the arg-max tape
+static int cnn_forward(StepFrame &f) {
+  sse_handle *h = f.h;
+  TrainState &ts = *f.ts;
+  const int B = f.B, T = f.T, V = h->cfg.vocab_size;
+  HIPCHECK(h, hipMemsetAsync(ts.feat_rm.p, 0, (size_t)f.Bp * 576 * sizeof(float), f.st));  // padding rows feed the dM GEMM
   if (h->cnn_bf16) {
     // option cnn_bf16 (BASELINE configs[4]): convolution on the bf16 matrix pipe over bf16-rounded embeddings and
     // filters (fp32 masters, copies refreshed by ensure_packed after every update), fp32 accumulation; bias, ReLU,
     // pooling, projection, loss and the optimizer in fp32
-    HIPCHECK(h, launch_cnn_fwd_bf16((const int32_t *)ts.ids[0].p, h->emb_bf16, h->cnn_Wc16, h->cnn_bias, (float *)h->s_feat.p,
-                                    h->err_flag, B, T, V, Ep8, (float *)ts.feat_rm.p, (int32_t *)ts.pos.p, st));
-    HIPCHECK(h, launch_cnn_proj_x3((const float *)h->s_feat.p, h->cnn_Mx3, (float *)ts.raw[0].p, B, S, 0, st));
+    HIPCHECK(h, launch_cnn_fwd_bf16(f.ids(0), h->emb_bf16, h->cnn_Wc16, h->cnn_bias, (float *)h->s_feat.p, h->err_flag, B, T, V,
+                                    round_up(h->cfg.embedding_size, 8), (float *)ts.feat_rm.p, (int32_t *)ts.pos.p, f.st));
+    HIPCHECK(h, launch_cnn_proj_x3((const float *)h->s_feat.p, h->cnn_Mx3, f.raw(0), B, f.S, 0, f.st));
   } else {
-    HIPCHECK(h, launch_cnn_fwd((const int32_t *)ts.ids[0].p, h->emb_pad, h->cnn_Wc, h->cnn_bias, h->cnn_Mp,
-                               (float *)h->s_feat.p, (float *)ts.raw[0].p, h->err_flag, B, T, V, Ep, S, 0,
-                               (float *)ts.feat_rm.p, (int32_t *)ts.pos.p, st));
+    HIPCHECK(h, launch_cnn_fwd(f.ids(0), h->emb_pad, h->cnn_Wc, h->cnn_bias, h->cnn_Mp, (float *)h->s_feat.p, f.raw(0), h->err_flag,
+                               B, T, V, emb_cols(h->cfg), f.S, 0, (float *)ts.feat_rm.p, (int32_t *)ts.pos.p, f.st));
   }
-  HIPCHECK(h, launch_rows_gather(table.dev, (const int32_t *)ts.ids[1].p, B, Bp, table.rows, S, (float *)ts.raw[1].p,
-                                 h->err_flag, st));
-  // (the backward kernels validate every token id / target row themselves: the fused step reads the flag once at its end --
-  // train_apply_locked; a flagged step cancels its own update on the device)
-  if (!ts.defer_err && check_err_flag(h, st)) return 1;
-  HIPCHECK(h, launch_loss((const float *)ts.raw[0].p, (const float *)ts.raw[1].p, (const float *)ts.labels.p,
-                          (float *)ts.draw[0].p, (float *)ts.draw[1].p, (float *)ts.row_loss.p, (float *)ts.row_acc.p,
-                          tail + 1, B, Bp, S, inv_rows, st));
+  return 0;
+}
 
-  // ---- backward
-  HIPCHECK(h, hipMemsetAsync(emb.grad, 0, emb.count * sizeof(float), st));
-  HIPCHECK(h, hipMemsetAsync(table.grad, 0, table.count * sizeof(float), st));
-  HIPCHECK(h, launch_proj_bwd((const float *)ts.feat_rm.p, (const float *)ts.draw[0].p, M.dev, Bp, 576, 576, S, M.grad,
-                              (float *)ts.dfeat.p, (float *)ts.dm_part[0].p, st));
+static int cnn_backward(StepFrame &f) {
+  sse_handle *h = f.h;
+  TrainState &ts = *f.ts;
+  Variable &M = h->vars[h->cnn_M];
+  HIPCHECK(h, launch_proj_bwd((const float *)ts.feat_rm.p, f.draw(0), M.dev, f.Bp, 576, 576, f.S, M.grad, (float *)ts.dfeat.p,
+                              (float *)ts.dm_part[0].p, f.st));
   const float *W[4];
   float *dW[4], *db[4];
   for (int i = 0; i < 4; ++i) {
@@ -3145,49 +3153,95 @@ static int cnn_train_grads_locked(sse_handle *h, const int32_t *src_ids_host, co
     dW[i] = h->vars[h->cnn_W[i]].grad;
     db[i] = h->vars[h->cnn_b[i]].grad;
   }
-  float *sq = (float *)ts.sq_part.p;
-  HIPCHECK(h, launch_cnn_bwd((const int32_t *)ts.ids[0].p, emb.dev, (const float *)ts.dfeat.p, (const float *)ts.feat_rm.p,
-                             (const int32_t *)ts.pos.p, W, dW, db, (float *)ts.dw_part.p, (float *)ts.dbias_part.p,
-                             (float *)ts.wt.p, (unsigned short *)ts.wct.p, emb.grad, sq, (float *)ts.hot_part[0].p, B, T, E, V, h->cnn_bf16 ? 1 : 0, st));
-  HIPCHECK(h, launch_rows_scatter((const float *)ts.draw[1].p, (const int32_t *)ts.ids[1].p, B, S, table.rows, table.grad, sq + B, st));
-  // tail[0]: both lookups are IndexedSlices -> raw slice norms
-  HIPCHECK(h, launch_sum(sq, 2 * B, (float)B, tail, st));
-  ts.grads_ready = true;
+  HIPCHECK(h, launch_cnn_bwd(f.ids(0), f.emb->dev, (const float *)ts.dfeat.p, (const float *)ts.feat_rm.p, (const int32_t *)ts.pos.p,
+                             W, dW, db, (float *)ts.dw_part.p, (float *)ts.dbias_part.p, (float *)ts.wt.p, (unsigned short *)ts.wct.p,
+                             f.emb->grad, f.sq(), (float *)ts.hot_part[0].p, f.B, f.T, h->cfg.embedding_size, h->cfg.vocab_size,
+                             h->cnn_bf16 ? 1 : 0, f.st));
   return 0;
 }
 
-// The LSTM modes at shapes the fused training kernels are not laid out for (cell size > 256, embedding_size > 64): the same
+static int cnn_train_grads_locked(sse_handle *h, const TrainCall &call) {
+  const sse_config &c = h->cfg;
+  const int B = call.B, T = call.T, E = c.embedding_size, S = c.encoding_size;
+  if (T < 5) return fail(h, "source_only_cnn needs max_seq_length >= 5 (widest filter)");
+  if (E > 64) return fail(h, "train step: embedding_size %d > 64 not supported yet", E);
+  if ((h->cnn_bf16 ? cnn_bf16_lds_bytes(T, round_up(E, 8), 1) : cnn_lds_bytes(T, emb_cols(c), 1)) > 160 * 1024)
+    return fail(h, "source_only_cnn training: T*E = %d*%d does not fit the LDS tile of the gfx950 kernel", T, E);
+  // the weight-gradient kernel stages two [T][E] fp32 tiles + 384 floats (cnn_bwd.hip): its own limit, named here
+  if (((size_t)2 * T * E + 384) * sizeof(float) > (size_t)160 * 1024)
+    return fail(h, "source_only_cnn training: T*E = %d*%d needs %zu bytes of LDS in the weight-gradient kernel (limit 160 KiB: T*E <= 20288)",
+                T, E, ((size_t)2 * T * E + 384) * sizeof(float));
+  StepFrame f;
+  if (step_begin(h, call, 64, f)) return 1;
+  if (ensure_packed(h, f.st)) return 1;
+  if (step_stage_inputs(f, nullptr, 2 * B)) return 1;  // sq_part: one partial sum per source row, one per target row
+  TrainState &ts = *f.ts;
+  const int Bp = f.Bp;
+  if (reserve(h, h->s_feat, (size_t)((B + 31) / 32) * 72 * 256 * sizeof(float)) || reserve(h, ts.feat_rm, (size_t)Bp * 576 * sizeof(float)) ||
+      reserve(h, ts.pos, (size_t)Bp * 576 * sizeof(int32_t)) || reserve(h, ts.dfeat, (size_t)Bp * 576 * sizeof(float)) ||
+      reserve(h, ts.dw_part, cnn_dw_part_floats(E, B) * sizeof(float)) || reserve(h, ts.dbias_part, (size_t)cnn_bwd_chunks(B) * 576 * sizeof(float)) ||
+      reserve(h, ts.wt, (size_t)E * 1728 * sizeof(float)) || reserve(h, ts.wct, cnn_wct_elems(E) * sizeof(unsigned short)) ||
+      reserve(h, ts.hot_part[0], (size_t)std::max(B, cnn_dx_mfma_blocks(B)) * 2 * 64 * sizeof(float)) ||
+      reserve(h, ts.dm_part[0], (size_t)proj_bwd_chunks(Bp) * 576 * S * sizeof(float)))
+    return 1;
+  return cnn_forward(f) || step_table_forward(f) || step_loss(f) || cnn_backward(f) || step_table_backward(f) || step_finish(f);
+}
+
+// ---- The LSTM modes at shapes the fused training kernels are not laid out for (cell size > 256, embedding_size > 64): the same
 // step through lstm_generic.hip -- per-step GEMM + gate kernels, latency-bound but exact fp32 -- so that no reference flag
 // combination (sse_train.py:60-74) is rejected.  Same arena layout, same loss / projection-backward / optimizer kernels.
-static int train_grads_generic_locked(sse_handle *h, const int32_t *src_ids_host, const int32_t *tgt_ids_host,
-                                      const float *labels_host, int32_t B, int32_t T, int64_t rows_global) {
-  const sse_config &c = h->cfg;
-  const bool table_tgt = c.network_mode == SSE_MODE_SOURCE_ENCODER_ONLY;
-  const int nside = table_tgt ? 1 : 2;
-  const bool shared = c.network_mode == SSE_MODE_SHARED_ENCODER;
-  hipStream_t st = h->stream;
-  TrainState &ts = *h->train;
-  const int E = c.embedding_size, S = c.encoding_size, V = c.vocab_size;
-  if (ensure_arena(h)) return 1;
-  float *tail = ts.arena + grad_arena_count(h) - 4;
-  const float inv_rows = 1.0f / (float)rows_global;
-  const int Bp = round_up(B, 32);
-  const int32_t *ids_host[2] = {src_ids_host, tgt_ids_host};
-  for (int s = 0; s < 2; ++s) {
-    if (s == 1 && table_tgt) {
-      if (reserve(h, ts.ids[s], (size_t)B * sizeof(int32_t))) return 1;
-      HIPCHECK(h, hipMemcpyAsync(ts.ids[s].p, ids_host[s], (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    } else if (stage_ids(h, ts, s, ids_host[s], B, T, nullptr, st)) {
-      return 1;
-    }
+
+// forward of one encoder with tapes (un-normalised encodings; the loss kernel normalises)
+static int generic_forward_side(StepFrame &f, const GenLstmDims &d, int s) {
+  sse_handle *h = f.h;
+  TrainState &ts = *f.ts;
+  Encoder &e = h->enc[s];
+  const int S = f.S, V = h->cfg.vocab_size;
+  if (reserve(h, ts.gen_A[s], gen_lstm_a_floats(d) * sizeof(float)) || reserve(h, ts.gen_tape[s], gen_lstm_tape_floats(d) * sizeof(float)) ||
+      reserve(h, ts.gen_dG[s], gen_lstm_dg_floats(d) * sizeof(float)) || reserve(h, ts.gen_hl[s], (size_t)d.Bp * d.Hq * sizeof(float)) ||
+      reserve(h, ts.gen_KT[s], gen_lstm_kt_floats(d) * sizeof(float)) || reserve(h, ts.gen_Kq[s], gen_lstm_kt_floats(d) * sizeof(float)) ||
+      reserve(h, ts.gen_MT[s], (size_t)S * d.Hq * sizeof(float)))
+    return 1;
+  if (ts.gen_ver[s] != h->weights_version) {  // (every step changes the weights; repeated sse_train_grads calls on one set do not)
+    HIPCHECK(h, launch_gen_pack(h->vars[e.kernel].dev, h->vars[e.proj].dev, d, S, (float *)ts.gen_KT[s].p, (float *)ts.gen_Kq[s].p,
+                                (float *)ts.gen_MT[s].p, f.st));
+    ts.gen_ver[s] = h->weights_version;
   }
-  if (reserve(h, ts.labels, (size_t)B * sizeof(float))) return 1;
-  HIPCHECK(h, hipMemcpyAsync(ts.labels.p, labels_host, (size_t)B * sizeof(float), hipMemcpyHostToDevice, st));
-  Variable &emb = h->vars[0];
+  HIPCHECK(h, launch_gen_forward(f.ids(s), f.emb->dev, V, (const float *)ts.gen_KT[s].p, h->vars[e.bias].dev, d, (float *)ts.gen_A[s].p,
+                                 (float *)ts.gen_G.p, (float *)ts.gen_c.p, (float *)ts.gen_tape[s].p, (float *)ts.gen_hl[s].p,
+                                 h->err_flag, f.st));
+  HIPCHECK(h, launch_gen_project((const float *)ts.gen_hl[s].p, (const float *)ts.gen_MT[s].p, d, S, f.raw(s), f.st));
+  return 0;
+}
+
+static int generic_backward_side(StepFrame &f, const GenLstmDims &d, int s) {
+  sse_handle *h = f.h;
+  TrainState &ts = *f.ts;
+  Encoder &e = h->enc[s];
+  const bool shared = h->cfg.network_mode == SSE_MODE_SHARED_ENCODER;
+  if (reserve(h, ts.dh_last[s], (size_t)d.Bp * d.Hq * sizeof(float))) return 1;
+  if (reserve(h, ts.dm_part[s], (size_t)proj_bwd_chunks(d.Bp) * e.H * f.S * sizeof(float))) return 1;
+  HIPCHECK(h, launch_proj_bwd((const float *)ts.gen_hl[s].p, f.draw(s), h->vars[e.proj].dev, d.Bp, e.H, d.Hq, f.S, h->vars[e.proj].grad,
+                              (float *)ts.dh_last[s].p, (float *)ts.dm_part[s].p, f.st));
+  HIPCHECK(h, launch_gen_backward(f.ids(s), (const float *)ts.gen_Kq[s].p, d, (const float *)ts.gen_A[s].p,
+                                  (const float *)ts.gen_tape[s].p, (const float *)ts.dh_last[s].p, d.Hq, (float *)ts.gen_dG[s].p,
+                                  (float *)ts.gen_dA.p, (float *)ts.gen_dc.p, (float *)ts.gen_dkp.p, (shared && s == 1) ? 1 : 0,
+                                  h->vars[e.kernel].grad, h->vars[e.bias].grad, f.emb->grad, f.sq() + (size_t)s * f.T * f.B,
+                                  h->cfg.vocab_size, f.st));
+  return 0;
+}
+
+static int train_grads_generic_locked(sse_handle *h, const TrainCall &call) {
+  StepFrame f;
+  if (step_begin(h, call, 32, f)) return 1;
+  const int B = f.B, T = f.T, nside = f.nside;
+  // sq_part: one partial sum per (side, step, row), one per target row in source-encoder-only mode
+  if (step_stage_inputs(f, nullptr, nside * T * B + (f.table_tgt ? B : 0))) return 1;
+  TrainState &ts = *f.ts;
   GenLstmDims dims[2];
   size_t g_max = 0, c_max = 0, da_max = 0, dkp_max = 0;
   for (int s = 0; s < nside; ++s) {
-    dims[s] = gen_lstm_dims(B, T, E, h->enc[s].H);
+    dims[s] = gen_lstm_dims(B, T, h->cfg.embedding_size, h->enc[s].H);
     const GenLstmDims &d = dims[s];
     g_max = std::max(g_max, (size_t)d.Bp * 4 * d.Hq);
     c_max = std::max(c_max, (size_t)d.Bp * d.Hq);
@@ -3198,166 +3252,124 @@ static int train_grads_generic_locked(sse_handle *h, const int32_t *src_ids_host
       reserve(h, ts.gen_dA, da_max * sizeof(float)) || reserve(h, ts.gen_dc, c_max * sizeof(float)) ||
       reserve(h, ts.gen_dkp, dkp_max * sizeof(float)))
     return 1;
-  // ---- forward with tapes (un-normalised encodings; the loss kernel normalises)
-  for (int s = 0; s < 2; ++s) {
-    if (reserve(h, ts.raw[s], (size_t)Bp * S * sizeof(float))) return 1;
-    if (reserve(h, ts.draw[s], (size_t)Bp * S * sizeof(float))) return 1;
-  }
-  if (table_tgt) {
-    Variable &table = h->vars[h->tgt_table];
-    HIPCHECK(h, launch_rows_gather(table.dev, (const int32_t *)ts.ids[1].p, B, Bp, table.rows, S, (float *)ts.raw[1].p, h->err_flag, st));
-  }
-  for (int s = 0; s < nside; ++s) {
-    Encoder &e = h->enc[s];
-    const GenLstmDims &d = dims[s];
-    if (reserve(h, ts.gen_A[s], gen_lstm_a_floats(d) * sizeof(float)) || reserve(h, ts.gen_tape[s], gen_lstm_tape_floats(d) * sizeof(float)) ||
-        reserve(h, ts.gen_dG[s], gen_lstm_dg_floats(d) * sizeof(float)) || reserve(h, ts.gen_hl[s], (size_t)d.Bp * d.Hq * sizeof(float)) ||
-        reserve(h, ts.gen_KT[s], gen_lstm_kt_floats(d) * sizeof(float)) || reserve(h, ts.gen_Kq[s], gen_lstm_kt_floats(d) * sizeof(float)) ||
-        reserve(h, ts.gen_MT[s], (size_t)S * d.Hq * sizeof(float)))
-      return 1;
-    if (ts.gen_ver[s] != h->weights_version) {  // (every step changes the weights; repeated sse_train_grads calls on one set do not)
-      HIPCHECK(h, launch_gen_pack(h->vars[e.kernel].dev, h->vars[e.proj].dev, d, S, (float *)ts.gen_KT[s].p, (float *)ts.gen_Kq[s].p,
-                                  (float *)ts.gen_MT[s].p, st));
-      ts.gen_ver[s] = h->weights_version;
-    }
-    HIPCHECK(h, launch_gen_forward((const int32_t *)ts.ids[s].p, emb.dev, V, (const float *)ts.gen_KT[s].p, h->vars[e.bias].dev, d,
-                                   (float *)ts.gen_A[s].p, (float *)ts.gen_G.p, (float *)ts.gen_c.p, (float *)ts.gen_tape[s].p,
-                                   (float *)ts.gen_hl[s].p, h->err_flag, st));
-    HIPCHECK(h, launch_gen_project((const float *)ts.gen_hl[s].p, (const float *)ts.gen_MT[s].p, d, S, (float *)ts.raw[s].p, st));
-  }
-  // token ids / target rows out of range: gen_dx_scatter_kernel validates the ids itself, as rows_scatter_kernel and cnn_dx_kernel
-  // do, so the fused step (sse_train_step) reads the flag once with the loss and cancels its update on the device; sse_train_grads
-  // reads it now, as the other two paths do, so that a rank with a bad id fails here instead of only in its own sse_train_apply
-  if (!ts.defer_err && check_err_flag(h, st)) return 1;
-  // ---- loss, train accuracy, d(raw encodings)
-  if (reserve(h, ts.row_loss, (size_t)B * sizeof(float))) return 1;
-  if (reserve(h, ts.row_acc, (size_t)B * sizeof(float))) return 1;
-  HIPCHECK(h, launch_loss((const float *)ts.raw[0].p, (const float *)ts.raw[1].p, (const float *)ts.labels.p, (float *)ts.draw[0].p,
-                          (float *)ts.draw[1].p, (float *)ts.row_loss.p, (float *)ts.row_acc.p, tail + 1, B, Bp, S, inv_rows, st));
-  // ---- backward
-  HIPCHECK(h, hipMemsetAsync(emb.grad, 0, emb.count * sizeof(float), st));
-  const int n_sq = nside * T * B + (table_tgt ? B : 0);
-  if (reserve(h, ts.sq_part, (size_t)n_sq * sizeof(float))) return 1;
-  if (table_tgt) {
-    Variable &table = h->vars[h->tgt_table];
-    HIPCHECK(h, hipMemsetAsync(table.grad, 0, table.count * sizeof(float), st));
-    HIPCHECK(h, launch_rows_scatter((const float *)ts.draw[1].p, (const int32_t *)ts.ids[1].p, B, S, table.rows, table.grad,
-                                    (float *)ts.sq_part.p + (size_t)nside * T * B, st));
-  }
-  for (int s = 0; s < nside; ++s) {
-    Encoder &e = h->enc[s];
-    const GenLstmDims &d = dims[s];
-    if (reserve(h, ts.dh_last[s], (size_t)d.Bp * d.Hq * sizeof(float))) return 1;
-    if (reserve(h, ts.dm_part[s], (size_t)proj_bwd_chunks(d.Bp) * e.H * S * sizeof(float))) return 1;
-    HIPCHECK(h, launch_proj_bwd((const float *)ts.gen_hl[s].p, (const float *)ts.draw[s].p, h->vars[e.proj].dev, d.Bp, e.H, d.Hq, S,
-                                h->vars[e.proj].grad, (float *)ts.dh_last[s].p, (float *)ts.dm_part[s].p, st));
-    HIPCHECK(h, launch_gen_backward((const int32_t *)ts.ids[s].p, (const float *)ts.gen_Kq[s].p, d, (const float *)ts.gen_A[s].p,
-                                    (const float *)ts.gen_tape[s].p, (const float *)ts.dh_last[s].p, d.Hq, (float *)ts.gen_dG[s].p,
-                                    (float *)ts.gen_dA.p, (float *)ts.gen_dc.p, (float *)ts.gen_dkp.p, (shared && s == 1) ? 1 : 0,
-                                    h->vars[e.kernel].grad, h->vars[e.bias].grad, emb.grad, (float *)ts.sq_part.p + (size_t)s * T * B, V, st));
-  }
-  HIPCHECK(h, launch_sum((const float *)ts.sq_part.p, n_sq, (float)B, tail, st));
-  ts.grads_ready = true;
-  return 0;
+  if (step_table_forward(f)) return 1;
+  for (int s = 0; s < nside; ++s)
+    if (generic_forward_side(f, dims[s], s)) return 1;
+  if (step_loss(f) || step_table_backward(f)) return 1;
+  for (int s = 0; s < nside; ++s)
+    if (generic_backward_side(f, dims[s], s)) return 1;
+  return step_finish(f);
 }
 
-// Forward, loss and backward of one batch of pair rows; gradients are scaled by 1/rows_global and left in
-// the arena (with the tail sums), nothing is updated.
-static int train_grads_locked(sse_handle *h, const int32_t *src_ids_host, const int32_t *tgt_ids_host,
-                              const float *labels_host, int32_t B, int32_t T, int64_t rows_global) {
-  const sse_config &c = h->cfg;
-  if (B < 1 || T < 1 || !src_ids_host || !tgt_ids_host || !labels_host || rows_global < B)
-    return fail(h, "bad arguments to the train step");
-  if (!h->train) h->train = new TrainState();
-  if (c.network_mode == SSE_MODE_SOURCE_ONLY_CNN)
-    return cnn_train_grads_locked(h, src_ids_host, tgt_ids_host, labels_host, B, T, rows_global);
-  // source-encoder-only (BUILDER-DEFINED like the CNN mode: the reference's loss is ill-shaped there,
-  // sse_model.py:233,290): LSTM source encoder, target side = embedding_lookup(tgt_seq_embedding, rows);
-  // tgt_ids_host is int32 [B] rows of the free target matrix.  nside = sequence encoders in the step.
-  const bool table_tgt = c.network_mode == SSE_MODE_SOURCE_ENCODER_ONLY;
-  const int nside = table_tgt ? 1 : 2;
-  {
-    // shapes outside the fused training kernels (cell size > 256, embedding_size > 64; option train_generic forces it: tests)
-    bool generic = h->train_generic || c.embedding_size > 64;
-    for (int s = 0; s < nside; ++s) generic = generic || h->enc[s].Hp > 256 || h->enc[s].generic;
-    if (generic) return train_grads_generic_locked(h, src_ids_host, tgt_ids_host, labels_host, B, T, rows_global);
-  }
-  hipStream_t st = h->stream;
-  TrainState &ts = *h->train;
-  if (!ts.side[0]) {
-    // The two encoders of a step run side by side on these two streams.  Streams of ONE priority share the runtime's small pool
-    // of hardware queues, and in a process that has created and destroyed many streams both can land on the same queue: the
-    // encoders then run one after the other (the qna recipe, T = 1000: 26 ms / step alone, 52 inside the whole test suite, equal
-    // to option train_serial; profiles/r06_notes.txt).  Different priorities come from different queue pools.
-    int prio_least = 0, prio_greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    for (int s = 0; s < 2; ++s) {
-      HIPCHECK(h, hipStreamCreateWithPriority(&ts.side[s], hipStreamNonBlocking, s == 0 ? prio_least : prio_greatest));
-      HIPCHECK(h, hipEventCreateWithFlags(&ts.ev_join[s], hipEventDisableTiming));
-    }
-    HIPCHECK(h, hipEventCreateWithFlags(&ts.ev_fork, hipEventDisableTiming));
-  }
-  const int E = c.embedding_size, S = c.encoding_size, V = c.vocab_size;
-  const int Bp = round_up(B, 64), NT32 = Bp / 32;
-  const bool shared = c.network_mode == SSE_MODE_SHARED_ENCODER;
-  if (ensure_arena(h)) return 1;
-  float *tail = ts.arena + grad_arena_count(h) - 4;
-  const float inv_rows = 1.0f / (float)rows_global;
+// ---- the fused LSTM path
 
-  // which kernel families this step runs on split bf16 operands (options train_fwd_x3 / train_bwd_x3 / train_dk_x3)
-  bool fwd_x3[2] = {false, false}, bwd_x3[2] = {false, false};
-  bool all_x3 = true;
-  for (int s = 0; s < nside; ++s) {
+// do the rows 2i and 2i + 1 of the source side carry the same sequence (by_rows: the same corpus row) for every i?  B even.
+static bool batch_is_paired(const int32_t *src, int B, int T, bool by_rows) {
+  for (int i = 0; i < B; i += 2) {
+    if (by_rows ? src[i] != src[i + 1]
+                : memcmp(src + (size_t)i * T, src + (size_t)(i + 1) * T, (size_t)T * sizeof(int32_t)) != 0)
+      return false;
+  }
+  return true;
+}
+
+static FusedPlan fused_plan(const StepFrame &f) {
+  sse_handle *h = f.h;
+  const int E = h->cfg.embedding_size, V = h->cfg.vocab_size;
+  FusedPlan p = {};
+  p.all_x3 = true;
+  for (int s = 0; s < f.nside; ++s) {
     const Encoder &e = h->enc[s];
-    fwd_x3[s] = h->train_fwd_x3 && h->train_dk_x3 && e.Hp <= 256 && e.H >= 64 && E < 64;
+    p.fwd_x3[s] = h->train_fwd_x3 && h->train_dk_x3 && e.Hp <= 256 && e.H >= 64 && E < 64;
     // (the in-kernel dX scatter addresses the dense embedding gradient through a 32-bit buffer descriptor: tables of
     // 2 GiB and more keep the fp32 dx kernel with its 64-bit pointers)
-    bwd_x3[s] = h->train_bwd_x3 && h->train_dk_x3 && e.H >= 64 && e.Hp <= 256 && (int64_t)V * E * 4 < ((int64_t)1 << 31);
-    all_x3 = all_x3 && fwd_x3[s] && bwd_x3[s];
+    p.bwd_x3[s] = h->train_bwd_x3 && h->train_dk_x3 && e.H >= 64 && e.Hp <= 256 && (int64_t)V * E * 4 < ((int64_t)1 << 31);
+    p.all_x3 = p.all_x3 && p.fwd_x3[s] && p.bwd_x3[s];
+    p.any_bwd_x3 = p.any_bwd_x3 || p.bwd_x3[s];
   }
   // Pure fp32 step (the default): second-generation kernels -- the forward in the inference orientation with register-built
   // tapes (lstm_fwd_kernel<.., TSW>), lstm_bwd2_kernel (dX inside, dG for the weight gradient straight from registers, no
   // A-operand dG copy in HBM), d(bias) as row E of the weight-gradient GEMM.  Any split-operand option, an embedding of 64
   // columns (no room for the constant-1 column in the 64-column x part of the A-tape) or a >= 2 GiB embedding table (32-bit
   // scatter offsets) keeps the first-generation kernels.
-  const bool bwd2 = !h->train_fwd_x3 && !h->train_bwd_x3 && !h->train_dk_x3 && !h->train_gen1 && E < 64 &&
-                    (int64_t)V * E * 4 < ((int64_t)1 << 31);
-  // layouts derived from the variables, rebuilt after every update: only the ones this step's kernels read (an all-split
-  // step needs the projections, Kh^T / Kx^T in split form and -- below -- the split kernel matrix and embedding table;
-  // the fp32 fragment copies wait for the next encode or fp32 step: 7 fewer launches on the critical path of a step)
-  if (bwd2 ? pack_train_fp32(h, ts, nside, st) : all_x3 ? ensure_proj_packed(h, st) : ensure_packed(h, st)) return 1;
-  bool any_bwd_x3 = false;
-  for (int s = 0; s < nside; ++s) any_bwd_x3 = any_bwd_x3 || bwd_x3[s];
-  // (the split Kh^T / Kx^T copies are only rebuilt by steps that run the split-operand BPTT: a pure fp32 step leaves them stale)
-  if ((any_bwd_x3 && ts.packed_dirty) || (!all_x3 && ts.fp32_dirty)) {
-    for (int s = 0; s < nside; ++s) {
-      Encoder &e = h->enc[s];
-      if (e.shares_lstm_with >= 0) {
-        ts.KhT[s] = ts.KhT[e.shares_lstm_with];
-        ts.KxT[s] = ts.KxT[e.shares_lstm_with];
-        ts.KhT16[s] = ts.KhT16[e.shares_lstm_with];
-        ts.KxT16[s] = ts.KxT16[e.shares_lstm_with];
-        continue;
-      }
-      if (any_bwd_x3 && ts.packed_dirty) {
-        if (!ts.KhT16[s]) HIPCHECK(h, hipMalloc((void **)&ts.KhT16[s], kT16_elems(e.Hp) * sizeof(unsigned short)));
-        HIPCHECK(h, launch_pack_kT16(h->vars[e.kernel].dev, E, e.H, e.Hp, ts.KhT16[s], st));
-        if (!ts.KxT16[s]) HIPCHECK(h, hipMalloc((void **)&ts.KxT16[s], kxT16_elems(e.Hp) * sizeof(unsigned short)));
-        HIPCHECK(h, launch_pack_kxT16(h->vars[e.kernel].dev, E, e.H, e.Hp, ts.KxT16[s], st));
-      }
-      if (!all_x3) {
-        if (!ts.KhT[s]) HIPCHECK(h, hipMalloc((void **)&ts.KhT[s], (size_t)(e.Hp / 32) * (e.Hp / 2) * 256 * sizeof(float)));
-        if (!ts.KxT[s]) HIPCHECK(h, hipMalloc((void **)&ts.KxT[s], (size_t)2 * (e.Hp / 2) * 256 * sizeof(float)));
-        HIPCHECK(h, launch_pack_kT(h->vars[e.kernel].dev, E, e.H, e.Hp / 32, e.H, e.Hp, ts.KhT[s], st));
-        HIPCHECK(h, launch_pack_kT(h->vars[e.kernel].dev, 0, E, 2, e.H, e.Hp, ts.KxT[s], st));
-      }
-    }
-    if (!all_x3) ts.fp32_dirty = false;
-    if (any_bwd_x3) ts.packed_dirty = false;
+  p.bwd2 = !h->train_fwd_x3 && !h->train_bwd_x3 && !h->train_dk_x3 && !h->train_gen1 && E < 64 &&
+           (int64_t)V * E * 4 < ((int64_t)1 << 31);
+  // Paired batch (data.py:95-115 builds every batch this way: source row 2i and 2i+1 are the same sequence, once with
+  // its positive and once with a sampled negative target): the rows are taken in the order [0,2,4,.. | 1,3,5,..], the
+  // source encoder runs on the first half only, and its tapes serve both halves of the backward pass.  The backward
+  // itself stays per row: clip_by_global_norm sees the two rows' embedding slices separately (sse_model.py:359-362).
+  p.paired = h->train_pair_dedup && f.B % 128 == 0 &&  // both halves whole 64-row tiles
+             batch_is_paired(f.call->src, f.B, f.T, f.call->by_rows);
+  p.NT32 = f.Bp / 32;
+  p.NT_half = p.NT32 / 2;
+  // partial sums of dx^2 per side: one per (tile, wave) when dX comes out of the split-operand BPTT kernel, one per
+  // (step, tile) from dx_kernel (+ one per target row in source-encoder-only mode)
+  for (int s = 0; s < f.nside; ++s)
+    p.sq_off[s + 1] = p.sq_off[s] + (p.bwd2 ? dx_scatter_blocks(f.T, p.NT32 * 32) : p.bwd_x3[s] ? p.NT32 * (h->enc[s].Hp / 32) : f.T * p.NT32);
+  p.n_sq = p.sq_off[f.nside] + (f.table_tgt ? f.B : 0);
+  return p;
+}
+
+static int ensure_side_streams(sse_handle *h, TrainState &ts) {
+  if (ts.side[0]) return 0;
+  // The two encoders of a step run side by side on these two streams.  Streams of ONE priority share the runtime's small pool
+  // of hardware queues, and in a process that has created and destroyed many streams both can land on the same queue: the
+  // encoders then run one after the other (the qna recipe, T = 1000: 26 ms / step alone, 52 inside the whole test suite, equal
+  // to option train_serial; profiles/r06_notes.txt).  Different priorities come from different queue pools.
+  int prio_least = 0, prio_greatest = 0;
+  (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
+  for (int s = 0; s < 2; ++s) {
+    HIPCHECK(h, hipStreamCreateWithPriority(&ts.side[s], hipStreamNonBlocking, s == 0 ? prio_least : prio_greatest));
+    HIPCHECK(h, hipEventCreateWithFlags(&ts.ev_join[s], hipEventDisableTiming));
   }
-  for (int s = 0; s < nside; ++s) {
-    // the BPTT kernels address the gate tape [T][rows/32][Hp/32][5][1024] floats through 32-bit offsets (both generations)
-    const size_t tape_bytes = (size_t)T * NT32 * (h->enc[s].Hp / 32) * 5 * 1024 * sizeof(float);
+  HIPCHECK(h, hipEventCreateWithFlags(&ts.ev_fork, hipEventDisableTiming));
+  return 0;
+}
+
+// layouts derived from the variables, rebuilt after every update: only the ones this step's kernels read (an all-split
+// step needs the projections, Kh^T / Kx^T in split form and -- fused_pack_split_inputs -- the split kernel matrix and embedding
+// table; the fp32 fragment copies wait for the next encode or fp32 step: 7 fewer launches on the critical path of a step)
+static int fused_refresh_layouts(StepFrame &f, const FusedPlan &p) {
+  sse_handle *h = f.h;
+  TrainState &ts = *f.ts;
+  hipStream_t st = f.st;
+  const int E = h->cfg.embedding_size;
+  if (p.bwd2 ? pack_train_fp32(h, ts, f.nside, st) : p.all_x3 ? ensure_proj_packed(h, st) : ensure_packed(h, st)) return 1;
+  // (the split Kh^T / Kx^T copies are only rebuilt by steps that run the split-operand BPTT: a pure fp32 step leaves them stale)
+  if (!((p.any_bwd_x3 && ts.packed_dirty) || (!p.all_x3 && ts.fp32_dirty))) return 0;
+  for (int s = 0; s < f.nside; ++s) {
+    Encoder &e = h->enc[s];
+    if (e.shares_lstm_with >= 0) {
+      ts.KhT[s] = ts.KhT[e.shares_lstm_with];
+      ts.KxT[s] = ts.KxT[e.shares_lstm_with];
+      ts.KhT16[s] = ts.KhT16[e.shares_lstm_with];
+      ts.KxT16[s] = ts.KxT16[e.shares_lstm_with];
+      continue;
+    }
+    if (p.any_bwd_x3 && ts.packed_dirty) {
+      if (!ts.KhT16[s]) HIPCHECK(h, hipMalloc((void **)&ts.KhT16[s], kT16_elems(e.Hp) * sizeof(unsigned short)));
+      HIPCHECK(h, launch_pack_kT16(h->vars[e.kernel].dev, E, e.H, e.Hp, ts.KhT16[s], st));
+      if (!ts.KxT16[s]) HIPCHECK(h, hipMalloc((void **)&ts.KxT16[s], kxT16_elems(e.Hp) * sizeof(unsigned short)));
+      HIPCHECK(h, launch_pack_kxT16(h->vars[e.kernel].dev, E, e.H, e.Hp, ts.KxT16[s], st));
+    }
+    if (!p.all_x3) {
+      if (!ts.KhT[s]) HIPCHECK(h, hipMalloc((void **)&ts.KhT[s], (size_t)(e.Hp / 32) * (e.Hp / 2) * 256 * sizeof(float)));
+      if (!ts.KxT[s]) HIPCHECK(h, hipMalloc((void **)&ts.KxT[s], (size_t)2 * (e.Hp / 2) * 256 * sizeof(float)));
+      HIPCHECK(h, launch_pack_kT(h->vars[e.kernel].dev, E, e.H, e.Hp / 32, e.H, e.Hp, ts.KhT[s], st));
+      HIPCHECK(h, launch_pack_kT(h->vars[e.kernel].dev, 0, E, 2, e.H, e.Hp, ts.KxT[s], st));
+    }
+  }
+  if (!p.all_x3) ts.fp32_dirty = false;
+  if (p.any_bwd_x3) ts.packed_dirty = false;
+  return 0;
+}
+
+// the BPTT kernels address the gate tape [T][rows/32][Hp/32][5][1024] floats through 32-bit offsets (both generations)
+static int fused_check_tape(StepFrame &f, const FusedPlan &p) {
+  sse_handle *h = f.h;
+  const int B = f.B, T = f.T;
+  for (int s = 0; s < f.nside; ++s) {
+    const size_t tape_bytes = (size_t)T * p.NT32 * (h->enc[s].Hp / 32) * 5 * 1024 * sizeof(float);
     if (tape_bytes >= ((size_t)1 << 31))
       return fail(h, "train step: batch x T x H too large -- %d rows x %d steps x cell size %d need a %.2f GiB gate tape per encoder, "
                      "the limit is 2 GiB (<= %lld rows at this T and cell size): use a smaller batch, or sse_train_grads per micro-batch with "
@@ -3365,251 +3377,248 @@ static int train_grads_locked(sse_handle *h, const int32_t *src_ids_host, const 
                   B, T, h->enc[s].H, (double)tape_bytes / (double)((size_t)1 << 30),
                   (long long)(((((size_t)1 << 31) - 1) / ((size_t)T * (h->enc[s].Hp / 32) * 5 * 1024 * sizeof(float))) * 32 / 64 * 64));
   }
-
-  // ---- inputs
-  // Paired batch (data.py:95-115 builds every batch this way: source row 2i and 2i+1 are the same sequence, once with
-  // its positive and once with a sampled negative target): the rows are taken in the order [0,2,4,.. | 1,3,5,..], the
-  // source encoder runs on the first half only, and its tapes serve both halves of the backward pass.  The backward
-  // itself stays per row: clip_by_global_norm sees the two rows' embedding slices separately (sse_model.py:359-362).
-  bool paired = h->train_pair_dedup && B % 128 == 0;  // both halves whole 64-row tiles
-  if (paired) {
-    if (ts.rows_mode) {
-      for (int i = 0; i < B && paired; i += 2) paired = src_ids_host[i] == src_ids_host[i + 1];
-    } else {
-      for (int i = 0; i < B && paired; i += 2)
-        paired = memcmp(src_ids_host + (size_t)i * T, src_ids_host + (size_t)(i + 1) * T, (size_t)T * sizeof(int32_t)) == 0;
-    }
-  }
-  const int32_t *perm = nullptr;
-  if (paired) {
-    if ((int)ts.h_perm.size() != B) {
-      ts.h_perm.resize(B);
-      for (int r = 0; r < B / 2; ++r) {
-        ts.h_perm[r] = 2 * r;
-        ts.h_perm[B / 2 + r] = 2 * r + 1;
-      }
-      ts.perm_B = 0;
-    }
-    perm = ts.h_perm.data();
-    if (ts.perm_B != B) {
-      if (reserve(h, ts.perm, (size_t)B * sizeof(int32_t))) return 1;
-      HIPCHECK(h, hipMemcpyAsync(ts.perm.p, perm, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      ts.perm_B = B;
-    }
-    ts.h_labels.resize(B);
-    for (int r = 0; r < B; ++r) ts.h_labels[r] = labels_host[perm[r]];
-    labels_host = ts.h_labels.data();
-  }
-  const int32_t *ids_host[2] = {src_ids_host, tgt_ids_host};
-  for (int s = 0; s < 2; ++s) {
-    if (s == 1 && table_tgt) {  // rows of the free target matrix
-      if (reserve(h, ts.ids[s], (size_t)B * sizeof(int32_t))) return 1;
-      const int32_t *src = ids_host[s];
-      if (perm) {
-        ts.h_tgt.resize(B);
-        for (int r = 0; r < B; ++r) ts.h_tgt[r] = src[perm[r]];
-        src = ts.h_tgt.data();
-      }
-      HIPCHECK(h, hipMemcpyAsync(ts.ids[s].p, src, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    } else if (stage_ids(h, ts, s, ids_host[s], B, T, perm, st)) {
-      return 1;
-    }
-  }
-  if (reserve(h, ts.labels, (size_t)B * sizeof(float))) return 1;
-  HIPCHECK(h, hipMemcpyAsync(ts.labels.p, labels_host, (size_t)B * sizeof(float), hipMemcpyHostToDevice, st));
-  const int NT_half = NT32 / 2;  // paired: 32-row tiles of one half (B % 128 == 0: Bp = B, NT_half even)
-
-  if (h->train_fwd_x3 && h->train_dk_x3 && E < 64) {  // split embedding table of this step's weights (both encoders read it)
-    if (!h->emb16) HIPCHECK(h, hipMalloc((void **)&h->emb16, lstm_x3_emb_elems(V, E) * sizeof(unsigned short)));
-    Encoder &e0 = h->enc[0];
-    if (!e0.Wx3t) HIPCHECK(h, hipMalloc((void **)&e0.Wx3t, lstm_x3_weight_elems(E, e0.Hp) * sizeof(unsigned short)));
-    HIPCHECK(h, launch_pack_lstm_x3(h->vars[e0.kernel].dev, h->vars[e0.bias].dev, h->vars[0].dev, V, E, e0.H, e0.Hp, e0.Wx3t,
-                                    h->emb16, 1, st));
-    h->emb16_valid = true;  // (ensure_packed above cleared it: the table matches the current weights again)
-  }
-  // ---- forward with tapes (un-normalised encodings; the loss kernel normalises); the two
-  // encoders are independent: fork onto two side streams, join before the loss
-  HIPCHECK(h, hipEventRecord(ts.ev_fork, st));
-  if (table_tgt) {
-    Variable &table = h->vars[h->tgt_table];
-    if (reserve(h, ts.raw[1], (size_t)Bp * S * sizeof(float))) return 1;
-    if (reserve(h, ts.draw[1], (size_t)Bp * S * sizeof(float))) return 1;
-    HIPCHECK(h, launch_rows_gather(table.dev, (const int32_t *)ts.ids[1].p, B, Bp, table.rows, S, (float *)ts.raw[1].p,
-                                   h->err_flag, st));
-  }
-  for (int s = 0; s < nside; ++s) {
-    hipStream_t fs = h->train_serial ? ts.side[0] : ts.side[s];
-    HIPCHECK(h, hipStreamWaitEvent(fs, ts.ev_fork, 0));
-    Encoder &e = h->enc[s];
-    const int KT = 2 + e.Hp / 32;
-    if (reserve(h, ts.raw[s], (size_t)Bp * S * sizeof(float))) return 1;
-    if (reserve(h, ts.draw[s], (size_t)Bp * S * sizeof(float))) return 1;
-    const bool half = paired && s == 0;  // the source encoder of a paired batch: first half of the rows only
-    const int NTf = half ? NT_half : NT32, Bf = half ? B / 2 : B;
-    if (reserve(h, ts.tape_g[s], (size_t)T * NTf * 4 * e.UB * 5 * 1024 * sizeof(float))) return 1;
-    if (reserve(h, ts.tape_a[s], (size_t)T * NTf * 4 * KT * 256 * sizeof(float))) return 1;
-    if (reserve(h, ts.h_last[s], (size_t)Bp * e.Hp * sizeof(float))) return 1;
-    LstmFwdArgs a;
-    a.ids = (const int32_t *)ts.ids[s].p;
-    a.emb = h->emb_pad;
-    a.Wp = e.Wp;
-      a.Mp = e.Mp;
-    a.out = (float *)ts.raw[s].p;
-    a.err = h->err_flag;
-    a.B = Bf;
-    a.T = T;
-    a.V = V;
-    a.Ep = e.Ep;
-    a.KGx = e.KGx;
-    a.KGh = e.KGh;
-    a.KGhe = (e.H + 7) / 8;
-    a.S = S;
-    a.NTS = (S + 31) / 32;
-    a.normalize = 0;
-    a.NT32 = NTf;
-    a.tiles_elsewhere = (nside == 2 && !h->train_serial) ? ((paired && s == 1) ? NT_half : NT32) : 0;  // the other encoder's forward runs beside this one
-    a.force_rows = h->lstm_train_rows;
-    a.tape_g = (float *)ts.tape_g[s].p;
-    a.tape_a = (float *)ts.tape_a[s].p;
-    a.tape_a_split = h->train_dk_x3 ? 1 : 0;
-    a.tape_swap = bwd2 ? 1 : 0;
-    a.h_last = (float *)ts.h_last[s].p;
-    if (fwd_x3[s]) {
-      // the gate GEMMs as three bf16 MFMAs on hi + lo split operands (lstm_fwd_x3.hip, TRAIN): same tapes, same outputs
-      Encoder &own = lstm_owner(h, e);
-      if (e.shares_lstm_with < 0 && s != 0) {  // (side 0 was packed ahead of the fork together with the embedding table)
-        if (!own.Wx3t) HIPCHECK(h, hipMalloc((void **)&own.Wx3t, lstm_x3_weight_elems(E, own.Hp) * sizeof(unsigned short)));
-        if (!h->emb16) HIPCHECK(h, hipMalloc((void **)&h->emb16, lstm_x3_emb_elems(V, E) * sizeof(unsigned short)));
-        // both depend on the weights of this step: repacked on the launch stream (the other side's stream waits for
-        // ev_fork, recorded before; the split embedding table is shared, so it is made on `st` ahead of the fork)
-        HIPCHECK(h, launch_pack_lstm_x3(h->vars[own.kernel].dev, h->vars[own.bias].dev, h->vars[0].dev, V, E, own.H, own.Hp,
-                                        own.Wx3t, nullptr, 1, fs));
-      }
-      LstmX3Args xa;
-      xa.ids = a.ids;
-      xa.emb16 = h->emb16;
-      xa.Wx3 = own.Wx3t;
-      xa.Mp = e.Mp;
-      xa.out = a.out;
-      xa.err = h->err_flag;
-      xa.B = Bf;
-      xa.T = T;
-      xa.V = V;
-      xa.KGX = lstm_x3_kgx(E);
-      xa.H = e.H;
-      xa.S = S;
-      xa.NTS = (S + 31) / 32;
-      xa.normalize = 0;
-      xa.tape_g = a.tape_g;
-      xa.tape_a = a.tape_a;
-      xa.h_last = a.h_last;
-      xa.NT32 = NTf;
-      xa.tiles_elsewhere = a.tiles_elsewhere;
-      HIPCHECK(h, launch_lstm_fwd_x3(xa, fs));
-    } else {
-      HIPCHECK(h, launch_lstm_fwd(a, e.Hp, fs));
-    }
-    if (half) {  // rows B/2 .. B-1 are the same sequences: the loss and the projection backward read them per row
-      HIPCHECK(h, hipMemcpyAsync((float *)ts.raw[s].p + (size_t)Bf * S, ts.raw[s].p, (size_t)Bf * S * sizeof(float),
-                                 hipMemcpyDeviceToDevice, fs));
-      HIPCHECK(h, hipMemcpyAsync((float *)ts.h_last[s].p + (size_t)Bf * e.Hp, ts.h_last[s].p, (size_t)Bf * e.Hp * sizeof(float),
-                                 hipMemcpyDeviceToDevice, fs));
-    }
-    HIPCHECK(h, hipEventRecord(ts.ev_join[s], fs));
-    HIPCHECK(h, hipStreamWaitEvent(st, ts.ev_join[s], 0));
-  }
-  // token ids / corpus rows out of range: the sequence-encoder backward kernels validate every id themselves, so the fused
-  // step reads the flag once at its end (train_apply_locked; a flagged step cancels its own update on the device) instead
-  // of stalling the queue here; the free-target-matrix scatter trusts its rows: checked now
-  if (!ts.defer_err && check_err_flag(h, st)) return 1;  // (rows_scatter validates the target rows itself since round 5)
-
-  // ---- loss, train accuracy, d(raw encodings)
-  if (reserve(h, ts.row_loss, (size_t)B * sizeof(float))) return 1;
-  if (reserve(h, ts.row_acc, (size_t)B * sizeof(float))) return 1;
-  HIPCHECK(h, launch_loss((const float *)ts.raw[0].p, (const float *)ts.raw[1].p, (const float *)ts.labels.p,
-                          (float *)ts.draw[0].p, (float *)ts.draw[1].p, (float *)ts.row_loss.p, (float *)ts.row_acc.p,
-                          tail + 1, B, Bp, S, inv_rows, st));
-
-  // ---- backward
-  Variable &emb = h->vars[0];
-  HIPCHECK(h, hipMemsetAsync(emb.grad, 0, emb.count * sizeof(float), st));
-  // partial sums of dx^2 per side: one per (tile, wave) when dX comes out of the split-operand BPTT kernel, one per
-  // (step, tile) from dx_kernel (+ one per target row in source-encoder-only mode)
-  int sq_off[3] = {0, 0, 0};
-  for (int s = 0; s < nside; ++s)
-    sq_off[s + 1] = sq_off[s] + (bwd2 ? dx_scatter_blocks(T, NT32 * 32) : bwd_x3[s] ? NT32 * (h->enc[s].Hp / 32) : T * NT32);
-  const int n_sq = sq_off[nside] + (table_tgt ? B : 0);
-  if (reserve(h, ts.sq_part, (size_t)n_sq * sizeof(float))) return 1;
-  if (table_tgt) {
-    Variable &table = h->vars[h->tgt_table];
-    HIPCHECK(h, hipMemsetAsync(table.grad, 0, table.count * sizeof(float), st));
-    HIPCHECK(h, launch_rows_scatter((const float *)ts.draw[1].p, (const int32_t *)ts.ids[1].p, B, S, table.rows, table.grad,
-                                    (float *)ts.sq_part.p + sq_off[1], st));
-  }
-  HIPCHECK(h, hipEventRecord(ts.ev_fork, st));  // loss + zeroed embedding gradient are ready
-  for (int s = 0; s < nside; ++s) {
-    Encoder &e = h->enc[s];
-    const bool half = paired && s == 0;
-    const int Hp = e.Hp, KGn = Hp / 2, NTn = Hp / 8, KT = 2 + Hp / 32, RG = T * NT32 * 4;
-    const int RGa = half ? RG / 2 : RG;  // r-groups of tape_a: the dK GEMM adds the two halves' dG fragments
-    const int SL = dk_slices(RGa);
-    // dual-encoder: the two backward chains are independent -> side streams; shared-encoder: the
-    // target side accumulates onto the source side's kernel/bias gradient -> one stream, in order
-    hipStream_t bs = (shared || h->train_serial) ? ts.side[0] : ts.side[s];
-    if (!shared || s == 0) HIPCHECK(h, hipStreamWaitEvent(bs, ts.ev_fork, 0));
-    if (reserve(h, ts.dh_last[s], (size_t)Bp * Hp * sizeof(float))) return 1;
-    if (!bwd_x3[s] && !bwd2 && reserve(h, ts.dg_a[s], (size_t)T * NT32 * KGn * 256 * sizeof(float))) return 1;
-    if (reserve(h, ts.hot_part[s], (size_t)std::max(T * NT32 * 2, dx_scatter_blocks(T, NT32 * 32)) * 2 * 64 * sizeof(float))) return 1;
-    if (bwd2 && reserve(h, ts.dg_a[s], (size_t)T * NT32 * 32 * 64 * sizeof(float))) return 1;  // (second generation: the dX rows)
-    BwdDxArgs bdx{ts.KxT16[s], (const int32_t *)ts.ids[s].p, emb.grad, (float *)ts.sq_part.p + sq_off[s], (float *)ts.hot_part[s].p,
-                  B, E, V};
-    if (reserve(h, ts.dg_b[s], (size_t)RG * NTn * 256 * sizeof(float))) return 1;
-    if (reserve(h, ts.db_part[s], (size_t)NT32 * 4 * Hp * sizeof(float))) return 1;
-    if (reserve(h, ts.dk_part[s], (size_t)SL * KT * 32 * NTn * 32 * sizeof(float))) return 1;
-    if (reserve(h, ts.dm_part[s], (size_t)proj_bwd_chunks(Bp) * e.H * S * sizeof(float))) return 1;
-    HIPCHECK(h, launch_proj_bwd((const float *)ts.h_last[s].p, (const float *)ts.draw[s].p, h->vars[e.proj].dev, Bp, e.H, Hp,
-                                S, h->vars[e.proj].grad, (float *)ts.dh_last[s].p, (float *)ts.dm_part[s].p, bs));
-    if (bwd2) {
-      HIPCHECK(h, launch_lstm_bwd2((const float *)ts.tape_g[s].p, (const float *)ts.dh_last[s].p, ts.KhT[s], ts.KxT[s],
-                                   (float *)ts.dg_b[s].p, (float *)ts.dg_a[s].p, (const int32_t *)ts.ids[s].p, emb.grad,
-                                   (float *)ts.sq_part.p + sq_off[s], (float *)ts.hot_part[s].p, T, NT32, half ? NT_half : NT32, Hp,
-                                   e.H, B, E, V, bs));
-      const int acc2 = (shared && s == 1) ? 1 : 0;
-      HIPCHECK(h, launch_dk((const float *)ts.tape_a[s].p, (const float *)ts.dg_b[s].p, (float *)ts.dk_part[s].p, RGa, KT, NTn, SL,
-                            E, e.H, Hp, acc2, h->vars[e.kernel].grad, half ? NT_half * 4 : 0, bs, h->vars[e.bias].grad));
-      HIPCHECK(h, launch_dx_hot_reduce((const float *)ts.hot_part[s].p, dx_scatter_blocks(T, NT32 * 32), E, V, emb.grad, bs));
-      if (!shared || s == 1) {
-        HIPCHECK(h, hipEventRecord(ts.ev_join[s], bs));
-        HIPCHECK(h, hipStreamWaitEvent(st, ts.ev_join[s], 0));
-      }
-      continue;
-    }
-    HIPCHECK(h, launch_lstm_bwd((const float *)ts.tape_g[s].p, (const float *)ts.dh_last[s].p, ts.KhT[s],
-                                (float *)ts.dg_a[s].p, (float *)ts.dg_b[s].p, (float *)ts.db_part[s].p, T, NT32,
-                                half ? NT_half : NT32, Hp, e.H, h->train_dk_x3 ? 1 : 0, bwd_x3[s] ? ts.KhT16[s] : nullptr, &bdx, bs));
-    const int accumulate = (shared && s == 1) ? 1 : 0;
-    if (h->train_dk_x3)  // the 8-row r-groups of the fp32 layout pair up into 16-row groups: the same bytes
-      HIPCHECK(h, launch_dk_x3(ts.tape_a[s].p, ts.dg_b[s].p, (float *)ts.dk_part[s].p, RGa / 2, KT, NTn, SL, E, e.H, Hp, accumulate,
-                               h->vars[e.kernel].grad, half ? NT_half * 2 : 0, bs));
-    else
-      HIPCHECK(h, launch_dk((const float *)ts.tape_a[s].p, (const float *)ts.dg_b[s].p, (float *)ts.dk_part[s].p, RGa, KT, NTn, SL,
-                            E, e.H, Hp, accumulate, h->vars[e.kernel].grad, half ? NT_half * 4 : 0, bs));
-    HIPCHECK(h, launch_db_reduce((const float *)ts.db_part[s].p, NT32, e.H, Hp, accumulate, h->vars[e.bias].grad, bs));
-    if (bwd_x3[s])  // dX left the BPTT kernel already; only the PAD / EOS rows are still to be added
-      HIPCHECK(h, launch_dx_hot_reduce((const float *)ts.hot_part[s].p, T * NT32 * 2, E, V, emb.grad, bs));
-    else
-      HIPCHECK(h, launch_dx((const float *)ts.dg_a[s].p, ts.KxT[s], (const int32_t *)ts.ids[s].p, emb.grad,
-                            (float *)ts.sq_part.p + sq_off[s], (float *)ts.hot_part[s].p, T, NT32, KGn, B, E, V, e.H, bs));
-    if (!shared || s == 1) {
-      HIPCHECK(h, hipEventRecord(ts.ev_join[s], bs));
-      HIPCHECK(h, hipStreamWaitEvent(st, ts.ev_join[s], 0));
-    }
-  }
-
-  // tail[0] = sum of squares of the raw (un-deduplicated) embedding-gradient slices, tail[3] = rows
-  HIPCHECK(h, launch_sum((const float *)ts.sq_part.p, n_sq, (float)B, tail, st));
-  ts.grads_ready = true;
   return 0;
+}
+
+// the internal row order of a paired batch, [rows 0,2,4,.. | rows 1,3,5,..], on the host (the result) and on the device (ts.perm)
+static int pair_permutation(StepFrame &f, const int32_t **perm) {
+  TrainState &ts = *f.ts;
+  const int B = f.B;
+  if ((int)ts.h_perm.size() != B) {
+    ts.h_perm.resize(B);
+    for (int r = 0; r < B / 2; ++r) {
+      ts.h_perm[r] = 2 * r;
+      ts.h_perm[B / 2 + r] = 2 * r + 1;
+    }
+    ts.perm_B = 0;
+  }
+  *perm = ts.h_perm.data();
+  if (ts.perm_B != B) {
+    if (reserve(f.h, ts.perm, (size_t)B * sizeof(int32_t))) return 1;
+    HIPCHECK(f.h, hipMemcpyAsync(ts.perm.p, *perm, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, f.st));
+    ts.perm_B = B;
+  }
+  return 0;
+}
+
+// options train_fwd_x3 + train_dk_x3: the split embedding table of this step's weights (both encoders read it) and the
+// source encoder's split kernel matrix, on the main stream ahead of the fork
+static int fused_pack_split_inputs(StepFrame &f) {
+  sse_handle *h = f.h;
+  const int E = h->cfg.embedding_size, V = h->cfg.vocab_size;
+  if (!(h->train_fwd_x3 && h->train_dk_x3 && E < 64)) return 0;
+  if (!h->emb16) HIPCHECK(h, hipMalloc((void **)&h->emb16, lstm_x3_emb_elems(V, E) * sizeof(unsigned short)));
+  Encoder &e0 = h->enc[0];
+  if (!e0.Wx3t) HIPCHECK(h, hipMalloc((void **)&e0.Wx3t, lstm_x3_weight_elems(E, e0.Hp) * sizeof(unsigned short)));
+  HIPCHECK(h, launch_pack_lstm_x3(h->vars[e0.kernel].dev, h->vars[e0.bias].dev, h->vars[0].dev, V, E, e0.H, e0.Hp, e0.Wx3t,
+                                  h->emb16, 1, f.st));
+  h->emb16_valid = true;  // (ensure_packed, in fused_refresh_layouts, cleared it: the table matches the current weights again)
+  return 0;
+}
+
+// the matrix kernel's arguments for the training forward of encoder s over NTf 32-row tiles (Bf rows).  Not fill_fwd_args:
+// that also sets H, gate_split and cu_count, which the training forward leaves at their defaults.
+static void fill_train_fwd_args(const StepFrame &f, const FusedPlan &p, int s, int Bf, int NTf, LstmFwdArgs &a) {
+  sse_handle *h = f.h;
+  TrainState &ts = *f.ts;
+  const Encoder &e = h->enc[s];
+  // inputs and output
+  a.ids = f.ids(s);  a.emb = h->emb_pad;  a.Wp = e.Wp;  a.Mp = e.Mp;  a.out = f.raw(s);  a.err = h->err_flag;
+  // shapes
+  a.B = Bf;  a.T = f.T;  a.V = h->cfg.vocab_size;  a.S = f.S;  a.NTS = (f.S + 31) / 32;  a.NT32 = NTf;
+  a.Ep = e.Ep;  a.KGx = e.KGx;  a.KGh = e.KGh;  a.KGhe = (e.H + 7) / 8;
+  a.normalize = 0;
+  a.tiles_elsewhere = (f.nside == 2 && !h->train_serial) ? ((p.paired && s == 1) ? p.NT_half : p.NT32) : 0;  // the other encoder's forward runs beside this one
+  a.force_rows = h->lstm_train_rows;
+  // tapes
+  a.tape_g = (float *)ts.tape_g[s].p;  a.tape_a = (float *)ts.tape_a[s].p;  a.h_last = (float *)ts.h_last[s].p;
+  a.tape_a_split = h->train_dk_x3 ? 1 : 0;  a.tape_swap = p.bwd2 ? 1 : 0;
+}
+
+// the same call for the split-operand forward (lstm_fwd_x3.hip, TRAIN): same tapes, same outputs
+static void fill_train_x3_args(sse_handle *h, const Encoder &e, const Encoder &own, const LstmFwdArgs &a, LstmX3Args &xa) {
+  xa.ids = a.ids;  xa.emb16 = h->emb16;  xa.Wx3 = own.Wx3t;  xa.Mp = e.Mp;  xa.out = a.out;  xa.err = h->err_flag;
+  xa.B = a.B;  xa.T = a.T;  xa.V = a.V;  xa.S = a.S;  xa.NTS = a.NTS;  xa.NT32 = a.NT32;
+  xa.KGX = lstm_x3_kgx(h->cfg.embedding_size);  xa.H = e.H;
+  xa.normalize = 0;
+  xa.tiles_elsewhere = a.tiles_elsewhere;
+  xa.tape_g = a.tape_g;  xa.tape_a = a.tape_a;  xa.h_last = a.h_last;
+}
+
+// forward of encoder s with tapes (un-normalised encodings; the loss kernel normalises) on its side stream, between the
+// fork event of the main stream and the join back into it
+static int fused_forward_side(StepFrame &f, const FusedPlan &p, int s) {
+  sse_handle *h = f.h;
+  TrainState &ts = *f.ts;
+  Encoder &e = h->enc[s];
+  const int E = h->cfg.embedding_size, V = h->cfg.vocab_size, T = f.T;
+  hipStream_t fs = h->train_serial ? ts.side[0] : ts.side[s];
+  HIPCHECK(h, hipStreamWaitEvent(fs, ts.ev_fork, 0));
+  const int KT = 2 + e.Hp / 32;
+  const bool half = p.paired && s == 0;  // the source encoder of a paired batch: first half of the rows only
+  const int NTf = half ? p.NT_half : p.NT32, Bf = half ? f.B / 2 : f.B;
+  if (reserve(h, ts.tape_g[s], (size_t)T * NTf * 4 * e.UB * 5 * 1024 * sizeof(float))) return 1;
+  if (reserve(h, ts.tape_a[s], (size_t)T * NTf * 4 * KT * 256 * sizeof(float))) return 1;
+  if (reserve(h, ts.h_last[s], (size_t)f.Bp * e.Hp * sizeof(float))) return 1;
+  LstmFwdArgs a;
+  fill_train_fwd_args(f, p, s, Bf, NTf, a);
+  if (p.fwd_x3[s]) {
+    // the gate GEMMs as three bf16 MFMAs on hi + lo split operands
+    Encoder &own = lstm_owner(h, e);
+    if (e.shares_lstm_with < 0 && s != 0) {  // (side 0 was packed ahead of the fork together with the embedding table)
+      if (!own.Wx3t) HIPCHECK(h, hipMalloc((void **)&own.Wx3t, lstm_x3_weight_elems(E, own.Hp) * sizeof(unsigned short)));
+      if (!h->emb16) HIPCHECK(h, hipMalloc((void **)&h->emb16, lstm_x3_emb_elems(V, E) * sizeof(unsigned short)));
+      // both depend on the weights of this step: repacked on the launch stream (the other side's stream waits for
+      // ev_fork, recorded before; the split embedding table is shared, so it is made on `st` ahead of the fork)
+      HIPCHECK(h, launch_pack_lstm_x3(h->vars[own.kernel].dev, h->vars[own.bias].dev, h->vars[0].dev, V, E, own.H, own.Hp,
+                                      own.Wx3t, nullptr, 1, fs));
+    }
+    LstmX3Args xa;
+    fill_train_x3_args(h, e, own, a, xa);
+    HIPCHECK(h, launch_lstm_fwd_x3(xa, fs));
+  } else {
+    HIPCHECK(h, launch_lstm_fwd(a, e.Hp, fs));
+  }
+  if (half) {  // rows B/2 .. B-1 are the same sequences: the loss and the projection backward read them per row
+    HIPCHECK(h, hipMemcpyAsync(f.raw(s) + (size_t)Bf * f.S, f.raw(s), (size_t)Bf * f.S * sizeof(float), hipMemcpyDeviceToDevice, fs));
+    HIPCHECK(h, hipMemcpyAsync((float *)ts.h_last[s].p + (size_t)Bf * e.Hp, ts.h_last[s].p, (size_t)Bf * e.Hp * sizeof(float),
+                               hipMemcpyDeviceToDevice, fs));
+  }
+  HIPCHECK(h, hipEventRecord(ts.ev_join[s], fs));
+  HIPCHECK(h, hipStreamWaitEvent(f.st, ts.ev_join[s], 0));
+  return 0;
+}
+
+// second generation, pure fp32: dX inside the BPTT kernel, d(bias) as row E of the weight-gradient GEMM
+static int fused_bwd_gen2(StepFrame &f, const FusedPlan &p, const FusedBwdSide &b) {
+  sse_handle *h = f.h;
+  TrainState &ts = *f.ts;
+  const Encoder &e = h->enc[b.s];
+  const int s = b.s, T = f.T, E = h->cfg.embedding_size, V = h->cfg.vocab_size;
+  HIPCHECK(h, launch_lstm_bwd2((const float *)ts.tape_g[s].p, (const float *)ts.dh_last[s].p, ts.KhT[s], ts.KxT[s],
+                               (float *)ts.dg_b[s].p, (float *)ts.dg_a[s].p, f.ids(s), f.emb->grad, b.sq, (float *)ts.hot_part[s].p, T,
+                               p.NT32, b.NTa, b.Hp, e.H, f.B, E, V, b.bs));
+  HIPCHECK(h, launch_dk((const float *)ts.tape_a[s].p, (const float *)ts.dg_b[s].p, (float *)ts.dk_part[s].p, b.RGa, b.KT, b.NTn, b.SL,
+                        E, e.H, b.Hp, b.accumulate, h->vars[e.kernel].grad, b.half ? p.NT_half * 4 : 0, b.bs, h->vars[e.bias].grad));
+  HIPCHECK(h, launch_dx_hot_reduce((const float *)ts.hot_part[s].p, dx_scatter_blocks(T, p.NT32 * 32), E, V, f.emb->grad, b.bs));
+  return 0;
+}
+
+// first generation, pure fp32 (option train_gen1, E = 64, a >= 2 GiB embedding table): lstm_bwd_kernel, d(bias) from its
+// partials, dX by dx_kernel from the A-operand dG copy
+static int fused_bwd_gen1(StepFrame &f, const FusedPlan &p, const FusedBwdSide &b) {
+  sse_handle *h = f.h;
+  TrainState &ts = *f.ts;
+  const Encoder &e = h->enc[b.s];
+  const int s = b.s, T = f.T, E = h->cfg.embedding_size, V = h->cfg.vocab_size;
+  BwdDxArgs bdx{ts.KxT16[s], f.ids(s), f.emb->grad, b.sq, (float *)ts.hot_part[s].p, f.B, E, V};
+  HIPCHECK(h, launch_lstm_bwd((const float *)ts.tape_g[s].p, (const float *)ts.dh_last[s].p, ts.KhT[s], (float *)ts.dg_a[s].p,
+                              (float *)ts.dg_b[s].p, (float *)ts.db_part[s].p, T, p.NT32, b.NTa, b.Hp, e.H, 0, nullptr, &bdx, b.bs));
+  HIPCHECK(h, launch_dk((const float *)ts.tape_a[s].p, (const float *)ts.dg_b[s].p, (float *)ts.dk_part[s].p, b.RGa, b.KT, b.NTn, b.SL,
+                        E, e.H, b.Hp, b.accumulate, h->vars[e.kernel].grad, b.half ? p.NT_half * 4 : 0, b.bs));
+  HIPCHECK(h, launch_db_reduce((const float *)ts.db_part[s].p, p.NT32, e.H, b.Hp, b.accumulate, h->vars[e.bias].grad, b.bs));
+  HIPCHECK(h, launch_dx((const float *)ts.dg_a[s].p, ts.KxT[s], f.ids(s), f.emb->grad, b.sq, (float *)ts.hot_part[s].p, T, p.NT32, b.KGn,
+                        f.B, E, V, e.H, b.bs));
+  return 0;
+}
+
+// split operands (option train_dk_x3, with or without train_bwd_x3 for this encoder): the weight-gradient GEMM on the bf16
+// matrix pipe; with bwd_x3 the recurrent GEMM too, and dX leaves the BPTT kernel
+static int fused_bwd_split(StepFrame &f, const FusedPlan &p, const FusedBwdSide &b) {
+  sse_handle *h = f.h;
+  TrainState &ts = *f.ts;
+  const Encoder &e = h->enc[b.s];
+  const int s = b.s, T = f.T, E = h->cfg.embedding_size, V = h->cfg.vocab_size;
+  BwdDxArgs bdx{ts.KxT16[s], f.ids(s), f.emb->grad, b.sq, (float *)ts.hot_part[s].p, f.B, E, V};
+  HIPCHECK(h, launch_lstm_bwd((const float *)ts.tape_g[s].p, (const float *)ts.dh_last[s].p, ts.KhT[s], (float *)ts.dg_a[s].p,
+                              (float *)ts.dg_b[s].p, (float *)ts.db_part[s].p, T, p.NT32, b.NTa, b.Hp, e.H, 1,
+                              p.bwd_x3[s] ? ts.KhT16[s] : nullptr, &bdx, b.bs));
+  // the 8-row r-groups of the fp32 layout pair up into 16-row groups: the same bytes
+  HIPCHECK(h, launch_dk_x3(ts.tape_a[s].p, ts.dg_b[s].p, (float *)ts.dk_part[s].p, b.RGa / 2, b.KT, b.NTn, b.SL, E, e.H, b.Hp, b.accumulate,
+                           h->vars[e.kernel].grad, b.half ? p.NT_half * 2 : 0, b.bs));
+  HIPCHECK(h, launch_db_reduce((const float *)ts.db_part[s].p, p.NT32, e.H, b.Hp, b.accumulate, h->vars[e.bias].grad, b.bs));
+  if (p.bwd_x3[s])  // dX left the BPTT kernel already; only the PAD / EOS rows are still to be added
+    HIPCHECK(h, launch_dx_hot_reduce((const float *)ts.hot_part[s].p, T * p.NT32 * 2, E, V, f.emb->grad, b.bs));
+  else
+    HIPCHECK(h, launch_dx((const float *)ts.dg_a[s].p, ts.KxT[s], f.ids(s), f.emb->grad, b.sq, (float *)ts.hot_part[s].p, T, p.NT32, b.KGn,
+                          f.B, E, V, e.H, b.bs));
+  return 0;
+}
+
+// backward of encoder s: the projection, one of the three BPTT bodies, the join into the main stream
+static int fused_backward_side(StepFrame &f, const FusedPlan &p, int s) {
+  sse_handle *h = f.h;
+  TrainState &ts = *f.ts;
+  Encoder &e = h->enc[s];
+  const bool shared = h->cfg.network_mode == SSE_MODE_SHARED_ENCODER;
+  const int T = f.T, Hp = e.Hp, RG = T * p.NT32 * 4;
+  FusedBwdSide b;
+  b.s = s;
+  // dual-encoder: the two backward chains are independent -> side streams; shared-encoder: the
+  // target side accumulates onto the source side's kernel/bias gradient -> one stream, in order
+  b.bs = (shared || h->train_serial) ? ts.side[0] : ts.side[s];
+  b.Hp = Hp;  b.KGn = Hp / 2;  b.NTn = Hp / 8;  b.KT = 2 + Hp / 32;
+  b.half = p.paired && s == 0;
+  b.NTa = b.half ? p.NT_half : p.NT32;  b.RGa = b.half ? RG / 2 : RG;  b.SL = dk_slices(b.RGa);
+  b.accumulate = (shared && s == 1) ? 1 : 0;
+  b.sq = f.sq() + p.sq_off[s];
+  if (!shared || s == 0) HIPCHECK(h, hipStreamWaitEvent(b.bs, ts.ev_fork, 0));
+  if (reserve(h, ts.dh_last[s], (size_t)f.Bp * Hp * sizeof(float))) return 1;
+  // dg_a: the A-operand dG copy of the first generation (not written when dX leaves the BPTT kernel); second generation: the dX rows
+  if (p.bwd2 ? reserve(h, ts.dg_a[s], (size_t)T * p.NT32 * 32 * 64 * sizeof(float))
+             : !p.bwd_x3[s] && reserve(h, ts.dg_a[s], (size_t)T * p.NT32 * b.KGn * 256 * sizeof(float)))
+    return 1;
+  if (reserve(h, ts.hot_part[s], (size_t)std::max(T * p.NT32 * 2, dx_scatter_blocks(T, p.NT32 * 32)) * 2 * 64 * sizeof(float)) ||
+      reserve(h, ts.dg_b[s], (size_t)RG * b.NTn * 256 * sizeof(float)) || reserve(h, ts.db_part[s], (size_t)p.NT32 * 4 * Hp * sizeof(float)) ||
+      reserve(h, ts.dk_part[s], (size_t)b.SL * b.KT * 32 * b.NTn * 32 * sizeof(float)) ||
+      reserve(h, ts.dm_part[s], (size_t)proj_bwd_chunks(f.Bp) * e.H * f.S * sizeof(float)))
+    return 1;
+  HIPCHECK(h, launch_proj_bwd((const float *)ts.h_last[s].p, f.draw(s), h->vars[e.proj].dev, f.Bp, e.H, Hp, f.S, h->vars[e.proj].grad,
+                              (float *)ts.dh_last[s].p, (float *)ts.dm_part[s].p, b.bs));
+  if (p.bwd2 ? fused_bwd_gen2(f, p, b) : h->train_dk_x3 ? fused_bwd_split(f, p, b) : fused_bwd_gen1(f, p, b)) return 1;
+  if (!shared || s == 1) {
+    HIPCHECK(h, hipEventRecord(ts.ev_join[s], b.bs));
+    HIPCHECK(h, hipStreamWaitEvent(f.st, ts.ev_join[s], 0));
+  }
+  return 0;
+}
+
+// Cell sizes up to 256 and embeddings up to 64 columns: MFMA forward with tapes and BPTT, the two encoders side by side
+static int train_grads_fused_locked(sse_handle *h, const TrainCall &call) {
+  if (ensure_side_streams(h, *h->train)) return 1;
+  StepFrame f;
+  if (step_begin(h, call, 64, f)) return 1;
+  TrainState &ts = *f.ts;
+  const FusedPlan p = fused_plan(f);
+  if (fused_refresh_layouts(f, p) || fused_check_tape(f, p)) return 1;
+  const int32_t *perm = nullptr;
+  if (p.paired && pair_permutation(f, &perm)) return 1;
+  if (step_stage_inputs(f, perm, p.n_sq) || fused_pack_split_inputs(f)) return 1;
+  // the two encoders are independent: fork onto two side streams, join before the loss
+  HIPCHECK(h, hipEventRecord(ts.ev_fork, f.st));
+  if (step_table_forward(f)) return 1;
+  for (int s = 0; s < f.nside; ++s)
+    if (fused_forward_side(f, p, s)) return 1;
+  if (step_loss(f) || step_table_backward(f)) return 1;
+  HIPCHECK(h, hipEventRecord(ts.ev_fork, f.st));  // loss + zeroed embedding gradient are ready
+  for (int s = 0; s < f.nside; ++s)
+    if (fused_backward_side(f, p, s)) return 1;
+  return step_finish(f);
+}
+
+// Forward, loss and backward of one batch of pair rows; gradients are scaled by 1/rows_global and left in
+// the arena (with the tail sums), nothing is updated.
+static int train_grads_locked(sse_handle *h, const TrainCall &call) {
+  const sse_config &c = h->cfg;
+  if (call.B < 1 || call.T < 1 || !call.src || !call.tgt || !call.labels || call.rows_global < call.B)
+    return fail(h, "bad arguments to the train step");
+  if (!h->train) h->train = new TrainState();
+  if (c.network_mode == SSE_MODE_SOURCE_ONLY_CNN) return cnn_train_grads_locked(h, call);
+  // shapes outside the fused training kernels (cell size > 256, embedding_size > 64; option train_generic forces it: tests)
+  bool generic = h->train_generic || c.embedding_size > 64;
+  for (int s = 0; s < (c.network_mode == SSE_MODE_SOURCE_ENCODER_ONLY ? 1 : 2); ++s)
+    generic = generic || h->enc[s].Hp > 256 || h->enc[s].generic;
+  return generic ? train_grads_generic_locked(h, call) : train_grads_fused_locked(h, call);
 }
 
 // clip_by_global_norm over the (possibly all-reduced) arena + Adagrad + global_step (sse_model.py:355-364)
@@ -3669,7 +3678,7 @@ static int train_apply_locked(sse_handle *h, float *loss, float *train_acc) {
 int sse_train_grads(sse_handle *h, const int32_t *src_ids_host, const int32_t *tgt_ids_host, const float *labels_host,
                     int32_t B, int32_t T, int64_t rows_global) {
   SSE_ENTER(h);
-  return train_grads_locked(h, src_ids_host, tgt_ids_host, labels_host, B, T, rows_global);
+  return train_grads_locked(h, TrainCall{src_ids_host, tgt_ids_host, labels_host, B, T, rows_global, false, false});
 }
 
 int sse_corpus_upload(sse_handle *h, int side, const int32_t *ids_host, int64_t N, int32_t T) {
@@ -3689,22 +3698,14 @@ int sse_train_grads_rows(sse_handle *h, const int32_t *src_rows_host, const int3
                          int32_t B, int64_t rows_global) {
   SSE_ENTER(h);
   if (!h->train || !h->train->corpus[0].p) return fail(h, "train step by rows: no source corpus on the device (sse_corpus_upload)");
-  h->train->rows_mode = true;
-  const int rc = train_grads_locked(h, src_rows_host, tgt_rows_host, labels_host, B, h->train->corpus_T[0], rows_global);
-  h->train->rows_mode = false;
-  return rc;
+  return train_grads_locked(h, TrainCall{src_rows_host, tgt_rows_host, labels_host, B, h->train->corpus_T[0], rows_global, true, false});
 }
 
 int sse_train_step_rows(sse_handle *h, const int32_t *src_rows_host, const int32_t *tgt_rows_host, const float *labels_host,
                         int32_t B, float *loss, float *train_acc) {
   SSE_ENTER(h);
   if (!h->train || !h->train->corpus[0].p) return fail(h, "train step by rows: no source corpus on the device (sse_corpus_upload)");
-  h->train->rows_mode = true;
-  h->train->defer_err = true;
-  const int rc = train_grads_locked(h, src_rows_host, tgt_rows_host, labels_host, B, h->train->corpus_T[0], B);
-  h->train->rows_mode = false;
-  h->train->defer_err = false;
-  if (rc) return 1;
+  if (train_grads_locked(h, TrainCall{src_rows_host, tgt_rows_host, labels_host, B, h->train->corpus_T[0], B, true, true})) return 1;
   return train_apply_locked(h, loss, train_acc);
 }
 
@@ -3737,14 +3738,13 @@ int sse_train_apply(sse_handle *h, float *loss, float *train_acc) {
 
 int sse_train_step(sse_handle *h, const int32_t *src_ids_host, const int32_t *tgt_ids_host, const float *labels_host,
                    int32_t B, int32_t T, float *loss, float *train_acc) {
+  // (not SSE_ENTER: a null loss / train_acc is refused here, ahead of the lock, without a step and without an error text;
+  // sse_train_step_rows and sse_train_apply accept either as "not wanted")
   if (!h || !loss || !train_acc) return 1;
   std::lock_guard<std::mutex> lk(h->mu);
   HIPCHECK(h, hipSetDevice(h->cfg.device));
-  if (!h->train) h->train = new TrainState();
-  h->train->defer_err = true;  // one host sync per step: the error flag is read with the loss
-  const int rc = train_grads_locked(h, src_ids_host, tgt_ids_host, labels_host, B, T, B);
-  h->train->defer_err = false;
-  if (rc) return 1;
+  // defer_err: one host sync per step, the error flag is read with the loss
+  if (train_grads_locked(h, TrainCall{src_ids_host, tgt_ids_host, labels_host, B, T, B, false, true})) return 1;
   return train_apply_locked(h, loss, train_acc);
 }
 
@@ -3770,10 +3770,7 @@ static int eval_loss_locked(sse_handle *h, const int32_t *src_host, const int32_
   hipStream_t st = h->stream;
 
   // paired batch (data.py:95-115): rows 2i, 2i + 1 carry the same source -> one source-encoder row per pair
-  bool paired = h->train_pair_dedup && B % 2 == 0;
-  for (int i = 0; i < B && paired; i += 2)
-    paired = by_rows ? src_host[i] == src_host[i + 1]
-                     : memcmp(src_host + (size_t)i * T, src_host + (size_t)(i + 1) * T, (size_t)T * sizeof(int32_t)) == 0;
+  const bool paired = h->train_pair_dedup && B % 2 == 0 && batch_is_paired(src_host, B, T, by_rows);
   if (paired) h->eval_paired_calls += 1;
 
   const int chunk = std::min<int>(B, h->eval_chunk_rows);  // (even, or the whole batch)

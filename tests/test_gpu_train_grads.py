@@ -122,6 +122,21 @@ CASES = [
     # this rank's share of a mean over 3 B rows; batches by row number from uploaded corpora (device id gather)
     _case("rows-global-3b", "dual-encoder", 300, 50, 128, 128, 64, 10, 64, rows_factor=3),
     _case("by-rows", "dual-encoder", 300, 50, 128, 128, 64, 10, 64, by_rows=True),
+    # Branches of the step frame that the three paths share and that no case above reaches: every paired case above (a pair
+    # needs B % 128 == 0) is dual-encoder with id matrices.  B 128 is the smallest paired shape; everything else is small.
+    # permuted free-matrix rows together with rows_scatter and its offset behind the encoder's partial sums (N 300: more rows
+    # than the batch, so that some stay untouched -- asserted)
+    _case("seo-paired", "source-encoder-only", 200, 32, 96, 96, 48, 6, 128, N=300),
+    # the half-row source side accumulating onto the shared kernel gradient on one stream
+    _case("shared-paired", "shared-encoder", 200, 24, 64, 64, 32, 7, 128),
+    # row numbers under the pair permutation, then the device gather (pair_rows: the two rows of a pair name ONE corpus row,
+    # which is how a batch by row numbers is recognised as paired)
+    _case("by-rows-paired", "dual-encoder", 200, 40, 96, 64, 64, 8, 128, by_rows=True, pair_rows=True),
+    _case("seo-by-rows-paired", "source-encoder-only", 200, 16, 64, 64, 40, 5, 128, N=300, by_rows=True, pair_rows=True),
+    # both encoders on one stream (the h128 shape)
+    _case("serial", "dual-encoder", 300, 50, 128, 128, 64, 10, 96, opts=dict(train_serial=1)),
+    # a pairable batch with the pair deduplication switched off (the c1 shape at T 8)
+    _case("pair-dedup-off", "dual-encoder", 400, 50, 256, 256, 256, 8, 128, opts=dict(train_pair_dedup=0)),
 ]
 
 
@@ -251,6 +266,27 @@ def _model(c):
     return params, m, p
 
 
+def case_arena(c, m, src, tgt, z, rows_global):
+    """The raw arena of the case's batch: sse_train_grads, or -- by_rows -- sse_train_grads_rows on uploaded, shuffled corpora."""
+    if not c["by_rows"]:
+        return arena_grads(m, src, tgt, z, rows_global)
+    B = len(z)
+    order = np.random.RandomState(5).permutation(B).astype(np.int32)
+    inv = np.argsort(order).astype(np.int32)        # row numbers into the shuffled corpora that give back the batch
+    src_rows = inv
+    if c.get("pair_rows"):                          # a source corpus of the B / 2 distinct sequences: rows 2i, 2i + 1 share a number
+        assert np.array_equal(src[0::2], src[1::2])
+        half = np.random.RandomState(6).permutation(B // 2).astype(np.int32)
+        m.handle.corpus_upload(0, src[0::2][half])
+        src_rows = np.repeat(np.argsort(half).astype(np.int32), 2)
+    else:
+        m.handle.corpus_upload(0, src[order])
+    if tgt.ndim == 2:
+        m.handle.corpus_upload(1, tgt[order])
+        return arena_grads(m, src_rows, inv, z, rows_global, rows=True)
+    return arena_grads(m, src_rows, tgt, z, rows_global, rows=True)   # table modes: the target side stays row numbers of the free matrix
+
+
 @pytest.mark.parametrize("c", CASES)
 def test_raw_gradients_and_apply_match_float64(c):
     params, m, p = _model(c)
@@ -261,17 +297,7 @@ def test_raw_gradients_and_apply_match_float64(c):
     cnn_preconditions(c, p, src)
     bars = case_bars(c)
     want, want_tail = reference_grads(p, params, src, tgt, z, rows_global, cnn_bf16=cnn_bf16)
-    if c["by_rows"]:
-        order = np.random.RandomState(5).permutation(B).astype(np.int32)
-        inv = np.argsort(order).astype(np.int32)    # row numbers into the shuffled corpora that give back the batch
-        m.handle.corpus_upload(0, src[order])
-        if tgt.ndim == 2:
-            m.handle.corpus_upload(1, tgt[order])
-            got, tail = arena_grads(m, inv, inv, z, rows_global, rows=True)
-        else:                                       # table modes: the target side stays row numbers of the free matrix
-            got, tail = arena_grads(m, inv, tgt, z, rows_global, rows=True)
-    else:
-        got, tail = arena_grads(m, src, tgt, z, rows_global)
+    got, tail = case_arena(c, m, src, tgt, z, rows_global)
     errs = check_grads(got, want, bars, what="%s: " % c["id"], var_bars=c.get("var_bars"))
     check_tail(tail, want_tail, bars, LOSS_REL_SPLIT if c["opts"].get("train_fwd_x3") else LOSS_REL_EXACT)
     if c.get("dead") == (1.0, 1.0):                 # nothing alive: the clamp's 1e6 slope reaches only masked features
