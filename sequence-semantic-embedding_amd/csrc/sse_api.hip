@@ -1078,20 +1078,64 @@ static int choose_nsplit(int NQ, int QB, int64_t NT) {
   return nsplit;
 }
 
+// Splits of the two list-free sweeps of the two-pass route: the list sweep's choice (nsplit) weighs list warm-up against rounds;
+// without lists only the rounds count -- workgroups are one per CU (VGPRs), so QB x splits should sit just below a multiple of
+// the CU count: 129 query blocks x 4 splits = 2.02 rounds run as 3, x 16 = 8.06 run as 9.  At most 16 (the threshold kernel
+// takes 16 x 16 lane maxima per query), at least 32 tiles per split.
+static int choose_two_pass_splits(const sse_handle *h, int QB, int64_t NT, int nsplit) {
+  static const int force = getenv("SSE_TWO_PASS_SPLITS") ? atoi(getenv("SSE_TWO_PASS_SPLITS")) : 0;  // (env: measurement aid)
+  if (force == 1 || force == 2 || force == 4 || force == 8 || force == 16) return force;
+  int ns2 = std::min(nsplit, 16);
+  const int cus = h->cu_count > 0 ? h->cu_count : 256;
+  double best = 0.0;
+  for (int ns = 1; ns <= 16; ns *= 2) {
+    if (ns > 1 && NT / ns < 32) break;
+    const double r = (double)QB * ns / cus, eff = r / std::ceil(r);
+    if (eff > best + 0.02) {
+      best = eff;
+      ns2 = ns;
+    }
+  }
+  return ns2;
+}
+
+// query tiles per workgroup of a sweep for P columns of the resident index; the one place that refuses a dimension whose
+// query block does not fit LDS
+static int pick_nq(sse_handle *h, int P, bool bf, int &NQ) {
+  NQ = score_pick_nq(P, h->idx_S, bf ? 1 : 0);
+  if (NQ == 0) return fail(h, "index dimension %d does not fit the scoring kernel's LDS query block", h->idx_S);
+  return 0;
+}
+
 // NQ, query blocks and base split count of one sweep over P columns (queries or pairs) of the resident index
 struct SweepChunk {
   int NQ, QB, nsplit;
 };
-static int sweep_chunk(sse_handle *h, int P, SweepChunk &c) {
-  c.NQ = score_pick_nq(P, h->idx_S, 0);
-  if (c.NQ == 0) return fail(h, "index dimension %d does not fit the scoring kernel's LDS query block", h->idx_S);
+static int sweep_chunk(sse_handle *h, int P, SweepChunk &c, bool bf = false) {
+  if (pick_nq(h, P, bf, c.NQ)) return 1;
   c.QB = (P + c.NQ * 32 - 1) / (c.NQ * 32);
   c.nsplit = choose_nsplit(c.NQ, c.QB, (h->idx_N + 31) / 32);
   return 0;
 }
 
-// |fp32 MFMA score - float64 score| <= score_eps32 |q| for every row of the resident index (DESIGN K6/K7)
+// The three bounds on |candidate score - float64 score| / |q| over the rows of the resident index (DESIGN K6/K7).
+// fp32 MFMA candidates: |fp32 fma-chain dot - exact| <= S * 2^-24 * |q||t| (+ the f32 rounding of f64 rows); use 2x margin
 static float score_eps32(const sse_handle *h) { return (float)(2.0 * (h->idx_S + 2) * 5.97e-8 * h->idx_norm_max); }
+// bf16 operands: |q^.t^ - q.t| <= ((1+u)^2 - 1) sum|q_i t_i| <= (2^-8 + 2^-18) |q||t|, u = 2^-9 (round to nearest), on top of
+// the fp32 accumulation's bound
+static float score_eps_bf16(const sse_handle *h) {
+  return score_eps32(h) + (float)(1.02 * (1.0 / 256.0 + 1.0 / 262144.0) * h->idx_norm_max);
+}
+// split-bf16 candidates of the small-index scorer (DESIGN K6).  bf16 keeps 8 significant bits: hi = rne(x) leaves
+// |x - hi| <= 2^-8 |x|, lo = rne(x - hi) leaves e = x - hi - lo with |e| <= 2^-17 |x| (and |lo| <= 2^-8 (1 + 2^-9) |x|).  The
+// dropped terms ql.tl + eq.t + (q - eq).et are <= (2^-16 + 2 * 2^-17)(1 + 2^-7) sum|q_i t_i| <= 2^-15 (1 + 2^-6) |q||t| -- reached
+// to 2 % by mantissas that sit halfway in both roundings.  The 3 S kept products are exact in fp32 and are added in an order
+// the matrix pipe chooses: (3 S + 2) additions of <= 2^-24 sum|terms| each (+ the f32 rounding of f64 rows), sum|terms| <=
+// (1 + 2^-5) sum|q_i t_i|, with the fp32 bound's 2x margin.  1.26e-4 at S = 256 (fp32: 3.1e-5); rows or queries of norm
+// below 2^-100 are outside the claim (a lo part may underflow bf16's range).
+static float score_eps_split_bf16(const sse_handle *h) {
+  return (float)(((1.0 + 1.0 / 64.0) / 32768.0 + 2.0 * (3 * h->idx_S + 2) * 5.97e-8 * (1.0 + 1.0 / 32.0)) * h->idx_norm_max);
+}
 
 // n_words device counters in b, zeroed when they are first reserved (they accumulate over the handle's life)
 static int ensure_zeroed_once(sse_handle *h, DevBuf &b, bool &init, int n_words, hipStream_t st) {
@@ -1147,74 +1191,6 @@ static int reserve_collect(sse_handle *h, int Q, int slots) {
   if (reserve(h, h->s_cslot, (size_t)Q * sizeof(int32_t))) return 1;
   if (reserve(h, h->s_ccnt, (size_t)(slots + 1) * sizeof(int32_t))) return 1;
   if (reserve(h, h->s_cbuf, (size_t)slots * SSE_COLLECT_CAP * sizeof(int32_t))) return 1;
-  return 0;
-}
-
-// k > 16 (sse_demo.py:128-134 and webserver.py take a user-chosen nbest): candidate sweep with enough per-split
-// lists that the k-th best candidate is a tight lower bound of the k-th best row, then a collect sweep of every row
-// that can still be in the exact top-k and a float64 sort of those -- two grid-wide sweeps instead of the
-// one-workgroup-per-query float64 brute force (which stays as the fallback: k > SSE_MAX_SELECT_K, or more than
-// SSE_COLLECT_CAP rows within the bound of the k-th score).
-static int score_select_locked(sse_handle *h, const float *q, int Q, int k, double *out_s, int64_t *out_i, hipStream_t st) {
-  const int S = h->idx_S, KG = (S + 7) / 8;
-  const int64_t NT = (h->idx_N + 31) / 32;
-  const int POOL = 2048;
-  const float eps32 = score_eps32(h);
-  if (ensure_counters(h, st)) return 1;
-  unsigned long long *counters = (unsigned long long *)h->s_fb_cnt.p;
-  for (int q0 = 0; q0 < Q; q0 += POOL) {
-    const int Qc = std::min(POOL, Q - q0);
-    const float *qc = q + (size_t)q0 * S;
-    const int QT = (Qc + 31) / 32;
-    const int NQ = score_pick_nq(Qc, S, 0);
-    if (NQ == 0) return fail(h, "index dimension %d does not fit the scoring kernel's LDS query block", S);
-    const int QB = (QT + NQ - 1) / NQ;
-    int nsplit = choose_nsplit(NQ, QB, NT);
-    // at least 4k candidates (k-th candidate close to the k-th row), at most RS_MAXNC = 4096, >= 2 tiles per split
-    const int max_split = (NQ == 1) ? 256 : 128;
-    while (nsplit < max_split && nsplit * 16 < 4 * k && NT / (nsplit * 2) >= 2) nsplit *= 2;
-    const int NC = nsplit * 16;
-    if (reserve(h, h->s_qp, (size_t)QB * NQ * KG * 256 * sizeof(float))) return 1;
-    if (reserve(h, h->s_ps, (size_t)Qc * NC * sizeof(float))) return 1;
-    if (reserve(h, h->s_pi, (size_t)Qc * NC * sizeof(int32_t))) return 1;
-    if (reserve(h, h->s_pb, (size_t)Qc * nsplit * sizeof(float))) return 1;
-    if (reserve(h, h->s_cert, (size_t)Qc * sizeof(int32_t))) return 1;
-    if (reserve_collect(h, Qc, Qc)) return 1;
-    HIPCHECK(h, launch_pack_rows(qc, Qc, S, (float *)h->s_qp.p, st));
-    ScoreArgs a;
-    a.idxp = h->idxp;
-    a.qp = (const float *)h->s_qp.p;
-    a.part_scores = (float *)h->s_ps.p;
-    a.part_ids = (int32_t *)h->s_pi.p;
-    a.part_bnd = (float *)h->s_pb.p;
-    a.N = h->idx_N;
-    a.Q = Qc;
-    a.KG = KG;
-    a.NT = (int)NT;
-    a.QT = QT;
-    a.NSPLIT = nsplit;
-    a.KC = 16;
-    a.NQ = NQ;
-    HIPCHECK(h, launch_score_topk(a, st));
-    HIPCHECK(h, launch_kth_bound(qc, a.part_scores, a.part_ids, Qc, S, NC, k, eps32, (float *)h->s_cthr.p,
-                                 (int32_t *)h->s_cslot.p, st));
-    HIPCHECK(h, hipMemsetAsync(h->s_ccnt.p, 0, (size_t)(Qc + 1) * sizeof(int32_t), st));
-    HIPCHECK(h, hipMemsetAsync(h->s_cert.p, 0, (size_t)Qc * sizeof(int32_t), st));
-    ScoreArgs c = a;
-    c.COLLECT = 1;
-    c.col_thr = (const float *)h->s_cthr.p;
-    c.col_slot = (const int32_t *)h->s_cslot.p;
-    c.col_cnt = (int32_t *)h->s_ccnt.p;
-    c.col_buf = (int32_t *)h->s_cbuf.p;
-    c.col_cap = SSE_COLLECT_CAP;
-    HIPCHECK(h, launch_score_topk(c, st));
-    SelectArgs sel{qc, h->idxp, h->idx64, c.col_slot, c.col_cnt, c.col_buf, SSE_COLLECT_CAP,
-                   out_s + (size_t)q0 * k, out_i + (size_t)q0 * k, (int32_t *)h->s_cert.p, h->idx_base, Qc, S, k, counters + 1};
-    HIPCHECK(h, launch_select_topk(sel, st));
-    // whatever overflowed its buffer: float64 brute force (pages of 16)
-    HIPCHECK(h, launch_exact_topk(qc, h->idxp, h->idx64, (const int32_t *)h->s_cert.p, out_s + (size_t)q0 * k,
-                                  out_i + (size_t)q0 * k, h->idx_base, h->idx_N, Qc, S, k, st, counters + 2));
-  }
   return 0;
 }
 
@@ -1602,66 +1578,100 @@ static int score_grouped_dev_locked(sse_handle *h, const TopkIo &io, int Q, int 
   return 0;
 }
 
-// phase: SCORE_ALL queues every stage (the asynchronous *_dev entry point: no host sync, the follow-up stages return at once
-// when every query is certified).  The host-buffer entry points split the call: SCORE_FIRST = candidate sweep + float64
-// re-scoring (results and certificates final for every certified query), then -- only if the certificates they read back
-// with the results say so -- SCORE_REST = second chance / collect / select / brute force: the common call saves five to nine
-// empty launches (~4.5 us each: a third of a single-query call, profiles/r02z_demo_kernel_stats.csv).
-enum { SCORE_ALL = 0, SCORE_FIRST = 1, SCORE_REST = 2 };
-// Host mirror of a SCORE_FIRST call of few queries (see RescoreArgs): pinned, device-visible host pointers the re-scoring pass
-// stores results, certificates, the error flag of the encoder in front of it and -- last, released at system scope -- one
-// completion word per query through.  The host polls the words: no read-back copies, no stream synchronisation.
-struct ScoreMirror {
-  double *scores;
-  int64_t *ids;
-  int32_t *cert, *err, *flag;
-  int32_t seq;
+// ---- sse_score_topk*: plan -> prepare -> route (DESIGN K6/K7) ----
+// Paging: k > SSE_MAX_SELECT_K, exact float64 paging.  Select: 16 < k <= SSE_MAX_SELECT_K.  TwoPass: mid-size indexes under
+// many queries.  Lists: everything else, in two stages (lists_first, lists_rest).  None: no queries.
+enum class TopkRoute { None, Paging, Select, TwoPass, Lists };
+
+// What one call does, decided once from (handle, Q, k) by topk_plan and const afterwards.  Paging and Select use the fields
+// down to eps32 only (Select shapes its sweeps per pool of queries).
+struct TopkPlan {
+  TopkRoute route;
+  int Q, k, S, KG, KG16, QT;
+  int64_t NT;
+  float eps32, eps_bf16, eps_split;  // score_eps32 / score_eps_bf16 / score_eps_split_bf16
+  bool bf;           // bf16 candidate pass
+  int NQ, QB;        // query tiles per workgroup, query blocks
+  int nsplit;        // splits of the candidate sweep: 16 candidates each
+  int nsplit2;       // splits of the bf16 route's fp32 second chance
+  int two_pass_splits;
+  bool small_idx, small_x3;  // the small-index scorer instead of the list sweep; on split-bf16 operands
+  bool rows_direct;  // the sweeps build their query fragments from the rows themselves: no pack launch
+  int NC, NCmax;     // candidates per query of the first stage; of the larger of the two sweeps
+  int POOL;          // collect-buffer slots for uncertified queries (the rest: float64 brute force)
+  bool own_slots;    // every query has a collect slot of its own: the re-scoring pass hands them out
+  bool has_rest;     // a second stage exists: what the first one left uncertified is served by lists_rest
+  float cand_eps() const { return small_x3 ? eps_split : bf ? eps_bf16 : eps32; }
 };
-// *split (out, may be null): 1 when the call has a FIRST / REST split (k <= 16), 0 when SCORE_FIRST did everything
-int score_dev_locked(sse_handle *h, const float *q, int Q, int k, double *out_s, int64_t *out_i, hipStream_t st,
-                     int phase = SCORE_ALL, int *split = nullptr, const ScoreMirror *mirror = nullptr) {
-  if (split) *split = 0;
+
+static int topk_plan(sse_handle *h, int Q, int k, TopkPlan &p) {
+  p = TopkPlan{};
+  p.route = TopkRoute::None;
   if (!h->idxp) return fail(h, "no index uploaded");
   if (Q < 0) return fail(h, "bad Q");
   if (Q == 0) return 0;
   if (k < 1 || k > h->idx_N) return fail(h, "k=%d must be in [1, N=%lld]", k, (long long)h->idx_N);
-  if ((k > 16) && phase == SCORE_REST) return 0;
-  if (k > SSE_MAX_SELECT_K) {
-    // beyond the collect path's buffers: exact float64 paging (correct for any k <= N, one workgroup per query)
-    HIPCHECK(h, launch_exact_topk(q, h->idxp, h->idx64, nullptr, out_s, out_i, h->idx_base, h->idx_N, Q, h->idx_S, k, st));
+  const int S = h->idx_S;
+  p.Q = Q;
+  p.k = k;
+  p.S = S;
+  p.KG = (S + 7) / 8;
+  p.KG16 = (S + 15) / 16;
+  p.QT = (Q + 31) / 32;
+  p.NT = (h->idx_N + 31) / 32;
+  p.eps32 = score_eps32(h);
+  p.eps_bf16 = score_eps_bf16(h);
+  p.eps_split = score_eps_split_bf16(h);
+  if (k > 16) {
+    p.route = k > SSE_MAX_SELECT_K ? TopkRoute::Paging : TopkRoute::Select;
     return 0;
   }
-  if (k > 16) return score_select_locked(h, q, Q, k, out_s, out_i, st);
-  const int S = h->idx_S, KG = (S + 7) / 8;
-  const int QT = (Q + 31) / 32;
   // bf16 candidate pass (option score_bf16): 16x the matrix rate for the 128-query-block variant, half the index
   // bytes for the HBM-bound few-queries sweep
   // (small indexes stay on the fp32 pass: nothing to win, and no bf16 copy / second-chance launches to pay for)
-  const bool bf = h->score_bf16 && h->idx_N >= 8192;
+  p.bf = h->score_bf16 && h->idx_N >= 8192;
   // <= 32 queries (demo / web): single query tile, HBM-bound sweep; else 128-query blocks while they fit LDS (index
-  // dimension <= 296), 64-query blocks up to 616 (configs[4]: 512), 32-query blocks beyond
-  const int NQ = score_pick_nq(Q, S, bf ? 1 : 0);
-  if (NQ == 0) return fail(h, "index dimension %d does not fit the scoring kernel's LDS query block", S);
-  const int QB = (QT + NQ - 1) / NQ;
-  const int64_t NT = (h->idx_N + 31) / 32;
-  // the 16 lane lists of a workgroup are always merged in-kernel (a few tens of microseconds per workgroup): the
+  // dimension <= 296), 64-query blocks up to 616 (configs[4]: 512), 32-query blocks beyond.
+  // The 16 lane lists of a workgroup are always merged in-kernel (a few tens of microseconds per workgroup): the
   // re-scoring pass ranks 16 candidates per split
-  const int nsplit = choose_nsplit(NQ, QB, NT);
+  SweepChunk ck;
+  if (sweep_chunk(h, Q, ck, p.bf)) return 1;
+  p.NQ = ck.NQ;
+  p.QB = ck.QB;
+  p.nsplit = ck.nsplit;
+  // Mid-size indexes under many queries: the two-pass route.  (A host call of few queries, the only kind with a mirror,
+  // never comes here: a mirror needs Q <= 64, this route Q >= 1024.)
+  if (p.bf && p.NQ == 4 && Q >= 1024 && h->idx_N >= h->score_two_pass_min_rows && h->idx_N <= h->score_two_pass_rows) {
+    p.route = TopkRoute::TwoPass;
+    p.two_pass_splits = choose_two_pass_splits(h, p.QB, p.NT, p.nsplit);
+    return 0;
+  }
+  p.route = TopkRoute::Lists;
+  p.has_rest = true;
   // the fp32 second chance of the bf16 pass sweeps for a dense set of FEW queries (typically a handful of query blocks): it
   // takes its parallelism from the index instead -- up to 128 splits -- or three workgroups would walk 1.25 M rows alone
-  int nsplit2 = nsplit;
   // (up to 128 since round 6: with 32, the 30 uncertified of 16384 random queries against 1.25 M rows -- one query block -- kept 32
   // workgroups busy for 4 ms on an otherwise idle chip: 13.5 ms per pass, 9.75 with 128; env: measurement aid)
   static const int split2_max = getenv("SSE_SPLIT2_MAX") ? atoi(getenv("SSE_SPLIT2_MAX")) : 128;
-  while (nsplit2 < split2_max && NT / (nsplit2 * 2 * 2) >= 16) nsplit2 *= 2;
+  p.nsplit2 = p.nsplit;
+  while (p.nsplit2 < split2_max && p.NT / (p.nsplit2 * 2 * 2) >= 16) p.nsplit2 *= 2;
   // many queries against a small index (the evaluator's 16384 x 571): one launch forms all N scores per query and selects the
   // 16 best exactly (launch_score_small_index) instead of the list sweep
-  const bool small_idx = h->score_small_index && !bf && score_small_index_applies(Q, KG, NT);
-  const bool small_x3 = small_idx && h->score_small_x3 && h->idx_x3_valid;
-  const int NC = small_idx ? 16 : nsplit * 16, NCmax = std::max(nsplit, nsplit2) * 16;
-  const int KG16 = (S + 15) / 16;
-  if (bf && !h->idxp16_valid) {
-    const size_t need = (size_t)NT * KG16 * 1024;
+  p.small_idx = h->score_small_index && !p.bf && score_small_index_applies(Q, p.KG, p.NT);
+  p.small_x3 = p.small_idx && h->score_small_x3 && h->idx_x3_valid;
+  p.rows_direct = p.NQ == 1;  // <= 32 queries (the latency path)
+  p.NC = p.small_idx ? 16 : p.nsplit * 16;
+  p.NCmax = std::max(p.nsplit, p.nsplit2) * 16;
+  p.POOL = std::min(Q, 1024);
+  p.own_slots = Q <= p.POOL;
+  return 0;
+}
+
+// what every route but Paging needs before its first launch: the bf16 image of the index, built when the first bf16 call asks
+// for it, and the device counters
+static int topk_prepare(sse_handle *h, const TopkPlan &p, hipStream_t st) {
+  if (p.bf && !h->idxp16_valid) {
+    const size_t need = (size_t)p.NT * p.KG16 * 1024;
     if (need > h->idxp16_cap) {
       if (h->idxp16) HIPCHECK(h, hipFree(h->idxp16));
       h->idxp16 = nullptr;
@@ -1669,101 +1679,25 @@ int score_dev_locked(sse_handle *h, const float *q, int Q, int k, double *out_s,
       HIPCHECK(h, hipMalloc(&h->idxp16, need));
       h->idxp16_cap = need;
     }
-    HIPCHECK(h, launch_frag32_to_bf16(h->idxp, NT, KG, h->idxp16, st));
+    HIPCHECK(h, launch_frag32_to_bf16(h->idxp, p.NT, p.KG, h->idxp16, st));
     h->idxp16_valid = true;
   }
-  if (ensure_counters(h, st)) return 1;
-  unsigned long long *counters = (unsigned long long *)h->s_fb_cnt.p;
-  // ---- mid-size indexes under many queries: max-only sweep -> per-query threshold -> collect sweep -> float64 select (see
-  // lane_max_threshold_kernel in score_topk.hip for the argument).  Everything is final after it: no certificates to follow up.
-  if (bf && NQ == 4 && Q >= 1024 && h->idx_N >= h->score_two_pass_min_rows && h->idx_N <= h->score_two_pass_rows && !mirror) {
-    // Splits of the two list-free sweeps: the list sweep's choice weighs list warm-up against rounds; without lists only the rounds
-    // count -- workgroups are one per CU (VGPRs), so QB x splits should sit just below a multiple of the CU count: 129 query blocks x 4
-    // splits = 2.02 rounds run as 3, x 16 = 8.06 run as 9.  At most 16 (the threshold kernel takes 16 x 16 lane maxima per query),
-    // at least 32 tiles per split.
-    int ns2 = std::min(nsplit, 16);
-    {
-      static const int force = getenv("SSE_TWO_PASS_SPLITS") ? atoi(getenv("SSE_TWO_PASS_SPLITS")) : 0;  // (env: measurement aid)
-      const int cus = h->cu_count > 0 ? h->cu_count : 256;
-      double best = 0.0;
-      for (int ns = 1; ns <= 16; ns *= 2) {
-        if (ns > 1 && NT / ns < 32) break;
-        const double r = (double)QB * ns / cus, eff = r / std::ceil(r);
-        if (eff > best + 0.02) {
-          best = eff;
-          ns2 = ns;
-        }
-      }
-      if (force == 1 || force == 2 || force == 4 || force == 8 || force == 16) ns2 = force;
-    }
-    if (phase == SCORE_REST) return 0;
-    h->two_pass_calls += 1;
-    constexpr int MID_CAP = 512;  // rows one query may collect (typically 20 - 30); more: float64 brute force for that query
-    const float eps32 = score_eps32(h);
-    const float eps_bf = eps32 + (float)(1.02 * (1.0 / 256.0 + 1.0 / 262144.0) * h->idx_norm_max);
-    if (reserve(h, h->s_qp, (size_t)QB * NQ * KG * 256 * sizeof(float))) return 1;
-    if (reserve(h, h->s_lmax, (size_t)Q * ns2 * 16 * sizeof(float))) return 1;
-    if (reserve(h, h->s_cert, (size_t)Q * sizeof(int32_t))) return 1;
-    if (reserve(h, h->s_cthr, (size_t)Q * sizeof(float)) || reserve(h, h->s_cslot, (size_t)Q * sizeof(int32_t)) ||
-        reserve(h, h->s_ccnt, (size_t)(Q + 1) * sizeof(int32_t)) || reserve(h, h->s_cbuf, (size_t)Q * MID_CAP * sizeof(int32_t)))
-      return 1;
-    HIPCHECK(h, launch_pack_rows_bf16(q, Q, S, h->s_qp.p, st));
-    HIPCHECK(h, hipMemsetAsync(h->s_ccnt.p, 0, (size_t)(Q + 1) * sizeof(int32_t), st));
-    HIPCHECK(h, hipMemsetAsync(h->s_cert.p, 0, (size_t)Q * sizeof(int32_t), st));
-    ScoreArgs m1;
-    m1.BF = 1;
-    m1.COLLECT = 1;
-    m1.idxp = (const float *)h->idxp16;
-    m1.qp = (const float *)h->s_qp.p;
-    m1.N = h->idx_N;
-    m1.Q = Q;
-    m1.KG = KG16;
-    m1.NT = (int)NT;
-    m1.QT = QT;
-    m1.NSPLIT = ns2;
-    m1.KC = 16;
-    m1.NQ = NQ;
-    m1.lane_max = (float *)h->s_lmax.p;
-    HIPCHECK(h, launch_score_topk(m1, st));
-    HIPCHECK(h, launch_lane_max_threshold(q, (const float *)h->s_lmax.p, Q, S, ns2 * 16, eps_bf, (float *)h->s_cthr.p,
-                                          (int32_t *)h->s_cslot.p, st));
-    ScoreArgs m2 = m1;
-    m2.lane_max = nullptr;
-    m2.col_thr = (const float *)h->s_cthr.p;
-    m2.col_slot = (const int32_t *)h->s_cslot.p;
-    m2.col_cnt = (int32_t *)h->s_ccnt.p;
-    m2.col_buf = (int32_t *)h->s_cbuf.p;
-    m2.col_cap = MID_CAP;
-    HIPCHECK(h, launch_score_topk(m2, st));
-    SelectArgs sel{q, h->idxp, h->idx64, m2.col_slot, m2.col_cnt, m2.col_buf, MID_CAP, out_s, out_i, (int32_t *)h->s_cert.p, h->idx_base,
-                   Q, S, k, nullptr};
-    HIPCHECK(h, launch_select_topk(sel, st));
-    // a query whose buffer overflowed (or that saw fewer than k rows): float64 brute force
-    HIPCHECK(h, launch_exact_topk(q, h->idxp, h->idx64, (const int32_t *)h->s_cert.p, out_s, out_i, h->idx_base, h->idx_N, Q, S, k, st,
-                                  counters + 2));
-    if (split) *split = 0;  // nothing is left for a SCORE_REST call
-    return 0;
-  }
-  const int POOL = std::min(Q, 1024);  // collect-buffer slots for uncertified queries (the rest: float64 brute force)
-  if (reserve(h, h->s_qp, (size_t)QB * NQ * KG * 256 * sizeof(float))) return 1;
-  if (reserve(h, h->s_ps, (size_t)Q * (bf ? NCmax : NC) * sizeof(float))) return 1;
-  if (reserve(h, h->s_pi, (size_t)Q * (bf ? NCmax : NC) * sizeof(int32_t))) return 1;
-  if (reserve(h, h->s_pb, (size_t)Q * (bf ? NCmax / 16 : nsplit) * sizeof(float))) return 1;
-  if (reserve(h, h->s_cert, (size_t)Q * sizeof(int32_t))) return 1;
-  if (reserve_collect(h, Q, POOL)) return 1;
-  if (split) *split = 1;
-  const bool first = phase != SCORE_REST, rest = phase != SCORE_FIRST;
-  // <= 32 queries (the latency path): the sweeps build their query fragments from the rows themselves -- no pack launch
-  const bool rows_direct = NQ == 1;
-  if (first && !rows_direct && !small_idx) {
-    if (bf) HIPCHECK(h, launch_pack_rows_bf16(q, Q, S, h->s_qp.p, st));
-    else HIPCHECK(h, launch_pack_rows(q, Q, S, (float *)h->s_qp.p, st));
-  }
+  return ensure_counters(h, st);
+}
+
+static unsigned long long *topk_counters(const sse_handle *h) { return (unsigned long long *)h->s_fb_cnt.p; }
+
+// the caller's side of a call: query rows [Q][S] and results [Q][k], all on the device
+struct TopkBufs {
+  const float *q;
+  double *out_s;
+  int64_t *out_i;
+};
+
+// The fields every sweep of this driver shares: Q queries in blocks of NQ tiles against the fp32 or the bf16 image of the
+// index in nsplit splits, fragments from s_qp, candidate lists in s_ps / s_pi / s_pb.
+static ScoreArgs sweep_args(const sse_handle *h, bool bf, int Q, int NQ, int nsplit) {
   ScoreArgs a;
-  if (rows_direct) {
-    a.q_rows = q;
-    a.S = S;
-  }
   a.BF = bf ? 1 : 0;
   a.idxp = bf ? (const float *)h->idxp16 : h->idxp;
   a.qp = (const float *)h->s_qp.p;
@@ -1772,150 +1706,288 @@ int score_dev_locked(sse_handle *h, const float *q, int Q, int k, double *out_s,
   a.part_bnd = (float *)h->s_pb.p;
   a.N = h->idx_N;
   a.Q = Q;
-  a.KG = bf ? KG16 : KG;
-  a.NT = (int)NT;
-  a.QT = QT;
+  a.KG = bf ? (h->idx_S + 15) / 16 : (h->idx_S + 7) / 8;
+  a.NT = (int)((h->idx_N + 31) / 32);
+  a.QT = (Q + 31) / 32;
   a.NSPLIT = nsplit;
   a.KC = 16;
   a.NQ = NQ;
-  if (first) {
-    if (small_idx) {
-      SmallIndexArgs si{q, h->idxp, a.part_scores, a.part_ids, a.part_bnd, h->idx_N, Q, S, KG, (int)NT};
-      if (small_x3) si.idx_x3 = h->idx_x3.p;
-      HIPCHECK(h, launch_score_small_index(si, st));
-    } else {
-      HIPCHECK(h, launch_score_topk(a, st));
-    }
-  }
-  RescoreArgs r;
-  r.q = q;
-  r.idx32 = h->idxp;
-  r.idx64 = h->idx64;
-  r.idx_rm = h->idx_rm_valid ? (const float *)h->idx_rm.p : nullptr;
-  r.part_scores = a.part_scores;
-  r.part_ids = a.part_ids;
-  r.part_bnd = a.part_bnd;
-  r.out_scores = out_s;
-  r.out_ids = out_i;
-  r.cert = (int32_t *)h->s_cert.p;
-  r.id_base = h->idx_base;
-  r.N = h->idx_N;
-  r.Q = Q;
-  r.S = S;
-  r.NC = NC;
-  r.k = k;
-  // |fp32 fma-chain dot - exact| <= S * 2^-24 * |q||t| (+ the f32 rounding of f64 rows); use 2x margin
-  const float eps32 = score_eps32(h);
-  r.eps = eps32;
-  r.eps32 = eps32;
-  r.col_thr = (float *)h->s_cthr.p;
-  // the follow-up launches below are queued unconditionally; this word lets their workgroups leave at once (and their grids
-  // stay small) when the re-scoring pass certified every query -- the usual call.  Two words, used in turn: a call's
-  // re-scoring pass zeroes the one the next call will count in.
-  if (first) h->uncert_word ^= 1;
-  int32_t *const uncert = (int32_t *)(counters + 4) + h->uncert_word;
-  const int follow_grid = 2 * (h->cu_count > 0 ? h->cu_count : 256);
-  r.uncert = uncert;
-  r.uncert_clear = (int32_t *)(counters + 4) + (h->uncert_word ^ 1);
-  // every query has a collect slot of its own (the usual call): the re-scoring pass hands them out (slot = query for an
-  // uncertified one) and zeroes their counters -- no memset / launch_assign_slots between the passes
-  const bool own_slots = Q <= POOL;
-  if (own_slots) {
-    r.col_slot = (int32_t *)h->s_cslot.p;
-    r.col_cnt = (int32_t *)h->s_ccnt.p;
-  }
-  // bf16 operands: |q^.t^ - q.t| <= ((1+u)^2 - 1) sum|q_i t_i| <= (2^-8 + 2^-18) |q||t|, u = 2^-9 (round to nearest)
-  if (bf) r.eps += (float)(1.02 * (1.0 / 256.0 + 1.0 / 262144.0) * h->idx_norm_max);
-  // split-bf16 candidates of the small-index scorer (DESIGN K6).  bf16 keeps 8 significant bits: hi = rne(x) leaves
-  // |x - hi| <= 2^-8 |x|, lo = rne(x - hi) leaves e = x - hi - lo with |e| <= 2^-17 |x| (and |lo| <= 2^-8 (1 + 2^-9) |x|).  The
-  // dropped terms ql.tl + eq.t + (q - eq).et are <= (2^-16 + 2 * 2^-17)(1 + 2^-7) sum|q_i t_i| <= 2^-15 (1 + 2^-6) |q||t| -- reached
-  // to 2 % by mantissas that sit halfway in both roundings.  The 3 S kept products are exact in fp32 and are added in an order
-  // the matrix pipe chooses: (3 S + 2) additions of <= 2^-24 sum|terms| each (+ the f32 rounding of f64 rows), sum|terms| <=
-  // (1 + 2^-5) sum|q_i t_i|, with the fp32 bound's 2x margin.  1.26e-4 at S = 256 (fp32: 3.1e-5); rows or queries of norm
-  // below 2^-100 are outside the claim (a lo part may underflow bf16's range).
-  if (small_x3)
-    r.eps = (float)(((1.0 + 1.0 / 64.0) / 32768.0 + 2.0 * (3 * S + 2) * 5.97e-8 * (1.0 + 1.0 / 32.0)) * h->idx_norm_max);
-  if (first) {
-    RescoreArgs rf = r;
-    if (mirror) {
-      rf.host_scores = mirror->scores;
-      rf.host_ids = mirror->ids;
-      rf.host_cert = mirror->cert;
-      rf.host_err = mirror->err;
-      rf.host_flag = mirror->flag;
-      rf.err_in = h->err_flag;
-      rf.seq = mirror->seq;
-    }
-    HIPCHECK(h, launch_rescore(rf, st));
-  }
-  if (!rest) return 0;
-  const float *qp32 = (const float *)h->s_qp.p;  // fp32 query fragments for the collect sweep
-  // (<= 32 queries skip the second chance: for one query block it is the same fp32 sweep of the whole index as the collect
-  // pass, which is final)
-  if (bf && Q > 32) {
-    // Second chance, entirely on the device (the call stays asynchronous): queries whose bf16-candidate result missed
-    // its certificate (top scores packed closer than the bf16 bound) are swept again with fp32 candidates -- the same
-    // kernels, where a workgroup whose whole query block is certified returns at once and a certified query is left
-    // alone -- before anything falls through to the collect path.
-    if (reserve(h, h->s_qp32, (size_t)QB * NQ * KG * 256 * sizeof(float))) return 1;
-    if (reserve(h, h->s_qmap, (size_t)(Q + 1) * sizeof(int32_t))) return 1;
-    if (reserve(h, h->s_qc, (size_t)QT * 32 * S * sizeof(float))) return 1;
-    HIPCHECK(h, launch_count_uncert(r.cert, Q, counters, st));
-    // the uncertified queries as a dense set: the sweep and the re-scoring below cost what THEY cost (launches sized for all
-    // Q; workgroups past the set return at once)
-    int32_t *qmap = (int32_t *)h->s_qmap.p, *qcount = qmap + Q;
-    HIPCHECK(h, launch_compact_uncert(q, r.cert, Q, S, qmap, qcount, (float *)h->s_qc.p, st));
-    if (!rows_direct) HIPCHECK(h, launch_pack_rows((const float *)h->s_qc.p, Q, S, (float *)h->s_qp32.p, st));
-    ScoreArgs a2 = a;
-    a2.BF = 0;
-    a2.idxp = h->idxp;
-    a2.qp = (const float *)h->s_qp32.p;
-    if (rows_direct) a2.q_rows = (const float *)h->s_qc.p;
-    a2.KG = KG;
-    a2.q_count = qcount;
-    a2.NSPLIT = nsplit2;
-    HIPCHECK(h, launch_score_topk(a2, st));
-    RescoreArgs r2 = r;
-    r2.q = (const float *)h->s_qc.p;
-    r2.NC = nsplit2 * 16;
-    r2.eps = eps32;
-    r2.qmap = qmap;
-    r2.q_count = qcount;
-    r2.uncert = r2.uncert_clear = nullptr;  // (the word keeps the first pass's count: an upper bound, zero only if nothing is left)
-    HIPCHECK(h, launch_rescore(r2, st));
-    qp32 = (const float *)h->s_qp32.p;  // (unused by the collect sweep: it reads the rows)
-  }
-  // What is still uncertified has its k-th score tied with (or within the fp32 bound of) rows outside the candidate
-  // lists -- e.g. an index holding many exact duplicates of a query's best rows.  Collect path: every row whose fp32
-  // score reaches (exact k-th of the candidates) - bound is gathered by a grid-wide sweep and sorted in float64:
-  // provably the exact top-k, at the cost of one more fp32 sweep for the query blocks concerned.  Launched
-  // unconditionally (no host sync); with everything certified all workgroups return at once.
-  if (!own_slots) {
-    HIPCHECK(h, hipMemsetAsync(h->s_ccnt.p, 0, (size_t)(POOL + 1) * sizeof(int32_t), st));
-    HIPCHECK(h, launch_assign_slots(r.cert, Q, POOL, (int32_t *)h->s_cslot.p, (int32_t *)h->s_ccnt.p + POOL, st));
-  }
-  ScoreArgs c = a;
-  c.BF = 0;
-  c.idxp = h->idxp;
-  c.qp = qp32;
-  c.q_rows = q;  // (the collect sweep builds its fp32 fragments from the rows: nothing packed for it)
-  c.S = S;
-  c.KG = KG;
+  return a;
+}
+
+// What the collect tails of the three routes differ in (besides the sweep they start from)
+struct CollectTail {
+  int cap;                              // rows one query may collect: SSE_COLLECT_CAP, or the two-pass route's MID_CAP
+  unsigned long long *served, *brute;   // counter words of the select and of the float64 brute force (null: not counted)
+  const int32_t *uncert;                // RescoreArgs::uncert of the call or null: the launches are sized for all queries
+  int follow_grid;
+};
+// The end of every route: `c` as a collect sweep of every row at or above a query's threshold (s_cthr) into its slot (s_cslot,
+// s_ccnt, s_cbuf), the float64 select of those rows, and the float64 brute force for whatever overflowed its buffer, saw fewer
+// than k rows or had no slot (pages of 16).  The caller has reserved and cleared the buffers and s_cert.
+static int collect_tail(sse_handle *h, ScoreArgs c, const TopkBufs &io, int k, const CollectTail &t, hipStream_t st) {
+  const int S = h->idx_S;
+  int32_t *cert = (int32_t *)h->s_cert.p;
   c.COLLECT = 1;
   c.col_thr = (const float *)h->s_cthr.p;
   c.col_slot = (const int32_t *)h->s_cslot.p;
   c.col_cnt = (int32_t *)h->s_ccnt.p;
   c.col_buf = (int32_t *)h->s_cbuf.p;
-  c.col_cap = SSE_COLLECT_CAP;
-  c.uncert = uncert;
+  c.col_cap = t.cap;
+  c.uncert = t.uncert;
   HIPCHECK(h, launch_score_topk(c, st));
-  SelectArgs sel{q, h->idxp, h->idx64, c.col_slot, c.col_cnt, c.col_buf, SSE_COLLECT_CAP, out_s, out_i, r.cert, h->idx_base, Q, S, k,
-                 counters + 1, uncert, follow_grid};
+  SelectArgs sel{io.q, h->idxp, h->idx64, c.col_slot, c.col_cnt, c.col_buf, t.cap, io.out_s, io.out_i, cert, h->idx_base, c.Q, S, k,
+                 t.served, t.uncert, t.follow_grid};
   HIPCHECK(h, launch_select_topk(sel, st));
-  // last resort (more than SSE_COLLECT_CAP rows within the bound of the k-th score, or no buffer slot left)
-  HIPCHECK(h, launch_exact_topk(q, h->idxp, h->idx64, r.cert, out_s, out_i, h->idx_base, h->idx_N, Q, S, k, st, counters + 2, uncert,
-                                follow_grid));
+  HIPCHECK(h, launch_exact_topk(io.q, h->idxp, h->idx64, cert, io.out_s, io.out_i, h->idx_base, h->idx_N, c.Q, S, k, st, t.brute,
+                                t.uncert, t.follow_grid));
   return 0;
+}
+
+// k > SSE_MAX_SELECT_K, beyond the collect path's buffers: exact float64 paging (correct for any k <= N, one workgroup per query)
+static int topk_paging(sse_handle *h, const TopkPlan &p, const TopkBufs &io, hipStream_t st) {
+  HIPCHECK(h, launch_exact_topk(io.q, h->idxp, h->idx64, nullptr, io.out_s, io.out_i, h->idx_base, h->idx_N, p.Q, p.S, p.k, st));
+  return 0;
+}
+
+// 16 < k <= SSE_MAX_SELECT_K (sse_demo.py:128-134 and webserver.py take a user-chosen nbest): candidate sweep with enough
+// per-split lists that the k-th best candidate is a tight lower bound of the k-th best row, then a collect sweep of every row
+// that can still be in the exact top-k and a float64 sort of those -- two grid-wide sweeps instead of the
+// one-workgroup-per-query float64 brute force (which stays as the fallback: more than SSE_COLLECT_CAP rows within the bound of
+// the k-th score).  Pools of 2048 queries, each a sweep shape of its own.
+static int topk_select(sse_handle *h, const TopkPlan &p, const TopkBufs &io, hipStream_t st) {
+  const int POOL = 2048, k = p.k;
+  unsigned long long *counters = topk_counters(h);
+  for (int q0 = 0; q0 < p.Q; q0 += POOL) {
+    const int Qc = std::min(POOL, p.Q - q0);
+    const TopkBufs ioc{io.q + (size_t)q0 * p.S, io.out_s + (size_t)q0 * k, io.out_i + (size_t)q0 * k};
+    SweepChunk ck;
+    if (sweep_chunk(h, Qc, ck)) return 1;
+    int nsplit = ck.nsplit;
+    // at least 4k candidates (k-th candidate close to the k-th row), at most RS_MAXNC = 4096, >= 2 tiles per split
+    const int max_split = (ck.NQ == 1) ? 256 : 128;
+    while (nsplit < max_split && nsplit * 16 < 4 * k && p.NT / (nsplit * 2) >= 2) nsplit *= 2;
+    const int NC = nsplit * 16;
+    if (reserve(h, h->s_qp, (size_t)ck.QB * ck.NQ * p.KG * 256 * sizeof(float))) return 1;
+    if (reserve(h, h->s_ps, (size_t)Qc * NC * sizeof(float))) return 1;
+    if (reserve(h, h->s_pi, (size_t)Qc * NC * sizeof(int32_t))) return 1;
+    if (reserve(h, h->s_pb, (size_t)Qc * nsplit * sizeof(float))) return 1;
+    if (reserve(h, h->s_cert, (size_t)Qc * sizeof(int32_t))) return 1;
+    if (reserve_collect(h, Qc, Qc)) return 1;
+    HIPCHECK(h, launch_pack_rows(ioc.q, Qc, p.S, (float *)h->s_qp.p, st));
+    const ScoreArgs a = sweep_args(h, false, Qc, ck.NQ, nsplit);
+    HIPCHECK(h, launch_score_topk(a, st));
+    HIPCHECK(h, launch_kth_bound(ioc.q, a.part_scores, a.part_ids, Qc, p.S, NC, k, p.eps32, (float *)h->s_cthr.p,
+                                 (int32_t *)h->s_cslot.p, st));
+    HIPCHECK(h, hipMemsetAsync(h->s_ccnt.p, 0, (size_t)(Qc + 1) * sizeof(int32_t), st));
+    HIPCHECK(h, hipMemsetAsync(h->s_cert.p, 0, (size_t)Qc * sizeof(int32_t), st));
+    if (collect_tail(h, a, ioc, k, {SSE_COLLECT_CAP, counters + 1, counters + 2, nullptr, 0}, st)) return 1;
+  }
+  return 0;
+}
+
+// Mid-size indexes under many queries: max-only sweep -> per-query threshold -> collect sweep -> float64 select (see
+// lane_max_threshold_kernel in score_topk.hip for the argument), all on the bf16 image.  Everything is final after it: no
+// certificates to follow up.
+static int topk_two_pass(sse_handle *h, const TopkPlan &p, const TopkBufs &io, hipStream_t st) {
+  constexpr int MID_CAP = 512;  // rows one query may collect (typically 20 - 30); more: float64 brute force for that query
+  const int Q = p.Q, ns2 = p.two_pass_splits;
+  h->two_pass_calls += 1;
+  if (reserve(h, h->s_qp, (size_t)p.QB * p.NQ * p.KG * 256 * sizeof(float))) return 1;
+  if (reserve(h, h->s_lmax, (size_t)Q * ns2 * 16 * sizeof(float))) return 1;
+  if (reserve(h, h->s_cert, (size_t)Q * sizeof(int32_t))) return 1;
+  if (reserve(h, h->s_cthr, (size_t)Q * sizeof(float)) || reserve(h, h->s_cslot, (size_t)Q * sizeof(int32_t)) ||
+      reserve(h, h->s_ccnt, (size_t)(Q + 1) * sizeof(int32_t)) || reserve(h, h->s_cbuf, (size_t)Q * MID_CAP * sizeof(int32_t)))
+    return 1;
+  HIPCHECK(h, launch_pack_rows_bf16(io.q, Q, p.S, h->s_qp.p, st));
+  HIPCHECK(h, hipMemsetAsync(h->s_ccnt.p, 0, (size_t)(Q + 1) * sizeof(int32_t), st));
+  HIPCHECK(h, hipMemsetAsync(h->s_cert.p, 0, (size_t)Q * sizeof(int32_t), st));
+  const ScoreArgs sweep = sweep_args(h, true, Q, p.NQ, ns2);
+  ScoreArgs m1 = sweep;
+  m1.COLLECT = 1;
+  m1.lane_max = (float *)h->s_lmax.p;
+  HIPCHECK(h, launch_score_topk(m1, st));
+  HIPCHECK(h, launch_lane_max_threshold(io.q, m1.lane_max, Q, p.S, ns2 * 16, p.eps_bf16, (float *)h->s_cthr.p, (int32_t *)h->s_cslot.p, st));
+  // (the select does not count: a query it cannot serve -- buffer overflowed, fewer than k rows -- goes to the brute force)
+  return collect_tail(h, sweep, io, p.k, {MID_CAP, nullptr, topk_counters(h) + 2, nullptr, 0}, st);
+}
+
+// Host mirror of the first stage of a call of few queries (see RescoreArgs): pinned, device-visible host pointers the
+// re-scoring pass stores results, certificates, the error flag of the encoder in front of it and -- last, released at system
+// scope -- one completion word per query through.  The host polls the words: no read-back copies, no stream synchronisation.
+struct ScoreMirror {
+  double *scores;
+  int64_t *ids;
+  int32_t *cert, *err, *flag;
+  int32_t seq;
+};
+
+// The word the follow-up launches of the Lists route read first (RescoreArgs::uncert): they are queued unconditionally by
+// the all-queued form, and the word lets their workgroups leave at once (and their grids stay small) when the re-scoring pass
+// certified every query -- the usual call.  Two words, used in turn (lists_first flips): a call's re-scoring pass zeroes the one
+// the next call will count in.
+static int32_t *lists_uncert(const sse_handle *h, int other = 0) { return (int32_t *)(topk_counters(h) + 4) + (h->uncert_word ^ other); }
+static int follow_grid(const sse_handle *h) { return 2 * (h->cu_count > 0 ? h->cu_count : 256); }
+
+// the candidate sweep of the Lists route
+static ScoreArgs lists_sweep_args(const sse_handle *h, const TopkPlan &p, const float *q) {
+  ScoreArgs a = sweep_args(h, p.bf, p.Q, p.NQ, p.nsplit);
+  if (p.rows_direct) {
+    a.q_rows = q;
+    a.S = p.S;
+  }
+  return a;
+}
+
+// the float64 re-scoring of the first stage's candidates, as both stages of the Lists route see it
+static RescoreArgs lists_rescore_args(const sse_handle *h, const TopkPlan &p, const TopkBufs &io) {
+  RescoreArgs r;
+  r.q = io.q;
+  r.idx32 = h->idxp;
+  r.idx64 = h->idx64;
+  r.idx_rm = h->idx_rm_valid ? (const float *)h->idx_rm.p : nullptr;
+  r.part_scores = (const float *)h->s_ps.p;
+  r.part_ids = (const int32_t *)h->s_pi.p;
+  r.part_bnd = (const float *)h->s_pb.p;
+  r.out_scores = io.out_s;
+  r.out_ids = io.out_i;
+  r.cert = (int32_t *)h->s_cert.p;
+  r.id_base = h->idx_base;
+  r.N = h->idx_N;
+  r.Q = p.Q;
+  r.S = p.S;
+  r.NC = p.NC;
+  r.k = p.k;
+  r.eps = p.cand_eps();
+  r.eps32 = p.eps32;
+  r.col_thr = (float *)h->s_cthr.p;
+  r.uncert = lists_uncert(h);
+  r.uncert_clear = lists_uncert(h, 1);
+  // every query has a collect slot of its own (the usual call): the re-scoring pass hands them out (slot = query for an
+  // uncertified one) and zeroes their counters -- no memset / launch_assign_slots between the passes
+  if (p.own_slots) {
+    r.col_slot = (int32_t *)h->s_cslot.p;
+    r.col_cnt = (int32_t *)h->s_ccnt.p;
+  }
+  return r;
+}
+
+// Lists route, first stage: candidate sweep (or the small-index scorer) + float64 re-scoring.  Results and certificates are
+// final for every certified query.  mirror (host form of few queries, else null): the re-scoring pass reports through it.
+static int lists_first(sse_handle *h, const TopkPlan &p, const TopkBufs &io, const ScoreMirror *mirror, hipStream_t st) {
+  const int Q = p.Q;
+  if (reserve(h, h->s_qp, (size_t)p.QB * p.NQ * p.KG * 256 * sizeof(float))) return 1;
+  if (reserve(h, h->s_ps, (size_t)Q * (p.bf ? p.NCmax : p.NC) * sizeof(float))) return 1;
+  if (reserve(h, h->s_pi, (size_t)Q * (p.bf ? p.NCmax : p.NC) * sizeof(int32_t))) return 1;
+  if (reserve(h, h->s_pb, (size_t)Q * (p.bf ? p.NCmax / 16 : p.nsplit) * sizeof(float))) return 1;
+  if (reserve(h, h->s_cert, (size_t)Q * sizeof(int32_t))) return 1;
+  if (reserve_collect(h, Q, p.POOL)) return 1;
+  if (p.small_idx) {
+    SmallIndexArgs si{io.q, h->idxp, (float *)h->s_ps.p, (int32_t *)h->s_pi.p, (float *)h->s_pb.p, h->idx_N, Q, p.S, p.KG, (int)p.NT};
+    if (p.small_x3) si.idx_x3 = h->idx_x3.p;
+    HIPCHECK(h, launch_score_small_index(si, st));
+  } else {
+    if (!p.rows_direct) {
+      if (p.bf) HIPCHECK(h, launch_pack_rows_bf16(io.q, Q, p.S, h->s_qp.p, st));
+      else HIPCHECK(h, launch_pack_rows(io.q, Q, p.S, (float *)h->s_qp.p, st));
+    }
+    HIPCHECK(h, launch_score_topk(lists_sweep_args(h, p, io.q), st));
+  }
+  h->uncert_word ^= 1;
+  RescoreArgs r = lists_rescore_args(h, p, io);
+  if (mirror) {
+    r.host_scores = mirror->scores;
+    r.host_ids = mirror->ids;
+    r.host_cert = mirror->cert;
+    r.host_err = mirror->err;
+    r.host_flag = mirror->flag;
+    r.err_in = h->err_flag;
+    r.seq = mirror->seq;
+  }
+  HIPCHECK(h, launch_rescore(r, st));
+  return 0;
+}
+
+// Second chance of the bf16 candidates, entirely on the device (the call stays asynchronous): queries whose bf16-candidate
+// result missed its certificate (top scores packed closer than the bf16 bound) are swept again with fp32 candidates -- the same
+// kernels, where a workgroup whose whole query block is certified returns at once and a certified query is left alone --
+// before anything falls through to the collect path.
+static int lists_second_chance(sse_handle *h, const TopkPlan &p, const TopkBufs &io, hipStream_t st) {
+  const int Q = p.Q;
+  if (reserve(h, h->s_qp32, (size_t)p.QB * p.NQ * p.KG * 256 * sizeof(float))) return 1;
+  if (reserve(h, h->s_qmap, (size_t)(Q + 1) * sizeof(int32_t))) return 1;
+  if (reserve(h, h->s_qc, (size_t)p.QT * 32 * p.S * sizeof(float))) return 1;
+  const RescoreArgs r = lists_rescore_args(h, p, io);
+  HIPCHECK(h, launch_count_uncert(r.cert, Q, topk_counters(h), st));
+  // the uncertified queries as a dense set: the sweep and the re-scoring below cost what THEY cost (launches sized for all
+  // Q; workgroups past the set return at once)
+  int32_t *qmap = (int32_t *)h->s_qmap.p, *qcount = qmap + Q;
+  HIPCHECK(h, launch_compact_uncert(io.q, r.cert, Q, p.S, qmap, qcount, (float *)h->s_qc.p, st));
+  if (!p.rows_direct) HIPCHECK(h, launch_pack_rows((const float *)h->s_qc.p, Q, p.S, (float *)h->s_qp32.p, st));
+  ScoreArgs a2 = lists_sweep_args(h, p, (const float *)h->s_qc.p);
+  a2.BF = 0;
+  a2.idxp = h->idxp;
+  a2.qp = (const float *)h->s_qp32.p;
+  a2.KG = p.KG;
+  a2.q_count = qcount;
+  a2.NSPLIT = p.nsplit2;
+  HIPCHECK(h, launch_score_topk(a2, st));
+  RescoreArgs r2 = r;
+  r2.q = (const float *)h->s_qc.p;
+  r2.NC = p.nsplit2 * 16;
+  r2.eps = p.eps32;
+  r2.qmap = qmap;
+  r2.q_count = qcount;
+  r2.uncert = r2.uncert_clear = nullptr;  // (the word keeps the first pass's count: an upper bound, zero only if nothing is left)
+  HIPCHECK(h, launch_rescore(r2, st));
+  return 0;
+}
+
+// Lists route, second stage, for what the first left uncertified: the second chance of bf16 candidates, then the collect
+// tail.  What is still uncertified there has its k-th score tied with (or within the fp32 bound of) rows outside the candidate
+// lists -- e.g. an index holding many exact duplicates of a query's best rows: every row whose fp32 score reaches (exact k-th
+// of the candidates) - bound is gathered by a grid-wide sweep and sorted in float64: provably the exact top-k, at the cost of
+// one more fp32 sweep for the query blocks concerned.  The all-queued form launches this unconditionally (no host sync); with
+// everything certified all workgroups return at once.
+static int lists_rest(sse_handle *h, const TopkPlan &p, const TopkBufs &io, hipStream_t st) {
+  // (<= 32 queries skip the second chance: for one query block it is the same fp32 sweep of the whole index as the collect
+  // pass, which is final)
+  const bool second = p.bf && p.Q > 32;
+  if (second && lists_second_chance(h, p, io, st)) return 1;
+  if (!p.own_slots) {
+    HIPCHECK(h, hipMemsetAsync(h->s_ccnt.p, 0, (size_t)(p.POOL + 1) * sizeof(int32_t), st));
+    HIPCHECK(h, launch_assign_slots((const int32_t *)h->s_cert.p, p.Q, p.POOL, (int32_t *)h->s_cslot.p, (int32_t *)h->s_ccnt.p + p.POOL, st));
+  }
+  ScoreArgs c = sweep_args(h, false, p.Q, p.NQ, p.nsplit);
+  if (second) c.qp = (const float *)h->s_qp32.p;  // (unused: the collect sweep builds its fp32 fragments from the rows, nothing packed for it)
+  c.q_rows = io.q;
+  c.S = p.S;
+  unsigned long long *counters = topk_counters(h);
+  // brute force: the last resort (more than SSE_COLLECT_CAP rows within the bound of the k-th score, or no buffer slot left)
+  return collect_tail(h, c, io, p.k, {SSE_COLLECT_CAP, counters + 1, counters + 2, lists_uncert(h), follow_grid(h)}, st);
+}
+
+// Everything of a call up to the point where the Lists route's certificates decide whether anything is left (p.has_rest); the
+// other routes are complete after it.
+static int topk_first(sse_handle *h, const TopkPlan &p, const TopkBufs &io, const ScoreMirror *mirror, hipStream_t st) {
+  if (p.route == TopkRoute::None) return 0;
+  if (p.route == TopkRoute::Paging) return topk_paging(h, p, io, st);
+  if (topk_prepare(h, p, st)) return 1;
+  if (p.route == TopkRoute::Select) return topk_select(h, p, io, st);
+  if (p.route == TopkRoute::TwoPass) return topk_two_pass(h, p, io, st);
+  return lists_first(h, p, io, mirror, st);
+}
+
+// sse_score_topk*_dev: every stage queued (no host sync; the follow-up stage returns at once when every query is certified).
+// The host-buffer entry points (score_to_host_locked) look at the certificates in between and usually skip the second stage:
+// the common call saves five to nine empty launches (~4.5 us each: a third of a single-query call,
+// profiles/r02z_demo_kernel_stats.csv).
+int score_dev_locked(sse_handle *h, const float *q, int Q, int k, double *out_s, int64_t *out_i, hipStream_t st) {
+  TopkPlan p;
+  if (topk_plan(h, Q, k, p)) return 1;
+  const TopkBufs io{q, out_s, out_i};
+  if (topk_first(h, p, io, nullptr, st)) return 1;
+  return p.has_rest ? lists_rest(h, p, io, st) : 0;
 }
 
 }  // namespace
@@ -2217,25 +2289,59 @@ int sse_encode(sse_handle *h, int side, const int32_t *ids_host, int32_t B, int3
   return 0;
 }
 
-// Scores + ids of Q queries (device rows q_dev) into host buffers: first phase, ONE pinned read-back of [scores | ids |
-// certificates] with one synchronisation, and the follow-up stages only when some query is not certified.
-// err_bits: (optional) the device error flag rides along in the first read-back (an encoder launched just before on the
+// The pinned block of one host-form scoring call: [scores | ids | certificates | error flag | completion words]
+struct ScorePin {
+  char *base;
+  size_t nb;  // bytes of the scores, and of the ids
+  int32_t *cert, *flag, *done;
+};
+
+// First results through the mirror: the host polls the completion words the re-scoring pass stores last; scores, ids,
+// certificates and the error flag are in the block when they are all there
+static int poll_mirror(sse_handle *h, const ScorePin &pin, int Q, int32_t seq, hipStream_t st) {
+  const auto t0 = std::chrono::steady_clock::now();
+  bool synced = false;
+  for (;;) {
+    bool all = true;
+    for (int i = 0; i < Q && all; ++i) all = __atomic_load_n(pin.done + i, __ATOMIC_ACQUIRE) == seq;
+    if (all) return 0;
+    if (synced) return fail(h, "the re-scoring pass did not report completion");
+    if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(3)) {
+      HIPCHECK(h, hipStreamSynchronize(st));  // (a launch that failed shows up here)
+      synced = true;
+    }
+  }
+}
+
+// Results by copies: scores and ids, with them (certs / err) the certificates and the device error flag, one synchronisation
+static int copy_back(sse_handle *h, const ScorePin &pin, int Q, bool certs, bool err, hipStream_t st) {
+  HIPCHECK(h, hipMemcpyAsync(pin.base, h->s_os.p, pin.nb, hipMemcpyDeviceToHost, st));
+  HIPCHECK(h, hipMemcpyAsync(pin.base + pin.nb, h->s_oi.p, pin.nb, hipMemcpyDeviceToHost, st));
+  if (certs) HIPCHECK(h, hipMemcpyAsync(pin.cert, h->s_cert.p, (size_t)Q * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (err) HIPCHECK(h, hipMemcpyAsync(pin.flag, h->err_flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHECK(h, sync_stream(st));
+  return 0;
+}
+
+// Scores + ids of Q queries (device rows q_dev) into host buffers: the first stage, its results, certificates and error flag
+// read back at once (polled through the mirror for few queries, else one pinned read-back with one synchronisation), and the
+// second stage with a read-back of its own only when some query is not certified.
+// err_bits: (optional) the device error flag rides along with the first results (an encoder launched just before on the
 // same stream with its check deferred); when it comes back non-zero the outputs are not written.
 static int score_to_host_locked(sse_handle *h, const float *q_dev, int Q, int k, double *out_scores, int64_t *out_ids,
                                 int32_t *err_bits = nullptr) {
   hipStream_t st = nullptr;
   if (reserve(h, h->s_os, (size_t)Q * k * sizeof(double))) return 1;
   if (reserve(h, h->s_oi, (size_t)Q * k * sizeof(int64_t))) return 1;
-  // pinned block: [scores | ids | certificates | error flag | completion words]
   const size_t nb = (size_t)Q * k * 8, need = 2 * nb + (size_t)(2 * Q + 1) * sizeof(int32_t);
   if (ensure_pin(h, need)) return 1;
-  char *pin = (char *)h->pin;
-  int32_t *cert = (int32_t *)(pin + 2 * nb), *flag = cert + Q, *done = flag + 1;
-  int split = 0;
+  char *base = (char *)h->pin;
+  int32_t *cert = (int32_t *)(base + 2 * nb);
+  const ScorePin pin{base, nb, cert, cert + Q, cert + Q + 1};
   // few queries (the demo / web call): the re-scoring pass stores its results through the pinned pointers itself and the
   // host polls the completion words -- three read-back copies and the stream synchronisation were ~40 us of a 0.19 ms call
   const bool use_mirror = Q <= 64 && k <= 16;
-  ScoreMirror hm{(double *)pin, (int64_t *)(pin + nb), cert, flag, done, 0};
+  ScoreMirror hm{(double *)base, (int64_t *)(base + nb), pin.cert, pin.flag, pin.done, 0};
   if (use_mirror) {
     h->score_seq = (h->score_seq == INT32_MAX) ? 1 : h->score_seq + 1;
     hm.seq = h->score_seq;
@@ -2243,59 +2349,28 @@ static int score_to_host_locked(sse_handle *h, const float *q_dev, int Q, int k,
     // shapes (scores, int64 ids, certificates) and with sse_encode's read-back: a stale word could equal this call's
     // sequence number.  Nothing of this handle is in flight here (the previous call returned after its last poll / sync),
     // so the host clears them before the launch.
-    for (int i = 0; i < Q; ++i) __atomic_store_n(done + i, 0, __ATOMIC_RELAXED);
-    __atomic_store_n(flag, 0, __ATOMIC_RELEASE);
+    for (int i = 0; i < Q; ++i) __atomic_store_n(pin.done + i, 0, __ATOMIC_RELAXED);
+    __atomic_store_n(pin.flag, 0, __ATOMIC_RELEASE);
   }
-  if (score_dev_locked(h, q_dev, Q, k, (double *)h->s_os.p, (int64_t *)h->s_oi.p, st, SCORE_FIRST, &split, use_mirror ? &hm : nullptr))
-    return 1;
-  int pass = 0;
-  if (use_mirror && split) {
-    const auto t0 = std::chrono::steady_clock::now();
-    bool synced = false;
-    for (;;) {
-      bool all = true;
-      for (int i = 0; i < Q && all; ++i) all = __atomic_load_n(done + i, __ATOMIC_ACQUIRE) == hm.seq;
-      if (all) break;
-      if (synced) return fail(h, "the re-scoring pass did not report completion");
-      if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(3)) {
-        HIPCHECK(h, hipStreamSynchronize(st));  // (a launch that failed shows up here)
-        synced = true;
-      }
-    }
-    if (err_bits) {
-      *err_bits = *flag;
-      if (*flag) return 0;  // the queries were not what the caller meant: it looks at the flag first
-    }
-    bool open_q = false;
-    for (int i = 0; i < Q && !open_q; ++i) open_q = cert[i] == 0;
-    if (open_q) {
-      // rare: ties / near-ties at the k-th score, or scores packed closer than the bf16 bound
-      if (score_dev_locked(h, q_dev, Q, k, (double *)h->s_os.p, (int64_t *)h->s_oi.p, st, SCORE_REST)) return 1;
-      pass = 1;
-    } else {
-      pass = 2;
-    }
+  TopkPlan p;
+  if (topk_plan(h, Q, k, p)) return 1;
+  const TopkBufs io{q_dev, (double *)h->s_os.p, (int64_t *)h->s_oi.p};
+  if (topk_first(h, p, io, use_mirror ? &hm : nullptr, st)) return 1;
+  const bool polled = use_mirror && p.has_rest;  // (the mirror belongs to lists_first)
+  if (polled ? poll_mirror(h, pin, Q, hm.seq, st) : copy_back(h, pin, Q, p.has_rest, err_bits != nullptr, st)) return 1;
+  if (err_bits) {
+    *err_bits = *pin.flag;
+    if (*pin.flag) return 0;  // the queries were not what the caller meant: it looks at the flag first
   }
-  for (; pass < 2; ++pass) {
-    HIPCHECK(h, hipMemcpyAsync(pin, h->s_os.p, nb, hipMemcpyDeviceToHost, st));
-    HIPCHECK(h, hipMemcpyAsync(pin + nb, h->s_oi.p, nb, hipMemcpyDeviceToHost, st));
-    if (split && pass == 0) HIPCHECK(h, hipMemcpyAsync(cert, h->s_cert.p, (size_t)Q * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (err_bits && pass == 0) HIPCHECK(h, hipMemcpyAsync(flag, h->err_flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHECK(h, sync_stream(st));
-    if (err_bits && pass == 0) {
-      *err_bits = *flag;
-      if (*flag) return 0;  // the queries were not what the caller meant: it looks at the flag first
-    }
-    bool open_q = false;
-    if (split && pass == 0) {
-      for (int i = 0; i < Q && !open_q; ++i) open_q = cert[i] == 0;
-    }
-    if (!open_q) break;
+  bool open_q = false;
+  for (int i = 0; i < Q && p.has_rest && !open_q; ++i) open_q = pin.cert[i] == 0;
+  if (open_q) {
     // rare: ties / near-ties at the k-th score, or scores packed closer than the bf16 bound
-    if (score_dev_locked(h, q_dev, Q, k, (double *)h->s_os.p, (int64_t *)h->s_oi.p, st, SCORE_REST)) return 1;
+    if (lists_rest(h, p, io, st)) return 1;
+    if (copy_back(h, pin, Q, false, false, st)) return 1;
   }
-  memcpy(out_scores, pin, nb);
-  memcpy(out_ids, pin + nb, nb);
+  memcpy(out_scores, pin.base, nb);
+  memcpy(out_ids, pin.base + nb, nb);
   return 0;
 }
 
@@ -2401,7 +2476,7 @@ static int read_dev_counter(sse_handle *h, const DevCounters &g, int word, int64
 }
 
 // The options that are one int of the handle: a switch (message null; stored as value != 0) or a value in [min, max], refused
-// with `message` outside.  What each one does stands beside its member in sse_handle.h.
+// with `message` outside.  What each one does stands beside its member in struct sse_handle (above).
 const struct {
   const char *name;
   int sse_handle::*member;

@@ -29,7 +29,7 @@ def _host_topk(h, q, k):
 
 
 def _dev_topk(h, q, k):
-    """sse_score_topk_dev: SCORE_ALL, every stage queued, no host check in between."""
+    """sse_score_topk_dev: every stage queued (first stage, then lists_rest), no host check in between."""
     import torch
     dev = torch.device("cuda:0")
     qd = torch.from_numpy(np.ascontiguousarray(q, np.float32)).to(dev)

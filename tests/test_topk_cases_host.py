@@ -60,7 +60,7 @@ def test_the_tie_group_reaches_the_places_it_is_meant_to():
     c = TC.BY_NAME["tie_across_kth"]
     _, _, group = TC.inputs(c)
     assert (group < 32).sum() >= 2 and (group >= (c.N // 32) * 32).sum() >= 2 and c.N % 32
-    # the select route sweeps this index in 8 splits of 8 tiles (63 tiles; score_select_locked doubles nsplit up to 4 k candidates)
+    # the select route sweeps this index in 8 splits of 8 tiles (63 tiles; topk_select doubles nsplit up to 4 k candidates)
     assert len(set((group // 32) // 8)) == 8
     ws, wi = TC.expected(c)
     assert np.array_equal(wi[c.planted[0]], group[:20]) and (ws[c.planted[0]] == ws[c.planted[0], 0]).all()

@@ -12,7 +12,7 @@ results must pass.  The counter deltas a call must cause are part of the case; t
                   SSE_COLLECT_CAP = 4096 rows at or above the threshold) goes to exact_topk_query, which adds 1 to
                   score_bruteforce_queries on the first page only
   k > 1024        launch_exact_topk is given no counter: both stay
-  k <= 16         an uncertified query takes a collect slot (1024 per call, POOL in score_dev_locked) and is served by the
+  k <= 16         an uncertified query takes a collect slot (1024 per call, TopkPlan::POOL set by topk_plan) and is served by the
                   select kernel unless its buffer overflows; without a slot, or after an overflow: brute force
 
 No GPU import here."""
@@ -24,7 +24,7 @@ from oracle import sse_oracle as O
 
 BASE = 1_000_000_007      # a shard's first global row id: not a multiple of anything, above 2^29
 COLLECT_CAP = 4096        # SSE_COLLECT_CAP
-SLOT_POOL = 1024          # POOL of score_dev_locked
+SLOT_POOL = 1024          # TopkPlan::POOL (topk_plan in csrc/sse_api.hip)
 
 
 class Case:
