@@ -371,6 +371,46 @@ int sse_score_topk_after_dev(sse_handle *h, const float *q_dev, int32_t Q, int32
                              const int64_t *after_id_dev, const uint64_t *q_any_dev, const uint64_t *q_none_dev,
                              double *out_scores_dev, int64_t *out_ids_dev, int32_t *out_counts_dev, void *stream);
 
+/* The confusions of a training source: the best k index rows that are NOT among its verified targets and score at or above a
+ * floor derived from them.  The reference declares get_hard_learning_train_batch and compute_training_confusion_sampes and
+ * leaves both empty (data.py:124-129: "Not implemented yet."); the only negatives it trains on are uniform draws
+ * (data.py:108-114).  A hard negative matters when it scores near or above the source's best verified target; that score
+ * differs per query and is formed here on the device, so mining is one call with no host round trip.
+ *   Positives: pos_ids is [Q][n_pos], 1 <= n_pos <= 64, the layout and cap of excl_ids.  Entries outside
+ *     [id_base, id_base + N) (a padding value such as -1, ids of another shard) are ignored, duplicates are allowed.  P(q) is
+ *     the set of in-range entries of row q.
+ *   Best positive: (m, b) is the first of {(score64(q, p), p) : p in P(q)} by score descending, then ascending id, where
+ *     score64 is the float64 dot product sse_score_topk returns for that row, bit for bit.  P(q) empty: (-inf, INT64_MAX).
+ *     out_pos_score / out_pos_id [Q] receive (m, b); either may be NULL.
+ *   Floor: f = m - margin, formed once in IEEE double on the device.  margin is finite or +inf; margin = +inf or an empty P(q)
+ *     give f = -inf, no cut.
+ *   Row r is a CONFUSION of q iff id_base + r is not in P(q) and score64(q, r) >= f.
+ *   out_counts [Q]: c = min(k, confusions of q).
+ *   out_scores / out_ids [Q][k]: columns 0 .. c of row q are exactly the columns of sse_score_topk(..., k = N) for that query
+ *     with the positives and the rows below f removed -- the same float64 score bits, score descending, equal scores by
+ *     ascending id, ids including id_base; columns c .. k hold (-inf, INT64_MAX).  1 <= k <= 1024; k may exceed N.
+ * The call takes no tag masks: every row is tag-eligible whatever tags the index carries, and no tile is skipped.  With
+ * margin = +inf the columns are those of sse_score_topk_filtered(excl_ids = pos_ids) without masks.  With e the certified fp32
+ * bound of the query, a first kernel scores the positives in float64 and forms f and flo = (f - e) rounded down to fp32; the
+ * filtered call's fp32 MFMA sweep keeps maxima over disjoint row sets; the collect threshold is the larger of the filtered
+ * call's (the (k + n_pos)-th largest maximum less 2 e) and flo: a row of the answer has score64 >= f, hence an fp32 score
+ * >= f - e >= flo, and it is among the best k non-positives, which the filtered call's argument puts at or above the other
+ * term.  The same sweep again collects every row at or above the threshold (counter "score_confusions_collected_rows": rows
+ * collected, the positives among them included); those are re-scored in float64 without the positives, the rows below f
+ * dropped, the rest sorted.  A query with more than 4096 collected rows is served by a float64 sweep of the whole index with
+ * the same tests ("score_confusions_bruteforce_queries"); "score_confusions_floor_queries" counts the queries whose
+ * threshold is flo.  Only the float64 comparison decides membership.  Scratch is bounded by the chunk of 4096 queries.  Rows
+ * or queries of norm below 2^-100 and non-finite input are outside the claim (no fault).
+ * Q == 0 succeeds.  No index, k or n_pos out of range, a margin that is NaN or -inf, pos_ids == NULL: error with a message,
+ * decided on the host before anything is queued, no output written, the handle stays usable.  The host form runs on the null
+ * stream and synchronises; the _dev form takes device pointers, enqueues on `stream` and never waits for the device. */
+int sse_score_confusions(sse_handle *h, const float *q_host, int32_t Q, int32_t k, const int64_t *pos_ids, int32_t n_pos,
+                         double margin, double *out_scores, int64_t *out_ids, int32_t *out_counts, double *out_pos_score,
+                         int64_t *out_pos_id);
+int sse_score_confusions_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, const int64_t *pos_ids_dev,
+                             int32_t n_pos, double margin, double *out_scores_dev, int64_t *out_ids_dev,
+                             int32_t *out_counts_dev, double *out_pos_score_dev, int64_t *out_pos_id_dev, void *stream);
+
 /* encode + score in one call, the encodings never leaving the device: session.run([src_seq_embedding | norm_...])
  * followed by np.dot + getSortedResults[:k] as sse_demo.py:121-129, webserver.py:144-151 (and the three other routes)
  * and sse_evaluator.py:107-111 do per query / batch.  enc_out_host (may be NULL) also receives the [B,S] encodings. */

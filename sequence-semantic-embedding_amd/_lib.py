@@ -61,6 +61,8 @@ SYMBOLS = {
     "sse_score_topk_grouped_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "sse_score_topk_after": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "sse_score_topk_after_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sse_score_confusions": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P]),
+    "sse_score_confusions_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P]),
     "sse_encode_score_topk": (C.c_int, [_P, C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_merge_topk_dev": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_merge_topk_strided_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
@@ -502,6 +504,42 @@ class Handle(object):
         None / 0), enqueued on `stream`."""
         self.check(self.lib.sse_score_topk_after_dev(self._h, q_ptr, int(Q), int(k), after_score_ptr or None, after_id_ptr or None,
                                                      any_ptr or None, none_ptr or None, scores_ptr, ids_ptr, counts_ptr, stream))
+
+    def score_confusions(self, queries, k, positives, margin=np.inf):
+        """The k best rows that are not among a query's positives and score at or above (its best positive's score) - margin
+        (data.py:124-129 declares the mining and leaves it empty).  positives: int64 [Q, n_pos] or a sequence of Q sequences
+        of row ids, padded with -1 (1 <= n_pos <= 64 after padding; ids outside the index are ignored); margin: finite or
+        +inf (no cut).  Returns (scores float64 [Q,k], ids int64 [Q,k], counts int32 [Q], pos_scores float64 [Q], pos_ids
+        int64 [Q]): the first counts[q] columns are score_topk's columns with the positives and the rows below the floor
+        removed, the rest hold (-inf, INT64_MAX); (pos_scores, pos_ids) is the best positive, (-inf, INT64_MAX) without one."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError("queries must be [Q,S]")
+        Q, k = q.shape[0], int(k)
+        if isinstance(positives, np.ndarray) and positives.ndim == 2:
+            pos = np.ascontiguousarray(positives, dtype=np.int64)
+        else:
+            rows = [np.asarray(p, np.int64).reshape(-1) for p in positives]
+            pos = np.full((len(rows), max([len(r) for r in rows] + [1])), -1, np.int64)   # -1: no row has this id
+            for i, r in enumerate(rows):
+                pos[i, :len(r)] = r
+        if pos.shape[0] != Q:
+            raise ValueError("positives must be int64 [Q, n_pos]")
+        scores = np.empty((Q, max(k, 0)), np.float64)
+        ids = np.empty((Q, max(k, 0)), np.int64)
+        counts = np.empty(Q, np.int32)
+        pos_scores = np.empty(Q, np.float64)
+        pos_ids = np.empty(Q, np.int64)
+        self.check(self.lib.sse_score_confusions(self._h, _ptr(q), Q, k, _ptr(pos), pos.shape[1], float(margin), _ptr(scores),
+                                                 _ptr(ids), _ptr(counts), _ptr(pos_scores), _ptr(pos_ids)))
+        return scores, ids, counts, pos_scores, pos_ids
+
+    def score_confusions_dev(self, q_ptr, Q, k, pos_ptr, n_pos, margin, scores_ptr, ids_ptr, counts_ptr, pos_score_ptr=None,
+                             pos_id_ptr=None, stream=0):
+        """score_confusions on device pointers (pos_score_ptr / pos_id_ptr may be None / 0), enqueued on `stream`."""
+        self.check(self.lib.sse_score_confusions_dev(self._h, q_ptr, int(Q), int(k), pos_ptr or None, int(n_pos), float(margin),
+                                                     scores_ptr, ids_ptr, counts_ptr, pos_score_ptr or None, pos_id_ptr or None,
+                                                     stream))
 
     def merge_topk_strided_dev(self, in_s, in_i, shard_stride, P, Q, k, out_s, out_i, stream=0):
         self.check(self.lib.sse_merge_topk_strided_dev(self._h, in_s, in_i, int(shard_stride), P, Q, k, out_s, out_i, stream))

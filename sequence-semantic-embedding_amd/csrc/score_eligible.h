@@ -1,5 +1,5 @@
-// The stages sse_score_topk_filtered, sse_score_topk_grouped and sse_score_topk_after share (score_filtered.hip,
-// score_grouped.hip, score_after.hip; DESIGN K6g / K6h / K6j), each written once:
+// The stages sse_score_topk_filtered, sse_score_topk_grouped, sse_score_topk_after and sse_score_confusions share
+// (score_filtered.hip, score_grouped.hip, score_after.hip, score_confusions.hip; DESIGN K6g / K6h / K6j / K6k), each written once:
 //   eligible_sweep_kernel<NQ, Stage>
 //                               the shared fp32 sweep (score_sweep.h) over tag-eligible rows: the block's OR of q_any and the
 //                               tile skip, the tail-tile row mask, the 16 tag words and the eligibility masks, then either the
@@ -11,6 +11,7 @@
 //   eligible_select_kernel<Sel> the buffer re-scored in float64 or -- buffer overflow -- the float64 sweep of the whole index
 //                               with its cuts, then the final reduction and the output.  A Sel supplies which rows are used,
 //                               which (score64, id) are kept, whether entries carry a group and how the area is reduced.
+//   ft_excluded                 is an id among a query's list of at most 64 (exclusions, positives)?
 //   eligible_args_ok, launch_eligible_sweep, launch_eligible_select
 //                               the launchers' argument checks, the NQ dispatch and the select launch.
 #pragma once
@@ -230,6 +231,12 @@ __device__ __forceinline__ int ft_reduce(unsigned long long *skey, int *srow, in
   }
   ft_sort_entries(skey, srow, n2, tid);
   return c;
+}
+
+// is id among the query's exclusion list?  One lane per entry (n_excl <= 64); the answer is wave-uniform.
+__device__ __forceinline__ bool ft_excluded(const int64_t *ex, int n_excl, int64_t id, int lane) {
+  if (n_excl == 0) return false;
+  return __ballot(lane < n_excl && ex[lane] == id) != 0ull;
 }
 
 // What a select stage does unless it says otherwise: every tag-eligible row is used, every re-scored row is kept, entries

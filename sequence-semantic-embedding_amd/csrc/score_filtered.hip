@@ -39,12 +39,6 @@ __global__ __launch_bounds__(256) void filtered_threshold_kernel(FilteredArgs a)
   if (tid == 0) a.thr[p] = ft_collect_threshold(th_key, a.NV, a.k + a.n_excl, ft_score_bound(a.eps32, s_qn));
 }
 
-// is id among the query's exclusion list?  One lane per entry (n_excl <= 64); the answer is wave-uniform.
-__device__ __forceinline__ bool ft_excluded(const int64_t *ex, int n_excl, int64_t id, int lane) {
-  if (n_excl == 0) return false;
-  return __ballot(lane < n_excl && ex[lane] == id) != 0ull;
-}
-
 // excluded ids are not re-scored (nor is a wave's group of four none of whose rows is used)
 struct FilteredSelect : PlainSelect {
   struct Query {
@@ -71,7 +65,15 @@ hipError_t launch_score_filtered(const FilteredArgs &a, hipStream_t st) {
   return launch_eligible_select<FilteredSelect>({a}, st);
 }
 
-// the collect sweep alone (stage 3), for callers with a threshold of their own: sse_score_topk_grouped (score_grouped.hip)
+// the max sweep alone (stage 1), for callers with a threshold stage of their own: sse_score_confusions (score_confusions.hip)
+hipError_t launch_filtered_max(const FilteredArgs &a, hipStream_t st) {
+  if (a.P <= 0) return hipSuccess;
+  if (!eligible_args_ok(a, true)) return hipErrorInvalidValue;
+  return launch_eligible_sweep<FilteredMaxStage>({a}, st);
+}
+
+// the collect sweep alone (stage 3), for callers with a threshold of their own: sse_score_topk_grouped (score_grouped.hip),
+// sse_score_confusions
 hipError_t launch_filtered_collect(const FilteredArgs &a, hipStream_t st) {
   if (a.P <= 0) return hipSuccess;
   if (!eligible_args_ok(a, false)) return hipErrorInvalidValue;

@@ -203,7 +203,11 @@ struct sse_handle {
   // [P] lo, [P] hi), the two "score_after_*" counters.  Maxima, thresholds and row buffers are the filtered call's.
   DevBuf s_af_bnd, s_af_cnt;
   bool af_cnt_init = false;
-  // staging of the host forms of the five calls above (stage_in): they hold the handle's mutex and finish all device work
+  // confusions of a query (sse_score_confusions*, score_confusions.hip): the floors of a chunk ([P] f as double, [P] flo), the
+  // three "score_confusions_*" counters.  Maxima, thresholds and row buffers are the filtered call's.
+  DevBuf s_cf_bnd, s_cf_cnt;
+  bool cf_cnt_init = false;
+  // staging of the host forms of the six calls above (stage_in): they hold the handle's mutex and finish all device work
   // before they return, so one buffer serves them all
   DevBuf s_stage;
   // forward-only pair loss (sse_eval_loss*, eval_loss.hip).  Option "eval_chunk_rows": pair rows staged and encoded per chunk (even).
@@ -1527,6 +1531,49 @@ static int score_after_dev_locked(sse_handle *h, const TopkIo &io, int Q, int k,
   return 0;
 }
 
+static const TopkCall CALL_CONFUSIONS = {"sse_score_confusions", SSE_CONFUSIONS_MAX_K, false};
+
+// argument errors of sse_score_confusions*, all decidable on the host
+static int score_confusions_check(sse_handle *h, int Q, int k, const void *pos_ids, int n_pos, double margin) {
+  if (score_topk_check(h, CALL_CONFUSIONS, Q, k, nullptr, nullptr)) return 1;
+  if (n_pos < 1 || n_pos > SSE_CONFUSIONS_MAX_POS)
+    return fail(h, "%s: n_pos = %d is not in [1, %d]", CALL_CONFUSIONS.name, n_pos, SSE_CONFUSIONS_MAX_POS);
+  if (!(margin > -INFINITY)) return fail(h, "%s: margin = %g is neither finite nor +inf", CALL_CONFUSIONS.name, margin);
+  if (!pos_ids) return fail(h, "%s: pos_ids is NULL", CALL_CONFUSIONS.name);
+  return 0;
+}
+
+// sse_score_confusions*: the filtered call's chunks, run without tags, with the floors beside them (DESIGN K6k): [P] f as
+// double, [P] flo.  The positives take the place of the exclusion list.
+static int score_confusions_dev_locked(sse_handle *h, const TopkIo &io, int Q, int k, const int64_t *pos, int n_pos, double margin,
+                                       double *out_ps, int64_t *out_pi, hipStream_t st) {
+  const int64_t NT = (h->idx_N + 31) / 32;
+  if (ensure_zeroed_once(h, h->s_cf_cnt, h->cf_cnt_init, 3, st)) return 1;
+  ConfusionArgs g;
+  FilteredArgs &a = g.f;
+  fill_filtered_common(h, a, k, n_pos, h->s_cf_cnt);
+  a.tags = a.tile_sum = nullptr;  // every row is tag-eligible
+  a.skip = 0;
+  g.margin = margin;
+  for (int q0 = 0; q0 < Q; q0 += TOPK_POOL) {
+    const int P = std::min(TOPK_POOL, Q - q0);
+    SweepChunk ck;
+    if (sweep_chunk(h, P, ck)) return 1;
+    const int nsplit = split_for_maxima(ck.nsplit, 2 * (k + n_pos), NT);
+    if (topk_chunk(h, a, io, q0, P, ck.NQ, nsplit, h->s_ft_max, (size_t)P * std::min(nsplit, 16) * 256 * sizeof(uint32_t), st, &h->s_cf_bnd,
+                   (size_t)P * (sizeof(double) + sizeof(float))))
+      return 1;
+    a.excl = pos + (size_t)q0 * n_pos;
+    a.maxima = (uint32_t *)h->s_ft_max.p;
+    g.floor64 = (double *)h->s_cf_bnd.p;
+    g.flo = (float *)(g.floor64 + P);
+    g.out_pos_score = out_ps ? out_ps + q0 : nullptr;
+    g.out_pos_id = out_pi ? out_pi + q0 : nullptr;
+    HIPCHECK(h, launch_score_confusions(g, st));
+  }
+  return 0;
+}
+
 // sse_index_set_groups*: the keys copied behind the index (device to device on `st`, or from the host).  Nothing changes
 // before every check and allocation has passed.
 static int index_set_groups_locked(sse_handle *h, const int64_t *groups, int64_t N, bool from_host, hipStream_t st) {
@@ -2409,11 +2456,12 @@ struct DevCounters {
   bool sse_handle::*init;
   int words;  // read back together
 };
-enum { CG_RANK, CG_ABOVE, CG_FILTERED, CG_GROUPED, CG_AFTER, CG_TOPK, CG_DEV_COUNT, CG_HOST = CG_DEV_COUNT, CG_PATH, CG_COOP };
+enum { CG_RANK, CG_ABOVE, CG_FILTERED, CG_GROUPED, CG_AFTER, CG_CONFUSIONS, CG_TOPK, CG_DEV_COUNT, CG_HOST = CG_DEV_COUNT, CG_PATH, CG_COOP };
 const DevCounters DEV_COUNTERS[CG_DEV_COUNT] = {
     {&sse_handle::s_rk_cnt, &sse_handle::rk_cnt_init, 2}, {&sse_handle::s_ab_cnt, &sse_handle::ab_cnt_init, 3},
     {&sse_handle::s_ft_cnt, &sse_handle::ft_cnt_init, 3}, {&sse_handle::s_gp_cnt, &sse_handle::gp_cnt_init, 3},
-    {&sse_handle::s_af_cnt, &sse_handle::af_cnt_init, 3}, {&sse_handle::s_fb_cnt, &sse_handle::fb_cnt_init, 4}};
+    {&sse_handle::s_af_cnt, &sse_handle::af_cnt_init, 3}, {&sse_handle::s_cf_cnt, &sse_handle::cf_cnt_init, 3},
+    {&sse_handle::s_fb_cnt, &sse_handle::fb_cnt_init, 4}};
 int64_t sse_handle::*const HOST_COUNTERS[] = {&sse_handle::persist_fallbacks, &sse_handle::two_pass_calls, &sse_handle::pad_sorted_calls,
                                               &sse_handle::eval_paired_calls, &sse_handle::x_table_builds};
 
@@ -2457,6 +2505,11 @@ const struct {
     {"score_grouped_bruteforce_queries", CG_GROUPED, 1},
     {"score_after_collected_rows", CG_AFTER, 0},
     {"score_after_bruteforce_queries", CG_AFTER, 1},
+    // sse_score_confusions* (score_confusions.hip): rows collected for the select stage, queries of the float64 sweep, queries
+    // whose stored collect threshold is the floor term
+    {"score_confusions_collected_rows", CG_CONFUSIONS, 0},
+    {"score_confusions_bruteforce_queries", CG_CONFUSIONS, 1},
+    {"score_confusions_floor_queries", CG_CONFUSIONS, 2},
     // sse_score_topk* (score_topk.hip): queries whose bf16-candidate result missed its certificate, queries served by the
     // collect path, queries that fell through to the float64 brute force
     {"score_bf16_second_chance_queries", CG_TOPK, 0},
@@ -2823,6 +2876,34 @@ int sse_score_topk_after(sse_handle *h, const float *q_host, int32_t Q, int32_t 
   if (stage_in(h, p)) return 1;
   const TopkIo io{p[6].as<float>(), p[4].as<uint64_t>(), p[5].as<uint64_t>(), p[0].as<double>(), p[1].as<int64_t>(), p[7].as<int32_t>()};
   if (score_after_dev_locked(h, io, Q, k, p[2].as<double>(), p[3].as<int64_t>(), nullptr)) return 1;
+  HIPCHECK(h, sync_stream(nullptr));
+  return stage_out(h, p);
+}
+
+int sse_score_confusions_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, const int64_t *pos_ids_dev, int32_t n_pos,
+                             double margin, double *out_scores_dev, int64_t *out_ids_dev, int32_t *out_counts_dev,
+                             double *out_pos_score_dev, int64_t *out_pos_id_dev, void *stream) {
+  SSE_ENTER(h);
+  if (score_confusions_check(h, Q, k, pos_ids_dev, n_pos, margin)) return 1;
+  if (Q == 0) return 0;
+  if (!q_dev || !out_scores_dev || !out_ids_dev || !out_counts_dev) return fail(h, "bad arguments to sse_score_confusions");
+  const TopkIo io{q_dev, nullptr, nullptr, out_scores_dev, out_ids_dev, out_counts_dev};
+  return score_confusions_dev_locked(h, io, Q, k, pos_ids_dev, n_pos, margin, out_pos_score_dev, out_pos_id_dev, (hipStream_t)stream);
+}
+
+int sse_score_confusions(sse_handle *h, const float *q_host, int32_t Q, int32_t k, const int64_t *pos_ids, int32_t n_pos,
+                         double margin, double *out_scores, int64_t *out_ids, int32_t *out_counts, double *out_pos_score,
+                         int64_t *out_pos_id) {
+  SSE_ENTER(h);
+  if (score_confusions_check(h, Q, k, pos_ids, n_pos, margin)) return 1;
+  if (Q == 0) return 0;
+  if (!q_host || !out_scores || !out_ids || !out_counts) return fail(h, "bad arguments to sse_score_confusions");
+  const size_t o8 = (size_t)Q * k * 8, m8 = (size_t)Q * 8;
+  StagePiece p[] = {{o8, nullptr, out_scores}, {o8, nullptr, out_ids}, {m8, nullptr, out_pos_score}, {m8, nullptr, out_pos_id},
+                    {m8 * n_pos, pos_ids}, {(size_t)Q * h->idx_S * sizeof(float), q_host}, {(size_t)Q * 4, nullptr, out_counts}};
+  if (stage_in(h, p)) return 1;
+  const TopkIo io{p[5].as<float>(), nullptr, nullptr, p[0].as<double>(), p[1].as<int64_t>(), p[6].as<int32_t>()};
+  if (score_confusions_dev_locked(h, io, Q, k, p[4].as<int64_t>(), n_pos, margin, p[2].as<double>(), p[3].as<int64_t>(), nullptr)) return 1;
   HIPCHECK(h, sync_stream(nullptr));
   return stage_out(h, p);
 }

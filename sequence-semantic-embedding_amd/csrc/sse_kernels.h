@@ -525,6 +525,7 @@ struct FilteredArgs {
 #define SSE_FILTERED_MAX_K 1024
 #define SSE_FILTERED_MAX_EXCL 64
 hipError_t launch_score_filtered(const FilteredArgs &a, hipStream_t st);  // every stage of one chunk
+hipError_t launch_filtered_max(const FilteredArgs &a, hipStream_t st);      // the max sweep alone: a.maxima zeroed
 hipError_t launch_filtered_collect(const FilteredArgs &a, hipStream_t st);  // the collect sweep alone: a.thr given, col_cnt zeroed
 
 // Exact top-k distinct groups among tag-eligible rows (score_grouped.hip, DESIGN K6h): the stages of FilteredArgs with a
@@ -553,6 +554,23 @@ struct AfterArgs {
 };
 #define SSE_AFTER_MAX_K 1024
 hipError_t launch_score_after(const AfterArgs &g, hipStream_t st);  // every stage of one chunk
+// The confusions of a query: the best k rows that are not among its positives and score at or above a floor derived from them
+// (score_confusions.hip, DESIGN K6k): the stages of FilteredArgs (no tags, no tile skip; f.excl / f.n_excl are the positives
+// [P][n_pos]) behind a kernel that scores the positives in float64 and forms f = (best positive score) - margin and
+// flo = rd(f - e).  The stored collect threshold is the larger of the filtered call's and flo; the select stage drops the
+// positives before and score64 < f after the re-scoring.  counters of `f`: [0] rows collected for the select stage, [1] queries
+// of the float64 sweep, [2] queries whose stored threshold is flo.
+struct ConfusionArgs {
+  FilteredArgs f;
+  double margin;            // finite or +inf
+  double *floor64;          // [P] scratch: f
+  float *flo;               // [P] scratch: rd(f - e)
+  double *out_pos_score;    // [P] or nullptr: m, the best positive's score (-inf: no positive in range)
+  int64_t *out_pos_id;      // [P] or nullptr: b, its id (INT64_MAX: none)
+};
+#define SSE_CONFUSIONS_MAX_K 1024
+#define SSE_CONFUSIONS_MAX_POS SSE_FILTERED_MAX_EXCL
+hipError_t launch_score_confusions(const ConfusionArgs &g, hipStream_t st);  // every stage of one chunk
 // tile_sum[t] = OR of tags[32 t .. 32 t + 32) (tags padded with zero words to NT * 32)
 hipError_t launch_tag_tile_summary(const uint64_t *tags, int64_t NT, uint64_t *tile_sum, hipStream_t st);
 

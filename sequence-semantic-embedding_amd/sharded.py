@@ -102,6 +102,41 @@ def merge_grouped_lists(scores, ids, groups, k):
     return out_s, out_i, out_g, take.sum(1).to(torch.int32)
 
 
+def merge_confusion_lists(scores, ids, pos_scores, pos_ids, margin, k):
+    """The merge of ShardedIndex.score_confusions on torch tensors of any device: the shards' local top-k non-positives side
+    by side (scores float64 [Q,M], ids int64 [Q,M]; padding entries carry id INT64_MAX) and every shard's local best
+    positive (pos_scores float64 [P,Q], pos_ids int64 [P,Q]; (-inf, INT64_MAX) where a shard holds none) -> (scores [Q,k],
+    ids [Q,k], counts int32 [Q], pos_scores [Q], pos_ids [Q]).  The best positive is the first of the shards' in (score
+    descending, id ascending); f = it - margin in IEEE double; the entries are ordered the same way, cut at f (>= stays)
+    and at k, padded with (-inf, INT64_MAX).  Exact: the global answer is a prefix of the merged non-positives, and every
+    shard's share of the best k of those is within its own best k."""
+    import torch
+    Q, M = scores.shape
+    pad = torch.iinfo(torch.int64).max
+    dev = scores.device
+    m = pos_scores.max(dim=0).values if pos_scores.shape[0] else torch.full((Q,), float("-inf"), dtype=torch.float64, device=dev)
+    if pos_ids.shape[0]:
+        b = torch.where(pos_scores == m.unsqueeze(0), pos_ids, torch.full_like(pos_ids, pad)).min(dim=0).values
+    else:
+        b = torch.full((Q,), pad, dtype=torch.int64, device=dev)
+    out_s = torch.full((Q, k), float("-inf"), dtype=torch.float64, device=dev)
+    out_i = torch.full((Q, k), pad, dtype=torch.int64, device=dev)
+    if Q == 0 or M == 0:
+        return out_s, out_i, torch.zeros(Q, dtype=torch.int32, device=dev), m, b
+    f = m - float(margin)
+    # (score descending, id ascending): two stable sorts, least significant key first
+    o = torch.sort(ids, dim=1, stable=True).indices
+    o = torch.gather(o, 1, torch.sort(torch.gather(scores, 1, o), dim=1, descending=True, stable=True).indices)
+    s, i = torch.gather(scores, 1, o), torch.gather(ids, 1, o)
+    keep = (i != pad) & (s >= f.unsqueeze(1))
+    rank = torch.cumsum(keep.to(torch.int64), 1) - 1           # column of a kept entry
+    take = keep & (rank < k)
+    rows = torch.arange(Q, device=dev).unsqueeze(1).expand(Q, M)[take]
+    cols = rank[take]
+    out_s[rows, cols], out_i[rows, cols] = s[take], i[take]
+    return out_s, out_i, take.sum(1).to(torch.int32), m, b
+
+
 class ShardedIndex(object):
     """One rank's view of the sharded index.  `handle` is an sse_amd Handle."""
 
@@ -285,6 +320,55 @@ class ShardedIndex(object):
         total = cnt.to(torch.int64)
         all_reduce_(total, group=self.group)
         return out[0].view(torch.float64), out[1], torch.clamp(total, max=k).to(torch.int32)
+
+    def score_confusions(self, queries, k, positives, margin=float("inf")):
+        """Handle.score_confusions over the whole sharded index: queries CUDA float32 [Q,S], positives int64 [Q, n_pos <= 64]
+        GLOBAL row ids padded with -1, identical on every rank.  Returns (scores float64 [Q,k], ids int64 [Q,k], counts int32
+        [Q], pos_scores float64 [Q], pos_ids int64 [Q]) on every rank: what the unsharded call returns.  The floor hangs on
+        the best positive, which one shard holds: every rank calls its handle with margin = +inf (its best k non-positives
+        and its own best positive), ONE all-gather carries lists and positives, merge_confusion_lists takes the best
+        positive over the ranks, forms the floor and cuts the merged lists at it.  No second device pass."""
+        import math
+        import torch
+        import torch.distributed as dist
+        from .collectives import all_gather_into
+        k, margin = int(k), float(margin)
+        if not 1 <= k <= 1024:
+            raise ValueError("k=%d must be in [1, 1024]" % k)
+        if math.isnan(margin) or margin == float("-inf"):
+            raise ValueError("margin=%r must be finite or +inf" % margin)
+        Q = int(queries.shape[0])
+        dev = queries.device
+        if positives.dim() != 2 or positives.shape[0] != Q or positives.dtype != torch.int64 or not 1 <= positives.shape[1] <= 64:
+            raise ValueError("positives must be int64 [Q, 1 <= n_pos <= 64]")
+        queries, positives = queries.contiguous(), positives.contiguous()
+        stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
+        single = self.world == 1 and not self.always_gather
+        pad = torch.iinfo(torch.int64).max
+        loc = torch.empty(2 * Q * k + 2 * Q, dtype=torch.int64, device=dev)   # score bits [Q,k] | ids [Q,k] | m bits [Q] | b [Q]
+        ls, li = loc[:Q * k].view(Q, k), loc[Q * k:2 * Q * k].view(Q, k)
+        lm, lb = loc[2 * Q * k:2 * Q * k + Q], loc[2 * Q * k + Q:]
+        cnt = torch.zeros(Q, dtype=torch.int32, device=dev)
+        if self.end > self.start and Q > 0:
+            self.handle.score_confusions_dev(queries.data_ptr(), Q, k, positives.data_ptr(), positives.shape[1],
+                                             margin if single else float("inf"), ls.data_ptr(), li.data_ptr(), cnt.data_ptr(),
+                                             lm.data_ptr(), lb.data_ptr(), stream)
+        else:
+            ls.view(torch.float64).fill_(float("-inf"))
+            li.fill_(pad)
+            lm.view(torch.float64).fill_(float("-inf"))
+            lb.fill_(pad)
+        if Q == 0 or single:
+            return ls.view(torch.float64), li, cnt, lm.view(torch.float64), lb
+        world = dist.get_world_size(self.group)
+        g = torch.empty(world * loc.shape[0], dtype=torch.int64, device=dev)
+        all_gather_into(g, loc, group=self.group)
+        g = g.view(world, -1)
+        gs = g[:, :Q * k].view(torch.float64).view(world, Q, k).permute(1, 0, 2).reshape(Q, world * k)
+        gi = g[:, Q * k:2 * Q * k].view(world, Q, k).permute(1, 0, 2).reshape(Q, world * k)
+        gm = g[:, 2 * Q * k:2 * Q * k + Q].contiguous().view(torch.float64)
+        gb = g[:, 2 * Q * k + Q:]
+        return merge_confusion_lists(gs, gi, gm, gb, margin, k)
 
     def set_local_groups(self, groups):
         """groups: CUDA int64 tensor [end-start] -- the group keys of this rank's rows, set after set_local_rows.  None

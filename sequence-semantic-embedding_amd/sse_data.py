@@ -248,6 +248,84 @@ class Data(object):
         src_rows = np.repeat(np.arange(start, stop, dtype=np.int32), 2)
         return src_rows, rows.astype(np.int32), np.tile(np.array([1.0, 0.0], np.float32), b)
 
+    # -- hard learning: data.py:124-129 declares the two methods below and prints "Not implemented yet." -----------------
+    def compute_training_confusion_samples(self, model, n=8, margin=0.1, chunk=8192):
+        """The confusion table of the training sources under the model's current weights: for every source, up to n targets
+        that are not verified for it and score at or above (its best verified target's cosine) - margin, best first
+        (Handle.score_confusions; data.py:126-129 is empty).  The target index is built in memory -- the normalised
+        encodings of the target corpus, or the l2-normalised free target matrix in source_only_cnn / source-encoder-only --
+        and uploaded to model.handle, where it stays.  Keeps self.confusions (int32 [n_train, n] target rows, -1 padded),
+        self.confusion_counts (int32 [n_train]) and self.confusion_stats, which it returns: sources, with_confusions,
+        mean_count, train_top1 (the share of the sources scored none of whose returned rows scores at or above its best
+        verified target: exact for any margin >= 0 whenever n >= 1) and skipped_over_64 (sources with more verified targets than the
+        call takes: they get count 0).  The default margin of 0.1 cosine is a hyper-parameter default only: nothing has
+        been measured to support it."""
+        src_arr, tgt_arr = self._corpus_arrays()
+        cnt, _, _, pad = self._positives_csr()
+        n, n_train = int(n), src_arr.shape[0]
+        if model.network_mode in ("source_only_cnn", "source-encoder-only"):
+            index = model.encode_target(np.zeros((int(model.targetSpaceSize), self.max_seq_length), np.int32), True)
+        else:
+            index = model.encode_target(tgt_arr, True)
+        model.handle.index_upload(np.ascontiguousarray(index, np.float32))
+        pad = pad[:, :64]
+        ok = cnt <= 64
+        table = np.full((n_train, n), -1, np.int32)
+        counts = np.zeros(n_train, np.int32)
+        top1 = 0
+        for c0 in range(0, n_train, int(chunk)):
+            idx = c0 + np.flatnonzero(ok[c0:c0 + int(chunk)])
+            if idx.size == 0:
+                continue
+            q = model.encode_source(src_arr[idx], True)
+            scores, ids, c, pos_scores, _ = model.handle.score_confusions(q, n, pad[idx], margin)
+            live = np.arange(n)[None, :] < c[:, None]
+            table[idx] = np.where(live, ids, -1).astype(np.int32)
+            counts[idx] = c
+            top1 += int((~(live & (scores >= pos_scores[:, None])).any(axis=1)).sum())
+        self.confusions, self.confusion_counts = table, counts
+        scored = int(ok.sum())
+        self.confusion_stats = {"sources": n_train, "with_confusions": int((counts > 0).sum()),
+                                "mean_count": float(counts.mean()) if n_train else 0.0,
+                                "train_top1": top1 / float(scored) if scored else 0.0,
+                                "skipped_over_64": int(n_train - scored)}
+        return self.confusion_stats
+
+    compute_training_confusion_sampes = compute_training_confusion_samples      # the reference's spelling (data.py:126)
+
+    def get_hard_learning_train_batch_rows(self, batch_size, hard_fraction=1.0):
+        """get_train_batch_rows (the window draw and the pos/neg interleaved layout of data.py:95-115, each source row
+        twice) with negatives from the confusion table: the positive is uniform among the verified targets; with
+        probability hard_fraction, and a non-zero count, the negative is uniform among the source's confusion_counts[i]
+        table entries, otherwise the reference's uniform rejection sample.  All draws come from self.rng."""
+        if getattr(self, "confusion_counts", None) is None:
+            raise RuntimeError("no confusion table: call compute_training_confusion_samples first")
+        n = len(self.rawTrainPosCorpus)
+        start = self.rng.randint(0, n - batch_size) + batch_size     # data.py:97 (window may be cut at the end)
+        stop = min(n, start + batch_size)
+        rows = np.empty(2 * (stop - start), np.int64)
+        for i in range(start, stop):
+            verified = self.rawTrainPosCorpus[i][1]
+            pos = verified[self.rng.randint(0, len(verified))]
+            rows[2 * (i - start)] = self.target_row(pos)
+            if hard_fraction > 0.0 and self.confusion_counts[i] > 0 and self.rng.random_sample() < hard_fraction:
+                rows[2 * (i - start) + 1] = self.confusions[i, self.rng.randint(0, self.confusion_counts[i])]
+                continue
+            positives = set(verified)
+            neg = self.fullSetTargetIds[self.rng.randint(0, self.rawnegSetLen)]
+            while neg in positives:
+                neg = self.fullSetTargetIds[self.rng.randint(0, self.rawnegSetLen)]
+            rows[2 * (i - start) + 1] = self.target_row(neg)
+        src_rows = np.repeat(np.arange(start, stop, dtype=np.int32), 2)
+        return src_rows, rows.astype(np.int32), np.tile(np.array([1.0, 0.0], np.float32), stop - start)
+
+    def get_hard_learning_train_batch(self, batch_size, target_rows=False, hard_fraction=1.0):
+        """data.py:124-125: the batch of get_hard_learning_train_batch_rows in the list form of get_train_batch (same seed ->
+        the same pairs)."""
+        src_rows, tgt_rows, labels = self.get_hard_learning_train_batch_rows(batch_size, hard_fraction)
+        tgt_of = (lambda r: int(r)) if target_rows else (lambda r: self.encodedFullTargetSpace[self.fullSetTargetIds[r]])
+        return ([self.rawTrainPosCorpus[r][0] for r in src_rows], [tgt_of(r) for r in tgt_rows], [float(x) for x in labels])
+
     def get_train_batch(self, batch_size, target_rows=False):
         """data.py:95-115.  target_rows=True (source_only_cnn): the target side of each pair is the row of the
         target id in the free target matrix instead of its token sequence."""

@@ -44,6 +44,12 @@ FLAGS = flags.FlagSet("sse_train", [
                           "EvalPairs (each with its first verified target and one sampled negative)"),
     ("eval_ranks", int, 0, "1: after each epoch's task evaluation, log the mean reciprocal rank and the mean / median rank of the "
                            "best-ranked verified target of every evaluation source over the whole index"),
+    ("hard_learning", int, 0, "N > 0: at the start of every epoch from --hard_start_epoch on, mine up to N confusions per training "
+                              "source (targets that are not verified for it and score near or above its best verified one) and draw "
+                              "negatives from them; 0 (default): uniform negatives only, like the reference"),
+    ("hard_margin", float, 0.1, "hard learning: a confusion scores at or above (best verified cosine) - this margin"),
+    ("hard_fraction", float, 0.5, "hard learning: share of negatives drawn from the confusion table"),
+    ("hard_start_epoch", int, 1, "hard learning: first epoch that uses the table"),
 ])
 
 
@@ -110,10 +116,25 @@ def train(f):
     eval_pairs = None                  # --eval_loss: the held-out pairs, built once
     for epoch in range(f.max_epoc):
         epoc_start = time.time()
+        hard = f.hard_learning > 0 and epoch >= f.hard_start_epoch
+        if hard:
+            # the confusion table under this epoch's weights (data.py:124-129 leaves it empty); the index it uploads is
+            # replaced by the Evaluator's own at the end of the epoch
+            model.set_forward_only(True)
+            st = data.compute_training_confusion_samples(model, n=f.hard_learning, margin=f.hard_margin)
+            logging.info("hard learning: %d of %d sources have confusions (mean %.2f per source), training top-1 %f"
+                         % (st["with_confusions"], st["sources"], st["mean_count"], st["train_top1"]))
         for _ in range(int(epoc_steps)):
             start = time.time()
             model.set_forward_only(False)
-            if f.device_corpus:
+            if hard and f.device_corpus:
+                src_rows, tgt_rows, labels = data.get_hard_learning_train_batch_rows(f.batch_size, f.hard_fraction)
+                step_loss, step_train_acc = model.handle.train_step_rows(src_rows, tgt_rows, labels)
+            elif hard:
+                src, tgt, labels = data.get_hard_learning_train_batch(f.batch_size, target_rows=table_tgt, hard_fraction=f.hard_fraction)
+                d = model.get_train_feed_dict(src, tgt, labels)
+                _, _, step_loss, step_train_acc = sess.run([model.train, summary_op, model.loss, model.train_acc], feed_dict=d)
+            elif f.device_corpus:
                 # the padded corpora live on the device: a step ships 2*batch row numbers, not token-id matrices
                 src_rows, tgt_rows, labels = data.get_train_batch_rows(f.batch_size, vectorized=f.seed < 0)
                 step_loss, step_train_acc = model.handle.train_step_rows(src_rows, tgt_rows, labels)
