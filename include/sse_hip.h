@@ -170,6 +170,11 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value);
  * (gate accumulators from the x-projection table; the others gathered embedding rows).  The pad-prefix table builds a
  * kernel does for itself are not counted.
  * "eval_paired_calls": sse_eval_loss* calls that ran the source encoder once per pair of rows (option train_pair_dedup).
+ * "train_path_fused" / "train_path_generic" / "train_path_cnn": train steps (sse_train_grads*, sse_train_step*) by path.
+ * "train_paired_steps": fused steps that ran the source encoder on one row of every pair (option train_pair_dedup).
+ * "train_fp32_repacks": steps that rebuilt the fp32 Kh^T / Kx^T fragment copies of the BPTT kernels.
+ * "train_split_repacks": steps that rebuilt their split-operand forms (options train_bwd_x3 + train_dk_x3).
+ * "train_generic_repacks": packs of the any-shape path built, one per encoder side.
  * "score_rank_band_rows" / "score_rank_bruteforce_pairs": see sse_score_rank.
  * "score_above_band_rows" / "score_above_bruteforce_pairs" / "score_above_long_segments": see sse_score_above.
  * "score_filtered_collected_rows" / "score_filtered_bruteforce_queries" / "score_filtered_tiles_skipped": see

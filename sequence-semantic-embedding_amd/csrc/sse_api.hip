@@ -219,6 +219,9 @@ struct sse_handle {
   float lr = 0.9f;
   int64_t global_step = 0;
   TrainState *train = nullptr;
+  // counters "train_path_*", "train_paired_steps", "train_*_repacks": the route of every train step and what it rebuilt
+  int64_t train_path_fused = 0, train_path_generic = 0, train_path_cnn = 0, train_paired_steps = 0;
+  int64_t train_fp32_repacks = 0, train_split_repacks = 0, train_generic_repacks = 0;
   std::vector<hipEvent_t> events;
 };
 
@@ -429,6 +432,7 @@ int pack_train_fp32(sse_handle *h, TrainState &ts, int nside, hipStream_t st) {
     }
   }
   if (ts.fp32_dirty) {
+    h->train_fp32_repacks += 1;
     for (int s = 0; s < nside; ++s) {
       Encoder &e = h->enc[s];
       if (e.shares_lstm_with >= 0) {
@@ -2463,7 +2467,10 @@ const DevCounters DEV_COUNTERS[CG_DEV_COUNT] = {
     {&sse_handle::s_af_cnt, &sse_handle::af_cnt_init, 3}, {&sse_handle::s_cf_cnt, &sse_handle::cf_cnt_init, 3},
     {&sse_handle::s_fb_cnt, &sse_handle::fb_cnt_init, 4}};
 int64_t sse_handle::*const HOST_COUNTERS[] = {&sse_handle::persist_fallbacks, &sse_handle::two_pass_calls, &sse_handle::pad_sorted_calls,
-                                              &sse_handle::eval_paired_calls, &sse_handle::x_table_builds};
+                                              &sse_handle::eval_paired_calls, &sse_handle::x_table_builds,
+                                              &sse_handle::train_path_fused, &sse_handle::train_path_generic, &sse_handle::train_path_cnn,
+                                              &sse_handle::train_paired_steps, &sse_handle::train_fp32_repacks,
+                                              &sse_handle::train_split_repacks, &sse_handle::train_generic_repacks};
 
 // every name sse_get_counter answers: its group and its word there (CG_HOST: entry of HOST_COUNTERS; CG_PATH: entry of
 // sse_handle::lstm_path_calls; a device group: the word the kernels of that family count in)
@@ -2476,6 +2483,14 @@ const struct {
     {"pad_sorted_calls", CG_HOST, 2},      // encodes of device-resident ids whose rows were bucketed by PAD prefix on the device
     {"eval_paired_calls", CG_HOST, 3},     // sse_eval_loss* calls whose source encoder ran once per (positive, negative) pair
     {"lstm_x_table_builds", CG_HOST, 4},   // x-projection tables built (option lstm_x_table)
+    // train steps (sse_train_grads*, sse_train_step*) by path, the fused path's paired steps, and the layouts a step rebuilt
+    {"train_path_fused", CG_HOST, 5},
+    {"train_path_generic", CG_HOST, 6},
+    {"train_path_cnn", CG_HOST, 7},
+    {"train_paired_steps", CG_HOST, 8},
+    {"train_fp32_repacks", CG_HOST, 9},     // the fp32 Kh^T / Kx^T fragment copies of the BPTT kernels
+    {"train_split_repacks", CG_HOST, 10},   // their split-operand forms KhT16 / KxT16
+    {"train_generic_repacks", CG_HOST, 11}, // the any-shape path's packs, once per side
     // LSTM inference encodes by kernel
     {"lstm_path_persist", CG_PATH, PATH_PERSIST},
     {"lstm_path_cluster", CG_PATH, PATH_CLUSTER},
@@ -3328,6 +3343,7 @@ static int cnn_train_grads_locked(sse_handle *h, const TrainCall &call) {
     return fail(h, "source_only_cnn training: T*E = %d*%d needs %zu bytes of LDS in the weight-gradient kernel (limit 160 KiB: T*E <= 20288)",
                 T, E, ((size_t)2 * T * E + 384) * sizeof(float));
   StepFrame f;
+  h->train_path_cnn += 1;
   if (step_begin(h, call, 64, f)) return 1;
   if (ensure_packed(h, f.st)) return 1;
   if (step_stage_inputs(f, nullptr, 2 * B)) return 1;  // sq_part: one partial sum per source row, one per target row
@@ -3362,6 +3378,7 @@ static int generic_forward_side(StepFrame &f, const GenLstmDims &d, int s) {
     HIPCHECK(h, launch_gen_pack(h->vars[e.kernel].dev, h->vars[e.proj].dev, d, S, (float *)ts.gen_KT[s].p, (float *)ts.gen_Kq[s].p,
                                 (float *)ts.gen_MT[s].p, f.st));
     ts.gen_ver[s] = h->weights_version;
+    h->train_generic_repacks += 1;
   }
   HIPCHECK(h, launch_gen_forward(f.ids(s), f.emb->dev, V, (const float *)ts.gen_KT[s].p, h->vars[e.bias].dev, d, (float *)ts.gen_A[s].p,
                                  (float *)ts.gen_G.p, (float *)ts.gen_c.p, (float *)ts.gen_tape[s].p, (float *)ts.gen_hl[s].p,
@@ -3389,6 +3406,7 @@ static int generic_backward_side(StepFrame &f, const GenLstmDims &d, int s) {
 
 static int train_grads_generic_locked(sse_handle *h, const TrainCall &call) {
   StepFrame f;
+  h->train_path_generic += 1;
   if (step_begin(h, call, 32, f)) return 1;
   const int B = f.B, T = f.T, nside = f.nside;
   // sq_part: one partial sum per (side, step, row), one per target row in source-encoder-only mode
@@ -3493,6 +3511,9 @@ static int fused_refresh_layouts(StepFrame &f, const FusedPlan &p) {
   if (p.bwd2 ? pack_train_fp32(h, ts, f.nside, st) : p.all_x3 ? ensure_proj_packed(h, st) : ensure_packed(h, st)) return 1;
   // (the split Kh^T / Kx^T copies are only rebuilt by steps that run the split-operand BPTT: a pure fp32 step leaves them stale)
   if (!((p.any_bwd_x3 && ts.packed_dirty) || (!p.all_x3 && ts.fp32_dirty))) return 0;
+  if (p.any_bwd_x3 && ts.packed_dirty) h->train_split_repacks += 1;
+  const bool fp32_stale = !p.all_x3 && ts.fp32_dirty;  // (a split-copy rebuild alone leaves current fp32 copies as they are)
+  if (fp32_stale) h->train_fp32_repacks += 1;
   for (int s = 0; s < f.nside; ++s) {
     Encoder &e = h->enc[s];
     if (e.shares_lstm_with >= 0) {
@@ -3508,7 +3529,7 @@ static int fused_refresh_layouts(StepFrame &f, const FusedPlan &p) {
       if (!ts.KxT16[s]) HIPCHECK(h, hipMalloc((void **)&ts.KxT16[s], kxT16_elems(e.Hp) * sizeof(unsigned short)));
       HIPCHECK(h, launch_pack_kxT16(h->vars[e.kernel].dev, E, e.H, e.Hp, ts.KxT16[s], st));
     }
-    if (!p.all_x3) {
+    if (fp32_stale) {
       if (!ts.KhT[s]) HIPCHECK(h, hipMalloc((void **)&ts.KhT[s], (size_t)(e.Hp / 32) * (e.Hp / 2) * 256 * sizeof(float)));
       if (!ts.KxT[s]) HIPCHECK(h, hipMalloc((void **)&ts.KxT[s], (size_t)2 * (e.Hp / 2) * 256 * sizeof(float)));
       HIPCHECK(h, launch_pack_kT(h->vars[e.kernel].dev, E, e.H, e.Hp / 32, e.H, e.Hp, ts.KhT[s], st));
@@ -3746,6 +3767,8 @@ static int train_grads_fused_locked(sse_handle *h, const TrainCall &call) {
   if (step_begin(h, call, 64, f)) return 1;
   TrainState &ts = *f.ts;
   const FusedPlan p = fused_plan(f);
+  h->train_path_fused += 1;
+  if (p.paired) h->train_paired_steps += 1;
   if (fused_refresh_layouts(f, p) || fused_check_tape(f, p)) return 1;
   const int32_t *perm = nullptr;
   if (p.paired && pair_permutation(f, &perm)) return 1;

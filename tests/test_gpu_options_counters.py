@@ -60,6 +60,8 @@ COUNTERS = [
     "score_grouped_collected_rows", "score_grouped_bruteforce_queries",
     "score_after_collected_rows", "score_after_bruteforce_queries",
     "score_bf16_second_chance_queries", "score_collect_queries", "score_bruteforce_queries",
+    "train_path_fused", "train_path_generic", "train_path_cnn", "train_paired_steps",
+    "train_fp32_repacks", "train_split_repacks", "train_generic_repacks",
 ]
 
 
@@ -83,7 +85,7 @@ def _refused(call, *args):
 @pytest.mark.parametrize("which", ["dual", "cnn"])
 def test_every_counter_of_a_fresh_handle(handles, which):
     h = handles[which]
-    assert len(COUNTERS) == 30 and len(set(COUNTERS)) == 30
+    assert len(COUNTERS) == 37 and len(set(COUNTERS)) == 37
     for name in COUNTERS:
         assert h.get_counter(name) == 0, name
     assert h.get_counter("lstm_coop_refused") >= 0      # process-wide
