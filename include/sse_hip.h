@@ -416,6 +416,53 @@ int sse_score_confusions_dev(sse_handle *h, const float *q_dev, int32_t Q, int32
                              int32_t n_pos, double margin, double *out_scores_dev, int64_t *out_ids_dev,
                              int32_t *out_counts_dev, double *out_pos_score_dev, int64_t *out_pos_id_dev, void *stream);
 
+/* Bias of the resident index: one float per row, copied and kept on the device -- an item prior (quality, recency, stock), the
+ * log-prior of a leaf category, the hubness correction of cross-lingual retrieval (CSLS ranks by 2 cos(x,t) - r_T(x) - r_S(t);
+ * r_T(x) is constant per query and r_S(t) is known at index time, so bias[t] = -0.5 r_S(t) with weight 1 gives the CSLS
+ * ranking).  N must equal the index's row count, otherwise the call errors with a message and the bias stays as it was.
+ * bias == NULL clears it; uploading or adopting a new index (sse_index_upload*, sse_index_set_dev) clears it too, exactly as
+ * tags and group keys are cleared.  The bias is independent of tags and group keys.  The host form reads the array once and
+ * refuses a non-finite value with a message (the bias stays as it was); in the _dev form, which takes a device pointer and
+ * enqueues the copy on `stream`, a non-finite value is outside the claim (no fault).  Beside the array the handle keeps
+ * bias_absmax = max |bias|, as it keeps the largest row norm of the index; it is formed on the device behind the copy and
+ * stays there, so neither form waits for anything the setters of tags and group keys do not wait for. */
+int sse_index_set_bias(sse_handle *h, const float *bias_host, int64_t N);
+int sse_index_set_bias_dev(sse_handle *h, const float *bias_dev, int64_t N, void *stream);
+
+/* Exact top-k by cosine + per-row prior.  The biased score of row r for query q is
+ *     sb(q, r) = score64(q, r) + (double)w[q] * (double)bias[r]
+ * where score64 is the float64 dot product sse_score_topk returns for that row, bit for bit, bias is the array of
+ * sse_index_set_bias* and w[q] = q_weight[q], or 1.0f for every query when q_weight == NULL.  Both factors are floats, so
+ * their product is exact in double and sb is rounded ONCE; contracting the expression into a fused multiply-add cannot
+ * change it.  That is why the weight is a float and not a double.  Row eligibility is the tag rule of
+ * sse_score_topk_filtered (q_any / q_none may be NULL; giving either while no tags are set is an error).
+ *   out_counts [Q]: c = min(k, eligible rows).
+ *   out_scores / out_ids [Q][k]: columns 0 .. c of row q are the eligible rows by sb descending, equal sb by ascending id, ids
+ *     including id_base, out_scores holding sb; columns c .. k hold (-inf, INT64_MAX).  1 <= k <= 1024; k may exceed N.
+ * With w[q] == 0, or an all-zero bias, row q is sse_score_topk_filtered's row (no exclusion list), bit for bit.  A re-ranking
+ * of sse_score_topk's columns on the host is NOT this call: a row outside the unbiased top-k may belong in the biased one.
+ * The route is the filtered call's, carried out on the biased fp32 value y = fmaf(w, bias[r], fp32 score): a first kernel forms
+ * per query e_b = e + u (|q| idx_norm_max + e + |w| bias_absmax), rounded outward, with e the certified fp32 bound of the
+ * query and u = 2^-23 over the one rounding of the fused add (and of sb); the fp32 MFMA sweep keeps maxima of y over disjoint
+ * row sets of the tag-eligible rows, their k-th largest less 2 e_b is a threshold no row of the answer has y below, the same
+ * sweep again collects every tag-eligible row at or above it, and those are re-scored in float64, the bias added, and sorted
+ * (counter "score_biased_collected_rows": rows re-scored); a query with more than 4096 such rows is served by a float64 sweep
+ * of the whole index that adds the bias likewise ("score_biased_bruteforce_queries").  Cost note: a large |w| bias_absmax
+ * widens the band 2 e_b and sends more rows to float64; the result stays exact.  Option "score_filtered_skip" governs the tile
+ * skip here too and changes no result.  Scratch is bounded by the chunk of 4096 queries.  Rows or queries of norm below
+ * 2^-100, non-finite rows or queries and a non-finite weight are outside the claim (no fault).
+ * Out of scope here: exclusion lists, the (score, id) cursor of sse_score_topk_after, the group reduction of
+ * sse_score_topk_grouped, and the web routes (they page, so they wait for a cursor form).
+ * Q == 0 succeeds.  No index, no bias set, k out of range, masks without tags: error with a message, decided on the host before
+ * anything is queued, no output written, the handle stays usable.  The host form runs on the null stream and synchronises;
+ * the _dev form takes device pointers, enqueues on `stream` and never waits for the device. */
+int sse_score_topk_biased(sse_handle *h, const float *q_host, int32_t Q, int32_t k, const float *q_weight,
+                          const uint64_t *q_any, const uint64_t *q_none, double *out_scores, int64_t *out_ids,
+                          int32_t *out_counts);
+int sse_score_topk_biased_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, const float *q_weight_dev,
+                              const uint64_t *q_any_dev, const uint64_t *q_none_dev, double *out_scores_dev,
+                              int64_t *out_ids_dev, int32_t *out_counts_dev, void *stream);
+
 /* encode + score in one call, the encodings never leaving the device: session.run([src_seq_embedding | norm_...])
  * followed by np.dot + getSortedResults[:k] as sse_demo.py:121-129, webserver.py:144-151 (and the three other routes)
  * and sse_evaluator.py:107-111 do per query / batch.  enc_out_host (may be NULL) also receives the [B,S] encodings. */

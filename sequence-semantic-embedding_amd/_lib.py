@@ -63,6 +63,10 @@ SYMBOLS = {
     "sse_score_topk_after_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sse_score_confusions": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P]),
     "sse_score_confusions_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P]),
+    "sse_index_set_bias": (C.c_int, [_P, _P, C.c_int64]),
+    "sse_index_set_bias_dev": (C.c_int, [_P, _P, C.c_int64, _P]),
+    "sse_score_topk_biased": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "sse_score_topk_biased_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "sse_encode_score_topk": (C.c_int, [_P, C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_merge_topk_dev": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_merge_topk_strided_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
@@ -540,6 +544,57 @@ class Handle(object):
         self.check(self.lib.sse_score_confusions_dev(self._h, q_ptr, int(Q), int(k), pos_ptr or None, int(n_pos), float(margin),
                                                      scores_ptr, ids_ptr, counts_ptr, pos_score_ptr or None, pos_id_ptr or None,
                                                      stream))
+
+    def index_set_bias(self, bias):
+        """One float32 bias per row of the resident index (bias=None clears it); a new index clears it too.  A non-finite
+        value is refused."""
+        if bias is None:
+            self.check(self.lib.sse_index_set_bias(self._h, None, 0))
+            return
+        b = np.ascontiguousarray(bias, dtype=np.float32).reshape(-1)
+        self.check(self.lib.sse_index_set_bias(self._h, _ptr(b), b.shape[0]))
+
+    def index_set_bias_dev(self, bias_ptr, N, stream=0):
+        """index_set_bias from a device pointer of N float32 values (None / 0 clears), copied on `stream`."""
+        self.check(self.lib.sse_index_set_bias_dev(self._h, bias_ptr or None, int(N), stream))
+
+    def score_topk_biased(self, queries, k, weight=None, any_of=None, none_of=None):
+        """Exact top-k by score + weight * bias[row] (bias: index_set_bias).  weight: None (1.0), a scalar or float32 [Q];
+        any_of / none_of: uint64 [Q] tag masks, the eligibility rule of score_topk_filtered.  Returns (scores float64 [Q,k],
+        ids int64 [Q,k], counts int32 [Q]): the first counts[q] columns are the eligible rows by biased score descending,
+        equal scores by ascending id, scores holding score_topk's float64 score + float64(weight) * float64(bias); the rest
+        hold (-inf, INT64_MAX)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError("queries must be [Q,S]")
+        Q, k = q.shape[0], int(k)
+        w = None
+        if weight is not None:
+            w = np.asarray(weight, dtype=np.float32)
+            w = np.full(Q, w, np.float32) if w.ndim == 0 else np.ascontiguousarray(w.reshape(-1))
+            if w.shape[0] != Q:
+                raise ValueError("weight must be a scalar or float32 [Q]")
+        masks = []
+        for m in (any_of, none_of):
+            if m is not None:
+                m = np.ascontiguousarray(m, dtype=np.uint64).reshape(-1)
+                if m.shape[0] != Q:
+                    raise ValueError("any_of / none_of must be uint64 [Q]")
+            masks.append(m)
+        scores = np.empty((Q, max(k, 0)), np.float64)
+        ids = np.empty((Q, max(k, 0)), np.int64)
+        counts = np.empty(Q, np.int32)
+        self.check(self.lib.sse_score_topk_biased(self._h, _ptr(q), Q, k, _ptr(w) if w is not None else None,
+                                                  _ptr(masks[0]) if masks[0] is not None else None,
+                                                  _ptr(masks[1]) if masks[1] is not None else None,
+                                                  _ptr(scores), _ptr(ids), _ptr(counts)))
+        return scores, ids, counts
+
+    def score_topk_biased_dev(self, q_ptr, Q, k, weight_ptr, any_ptr, none_ptr, scores_ptr, ids_ptr, counts_ptr, stream=0):
+        """score_topk_biased on device pointers (weight_ptr: float32 [Q]; weight_ptr / any_ptr / none_ptr may be None / 0),
+        enqueued on `stream`."""
+        self.check(self.lib.sse_score_topk_biased_dev(self._h, q_ptr, int(Q), int(k), weight_ptr or None, any_ptr or None,
+                                                      none_ptr or None, scores_ptr, ids_ptr, counts_ptr, stream))
 
     def merge_topk_strided_dev(self, in_s, in_i, shard_stride, P, Q, k, out_s, out_i, stream=0):
         self.check(self.lib.sse_merge_topk_strided_dev(self._h, in_s, in_i, int(shard_stride), P, Q, k, out_s, out_i, stream))

@@ -54,7 +54,7 @@ struct AfterMaxStage : FilteredMaxStage {
 // after collect: eligible rows with thr <= score <= top = hi
 struct AfterCollectStage {
   typedef AfterArgs Args;
-  static constexpr bool COLLECT = true, COUNT_SKIPS = false;
+  static constexpr bool COLLECT = true, COUNT_SKIPS = false, BIASED = false;
   static constexpr int MAX_NQ = 4;
   struct Col {
     float thr, top;

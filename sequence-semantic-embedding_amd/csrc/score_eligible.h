@@ -1,5 +1,6 @@
-// The stages sse_score_topk_filtered, sse_score_topk_grouped, sse_score_topk_after and sse_score_confusions share
-// (score_filtered.hip, score_grouped.hip, score_after.hip, score_confusions.hip; DESIGN K6g / K6h / K6j / K6k), each written once:
+// The stages sse_score_topk_filtered, sse_score_topk_grouped, sse_score_topk_after, sse_score_confusions and
+// sse_score_topk_biased share (score_filtered.hip, score_grouped.hip, score_after.hip, score_confusions.hip, score_biased.hip;
+// DESIGN K6g / K6h / K6j / K6k / K6l), each written once:
 //   eligible_sweep_kernel<NQ, Stage>
 //                               the shared fp32 sweep (score_sweep.h) over tag-eligible rows: the block's OR of q_any and the
 //                               tile skip, the tail-tile row mask, the 16 tag words and the eligibility masks, then either the
@@ -10,7 +11,8 @@
 //                               |q|^2, e = eps32 |q| (1 + 2^-20), and "m-th largest maximum theta -> thr = rd(theta - 2 e)".
 //   eligible_select_kernel<Sel> the buffer re-scored in float64 or -- buffer overflow -- the float64 sweep of the whole index
 //                               with its cuts, then the final reduction and the output.  A Sel supplies which rows are used,
-//                               which (score64, id) are kept, whether entries carry a group and how the area is reduced.
+//                               which (score64, id) are kept, whether entries carry a group and how the area is reduced
+//                               (BIASED: what is added to score64 first).
 //   ft_excluded                 is an id among a query's list of at most 64 (exclusions, positives)?
 //   eligible_args_ok, launch_eligible_sweep, launch_eligible_select
 //                               the launchers' argument checks, the NQ dispatch and the select launch.
@@ -36,6 +38,7 @@ struct FilteredMaxStage {
   typedef FilteredStageArgs Args;
   static constexpr bool COLLECT = false, COUNT_SKIPS = true;  // (the one sweep that counts skipped tiles into counters[2])
   static constexpr bool KEEP_TILE = false;  // true: Col has mt[16], the tile of each maximum, and the maximum is strict
+  static constexpr bool BIASED = false;     // true: Args has bias [NT * 32], Col has w; a score is fmaf(w, bias[row], dot) (K6l)
   static constexpr int MAX_NQ = 4;
   typedef uint32_t Slot;
   struct Col {
@@ -53,7 +56,7 @@ struct FilteredMaxStage {
 // filtered collect: eligible rows at or above thr
 struct FilteredCollectStage {
   typedef FilteredStageArgs Args;
-  static constexpr bool COLLECT = true, COUNT_SKIPS = false;
+  static constexpr bool COLLECT = true, COUNT_SKIPS = false, BIASED = false;
   static constexpr int MAX_NQ = 4;
   struct Col {
     float thr;
@@ -129,6 +132,15 @@ __global__ __launch_bounds__(SWEEP_THREADS) void eligible_sweep_kernel(typename 
     const int rbase = sweep_rbase(tile, lane);
     // rows of this tile that exist (the index's last tile is zero padded past N)
     const unsigned rowmask = (tile == tail_tile) ? sweep_tail_rowmask(rbase, nlim) : 0xFFFFu;  // (uniform condition)
+    if constexpr (Stage::BIASED) {  // the per-row prior, fused into the tile's scores before anything looks at them
+      float bs[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) bs[r] = g.bias[sweep_row(rbase, r)];  // (padded to NT * 32 floats)
+#pragma unroll
+      for (int q = 0; q < NQ; ++q)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[q][r] = fmaf(col[q].w, bs[r], acc[q][r]);
+    }
     unsigned em[NQ];  // eligible rows per query tile
     if (a.tags) {     // (uniform)
       uint64_t tg[16];
@@ -244,6 +256,7 @@ __device__ __forceinline__ bool ft_excluded(const int64_t *ex, int n_excl, int64
 struct PlainSelect {
   typedef FilteredStageArgs Args;
   static constexpr bool GROUPED = false, COUNT_COLLECTED = false;
+  static constexpr bool BIASED = false;  // true: Sel::score(args, query, score64, row) is what is kept, keyed and returned (K6l)
   struct Query {};  // what a workgroup holds of its query beside the row
   template <class A>
   static __device__ __forceinline__ Query query(const A &, int) { return Query{}; }
@@ -291,7 +304,9 @@ __global__ __launch_bounds__(256) void eligible_select_kernel(typename Sel::Args
     if (lane == 0) {
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
-        if (!use[b] || !Sel::keep(qu, sc[b], a.id_base + r[b])) continue;
+        if (!use[b]) continue;
+        if constexpr (Sel::BIASED) sc[b] = Sel::score(g, qu, sc[b], r[b]);
+        if (!Sel::keep(qu, sc[b], a.id_base + r[b])) continue;
         const unsigned long long key = ft_key64(sc[b]);
         // below the k-th entry: not a new answer (GROUPED: nor better than the entry its own group may hold)
         if (have_bar && !(key > bar_key || (key == bar_key && (int)r[b] < bar_row))) continue;

@@ -203,6 +203,12 @@ struct sse_handle {
   // [P] lo, [P] hi), the two "score_after_*" counters.  Maxima, thresholds and row buffers are the filtered call's.
   DevBuf s_af_bnd, s_af_cnt;
   bool af_cnt_init = false;
+  // top-k of cosine + per-row prior (sse_score_topk_biased*, score_biased.hip): one float per row of the resident index (zero
+  // padded to whole tiles) and bias_absmax = max |bias| beside it as one device word (as idx_norm_max is kept, but on the
+  // device: the _dev setter computes it there and never waits), valid while bias_set; e_b of a chunk ([P] double), the two
+  // "score_biased_*" counters.  Maxima, thresholds and row buffers are the filtered call's.
+  DevBuf idx_bias, idx_bias_absmax, s_bs_bnd, s_bs_cnt;
+  bool bias_set = false, bs_cnt_init = false;
   // confusions of a query (sse_score_confusions*, score_confusions.hip): the floors of a chunk ([P] f as double, [P] flo), the
   // three "score_confusions_*" counters.  Maxima, thresholds and row buffers are the filtered call's.
   DevBuf s_cf_bnd, s_cf_cnt;
@@ -1008,6 +1014,7 @@ int index_from_dev_rows(sse_handle *h, const float *rows_dev, int64_t N, int S, 
   const int64_t NT = (N + 31) / 32;
   h->tags_set = false;  // (tags belong to the rows they were set for)
   h->groups_set = false;  // (and so do group keys)
+  h->bias_set = false;    // (and the bias)
   // fragment-order copy of the index: grow-only (re-indexing with the same or a smaller shard reuses the allocation)
   const size_t need = (size_t)NT * KG * 256 * sizeof(float);
   if (need > h->idxp_cap) {
@@ -1533,6 +1540,69 @@ static int score_after_dev_locked(sse_handle *h, const TopkIo &io, int Q, int k,
     HIPCHECK(h, launch_score_after(g, st));
   }
   return 0;
+}
+
+static const TopkCall CALL_BIASED = {"sse_score_topk_biased", SSE_BIASED_MAX_K, false};
+
+// sse_index_set_bias*: the floats copied behind the index (device to device on `st`, or from the host after one pass that
+// refuses a non-finite value), zero padded to whole tiles, and max |bias| formed on the device beside them.  Nothing changes
+// before every check and allocation has passed.
+static int index_set_bias_locked(sse_handle *h, const float *bias, int64_t N, bool from_host, hipStream_t st) {
+  if (!bias) {
+    h->bias_set = false;
+    return 0;
+  }
+  if (!h->idxp) return fail(h, "sse_index_set_bias: no index uploaded");
+  if (N != h->idx_N) return fail(h, "sse_index_set_bias: %lld values for an index of %lld rows; the bias is unchanged", (long long)N, (long long)h->idx_N);
+  if (from_host)
+    for (int64_t i = 0; i < N; ++i)
+      if (!std::isfinite(bias[i])) return fail(h, "sse_index_set_bias: bias[%lld] = %g is not finite; the bias is unchanged", (long long)i, (double)bias[i]);
+  const int64_t NT = (N + 31) / 32;
+  if (!h->bias_set) {  // (a live bias is never reallocated: the sizes are the index's)
+    if (reserve(h, h->idx_bias, (size_t)NT * 32 * sizeof(float))) return 1;
+    if (reserve(h, h->idx_bias_absmax, sizeof(float))) return 1;
+  }
+  float *d = (float *)h->idx_bias.p;
+  if (from_host) HIPCHECK(h, hipMemcpy(d, bias, (size_t)N * sizeof(float), hipMemcpyHostToDevice));
+  else HIPCHECK(h, hipMemcpyAsync(d, bias, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, st));
+  HIPCHECK(h, hipMemsetAsync(h->idx_bias_absmax.p, 0, sizeof(float), st));
+  HIPCHECK(h, launch_bias_prepare(d, N, NT, (float *)h->idx_bias_absmax.p, st));
+  h->bias_set = true;
+  return 0;
+}
+
+// sse_score_topk_biased*: the filtered call's chunks with e_b beside them (DESIGN K6l): [P] double
+static int score_biased_dev_locked(sse_handle *h, const TopkIo &io, int Q, int k, const float *weight, hipStream_t st) {
+  const int64_t NT = (h->idx_N + 31) / 32;
+  if (ensure_zeroed_once(h, h->s_bs_cnt, h->bs_cnt_init, 3, st)) return 1;
+  BiasedArgs g;
+  FilteredArgs &a = g.f;
+  fill_filtered_common(h, a, k, 0, h->s_bs_cnt);
+  a.excl = nullptr;
+  g.bias = (const float *)h->idx_bias.p;
+  g.bias_absmax = (const float *)h->idx_bias_absmax.p;
+  g.norm_max = h->idx_norm_max;
+  for (int q0 = 0; q0 < Q; q0 += TOPK_POOL) {
+    const int P = std::min(TOPK_POOL, Q - q0);
+    SweepChunk ck;
+    if (sweep_chunk(h, P, ck)) return 1;
+    const int nsplit = split_for_maxima(ck.nsplit, 2 * k, NT);
+    if (topk_chunk(h, a, io, q0, P, ck.NQ, nsplit, h->s_ft_max, (size_t)P * std::min(nsplit, 16) * 256 * sizeof(uint32_t), st, &h->s_bs_bnd,
+                   (size_t)P * sizeof(double)))
+      return 1;
+    a.maxima = (uint32_t *)h->s_ft_max.p;
+    g.weight = weight ? weight + q0 : nullptr;
+    g.eb = (double *)h->s_bs_bnd.p;
+    HIPCHECK(h, launch_score_biased(g, st));
+  }
+  return 0;
+}
+
+// argument errors of sse_score_topk_biased*, all decidable on the host
+static int score_biased_check(sse_handle *h, int Q, int k, const void *q_any, const void *q_none) {
+  if (!h->idxp) return fail(h, "%s: no index uploaded", CALL_BIASED.name);
+  if (!h->bias_set) return fail(h, "%s: the index has no bias (sse_index_set_bias)", CALL_BIASED.name);
+  return score_topk_check(h, CALL_BIASED, Q, k, q_any, q_none);
 }
 
 static const TopkCall CALL_CONFUSIONS = {"sse_score_confusions", SSE_CONFUSIONS_MAX_K, false};
@@ -2460,12 +2530,12 @@ struct DevCounters {
   bool sse_handle::*init;
   int words;  // read back together
 };
-enum { CG_RANK, CG_ABOVE, CG_FILTERED, CG_GROUPED, CG_AFTER, CG_CONFUSIONS, CG_TOPK, CG_DEV_COUNT, CG_HOST = CG_DEV_COUNT, CG_PATH, CG_COOP };
+enum { CG_RANK, CG_ABOVE, CG_FILTERED, CG_GROUPED, CG_AFTER, CG_CONFUSIONS, CG_BIASED, CG_TOPK, CG_DEV_COUNT, CG_HOST = CG_DEV_COUNT, CG_PATH, CG_COOP };
 const DevCounters DEV_COUNTERS[CG_DEV_COUNT] = {
     {&sse_handle::s_rk_cnt, &sse_handle::rk_cnt_init, 2}, {&sse_handle::s_ab_cnt, &sse_handle::ab_cnt_init, 3},
     {&sse_handle::s_ft_cnt, &sse_handle::ft_cnt_init, 3}, {&sse_handle::s_gp_cnt, &sse_handle::gp_cnt_init, 3},
     {&sse_handle::s_af_cnt, &sse_handle::af_cnt_init, 3}, {&sse_handle::s_cf_cnt, &sse_handle::cf_cnt_init, 3},
-    {&sse_handle::s_fb_cnt, &sse_handle::fb_cnt_init, 4}};
+    {&sse_handle::s_bs_cnt, &sse_handle::bs_cnt_init, 3}, {&sse_handle::s_fb_cnt, &sse_handle::fb_cnt_init, 4}};
 int64_t sse_handle::*const HOST_COUNTERS[] = {&sse_handle::persist_fallbacks, &sse_handle::two_pass_calls, &sse_handle::pad_sorted_calls,
                                               &sse_handle::eval_paired_calls, &sse_handle::x_table_builds,
                                               &sse_handle::train_path_fused, &sse_handle::train_path_generic, &sse_handle::train_path_cnn,
@@ -2525,6 +2595,9 @@ const struct {
     {"score_confusions_collected_rows", CG_CONFUSIONS, 0},
     {"score_confusions_bruteforce_queries", CG_CONFUSIONS, 1},
     {"score_confusions_floor_queries", CG_CONFUSIONS, 2},
+    // sse_score_topk_biased* (score_biased.hip): rows re-scored by the select stage, queries of the float64 sweep
+    {"score_biased_collected_rows", CG_BIASED, 0},
+    {"score_biased_bruteforce_queries", CG_BIASED, 1},
     // sse_score_topk* (score_topk.hip): queries whose bf16-candidate result missed its certificate, queries served by the
     // collect path, queries that fell through to the float64 brute force
     {"score_bf16_second_chance_queries", CG_TOPK, 0},
@@ -2891,6 +2964,45 @@ int sse_score_topk_after(sse_handle *h, const float *q_host, int32_t Q, int32_t 
   if (stage_in(h, p)) return 1;
   const TopkIo io{p[6].as<float>(), p[4].as<uint64_t>(), p[5].as<uint64_t>(), p[0].as<double>(), p[1].as<int64_t>(), p[7].as<int32_t>()};
   if (score_after_dev_locked(h, io, Q, k, p[2].as<double>(), p[3].as<int64_t>(), nullptr)) return 1;
+  HIPCHECK(h, sync_stream(nullptr));
+  return stage_out(h, p);
+}
+
+int sse_index_set_bias(sse_handle *h, const float *bias_host, int64_t N) {
+  SSE_ENTER(h);
+  if (index_set_bias_locked(h, bias_host, N, true, nullptr)) return 1;
+  HIPCHECK(h, hipStreamSynchronize(nullptr));
+  return 0;
+}
+
+int sse_index_set_bias_dev(sse_handle *h, const float *bias_dev, int64_t N, void *stream) {
+  SSE_ENTER(h);
+  return index_set_bias_locked(h, bias_dev, N, false, (hipStream_t)stream);
+}
+
+int sse_score_topk_biased_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, const float *q_weight_dev,
+                              const uint64_t *q_any_dev, const uint64_t *q_none_dev, double *out_scores_dev,
+                              int64_t *out_ids_dev, int32_t *out_counts_dev, void *stream) {
+  SSE_ENTER(h);
+  if (score_biased_check(h, Q, k, q_any_dev, q_none_dev)) return 1;
+  if (Q == 0) return 0;
+  if (!q_dev || !out_scores_dev || !out_ids_dev || !out_counts_dev) return fail(h, "bad arguments to sse_score_topk_biased");
+  const TopkIo io{q_dev, q_any_dev, q_none_dev, out_scores_dev, out_ids_dev, out_counts_dev};
+  return score_biased_dev_locked(h, io, Q, k, q_weight_dev, (hipStream_t)stream);
+}
+
+int sse_score_topk_biased(sse_handle *h, const float *q_host, int32_t Q, int32_t k, const float *q_weight, const uint64_t *q_any,
+                          const uint64_t *q_none, double *out_scores, int64_t *out_ids, int32_t *out_counts) {
+  SSE_ENTER(h);
+  if (score_biased_check(h, Q, k, q_any, q_none)) return 1;
+  if (Q == 0) return 0;
+  if (!q_host || !out_scores || !out_ids || !out_counts) return fail(h, "bad arguments to sse_score_topk_biased");
+  const size_t o8 = (size_t)Q * k * 8, m8 = (size_t)Q * 8;
+  StagePiece p[] = {{o8, nullptr, out_scores}, {o8, nullptr, out_ids}, {m8, q_any}, {m8, q_none}, {(size_t)Q * sizeof(float), q_weight},
+                    {(size_t)Q * h->idx_S * sizeof(float), q_host}, {(size_t)Q * 4, nullptr, out_counts}};
+  if (stage_in(h, p)) return 1;
+  const TopkIo io{p[5].as<float>(), p[2].as<uint64_t>(), p[3].as<uint64_t>(), p[0].as<double>(), p[1].as<int64_t>(), p[6].as<int32_t>()};
+  if (score_biased_dev_locked(h, io, Q, k, p[4].as<float>(), nullptr)) return 1;
   HIPCHECK(h, sync_stream(nullptr));
   return stage_out(h, p);
 }

@@ -554,6 +554,22 @@ struct AfterArgs {
 };
 #define SSE_AFTER_MAX_K 1024
 hipError_t launch_score_after(const AfterArgs &g, hipStream_t st);  // every stage of one chunk
+// Exact top-k tag-eligible rows by cosine + per-row prior (score_biased.hip, DESIGN K6l): the stages of FilteredArgs (no
+// exclusion lists: excl = nullptr, n_excl = 0) carried out on y = fmaf(w[p], bias[r], fp32 score), with a bounds kernel in front
+// that widens e to e_b; the select stage adds (double)w[p] * (double)bias[r] to score64 before it keys a row.  counters of
+// `f`: [0] rows re-scored by the select stage, [1] queries of the float64 sweep.
+struct BiasedArgs {
+  FilteredArgs f;
+  const float *bias;        // [NT * 32] one prior per row of the resident index (zero past N)
+  const float *bias_absmax; // [1] max |bias| (device memory: the _dev setter never waits for it)
+  const float *weight;      // [P] or nullptr: 1.0f for every query
+  double *eb;               // [P] scratch: e_b
+  float norm_max;           // idx_norm_max
+};
+#define SSE_BIASED_MAX_K 1024
+hipError_t launch_score_biased(const BiasedArgs &g, hipStream_t st);  // every stage of one chunk
+// bias[N .. NT * 32) = 0 and *absmax = max |bias[0 .. N)| (as float bits; the caller zeroes it)
+hipError_t launch_bias_prepare(float *bias, int64_t N, int64_t NT, float *absmax, hipStream_t st);
 // The confusions of a query: the best k rows that are not among its positives and score at or above a floor derived from them
 // (score_confusions.hip, DESIGN K6k): the stages of FilteredArgs (no tags, no tile skip; f.excl / f.n_excl are the positives
 // [P][n_pos]) behind a kernel that scores the positives in float64 and forms f = (best positive score) - margin and

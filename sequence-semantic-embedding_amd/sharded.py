@@ -321,6 +321,72 @@ class ShardedIndex(object):
         all_reduce_(total, group=self.group)
         return out[0].view(torch.float64), out[1], torch.clamp(total, max=k).to(torch.int32)
 
+    def set_local_bias(self, bias):
+        """bias: CUDA float32 tensor [end-start] -- the bias of this rank's rows (Handle.index_set_bias), set after
+        set_local_rows.  None clears it; a rank without rows has nothing to bias."""
+        if bias is not None and bias.shape[0] != self.end - self.start:
+            raise ValueError("rank %d holds %d rows, got %d bias values" % (self.rank, self.end - self.start, bias.shape[0]))
+        if self.end == self.start:
+            return
+        if bias is None:
+            self.handle.index_set_bias_dev(None, 0)
+            return
+        import torch
+        if bias.dtype != torch.float32:
+            raise ValueError("bias must be a float32 tensor")
+        bias = bias.contiguous()
+        stream = torch.cuda.current_stream(bias.device).cuda_stream if bias.is_cuda else 0
+        self.handle.index_set_bias_dev(bias.data_ptr(), bias.shape[0], stream)
+
+    def score_topk_biased(self, queries, k, weight=None, any_of=None, none_of=None):
+        """Handle.score_topk_biased over the whole sharded index: queries CUDA float32 [Q,S], weight None, a number or a
+        float32 [Q] tensor, any_of / none_of int64 [Q] tensors holding the uint64 mask bits (or None), identical on every
+        rank.  Returns (scores float64 [Q,k], ids int64 [Q,k], counts int32 [Q]) on every rank: what the unsharded call
+        returns.  A biased score depends on the query and the row alone, so it is a global quantity: every rank makes the
+        local call with the full k, ONE all-gather exchanges the lists, the plain (score, id) merge of score_topk_filtered
+        ranks padding behind every real entry, ONE all-reduce adds the counts."""
+        import torch
+        import torch.distributed as dist
+        from .collectives import all_gather_into, all_reduce_
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise ValueError("k=%d must be in [1, 1024]" % k)
+        Q = int(queries.shape[0])
+        dev = queries.device
+        if weight is not None:
+            if not torch.is_tensor(weight):
+                weight = torch.full((Q,), float(weight), dtype=torch.float32, device=dev)
+            if weight.shape[0] != Q or weight.dtype != torch.float32:
+                raise ValueError("weight must be a number or a float32 [Q] tensor")
+            weight = weight.contiguous()
+        for m in (any_of, none_of):
+            if m is not None and (m.shape[0] != Q or m.dtype != torch.int64):
+                raise ValueError("any_of / none_of must be int64 [Q] tensors of mask bits")
+        queries = queries.contiguous()
+        any_of = any_of.contiguous() if any_of is not None else None
+        none_of = none_of.contiguous() if none_of is not None else None
+        stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
+        loc = torch.empty((2, Q, k), dtype=torch.int64, device=dev)        # [0] = float64 score bits, [1] = row ids
+        cnt = torch.zeros(Q, dtype=torch.int32, device=dev)
+        if self.end > self.start and Q > 0:
+            self.handle.score_topk_biased_dev(queries.data_ptr(), Q, k, weight.data_ptr() if weight is not None else None,
+                                              any_of.data_ptr() if any_of is not None else None,
+                                              none_of.data_ptr() if none_of is not None else None,
+                                              loc[0].data_ptr(), loc[1].data_ptr(), cnt.data_ptr(), stream)
+        else:
+            loc[0].view(torch.float64).fill_(float("-inf"))
+            loc[1].fill_(torch.iinfo(torch.int64).max)
+        if Q == 0 or (self.world == 1 and not self.always_gather):
+            return loc[0].view(torch.float64), loc[1], cnt
+        world = dist.get_world_size(self.group)
+        g = torch.empty((world * 2, Q, k), dtype=torch.int64, device=dev)
+        all_gather_into(g, loc, group=self.group)
+        out = torch.empty((2, Q, k), dtype=torch.int64, device=dev)
+        self.handle.merge_topk_strided_dev(g.data_ptr(), g[1].data_ptr(), 2 * Q * k, world, Q, k, out[0].data_ptr(), out[1].data_ptr(), stream)
+        total = cnt.to(torch.int64)
+        all_reduce_(total, group=self.group)
+        return out[0].view(torch.float64), out[1], torch.clamp(total, max=k).to(torch.int32)
+
     def score_confusions(self, queries, k, positives, margin=float("inf")):
         """Handle.score_confusions over the whole sharded index: queries CUDA float32 [Q,S], positives int64 [Q, n_pos <= 64]
         GLOBAL row ids padded with -1, identical on every rank.  Returns (scores float64 [Q,k], ids int64 [Q,k], counts int32

@@ -150,6 +150,24 @@ def hard_negatives(handle, queries, positives, n):
     return ids, scores
 
 
+def csls_bias(handle, target_rows, source_rows, k=10, block=4096):
+    """The per-row bias that turns Handle.score_topk_biased (weight 1.0) into the CSLS ranking of cross-lingual retrieval.
+    CSLS ranks a source x against targets t by 2 cos(x,t) - r_T(x) - r_S(t), r_S(t) the mean score of t's k nearest SOURCE
+    rows; r_T(x) is the same for every target of a query, so the order is that of cos(x,t) - 0.5 r_S(t).  `source_rows`
+    float32 [M,S] are uploaded as the handle's index (id_base 0), `target_rows` float32 [N,S] are scored against them with
+    Handle.score_topk(..., min(k, M)) in blocks of `block`; returns float32 [N], -0.5 * (mean of those scores) per target row.
+    The handle is left holding the SOURCE rows: upload the target index afterwards, then Handle.index_set_bias the result."""
+    src = np.ascontiguousarray(source_rows, dtype=np.float32)
+    tgt = np.ascontiguousarray(target_rows, dtype=np.float32)
+    kk = min(int(k), src.shape[0])
+    handle.index_upload(src)
+    out = np.empty(tgt.shape[0], np.float32)
+    for b0 in range(0, tgt.shape[0], int(block)):
+        scores, _ = handle.score_topk(tgt[b0:b0 + int(block)], kk)
+        out[b0:b0 + scores.shape[0]] = (-0.5 * np.asarray(scores, np.float64).mean(axis=1)).astype(np.float32)
+    return out
+
+
 def ranked_pages(handle, queries, page, any_of=None, none_of=None):
     """The whole ranked list of every query, page after page (the reference sorts all targets and cuts once, webserver.py:
     144-151): a generator of (scores float64 [Q,page], ids int64 [Q,page], counts int32 [Q]) from Handle.score_topk_after, each

@@ -1,0 +1,179 @@
+"""ShardedIndex.score_topk_biased as REAL ranks: processes on the one GPU of a test box, a `gloo` group between them
+(host-staged collectives), each holding its rows, tag words and bias values only.  Two ranks over uneven shards (4099 rows:
+2050 + 2049, id_base 2050 on rank 1) with an exact tie across the boundary whose rows carry one bias, a query whose eligible rows
+all live on rank 1, one with fewer than k eligible rows in total, one with none, and a weight per query, zero and negative
+included; three ranks over a two-row index (rank 2 holds nothing, k exceeds the rows).  Rows, queries, bias and weights are
+multiples of 1/4: every biased score is exact in any order, so the result on EVERY rank must equal the single-handle call on the
+whole index and the float64 oracle bit for bit -- including the (-inf, INT64_MAX) padding the merge writes into every slot
+past the real entries.  One launch of tests/biased_two_rank_worker.py per rank; a child that fails, or the cap, ends the launch
+and the other children are killed; a child that died of a signal ends the pytest session -- nothing more starts on the GPU
+after a fault."""
+import json
+import os
+import socket
+import subprocess
+import sys
+import time
+
+import numpy as np
+import pytest
+
+from oracle import sse_oracle as O
+from tests import filtered_cases as FC
+from tests import rank_cases as RC
+from tests.util import make_pair, model_params
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+WORKER = os.path.join(HERE, "biased_two_rank_worker.py")
+LAUNCH_CAP_S = 120                      # safety limit of the launch, not a measurement
+FAULT_CODES = (134, 139, 124, 137)
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _tail(path, n=25):
+    try:
+        with open(path, errors="replace") as f:
+            return "".join(f.readlines()[-n:])
+    except OSError:
+        return "(no output)"
+
+
+def _launch(tmp, world, job):
+    job_path = os.path.join(tmp, "job.json")
+    with open(job_path, "w") as f:
+        json.dump(job, f)
+    procs, logs = [], []
+    for r in range(world):
+        logs.append((os.path.join(tmp, "rank%d.out" % r), os.path.join(tmp, "rank%d.err" % r)))
+        with open(logs[r][0], "w") as fo, open(logs[r][1], "w") as fe:
+            procs.append(subprocess.Popen([sys.executable, WORKER, job_path, str(r)], stdout=fo, stderr=fe,
+                                          stdin=subprocess.DEVNULL, cwd=os.path.dirname(HERE)))
+    deadline = time.monotonic() + LAUNCH_CAP_S
+    ended, why = {}, None
+    while len(ended) < world and why is None:
+        for r, p in enumerate(procs):
+            if r not in ended and p.poll() is not None:
+                ended[r] = p.returncode
+                if p.returncode != 0:
+                    why = "rank %d ended with code %d" % (r, p.returncode)
+        if why is None and len(ended) < world:
+            if time.monotonic() > deadline:
+                why = "no result after %d s" % LAUNCH_CAP_S
+            else:
+                time.sleep(0.1)
+    for p in procs:                                              # nothing is left running, whatever happened
+        if p.poll() is None:
+            p.kill()
+    for p in procs:
+        p.wait()
+    if why is not None:
+        text = "launch of %d ranks: %s\n" % (world, why) + "".join(
+            "---- rank %d (%s) stderr:\n%s---- stdout:\n%s" % (r, ended.get(r, "killed"), _tail(logs[r][1]), _tail(logs[r][0], 5))
+            for r in range(world))
+        if any(rc < 0 or rc in FAULT_CODES for rc in ended.values()):
+            pytest.exit("a rank died of a signal; nothing more is started on the GPU\n" + text, returncode=3)
+        pytest.fail(text, pytrace=False)
+    return [np.load(os.path.join(tmp, "rank%d.npz" % r)) for r in range(world)]
+
+
+def _reference(q, t, tags, any_, none_, bias, w, k):
+    """the float64 oracle of the whole index (biased scores exact in any order: the quarter construction)"""
+    s = O.scores_f64(q, t.astype(np.float64)) + w.astype(np.float64)[:, None] * bias.astype(np.float64)[None, :]
+    Q, N = s.shape
+    e = ((any_[:, None] == 0) | ((tags[None, :] & any_[:, None]) != 0)) & ((tags[None, :] & none_[:, None]) == 0)
+    ws, wi, wc = np.full((Q, k), -np.inf), np.full((Q, k), FC.PAD_ID, np.int64), np.zeros(Q, np.int32)
+    for qi in range(Q):
+        cols = np.flatnonzero(e[qi])
+        c = min(k, cols.size)
+        if c:
+            ss, ii = O.topk(s[qi:qi + 1, cols], c)
+            ws[qi, :c], wi[qi, :c], wc[qi] = ss[0], cols[ii[0]], c
+    return ws, wi, wc
+
+
+def _single_handle(q, t, tags, any_, none_, bias, w, k):
+    m, _ = make_pair(model_params("dual-encoder", 50, 8, 16, 16, 8, 4))
+    m.handle.index_upload(t)
+    m.handle.index_set_tags(tags)
+    m.handle.index_set_bias(bias)
+    want = m.handle.score_topk_biased(q, k, weight=w, any_of=any_, none_of=none_)
+    m.handle.close()
+    ref = _reference(q, t, tags, any_, none_, bias, w, k)
+    for a, b in zip(want, ref):
+        assert np.array_equal(a, b)
+    return want
+
+
+def _check_ranks(out, want):
+    for r in range(len(out)):
+        assert np.array_equal(out[r]["ids"], want[1]), "rank %d" % r
+        assert np.array_equal(out[r]["scores"], want[0]), "rank %d" % r
+        assert np.array_equal(out[r]["counts"], want[2]) and out[r]["counts"].dtype == np.int32, "rank %d" % r
+        assert str(out[r]["bad_k"]).startswith("ValueError") and str(out[r]["bad_len"]).startswith("ValueError")
+        assert int(out[r]["bruteforce"]) == 0
+
+
+def test_biased_topk_on_two_ranks_equals_the_single_handle(tmp_path):
+    from sse_amd.sharded import shard_bounds
+    tmp = str(tmp_path)
+    q, t = RC.shard_case()                                       # multiples of 1/4: exact in any order; row 4000 == row 10
+    N, Q, k = t.shape[0], q.shape[0], 8
+    bounds = shard_bounds(N, 2)
+    assert bounds == [(0, 2050), (2050, 4099)]                   # uneven; id_base = 2050 on rank 1
+    cut = bounds[1][0]
+    b = int(np.argmax((t.astype(np.float64) ** 2).sum(1)))       # the row of largest norm: it and its copies are the strict
+    assert b not in (cut - 1, cut)                               # maxima of the query equal to it (Cauchy-Schwarz)
+    t[cut - 1] = t[cut] = t[b]                                   # a tie across the boundary itself
+    q[0] = t[b]
+    rng = np.random.RandomState(8)
+    bias = (rng.randint(-4, 5, size=N) / 4.0).astype(np.float32)
+    bias[[b, cut - 1, cut]] = np.float32(1.0)                    # ... whose rows carry one bias, the largest there is
+    w = (rng.randint(-2, 5, size=Q) / 2.0).astype(np.float32)
+    w[0], w[1], w[5], w[6] = 1.0, 0.5, 0.0, -1.0
+    tags = (FC.bit(0) | (FC.U1 << rng.randint(1, 4, size=N).astype(np.uint64))).astype(np.uint64)
+    tags[rng.choice(np.arange(cut, N), 30, replace=False)] |= FC.bit(5)      # rank 1 only
+    tags[[5, 700, 2049]] |= FC.bit(6)                                         # three rows of rank 0 ...
+    tags[[2050, 4098]] |= FC.bit(6)                                           # ... two of rank 1: five in all, fewer than k
+    any_ = (FC.U1 << rng.randint(0, 4, size=Q).astype(np.uint64)).astype(np.uint64)
+    any_[0], any_[1], any_[2], any_[3], any_[4] = FC.bit(0), FC.bit(5), FC.bit(6), FC.bit(7), np.uint64(0)
+    none_ = np.zeros(Q, np.uint64)
+    none_[5:] = FC.bit(3)
+    want = _single_handle(q, t, tags, any_, none_, bias, w, k)
+    assert want[1][0, :3].tolist() == sorted([b, cut - 1, cut]) and want[0][0, 0] == want[0][0, 2] > want[0][0, 3]
+    assert (want[1][1, :want[2][1]] >= cut).all() and want[2][1] == k        # every eligible row on rank 1
+    assert want[2][2] == 5 and (want[1][2, 5:] == FC.PAD_ID).all() and (want[0][2, 5:] == -np.inf).all()
+    assert want[2][3] == 0 and (want[1][3] == FC.PAD_ID).all()
+    assert (want[1][:, 0] < cut).any() and (want[1][:, 0] >= cut).any()     # best rows on either shard
+    unbiased = _reference(q, t, tags, any_, none_, np.zeros(N, np.float32), w, k)
+    assert (unbiased[1] != want[1]).any(), "the bias changes nothing"
+    np.savez(os.path.join(tmp, "inputs.npz"), t=t, q=q, tags=tags, any=any_, none=none_, bias=bias, w=w)
+    job = dict(world=2, port=_free_port(), inputs=os.path.join(tmp, "inputs.npz"), out_dir=tmp, bounds=[list(x) for x in bounds], k=k)
+    _check_ranks(_launch(tmp, 2, job), want)
+
+
+def test_biased_topk_with_an_empty_shard(tmp_path):
+    from sse_amd.sharded import shard_bounds
+    tmp = str(tmp_path)
+    q, t = RC.quarter_set(52, 3, 2, 16)
+    bounds = shard_bounds(2, 3)
+    assert bounds == [(0, 1), (1, 2), (2, 2)]                    # rank 2 holds nothing
+    tags = np.array([FC.bit(0), FC.bit(1)], np.uint64)
+    any_ = np.array([FC.bit(0), FC.bit(0) | FC.bit(1), FC.bit(2)], np.uint64)
+    none_ = np.zeros(3, np.uint64)
+    bias = np.array([0.25, -0.5], np.float32)
+    w = np.array([1.0, 2.0, 1.0], np.float32)
+    k = 4                                                        # more than the index has rows
+    want = _single_handle(q, t, tags, any_, none_, bias, w, k)
+    assert want[2].tolist() == [1, 2, 0]
+    np.savez(os.path.join(tmp, "inputs.npz"), t=t, q=q, tags=tags, any=any_, none=none_, bias=bias, w=w)
+    job = dict(world=3, port=_free_port(), inputs=os.path.join(tmp, "inputs.npz"), out_dir=tmp, bounds=[list(x) for x in bounds], k=k)
+    _check_ranks(_launch(tmp, 3, job), want)
