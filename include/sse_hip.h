@@ -152,7 +152,17 @@ int sse_encode_dev(sse_handle *h, int side, const int32_t *ids_dev, int32_t B, i
  * calls once a give-up was observed (another process on the device, or a refused cooperative launch).  "train_gen1" (default 0): the first-generation fp32 training
  * kernels instead of the round-4 ones (A/B and test aid; same results to fp32 summation order).
  * "eval_chunk_rows" (default 65536; >= 2, rounded down to even): sse_eval_loss* stages and encodes its pair rows in chunks of
- * at most this many, so that its scratch is bounded for any batch; the result does not depend on the value. */
+ * at most this many, so that its scratch is bounded for any batch; the result does not depend on the value.
+ * "train_loss" (default 0): the objective of sse_train_step* / sse_train_grads*, every network mode and every path.  0 = the
+ * reference's pair loss (sigmoid cross-entropy on 64 cos(src_b, tgt_b), sse_model.py:298); 1 = the in-batch softmax loss of
+ * sse_inbatch_loss_dev below over this call's rows, with keys the step forms itself: two rows carry the same source when
+ * their source token rows are equal, the same target when their target token rows are equal (dual- and shared-encoder, by
+ * ids or by corpus rows) or when they name the same row of the free target matrix (source-encoder-only, source_only_cnn).
+ * In a data-parallel job the negatives are the rank's own rows; the mean still runs over rows_global.  Any other value is
+ * refused.  "train_loss_scale" (default 64, accepted 1 .. 256): the logit scale c of the in-batch loss; the pair loss keeps
+ * the reference's 64.  Counter "train_inbatch_steps".  sse_eval_loss* evaluates the pair loss whatever train_loss says: its
+ * result is independent of how the rows are chunked, which a softmax over the whole batch cannot be; the held-out measure of
+ * the in-batch objective is sse_score_rank (MRR, recall@k). */
 int sse_set_option(sse_handle *h, const char *name, int32_t value);
 /* Diagnostic counters (cumulative).  "score_bf16_second_chance_queries": queries whose bf16-candidate result missed
  * its certificate and were re-run with fp32 candidates.  "score_collect_queries": queries served by the collect path
@@ -175,6 +185,7 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value);
  * "train_fp32_repacks": steps that rebuilt the fp32 Kh^T / Kx^T fragment copies of the BPTT kernels.
  * "train_split_repacks": steps that rebuilt their split-operand forms (options train_bwd_x3 + train_dk_x3).
  * "train_generic_repacks": packs of the any-shape path built, one per encoder side.
+ * "train_inbatch_steps": train steps whose loss stage ran the in-batch softmax head (option train_loss = 1).
  * "score_rank_band_rows" / "score_rank_bruteforce_pairs": see sse_score_rank.
  * "score_above_band_rows" / "score_above_bruteforce_pairs" / "score_above_long_segments": see sse_score_above.
  * "score_filtered_collected_rows" / "score_filtered_bruteforce_queries" / "score_filtered_tiles_skipped": see
@@ -184,6 +195,29 @@ int sse_get_counter(sse_handle *h, const char *name, int64_t *value);
 
 /* tf.nn.l2_normalize(x, dim=-1) on device rows (sse_model.py:282-283). */
 int sse_l2_normalize_dev(sse_handle *h, const float *x_dev, float *out_dev, int64_t rows, int32_t cols,
+                         void *stream);
+
+/* In-batch softmax loss (multiple-negatives ranking loss) over B pair rows of un-normalised encodings [B][S], with its
+ * gradient; the loss stage of the train step under option train_loss = 1, and usable with a caller's own encoders.
+ *   ns_i = s_i / sqrt(max(|s_i|^2, 1e-12)), nt_j likewise;  L_ij = scale * ns_i . nt_j
+ *   column j is admitted for row i when j == i, or when tgt_key_j != tgt_key_i and not (src_key_j == src_key_i and
+ *       labels_j != 0): a row with the same target, or another verified target of the same source, is no negative; a row
+ *       with label 0 still lends its target as a negative column
+ *   lse_i = log sum_{j admitted} exp(L_ij)  (row maximum subtracted);  row_loss_i = labels_i * (lse_i - L_ii)
+ *   row_acc_i = 1 when labels_i != 0 and no admitted j != i has L_ij > L_ii, else 0
+ *   G_ij = labels_i * scale * inv_rows * (p_ij - [i == j]), p_ij = exp(L_ij - lse_i) on admitted columns, else 0
+ *   d(ns_i) = sum_j G_ij nt_j, d(nt_j) = sum_i G_ij ns_i; d_src / d_tgt follow by the l2_normalize backward (below 1e-12
+ *       the clamp passes no gradient to the norm)
+ * The loss of the batch is inv_rows * sum_i row_loss_i, its accuracy inv_rows * sum_i row_acc_i; the caller adds them up.
+ * src_key_dev / tgt_key_dev: [B] int64 on the device, equal values = the same source / target; NULL = every row distinct.
+ * d_src_dev / d_tgt_dev: [B][S], or both NULL for loss and accuracy alone.  scale in (0, 256].
+ * All arithmetic is fp32 (logits and both gradient products on v_mfma_f32_32x32x2_f32); no B x B buffer exists, the logit
+ * tiles are recomputed by each of the three passes; every sum is taken in an order fixed by (B, S), no atomics: the same
+ * inputs give the same bits.  Queued on `stream`, no host synchronisation; the scratch (O(B * S + B)) belongs to the handle
+ * and only grows.  Bad arguments are refused before anything is queued. */
+int sse_inbatch_loss_dev(sse_handle *h, const float *src_raw_dev, const float *tgt_raw_dev, const float *labels_dev,
+                         const int64_t *src_key_dev, const int64_t *tgt_key_dev, int32_t B, int32_t S, float scale,
+                         float inv_rows, float *d_src_dev, float *d_tgt_dev, float *row_loss_dev, float *row_acc_dev,
                          void *stream);
 
 /* The target index (Evaluator.__init__ builds it from targetEncodingIndex.tsv,

@@ -42,6 +42,7 @@ SYMBOLS = {
     "sse_set_option": (C.c_int, [_P, C.c_char_p, C.c_int32]),
     "sse_get_counter": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
     "sse_l2_normalize_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, _P]),
+    "sse_inbatch_loss_dev": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
     "sse_index_upload": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64]),
     "sse_index_upload_f64": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64]),
     "sse_index_set_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, _P]),
@@ -253,6 +254,19 @@ class Handle(object):
 
     def l2_normalize_dev(self, x_ptr, out_ptr, rows, cols, stream=0):
         self.check(self.lib.sse_l2_normalize_dev(self._h, x_ptr, out_ptr, rows, cols, stream))
+
+    def inbatch_loss_dev(self, src_raw, tgt_raw, labels, src_key, tgt_key, B, S, scale, inv_rows, d_src, d_tgt, row_loss,
+                         row_acc, stream=0):
+        """sse_inbatch_loss_dev: the in-batch softmax loss head on device buffers.  Every buffer is a torch CUDA tensor
+        (contiguous; float32, keys int64) or a raw device pointer; src_key / tgt_key None = every row distinct; d_src and
+        d_tgt both None = loss and accuracy only.  Queued on `stream`, nothing is synchronised."""
+        def dev(x):
+            if x is None:
+                return None
+            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        self.check(self.lib.sse_inbatch_loss_dev(self._h, dev(src_raw), dev(tgt_raw), dev(labels), dev(src_key), dev(tgt_key),
+                                                 int(B), int(S), float(scale), float(inv_rows), dev(d_src), dev(d_tgt),
+                                                 dev(row_loss), dev(row_acc), stream))
 
     # -- index / scoring -----------------------------------------------------
     def index_upload(self, rows, id_base=0):

@@ -148,6 +148,8 @@ struct sse_handle {
   int train_gen1 = 0;    // option "train_gen1": the fp32 train step on the first-generation kernels (lstm_bwd_kernel + dx_kernel + db partials; A/B timing and tests)
   int train_pair_dedup = 1; // option "train_pair_dedup": run the source encoder once per (pos, neg) pair of rows that share it
   int train_serial = 0; // option "train_serial": both encoders on one stream (profiling: isolated kernel times)
+  int train_loss = 0;         // option "train_loss": 0 = the reference's pair loss, 1 = in-batch softmax (inbatch_loss.hip)
+  int train_loss_scale = 64;  // option "train_loss_scale": logit scale of the in-batch loss (the pair loss keeps the reference's 64)
   float *emb_pad = nullptr;  // [V][Ep]
   // source_only_cnn
   int cnn_W[4] = {-1, -1, -1, -1}, cnn_b[4] = {-1, -1, -1, -1}, cnn_M = -1, tgt_table = -1;
@@ -228,6 +230,10 @@ struct sse_handle {
   // counters "train_path_*", "train_paired_steps", "train_*_repacks": the route of every train step and what it rebuilt
   int64_t train_path_fused = 0, train_path_generic = 0, train_path_cnn = 0, train_paired_steps = 0;
   int64_t train_fp32_repacks = 0, train_split_repacks = 0, train_generic_repacks = 0;
+  int64_t train_inbatch_steps = 0;  // counter "train_inbatch_steps": steps whose loss stage ran the in-batch softmax head
+  // in-batch softmax loss (sse_inbatch_loss_dev and the train step under option train_loss = 1): staged operands, row
+  // statistics, un-normalised gradients (launch_inbatch_loss); the row keys [source | target | hash scratch] of a call
+  DevBuf s_inbatch, s_inbatch_keys;
   std::vector<hipEvent_t> events;
 };
 
@@ -2540,7 +2546,8 @@ int64_t sse_handle::*const HOST_COUNTERS[] = {&sse_handle::persist_fallbacks, &s
                                               &sse_handle::eval_paired_calls, &sse_handle::x_table_builds,
                                               &sse_handle::train_path_fused, &sse_handle::train_path_generic, &sse_handle::train_path_cnn,
                                               &sse_handle::train_paired_steps, &sse_handle::train_fp32_repacks,
-                                              &sse_handle::train_split_repacks, &sse_handle::train_generic_repacks};
+                                              &sse_handle::train_split_repacks, &sse_handle::train_generic_repacks,
+                                              &sse_handle::train_inbatch_steps};
 
 // every name sse_get_counter answers: its group and its word there (CG_HOST: entry of HOST_COUNTERS; CG_PATH: entry of
 // sse_handle::lstm_path_calls; a device group: the word the kernels of that family count in)
@@ -2561,6 +2568,7 @@ const struct {
     {"train_fp32_repacks", CG_HOST, 9},     // the fp32 Kh^T / Kx^T fragment copies of the BPTT kernels
     {"train_split_repacks", CG_HOST, 10},   // their split-operand forms KhT16 / KxT16
     {"train_generic_repacks", CG_HOST, 11}, // the any-shape path's packs, once per side
+    {"train_inbatch_steps", CG_HOST, 12},   // steps whose loss stage ran the in-batch softmax head (option train_loss = 1)
     // LSTM inference encodes by kernel
     {"lstm_path_persist", CG_PATH, PATH_PERSIST},
     {"lstm_path_cluster", CG_PATH, PATH_CLUSTER},
@@ -2651,6 +2659,8 @@ const struct {
     {"lstm_small_rows", &sse_handle::lstm_small_rows, 0, INT32_MAX, "lstm_small_rows must be >= 0"},
     {"lstm_x_table", &sse_handle::lstm_x_table, 0, 2, "lstm_x_table must be 0 (off), 1 (batches with B * T >= vocab_size) or 2 (always)"},
     {"lstm_x_table_mb", &sse_handle::lstm_x_table_mb, 0, INT32_MAX, "lstm_x_table_mb must be >= 0"},
+    {"train_loss", &sse_handle::train_loss, 0, 1, "train_loss must be 0 (pair) or 1 (in-batch softmax)"},
+    {"train_loss_scale", &sse_handle::train_loss_scale, 1, 256, "train_loss_scale must be in 1 .. 256"},
 };
 
 }  // namespace
@@ -2711,6 +2721,31 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value) {
 int sse_l2_normalize_dev(sse_handle *h, const float *x_dev, float *out_dev, int64_t rows, int32_t cols, void *stream) {
   SSE_ENTER(h);
   HIPCHECK(h, launch_l2_normalize(x_dev, out_dev, rows, cols, (hipStream_t)stream));
+  return 0;
+}
+
+// the handle's scratch of one in-batch loss call over B rows of S columns; keys: [source keys | target keys | hash words], B each
+static int reserve_inbatch(sse_handle *h, int B, int S) {
+  return reserve(h, h->s_inbatch, inbatch_scratch_bytes(B, S)) || reserve(h, h->s_inbatch_keys, (size_t)3 * B * sizeof(int32_t));
+}
+
+int sse_inbatch_loss_dev(sse_handle *h, const float *src_raw_dev, const float *tgt_raw_dev, const float *labels_dev,
+                         const int64_t *src_key_dev, const int64_t *tgt_key_dev, int32_t B, int32_t S, float scale, float inv_rows,
+                         float *d_src_dev, float *d_tgt_dev, float *row_loss_dev, float *row_acc_dev, void *stream) {
+  SSE_ENTER(h);
+  if (B < 1 || S < 1) return fail(h, "sse_inbatch_loss_dev: B and S must be >= 1");
+  if (!src_raw_dev || !tgt_raw_dev || !labels_dev || !row_loss_dev || !row_acc_dev)
+    return fail(h, "sse_inbatch_loss_dev: encodings, labels, row_loss and row_acc must not be NULL");
+  if ((d_src_dev == nullptr) != (d_tgt_dev == nullptr))
+    return fail(h, "sse_inbatch_loss_dev: d_src and d_tgt must both be given, or both be NULL (forward only)");
+  if (!(scale > 0.0f && scale <= 256.0f)) return fail(h, "sse_inbatch_loss_dev: scale must be in (0, 256]");
+  if (reserve_inbatch(h, B, S)) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  int32_t *ks = (int32_t *)h->s_inbatch_keys.p, *kt = ks + B;
+  HIPCHECK(h, launch_inbatch_value_keys(src_key_dev, 64, B, ks, st));
+  HIPCHECK(h, launch_inbatch_value_keys(tgt_key_dev, 64, B, kt, st));
+  HIPCHECK(h, launch_inbatch_loss(src_raw_dev, tgt_raw_dev, labels_dev, ks, kt, B, B, S, scale, inv_rows, h->s_inbatch.p, d_src_dev,
+                                  d_tgt_dev, row_loss_dev, row_acc_dev, st));
   return 0;
 }
 
@@ -3368,6 +3403,27 @@ static int step_table_forward(StepFrame &f) {
   return 0;
 }
 
+// option train_loss = 1: the in-batch softmax head over this step's rows.  The keys come from what the step staged, in its
+// internal row order: a row's source key is the first row with the same source tokens; its target key the first row with
+// the same target tokens, or -- table target -- the row of the free target matrix itself.
+static int step_loss_inbatch(StepFrame &f) {
+  sse_handle *h = f.h;
+  TrainState &ts = *f.ts;
+  if (reserve_inbatch(h, f.B, f.S)) return 1;
+  int32_t *ks = (int32_t *)h->s_inbatch_keys.p, *kt = ks + f.B;
+  uint32_t *hash = (uint32_t *)(kt + f.B);
+  HIPCHECK(h, launch_inbatch_token_keys(f.ids(0), f.B, f.T, hash, ks, f.st));
+  if (f.table_tgt)
+    HIPCHECK(h, launch_inbatch_value_keys(f.ids(1), 32, f.B, kt, f.st));
+  else
+    HIPCHECK(h, launch_inbatch_token_keys(f.ids(1), f.B, f.T, hash, kt, f.st));
+  HIPCHECK(h, launch_inbatch_loss(f.raw(0), f.raw(1), (const float *)ts.labels.p, ks, kt, f.B, f.Bp, f.S, (float)h->train_loss_scale,
+                                  f.inv_rows, h->s_inbatch.p, f.draw(0), f.draw(1), (float *)ts.row_loss.p, (float *)ts.row_acc.p, f.st));
+  HIPCHECK(h, launch_loss_reduce((const float *)ts.row_loss.p, (const float *)ts.row_acc.p, f.B, f.inv_rows, f.tail + 1, f.st));
+  h->train_inbatch_steps += 1;
+  return 0;
+}
+
 // loss, train accuracy, d(raw encodings); then the two lookup tables' gradients zeroed for the scatters of the backward
 static int step_loss(StepFrame &f) {
   sse_handle *h = f.h;
@@ -3378,8 +3434,12 @@ static int step_loss(StepFrame &f) {
   // flagged step cancels its own update on the device -- instead of stalling the queue here.  sse_train_grads reads it now,
   // on every path, so that a rank with a bad id fails here instead of only in its own sse_train_apply.
   if (!f.call->defer_err && check_err_flag(h, f.st)) return 1;
-  HIPCHECK(h, launch_loss(f.raw(0), f.raw(1), (const float *)ts.labels.p, f.draw(0), f.draw(1), (float *)ts.row_loss.p,
-                          (float *)ts.row_acc.p, f.tail + 1, f.B, f.Bp, f.S, f.inv_rows, f.st));
+  if (h->train_loss == 1) {
+    if (step_loss_inbatch(f)) return 1;
+  } else {
+    HIPCHECK(h, launch_loss(f.raw(0), f.raw(1), (const float *)ts.labels.p, f.draw(0), f.draw(1), (float *)ts.row_loss.p,
+                            (float *)ts.row_acc.p, f.tail + 1, f.B, f.Bp, f.S, f.inv_rows, f.st));
+  }
   HIPCHECK(h, hipMemsetAsync(f.emb->grad, 0, f.emb->count * sizeof(float), f.st));
   if (f.table_tgt) HIPCHECK(h, hipMemsetAsync(f.table->grad, 0, f.table->count * sizeof(float), f.st));
   return 0;

@@ -629,6 +629,20 @@ hipError_t launch_pack_rows_norm(const float *rows, int64_t R, int C, float *out
 hipError_t launch_f64_to_f32(const double *in, float *out, int64_t n, hipStream_t stream);
 hipError_t launch_l2_normalize(const float *x, float *out, int64_t rows, int cols, hipStream_t stream);
 
+// ------------------------------ in-batch softmax loss (inbatch_loss.hip) -----------------------------
+// Row keys of a step: key[b] = the smallest row of ids [B][T] holding the same T tokens as row b (a hash pre-filters, equal
+// hashes are confirmed on the tokens).  hash: [B] words of scratch.
+hipError_t launch_inbatch_token_keys(const int32_t *ids, int B, int T, uint32_t *hash, int32_t *key, hipStream_t st);
+// key[b] = the smallest row whose 64-bit key equals row b's (keys == nullptr: key[b] = b); with == 32: the same over 32-bit keys
+hipError_t launch_inbatch_value_keys(const void *keys, int width /* 32 | 64 */, int B, int32_t *key, hipStream_t st);
+// bytes of scratch launch_inbatch_loss needs: O(B * S + B)
+size_t inbatch_scratch_bytes(int B, int S);
+// The head (definition: DESIGN "In-batch softmax loss").  src_key / tgt_key: [B] keys >= 0 as the two launchers above leave them.
+// d_src / d_tgt: [rows_out][S] with rows B .. rows_out-1 zeroed, or both nullptr (forward only).  row_loss / row_acc: [B].
+hipError_t launch_inbatch_loss(const float *src_raw, const float *tgt_raw, const float *labels, const int32_t *src_key,
+                               const int32_t *tgt_key, int B, int rows_out, int S, float scale, float inv_rows, void *scratch,
+                               float *d_src, float *d_tgt, float *row_loss, float *row_acc, hipStream_t st);
+
 hipError_t launch_pack_lstm(const float *K, const float *b, int E, int H, int Ep, int Hp, int UB, float *Wp,
                             hipStream_t stream);
 // several re-layouts in one launch (the train step's: padded embedding table, packed kernels / projections, Kh^T / Kx^T)

@@ -6,6 +6,8 @@
 hipError_t launch_loss(const float *src_raw, const float *tgt_raw, const float *labels, float *d_src, float *d_tgt,
                        float *row_loss, float *row_acc, float *out2, int B, int Bp, int S, float inv_rows,
                        hipStream_t st);
+// out2[0] = inv_rows * sum(row_loss), out2[1] = inv_rows * sum(row_acc), fixed order (the second half of launch_loss)
+hipError_t launch_loss_reduce(const float *row_loss, const float *row_acc, int B, float inv_rows, float *out2, hipStream_t st);
 int proj_bwd_chunks(int Bp);
 hipError_t launch_proj_bwd(const float *hT, const float *d, const float *M, int Bp, int H, int Hp, int S, float *dM,
                            float *dh, float *dm_part /* [proj_bwd_chunks(Bp)][H*S] */, hipStream_t st);

@@ -1619,6 +1619,11 @@ hipError_t launch_loss(const float *src_raw, const float *tgt_raw, const float *
   return hipGetLastError();
 }
 
+hipError_t launch_loss_reduce(const float *row_loss, const float *row_acc, int B, float inv_rows, float *out2, hipStream_t st) {
+  hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, st, row_loss, row_acc, B, inv_rows, out2);
+  return hipGetLastError();
+}
+
 // dh on the fp32 matrix pipe (round 5; the 64 x 64 LDS-tiled VALU kernel above took 0.12 ms for 8192 x 576 x 512, 40 TFLOP/s):
 // D[b][j] = sum_s d[b][s] * M[j][s] -- both operands are read along s as they lie in memory: lane (row, k half) takes one
 // float4 of its row, s0 + 4 * (k half) .. + 3, and component u of the two halves is the k pair of the u-th

@@ -19,15 +19,20 @@ leaves the step before the all-reduce while its peers wait in it until the proce
 
 
 class DataParallelTrainer(object):
-    def __init__(self, engine, device=None, group=None, always_reduce=False, sparse_embedding=None):
+    def __init__(self, engine, device=None, group=None, always_reduce=False, sparse_embedding=None, options=None):
         """always_reduce: issue the collective even in a 1-rank group (exercises the RCCL path on one GPU).
+        options: {name: value} set on this rank's engine (engine.set_option) before the first step, e.g.
+        {"train_loss": 1, "train_loss_scale": 64} for the in-batch softmax loss: every rank passes the same dict, so every
+        rank's handle computes the same objective (its negatives are the rank's own rows; the mean runs over rows_global).
         sparse_embedding: exchange the word-embedding gradient as (row id, gradient row) pairs -- SURVEY 8e's shape for
         large vocabularies (the 1M-title ranking vocabulary, reference README.md:116) -- instead of all-reducing the
         dense [V,E] block; None = automatic (sparse when the GLOBAL batch touches fewer than V/4 rows: 2 * rows_global * T < V / 4)."""
         import torch
         self.engine, self.group, self.always_reduce = engine, group, bool(always_reduce)
         self.sparse_embedding = sparse_embedding
-        self.arena = torch.zeros(engine.train_grad_count(), dtype=torch.float32, device=device or "cpu")
+        for name, value in (options or {}).items():
+            engine.set_option(name, value)
+        self.arena =torch.zeros(engine.train_grad_count(), dtype=torch.float32, device=device or "cpu")
         engine.train_bind_arena(self.arena)
         self._stream = None
         # where the dense word_embedding gradient sits in the arena: (offset, V, E); the HIP handle keeps it first

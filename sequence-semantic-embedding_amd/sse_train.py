@@ -44,6 +44,10 @@ FLAGS = flags.FlagSet("sse_train", [
                           "EvalPairs (each with its first verified target and one sampled negative)"),
     ("eval_ranks", int, 0, "1: after each epoch's task evaluation, log the mean reciprocal rank and the mean / median rank of the "
                            "best-ranked verified target of every evaluation source over the whole index"),
+    ("loss", str, "pair", "pair (default): the reference's sigmoid cross-entropy on 64 cos(src, tgt) of every pair row; inbatch: "
+                          "softmax over the batch -- every other row's target is a negative of a source, its own verified "
+                          "targets and repeated targets masked out (library option train_loss)"),
+    ("loss_scale", int, 64, "--loss inbatch: the logit scale, 1 .. 256 (library option train_loss_scale)"),
     ("hard_learning", int, 0, "N > 0: at the start of every epoch from --hard_start_epoch on, mine up to N confusions per training "
                               "source (targets that are not verified for it and score near or above its best verified one) and draw "
                               "negatives from them; 0 (default): uniform negatives only, like the reference"),
@@ -67,7 +71,12 @@ def create_model(f, session, targetSpaceSize, vocabsize, forward_only):
     if getattr(f, "train_x3", 0) and f.network_mode != "source_only_cnn":   # opt-in split-operand train step (library default: float32)
         for opt in ("train_dk_x3", "train_fwd_x3", "train_bwd_x3"):
             model.handle.set_option(opt, 1)
-    ckpt = get_checkpoint_state(f.model_dir)
+    loss = getattr(f, "loss", "pair")
+    if loss not in ("pair", "inbatch"):
+        raise ValueError("--loss must be pair or inbatch, not %r" % (loss,))
+    model.handle.set_option("train_loss", 1 if loss == "inbatch" else 0)
+    model.handle.set_option("train_loss_scale", int(getattr(f, "loss_scale", 64)))
+    ckpt =get_checkpoint_state(f.model_dir)
     if ckpt:
         logging.info("Reading model parameters from %s" % ckpt)
         model.saver.restore(session, ckpt)
@@ -99,8 +108,8 @@ def train(f):
     data = sse_data.Data(f.model_dir, f.data_dir, f.vocab_size, f.max_seq_length,
                          seed=None if f.seed < 0 else f.seed, log=logging.info)
     epoc_steps = len(data.rawTrainPosCorpus) / f.batch_size
-    logging.info("Training Data: %d total positive samples, each epoch need %d steps"
-                 % (len(data.rawTrainPosCorpus), epoc_steps))
+    logging.info("Training Data: %d total positive samples, each epoch need %d steps; loss: %s%s"
+                 % (len(data.rawTrainPosCorpus), epoc_steps, f.loss, " (scale %d)" % f.loss_scale if f.loss == "inbatch" else ""))
     model = create_model(f, None, data.rawnegSetLen, data.vocab_size, False)
     sess = Session(model)
     summary_op = model.add_summaries()
