@@ -162,7 +162,8 @@ int sse_encode_dev(sse_handle *h, int side, const int32_t *ids_dev, int32_t B, i
  * refused.  "train_loss_scale" (default 64, accepted 1 .. 256): the logit scale c of the in-batch loss; the pair loss keeps
  * the reference's 64.  Counter "train_inbatch_steps".  sse_eval_loss* evaluates the pair loss whatever train_loss says: its
  * result is independent of how the rows are chunked, which a softmax over the whole batch cannot be; the held-out measure of
- * the in-batch objective is sse_score_rank (MRR, recall@k). */
+ * the in-batch objective is sse_score_rank (MRR, recall@k), and sse_score_lse for the softmax over the whole INDEX, which
+ * is chunk-independent: the full-softmax cross-entropy that the in-batch loss estimates. */
 int sse_set_option(sse_handle *h, const char *name, int32_t value);
 /* Diagnostic counters (cumulative).  "score_bf16_second_chance_queries": queries whose bf16-candidate result missed
  * its certificate and were re-run with fp32 candidates.  "score_collect_queries": queries served by the collect path
@@ -190,7 +191,8 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value);
  * "score_above_band_rows" / "score_above_bruteforce_pairs" / "score_above_long_segments": see sse_score_above.
  * "score_filtered_collected_rows" / "score_filtered_bruteforce_queries" / "score_filtered_tiles_skipped": see
  * sse_score_topk_filtered.
- * "score_grouped_collected_rows" / "score_grouped_bruteforce_queries": see sse_score_topk_grouped. */
+ * "score_grouped_collected_rows" / "score_grouped_bruteforce_queries": see sse_score_topk_grouped.
+ * "score_lse_calls" / "score_lse_tiles_skipped": see sse_score_lse. */
 int sse_get_counter(sse_handle *h, const char *name, int64_t *value);
 
 /* tf.nn.l2_normalize(x, dim=-1) on device rows (sse_model.py:282-283). */
@@ -496,6 +498,38 @@ int sse_score_topk_biased(sse_handle *h, const float *q_host, int32_t Q, int32_t
 int sse_score_topk_biased_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, const float *q_weight_dev,
                               const uint64_t *q_any_dev, const uint64_t *q_none_dev, double *out_scores_dev,
                               int64_t *out_ids_dev, int32_t *out_counts_dev, void *stream);
+
+/* Softmax log-partition over the whole index: the denominator that turns a returned score into P(row | query), and the
+ * first term of the full-softmax cross-entropy that the in-batch loss (option train_loss = 1) estimates.  Row r is eligible
+ * for query q by the tag rule of sse_score_topk_filtered (no exclusion list; q_any / q_none may be NULL), and
+ *     z_r = (double)scale * (score64(q, r) + (double)q_weight[q] * (double)bias[r])
+ * where score64 is the float64 dot product sse_score_topk returns and the parenthesis is the value sse_score_topk_biased
+ * returns; q_weight == NULL means no bias term.  So for any row the biased, the filtered or the plain top-k call returns,
+ *     P(row | q) = exp(scale * returned_score - out_lse[q]).
+ *   out_lse [Q]:   log of the sum of exp(z_r) over the eligible rows; -inf when no row is eligible; never NaN inside the claim.
+ *   out_count [Q]: the exact number of eligible rows.
+ *   out_bound [Q] (may be NULL): a certified bound on |out_lse[q] - LSE64(q)|, LSE64 the same sum taken in float64 from
+ *     score64: scale * e_b + 2^-16, with e_b the bound of sse_score_topk_biased on |fp32 biased score - its float64 value|
+ *     (e = eps32 |q| (1 + 2^-20) without a bias term).  Moving every logit by at most d moves the log of the sum by at most d;
+ *     the 2^-16 covers everything behind the dot product for every N (DESIGN K6m).
+ * Route: one fp32 MFMA sweep of the index (the bf16 images are not used: their score error times the scale is a fraction of
+ * a nat).  A lane keeps (m, sum of 2^(x - m), count) per query with x = z log2(e) and m an INTEGER reference, so a rising
+ * maximum rescales by an exact power of two and an index sorted by ascending score loses nothing; sums run in fp32 over the
+ * 16 rows of a tile and in float64 across tiles; the per (split, wave, lane half) partials are merged per query in a fixed
+ * order by a second kernel.  No floating-point atomics: the same inputs give the same bits.  Option "score_filtered_skip"
+ * governs the tile skip here too and changes no result.  Counters "score_lse_calls" (calls that passed their checks) and
+ * "score_lse_tiles_skipped".  Scratch is bounded by the chunk of 4096 queries.
+ * Rows or queries of norm below 2^-100, non-finite input and scale * |q| * (largest row norm + |w| bias_absmax) above 2^16
+ * are outside the claim (no fault).  This is the held-out measure of the softmax objective that sse_eval_loss* cannot be:
+ * nll(q, g) = out_lse[q] - scale * score64(q, g), the second term from sse_score_rank's out_score.
+ * Q == 0 succeeds.  No index, scale outside (0, 256], q_weight with no bias set, masks without tags: error with a message,
+ * decided on the host before anything is queued, no output written, the handle stays usable.  The host form runs on the null
+ * stream and synchronises; the _dev form takes device pointers, enqueues on `stream` and never waits for the device. */
+int sse_score_lse(sse_handle *h, const float *q_host, int32_t Q, float scale, const float *q_weight, const uint64_t *q_any,
+                  const uint64_t *q_none, double *out_lse, int64_t *out_count, double *out_bound);
+int sse_score_lse_dev(sse_handle *h, const float *q_dev, int32_t Q, float scale, const float *q_weight_dev,
+                      const uint64_t *q_any_dev, const uint64_t *q_none_dev, double *out_lse_dev, int64_t *out_count_dev,
+                      double *out_bound_dev, void *stream);
 
 /* encode + score in one call, the encodings never leaving the device: session.run([src_seq_embedding | norm_...])
  * followed by np.dot + getSortedResults[:k] as sse_demo.py:121-129, webserver.py:144-151 (and the three other routes)

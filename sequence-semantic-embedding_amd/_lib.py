@@ -68,6 +68,8 @@ SYMBOLS = {
     "sse_index_set_bias_dev": (C.c_int, [_P, _P, C.c_int64, _P]),
     "sse_score_topk_biased": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "sse_score_topk_biased_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "sse_score_lse": (C.c_int, [_P, _P, C.c_int32, C.c_float, _P, _P, _P, _P, _P, _P]),
+    "sse_score_lse_dev": (C.c_int, [_P, _P, C.c_int32, C.c_float, _P, _P, _P, _P, _P, _P, _P]),
     "sse_encode_score_topk": (C.c_int, [_P, C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_merge_topk_dev": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_merge_topk_strided_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
@@ -609,6 +611,44 @@ class Handle(object):
         enqueued on `stream`."""
         self.check(self.lib.sse_score_topk_biased_dev(self._h, q_ptr, int(Q), int(k), weight_ptr or None, any_ptr or None,
                                                       none_ptr or None, scores_ptr, ids_ptr, counts_ptr, stream))
+
+    def score_lse(self, queries, scale, weight=None, any_of=None, none_of=None):
+        """Softmax log-partition over the tag-eligible rows of the resident index: lse[q] = log sum_r exp(scale * (score +
+        weight[q] * bias[r])), scores and biased scores as score_topk / score_topk_biased return them, so that
+        exp(scale * returned_score - lse[q]) is P(row | q) (sse_index.softmax_probs).  weight: None (no bias term), a scalar
+        or float32 [Q]; any_of / none_of: uint64 [Q] tag masks, the eligibility rule of score_topk_filtered; 0 < scale <= 256.
+        Returns (lse float64 [Q], -inf where no row is eligible; count int64 [Q], the eligible rows; bound float64 [Q], a
+        certified bound on |lse - its float64 value|)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError("queries must be [Q,S]")
+        Q = q.shape[0]
+        w = None
+        if weight is not None:
+            w = np.asarray(weight, dtype=np.float32)
+            w = np.full(Q, w, np.float32) if w.ndim == 0 else np.ascontiguousarray(w.reshape(-1))
+            if w.shape[0] != Q:
+                raise ValueError("weight must be a scalar or float32 [Q]")
+        masks = []
+        for m in (any_of, none_of):
+            if m is not None:
+                m = np.ascontiguousarray(m, dtype=np.uint64).reshape(-1)
+                if m.shape[0] != Q:
+                    raise ValueError("any_of / none_of must be uint64 [Q]")
+            masks.append(m)
+        lse = np.empty(Q, np.float64)
+        count = np.empty(Q, np.int64)
+        bound = np.empty(Q, np.float64)
+        self.check(self.lib.sse_score_lse(self._h, _ptr(q), Q, float(scale), _ptr(w) if w is not None else None,
+                                          _ptr(masks[0]) if masks[0] is not None else None,
+                                          _ptr(masks[1]) if masks[1] is not None else None, _ptr(lse), _ptr(count), _ptr(bound)))
+        return lse, count, bound
+
+    def score_lse_dev(self, q_ptr, Q, scale, weight_ptr, any_ptr, none_ptr, lse_ptr, count_ptr, bound_ptr=None, stream=0):
+        """score_lse on device pointers (weight_ptr: float32 [Q]; weight_ptr / any_ptr / none_ptr / bound_ptr may be None / 0;
+        lse_ptr / bound_ptr: float64 [Q], count_ptr: int64 [Q]), enqueued on `stream`."""
+        self.check(self.lib.sse_score_lse_dev(self._h, q_ptr, int(Q), float(scale), weight_ptr or None, any_ptr or None,
+                                              none_ptr or None, lse_ptr, count_ptr, bound_ptr or None, stream))
 
     def merge_topk_strided_dev(self, in_s, in_i, shard_stride, P, Q, k, out_s, out_i, stream=0):
         self.check(self.lib.sse_merge_topk_strided_dev(self._h, in_s, in_i, int(shard_stride), P, Q, k, out_s, out_i, stream))

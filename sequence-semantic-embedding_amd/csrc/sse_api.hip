@@ -215,6 +215,11 @@ struct sse_handle {
   // three "score_confusions_*" counters.  Maxima, thresholds and row buffers are the filtered call's.
   DevBuf s_cf_bnd, s_cf_cnt;
   bool cf_cnt_init = false;
+  // softmax log-partition (sse_score_lse*, score_lse.hip): the (m, sum, count) partials of a chunk, the device word of
+  // "score_lse_tiles_skipped", and "score_lse_calls": calls that passed their checks (host and _dev forms alike)
+  DevBuf s_lse_part, s_lse_cnt;
+  bool lse_cnt_init = false;
+  int64_t score_lse_calls = 0;
   // staging of the host forms of the six calls above (stage_in): they hold the handle's mutex and finish all device work
   // before they return, so one buffer serves them all
   DevBuf s_stage;
@@ -1611,6 +1616,53 @@ static int score_biased_check(sse_handle *h, int Q, int k, const void *q_any, co
   return score_topk_check(h, CALL_BIASED, Q, k, q_any, q_none);
 }
 
+// sse_score_lse*: one sweep and one merge per chunk of 4096 queries, queued on `st` (device pointers throughout); the partials
+// [P][nsplit * 16] are the only scratch
+static int score_lse_dev_locked(sse_handle *h, const float *q, int Q, float scale, const float *weight, const uint64_t *q_any,
+                                const uint64_t *q_none, double *out_lse, int64_t *out_count, double *out_bound, hipStream_t st) {
+  if (ensure_zeroed_once(h, h->s_lse_cnt, h->lse_cnt_init, 1, st)) return 1;
+  LseArgs g{};  // (of FilteredArgs the sweep reads what fill_filtered_common and the chunk loop set; the rest stays null)
+  FilteredArgs &a = g.f;
+  fill_filtered_common(h, a, 0, 0, h->s_lse_cnt);
+  g.bias = weight ? (const float *)h->idx_bias.p : nullptr;
+  g.bias_absmax = weight ? (const float *)h->idx_bias_absmax.p : nullptr;
+  g.norm_max = h->idx_norm_max;
+  const double c = (double)scale * 1.4426950408889634;
+  g.scale = scale;
+  g.c_hi = (float)c;
+  g.c_lo = (float)(c - (double)g.c_hi);
+  for (int q0 = 0; q0 < Q; q0 += TOPK_POOL) {
+    const int P = std::min(TOPK_POOL, Q - q0);
+    SweepChunk ck;
+    if (sweep_chunk(h, P, ck)) return 1;
+    if (reserve(h, h->s_lse_part, score_lse_part_bytes(P, ck.nsplit))) return 1;
+    a.q = q + (size_t)q0 * h->idx_S;
+    a.q_any = q_any ? q_any + q0 : nullptr;
+    a.q_none = q_none ? q_none + q0 : nullptr;
+    a.P = P;
+    a.NQ = ck.NQ;
+    a.NSPLIT = ck.nsplit;
+    g.weight = weight ? weight + q0 : nullptr;
+    g.part = (LsePartial *)h->s_lse_part.p;
+    g.out_lse = out_lse + q0;
+    g.out_count = out_count + q0;
+    g.out_bound = out_bound ? out_bound + q0 : nullptr;
+    HIPCHECK(h, launch_score_lse(g, st));
+  }
+  h->score_lse_calls += 1;
+  return 0;
+}
+
+// argument errors of sse_score_lse*, all decidable on the host
+static int score_lse_check(sse_handle *h, int Q, float scale, const void *weight, const void *q_any, const void *q_none) {
+  if (!h->idxp) return fail(h, "sse_score_lse: no index uploaded");
+  if (Q < 0) return fail(h, "bad arguments to sse_score_lse");
+  if (!(scale > 0.0f && scale <= 256.0f)) return fail(h, "sse_score_lse: scale = %g is not in (0, 256]", (double)scale);
+  if (weight && !h->bias_set) return fail(h, "sse_score_lse: q_weight given but the index has no bias (sse_index_set_bias)");
+  if ((q_any || q_none) && !h->tags_set) return fail(h, "sse_score_lse: tag masks given but the index has no tags (sse_index_set_tags)");
+  return 0;
+}
+
 static const TopkCall CALL_CONFUSIONS = {"sse_score_confusions", SSE_CONFUSIONS_MAX_K, false};
 
 // argument errors of sse_score_confusions*, all decidable on the host
@@ -2536,18 +2588,19 @@ struct DevCounters {
   bool sse_handle::*init;
   int words;  // read back together
 };
-enum { CG_RANK, CG_ABOVE, CG_FILTERED, CG_GROUPED, CG_AFTER, CG_CONFUSIONS, CG_BIASED, CG_TOPK, CG_DEV_COUNT, CG_HOST = CG_DEV_COUNT, CG_PATH, CG_COOP };
+enum { CG_RANK, CG_ABOVE, CG_FILTERED, CG_GROUPED, CG_AFTER, CG_CONFUSIONS, CG_BIASED, CG_TOPK, CG_LSE, CG_DEV_COUNT, CG_HOST = CG_DEV_COUNT, CG_PATH, CG_COOP };
 const DevCounters DEV_COUNTERS[CG_DEV_COUNT] = {
     {&sse_handle::s_rk_cnt, &sse_handle::rk_cnt_init, 2}, {&sse_handle::s_ab_cnt, &sse_handle::ab_cnt_init, 3},
     {&sse_handle::s_ft_cnt, &sse_handle::ft_cnt_init, 3}, {&sse_handle::s_gp_cnt, &sse_handle::gp_cnt_init, 3},
     {&sse_handle::s_af_cnt, &sse_handle::af_cnt_init, 3}, {&sse_handle::s_cf_cnt, &sse_handle::cf_cnt_init, 3},
-    {&sse_handle::s_bs_cnt, &sse_handle::bs_cnt_init, 3}, {&sse_handle::s_fb_cnt, &sse_handle::fb_cnt_init, 4}};
+    {&sse_handle::s_bs_cnt, &sse_handle::bs_cnt_init, 3}, {&sse_handle::s_fb_cnt, &sse_handle::fb_cnt_init, 4},
+    {&sse_handle::s_lse_cnt, &sse_handle::lse_cnt_init, 1}};
 int64_t sse_handle::*const HOST_COUNTERS[] = {&sse_handle::persist_fallbacks, &sse_handle::two_pass_calls, &sse_handle::pad_sorted_calls,
                                               &sse_handle::eval_paired_calls, &sse_handle::x_table_builds,
                                               &sse_handle::train_path_fused, &sse_handle::train_path_generic, &sse_handle::train_path_cnn,
                                               &sse_handle::train_paired_steps, &sse_handle::train_fp32_repacks,
                                               &sse_handle::train_split_repacks, &sse_handle::train_generic_repacks,
-                                              &sse_handle::train_inbatch_steps};
+                                              &sse_handle::train_inbatch_steps, &sse_handle::score_lse_calls};
 
 // every name sse_get_counter answers: its group and its word there (CG_HOST: entry of HOST_COUNTERS; CG_PATH: entry of
 // sse_handle::lstm_path_calls; a device group: the word the kernels of that family count in)
@@ -2611,6 +2664,9 @@ const struct {
     {"score_bf16_second_chance_queries", CG_TOPK, 0},
     {"score_collect_queries", CG_TOPK, 1},
     {"score_bruteforce_queries", CG_TOPK, 2},
+    // sse_score_lse* (score_lse.hip): calls that passed their checks, index tiles its sweep skipped
+    {"score_lse_calls", CG_HOST, 13},
+    {"score_lse_tiles_skipped", CG_LSE, 0},
 };
 
 static int read_dev_counter(sse_handle *h, const DevCounters &g, int word, int64_t *value) {
@@ -3038,6 +3094,33 @@ int sse_score_topk_biased(sse_handle *h, const float *q_host, int32_t Q, int32_t
   if (stage_in(h, p)) return 1;
   const TopkIo io{p[5].as<float>(), p[2].as<uint64_t>(), p[3].as<uint64_t>(), p[0].as<double>(), p[1].as<int64_t>(), p[6].as<int32_t>()};
   if (score_biased_dev_locked(h, io, Q, k, p[4].as<float>(), nullptr)) return 1;
+  HIPCHECK(h, sync_stream(nullptr));
+  return stage_out(h, p);
+}
+
+int sse_score_lse_dev(sse_handle *h, const float *q_dev, int32_t Q, float scale, const float *q_weight_dev, const uint64_t *q_any_dev,
+                      const uint64_t *q_none_dev, double *out_lse_dev, int64_t *out_count_dev, double *out_bound_dev, void *stream) {
+  SSE_ENTER(h);
+  if (score_lse_check(h, Q, scale, q_weight_dev, q_any_dev, q_none_dev)) return 1;
+  if (Q == 0) return 0;
+  if (!q_dev || !out_lse_dev || !out_count_dev) return fail(h, "bad arguments to sse_score_lse");
+  return score_lse_dev_locked(h, q_dev, Q, scale, q_weight_dev, q_any_dev, q_none_dev, out_lse_dev, out_count_dev, out_bound_dev,
+                              (hipStream_t)stream);
+}
+
+int sse_score_lse(sse_handle *h, const float *q_host, int32_t Q, float scale, const float *q_weight, const uint64_t *q_any,
+                  const uint64_t *q_none, double *out_lse, int64_t *out_count, double *out_bound) {
+  SSE_ENTER(h);
+  if (score_lse_check(h, Q, scale, q_weight, q_any, q_none)) return 1;
+  if (Q == 0) return 0;
+  if (!q_host || !out_lse || !out_count) return fail(h, "bad arguments to sse_score_lse");
+  const size_t m8 = (size_t)Q * 8;
+  StagePiece p[] = {{m8, nullptr, out_lse}, {m8, nullptr, out_count}, {m8, nullptr, out_bound}, {m8, q_any}, {m8, q_none},
+                    {(size_t)Q * sizeof(float), q_weight}, {(size_t)Q * h->idx_S * sizeof(float), q_host}};
+  if (stage_in(h, p)) return 1;
+  if (score_lse_dev_locked(h, p[6].as<float>(), Q, scale, p[5].as<float>(), p[3].as<uint64_t>(), p[4].as<uint64_t>(), p[0].as<double>(),
+                           p[1].as<int64_t>(), p[2].as<double>(), nullptr))
+    return 1;
   HIPCHECK(h, sync_stream(nullptr));
   return stage_out(h, p);
 }

@@ -570,6 +570,26 @@ struct BiasedArgs {
 hipError_t launch_score_biased(const BiasedArgs &g, hipStream_t st);  // every stage of one chunk
 // bias[N .. NT * 32) = 0 and *absmax = max |bias[0 .. N)| (as float bits; the caller zeroes it)
 hipError_t launch_bias_prepare(float *bias, int64_t N, int64_t NT, float *absmax, hipStream_t st);
+// Softmax log-partition over the tag-eligible rows (score_lse.hip, DESIGN K6m): one fp32 sweep that keeps per (split, wave,
+// lane half) a partial (m, sum of 2^(x - m), count) of x = scale log2(e) fmaf(w[p], bias[r], fp32 score), and a merge kernel
+// that reduces a query's NSPLIT * 16 partials in a fixed order in float64 and writes log sum, count and bound.  Of `f` it
+// reads q, idxp, tags, tile_sum, q_any, q_none, N, S, KG, NT, P, NSPLIT (what sweep_decode takes), NQ, skip, eps32 and
+// counters: [0] tiles skipped.  weight == nullptr: no bias term (bias / bias_absmax unused).
+struct LsePartial;
+struct LseArgs {
+  FilteredArgs f;
+  const float *bias;         // [NT * 32] or nullptr
+  const float *bias_absmax;  // [1]
+  const float *weight;       // [P] or nullptr
+  LsePartial *part;          // [P][NSPLIT * 16] scratch, score_lse_part_bytes(P, NSPLIT); every entry is written by the sweep
+  double *out_lse;           // [P]
+  int64_t *out_count;        // [P]
+  double *out_bound;         // [P] or nullptr
+  float scale, c_hi, c_lo;   // c_hi + c_lo = scale * log2(e) to 2^-48
+  float norm_max;            // idx_norm_max
+};
+size_t score_lse_part_bytes(int P, int NSPLIT);
+hipError_t launch_score_lse(const LseArgs &g, hipStream_t st);  // both kernels of one chunk
 // The confusions of a query: the best k rows that are not among its positives and score at or above a floor derived from them
 // (score_confusions.hip, DESIGN K6k): the stages of FilteredArgs (no tags, no tile skip; f.excl / f.n_excl are the positives
 // [P][n_pos]) behind a kernel that scores the positives in float64 and forms f = (best positive score) - margin and

@@ -137,6 +137,27 @@ def merge_confusion_lists(scores, ids, pos_scores, pos_ids, margin, k):
     return out_s, out_i, take.sum(1).to(torch.int32), m, b
 
 
+def merge_lse_lists(lse, count, bound):
+    """The merge of ShardedIndex.score_lse on torch tensors of any device: the shards' results stacked in rank order (lse
+    float64 [W,Q], -inf where a shard has no eligible row; count int64 [W,Q]; bound float64 [W,Q]) -> (lse [Q], count [Q],
+    bound [Q]).  The log-partition of a union of disjoint row sets is the logaddexp of the parts: taken over the ranks in
+    rank order, so every rank forms the same bits.  Each part lies within its own bound of its float64 value, so their
+    logaddexp lies within the largest of them; the W - 1 float64 logaddexp of the merge add at most 2^-50 max(1, |lse|) each."""
+    import torch
+    W, Q = lse.shape
+    out = torch.full((Q,), float("-inf"), dtype=torch.float64, device=lse.device)
+    for r in range(W):
+        out = torch.logaddexp(out, lse[r])
+    total = count.sum(dim=0) if W else torch.zeros(Q, dtype=torch.int64, device=lse.device)
+    out = torch.where(total > 0, out, torch.full_like(out, float("-inf")))
+    if W:
+        b = bound.max(dim=0).values                          # (a rank without rows hands in 0)
+    else:
+        b = torch.zeros(Q, dtype=torch.float64, device=lse.device)
+    mag = torch.where(total > 0, out.abs(), torch.zeros_like(out)).clamp(min=1.0)
+    return out, total, b + max(W - 1, 0) * 2.0 ** -50 * mag
+
+
 class ShardedIndex(object):
     """One rank's view of the sharded index.  `handle` is an sse_amd Handle."""
 
@@ -386,6 +407,46 @@ class ShardedIndex(object):
         total = cnt.to(torch.int64)
         all_reduce_(total, group=self.group)
         return out[0].view(torch.float64), out[1], torch.clamp(total, max=k).to(torch.int32)
+
+    def score_lse(self, queries, scale, weight=None, any_of=None, none_of=None):
+        """Handle.score_lse over the whole sharded index: queries CUDA float32 [Q,S], weight None, a number or a float32 [Q]
+        tensor, any_of / none_of int64 [Q] tensors holding the uint64 mask bits (or None), identical on every rank.  Returns
+        (lse float64 [Q], count int64 [Q], bound float64 [Q]) on every rank.  The reduction is associative across row
+        shards: every rank makes the local call, ONE all-gather carries its [Q] results, merge_lse_lists takes the
+        logaddexp over the ranks in rank order, adds the counts and takes the largest bound.  A rank without rows, or
+        without an eligible row, contributes (-inf, 0)."""
+        import torch
+        import torch.distributed as dist
+        from .collectives import all_gather_into
+        Q = int(queries.shape[0])
+        dev = queries.device
+        if weight is not None:
+            if not torch.is_tensor(weight):
+                weight = torch.full((Q,), float(weight), dtype=torch.float32, device=dev)
+            if weight.shape[0] != Q or weight.dtype != torch.float32:
+                raise ValueError("weight must be a number or a float32 [Q] tensor")
+            weight = weight.contiguous()
+        for m in (any_of, none_of):
+            if m is not None and (m.shape[0] != Q or m.dtype != torch.int64):
+                raise ValueError("any_of / none_of must be int64 [Q] tensors of mask bits")
+        queries = queries.contiguous()
+        any_of = any_of.contiguous() if any_of is not None else None
+        none_of = none_of.contiguous() if none_of is not None else None
+        stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
+        loc = torch.zeros((3, Q), dtype=torch.int64, device=dev)           # [0] = lse bits, [1] = count, [2] = bound bits
+        loc[0].view(torch.float64).fill_(float("-inf"))
+        if self.end > self.start and Q > 0:
+            self.handle.score_lse_dev(queries.data_ptr(), Q, float(scale), weight.data_ptr() if weight is not None else None,
+                                      any_of.data_ptr() if any_of is not None else None,
+                                      none_of.data_ptr() if none_of is not None else None,
+                                      loc[0].data_ptr(), loc[1].data_ptr(), loc[2].data_ptr(), stream)
+        if Q == 0 or (self.world == 1 and not self.always_gather):
+            return loc[0].view(torch.float64), loc[1], loc[2].view(torch.float64)
+        world = dist.get_world_size(self.group)
+        g = torch.empty((world * 3, Q), dtype=torch.int64, device=dev)
+        all_gather_into(g, loc, group=self.group)
+        g = g.view(world, 3, Q)
+        return merge_lse_lists(g[:, 0].contiguous().view(torch.float64), g[:, 1], g[:, 2].contiguous().view(torch.float64))
 
     def score_confusions(self, queries, k, positives, margin=float("inf")):
         """Handle.score_confusions over the whole sharded index: queries CUDA float32 [Q,S], positives int64 [Q, n_pos <= 64]

@@ -68,6 +68,18 @@ def rank_metrics_from_ranks(ranks, top_n=(1, 3, 10), batch=600):
             "median_rank": float(np.median(1.0 + best)), "tight_acc": tight}
 
 
+def softmax_nll_from(lse, label_scores, scale):
+    """Full-softmax negative log-likelihood per source from the log-partition over the whole index (lse float64 [Q],
+    Handle.score_lse) and the float64 scores of each source's labels (a list of Q arrays, Handle.score_rank's out_score):
+    nll = lse - log sum over its DISTINCT labels of exp(scale * score): the mass the softmax puts on the source's label set.
+    `label_scores` holds one score per distinct label.  Returns float64 [Q]; 0 when the labels are all the eligible rows."""
+    lse = np.asarray(lse, np.float64)
+    out = np.empty(len(label_scores), np.float64)
+    for i, s in enumerate(label_scores):
+        out[i] = lse[i] - np.logaddexp.reduce(float(scale) * np.asarray(s, np.float64))
+    return out
+
+
 class Evaluator(object):
     def __init__(self, model, eval_corpus, tgtIndexFile, session):
         self.model = model
@@ -120,6 +132,40 @@ class Evaluator(object):
             before, _ = h.score_rank(h.encode(0, ids, True), pair_q, pair_id)
             out.extend(np.split(before, np.cumsum(counts)[:-1]))
         return out
+
+    def softmax_terms(self, scale=64.0, batch=600):
+        """(lse float64 [Q], bound float64 [Q], label_scores: Q float64 arrays, one score per DISTINCT label in order of first
+        appearance) of the evaluation corpus: the two terms of softmax_nll.  Sources are encoded as ranks() encodes them
+        (same chunks, same bits); the log-partition is Handle.score_lse over the whole index, the label scores are
+        Handle.score_rank's out_score."""
+        h = self.model.handle
+        if h.index_gen != self._index_gen:      # as in ranked()
+            h.index_upload(self.targetEncodings)
+            self._index_gen = h.index_gen
+        chunk = max(batch, 32768 // batch * batch)
+        lses, bounds, scores = [], [], []
+        for c0 in range(0, len(self.srcSeq_batch), chunk):
+            ids = np.array(self.srcSeq_batch[c0:c0 + chunk], dtype=np.int32)
+            labels = [list(dict.fromkeys(l)) for l in self.eval_Labels[c0:c0 + chunk]]
+            counts = np.array([len(l) for l in labels], dtype=np.int64)
+            pair_q = np.repeat(np.arange(len(ids), dtype=np.int32), counts)
+            pair_id = np.array([t for l in labels for t in l], dtype=np.int64)
+            enc = h.encode(0, ids, True)
+            _, sc = h.score_rank(enc, pair_q, pair_id)
+            lse, _, bound = h.score_lse(enc, scale)
+            lses.append(lse)
+            bounds.append(bound)
+            scores.extend(np.split(sc, np.cumsum(counts)[:-1]))
+        return np.concatenate(lses), np.concatenate(bounds), scores
+
+    def softmax_nll(self, scale=64.0, batch=600):
+        """Held-out full-softmax cross-entropy over the WHOLE index at logit scale `scale`: per source nll = lse - log sum
+        over its distinct labels of exp(scale * score64(label)) -- the objective the in-batch loss (option train_loss = 1)
+        estimates, independent of how the sources are chunked.  Returns {"nll": mean nll, "label_prob": mean of exp(-nll)}."""
+        self.model.set_forward_only(True)
+        lse, _, scores = self.softmax_terms(scale, batch)
+        nll = softmax_nll_from(lse, scores, scale)
+        return {"nll": float(np.mean(nll)), "label_prob": float(np.mean(np.exp(-nll)))}
 
     def rank_metrics(self, top_n=(1, 3, 10), batch=600):
         """{mrr, mean_rank, median_rank, tight_acc} over the evaluation corpus (rank_metrics_from_ranks); tight_acc equals

@@ -168,6 +168,18 @@ def csls_bias(handle, target_rows, source_rows, k=10, block=4096):
     return out
 
 
+def softmax_probs(scores, lse, scale):
+    """P(row | query) of returned scores: exp(scale * scores - lse[:, None]) in float64, with `scores` float64 [Q,k] as
+    Handle.score_topk / score_topk_filtered / score_topk_biased return them and `lse` float64 [Q] from Handle.score_lse made
+    with the same scale, weight and masks.  Padding columns (-inf) give 0, and so does every column of a query whose
+    eligible set is empty (lse = -inf)."""
+    s = np.asarray(scores, np.float64)
+    l = np.asarray(lse, np.float64).reshape(-1, 1)
+    live = np.isfinite(s) & np.isfinite(l)
+    z = np.where(live, float(scale) * np.where(live, s, 0.0) - np.where(np.isfinite(l), l, 0.0), -np.inf)
+    return np.exp(z)
+
+
 def ranked_pages(handle, queries, page, any_of=None, none_of=None):
     """The whole ranked list of every query, page after page (the reference sorts all targets and cuts once, webserver.py:
     144-151): a generator of (scores float64 [Q,page], ids int64 [Q,page], counts int32 [Q]) from Handle.score_topk_after, each

@@ -24,6 +24,7 @@ import numpy as np
 
 from . import sse_data, sse_text
 from .sse_evaluator import load_index_file
+from .sse_index import softmax_probs
 from .sse_model import SSEModel, get_checkpoint_state
 
 # route -> (query argument, default nbest, normalised encoding?, response key of the query, key of the result list,
@@ -74,11 +75,13 @@ class Ranker(object):
         """webserver.py:135-142: encode(lower-cased text), left-pad / truncate to max_seq_length."""
         return sse_text.pad_tokens(self.encoder.encode(text.lower()), self.max_seq_length)
 
-    def rank(self, token_rows, nbest, normalize, after=None):
+    def rank(self, token_rows, nbest, normalize, after=None, prob_scale=None):
         """Top-`nbest` (score, target id, target name) per token row; one encode + one sweep for all rows.
         after = (scores [B], row ids [B]): the next `nbest` (at most 1024) after each row's (score, row id) cursor instead, in
         the same order (Handle.score_topk_after), as (score, target id, target name, row id) -- a list may be shorter than
-        `nbest`, or empty, when the ranked list ends."""
+        `nbest`, or empty, when the ranked list ends.
+        prob_scale (0 < scale <= 256): every tuple gains a trailing probability, the softmax over the WHOLE index at that
+        logit scale -- exp(scale * score - lse) with lse from one Handle.score_lse on the encodings this call already has."""
         h = self.model.handle
         if h.index_gen != self._index_gen:                  # somebody scored another index on this handle
             h.index_upload(self._encodings)
@@ -87,17 +90,27 @@ class Ranker(object):
         if after is not None:
             enc = h.encode(0, np.asarray(token_rows, np.int32), normalize)
             scores, rows, counts = h.score_topk_after(enc, min(k, 1024), after=after)
-            return [[(float(scores[i, j]), self.targetIDs[rows[i, j]], self.targetNames[rows[i, j]], int(rows[i, j]))
-                     for j in range(int(counts[i]))] for i in range(len(token_rows))]
-        scores, rows = h.encode_score_topk(0, np.asarray(token_rows, np.int32), normalize, k)
-        return [[(float(scores[i, j]), self.targetIDs[rows[i, j]], self.targetNames[rows[i, j]]) for j in range(k)]
-                for i in range(len(token_rows))]
+            out = [[(float(scores[i, j]), self.targetIDs[rows[i, j]], self.targetNames[rows[i, j]], int(rows[i, j]))
+                    for j in range(int(counts[i]))] for i in range(len(token_rows))]
+        elif prob_scale is None:
+            scores, rows = h.encode_score_topk(0, np.asarray(token_rows, np.int32), normalize, k)
+            return [[(float(scores[i, j]), self.targetIDs[rows[i, j]], self.targetNames[rows[i, j]]) for j in range(k)]
+                    for i in range(len(token_rows))]
+        else:
+            scores, rows, enc = h.encode_score_topk(0, np.asarray(token_rows, np.int32), normalize, k, want_encodings=True)
+            out = [[(float(scores[i, j]), self.targetIDs[rows[i, j]], self.targetNames[rows[i, j]]) for j in range(k)]
+                   for i in range(len(token_rows))]
+        if prob_scale is None:
+            return out
+        lse, _, _ = h.score_lse(enc, float(prob_scale))
+        probs = softmax_probs(scores, lse, float(prob_scale))
+        return [[t + (float(probs[i, j]),) for j, t in enumerate(row)] for i, row in enumerate(out)]
 
 
 class MicroBatcher(object):
     """Gathers concurrent requests into one encode + score call: whatever is queued when the worker wakes up (at most
     `max_batch`, waiting at most `max_wait_s` for company) shares one sweep of the index.  Requests of the two
-    encoding kinds (normalised / raw) and different nbest go in separate calls of the same wake-up."""
+    encoding kinds (normalised / raw), different nbest and different prob_scale go in separate calls of the same wake-up."""
 
     def __init__(self, ranker, max_batch=32, max_wait_s=0.002):
         self.ranker, self.max_batch, self.max_wait_s = ranker, max_batch, max_wait_s
@@ -107,8 +120,8 @@ class MicroBatcher(object):
         self._t = threading.Thread(target=self._run, daemon=True)
         self._t.start()
 
-    def submit(self, tokens, nbest, normalize, timeout_s=30.0):
-        item = {"tokens": tokens, "nbest": nbest, "normalize": normalize, "done": threading.Event()}
+    def submit(self, tokens, nbest, normalize, timeout_s=30.0, prob_scale=None):
+        item = {"tokens": tokens, "nbest": nbest, "normalize": normalize, "prob_scale": prob_scale, "done": threading.Event()}
         self.q.put(item)
         # never wait forever: a dead worker thread (or a wedged device) must turn into an error response, not a hung request
         deadline = time.monotonic() + timeout_s
@@ -133,10 +146,13 @@ class MicroBatcher(object):
                     pass
                 groups = {}
                 for it in items:
-                    groups.setdefault((bool(it["normalize"]), int(it["nbest"])), []).append(it)
-                for (norm, nbest), grp in groups.items():
+                    groups.setdefault((bool(it["normalize"]), int(it["nbest"]), it.get("prob_scale")), []).append(it)
+                for (norm, nbest, pscale), grp in groups.items():
                     try:
-                        res = self.ranker.rank([it["tokens"] for it in grp], nbest, norm)
+                        if pscale is None:
+                            res = self.ranker.rank([it["tokens"] for it in grp], nbest, norm)
+                        else:
+                            res = self.ranker.rank([it["tokens"] for it in grp], nbest, norm, prob_scale=pscale)
                         for it, r in zip(grp, res):
                             it["result"] = r
                     except Exception as e:                       # noqa: BLE001  (delivered to the waiting request)
@@ -170,7 +186,9 @@ def handle_request(path, args, rank_fn, tokens_fn):
     `args`: {name: value}; `rank_fn(tokens, nbest, normalize)` -> [(score, id, name)].  With after_score and after_id among
     the arguments the list is the next nbest after that cursor -- `rank_fn(tokens, nbest, normalize, after=(score, row id))`
     -> [(score, id, name, row id)] -- and the response carries next_after_score / next_after_id, the cursor of the page
-    after this one (the request's own when the list came back empty)."""
+    after this one (the request's own when the list came back empty).  With prob_scale among the arguments (a logit scale in
+    (0, 256]) `rank_fn` is called with prob_scale=<float>, its tuples end in a probability -- the softmax over the whole index
+    at that scale -- and every result carries it as "prob"; without it the calls and the responses are what they always were."""
     if path == "/":
         return 200, BANNER
     route = ROUTES.get(path)
@@ -187,16 +205,28 @@ def handle_request(path, args, rank_fn, tokens_fn):
         cursor = parse_cursor(args)
     except ValueError as e:
         return 400, "bad cursor: %s" % e
+    pscale = None
+    if "prob_scale" in args:
+        try:
+            pscale = float(args["prob_scale"])
+        except ValueError:
+            return 400, "bad prob_scale: %r" % (args["prob_scale"],)
+        if not 0.0 < pscale <= 256.0:
+            return 400, "bad prob_scale: %r is not in (0, 256]" % (args["prob_scale"],)
+    extra = {} if pscale is None else {"prob_scale": pscale}
     if cursor is not None:
-        ranked = rank_fn(tokens_fn(text), nbest, normalize, after=cursor)
-        results = [{idk: tid, namek: name, scorek: float(score)} for score, tid, name, _row in ranked]
+        ranked = rank_fn(tokens_fn(text), nbest, normalize, after=cursor, **extra)
+        results = [dict({idk: t[1], namek: t[2], scorek: float(t[0])}, **({"prob": float(t[4])} if extra else {})) for t in ranked]
         nxt = (float(ranked[-1][0]), int(ranked[-1][3])) if ranked else cursor
         return 200, {qkey: text, rkey: results, "next_after_score": nxt[0], "next_after_id": nxt[1]}
-    ranked = rank_fn(tokens_fn(text), nbest, normalize)
+    ranked = rank_fn(tokens_fn(text), nbest, normalize, **extra)
     results = []
-    for i, (score, tid, name) in enumerate(ranked):
+    for i, t in enumerate(ranked):
+        score, tid, name = t[:3]
         logging.info("top%d:  %s , %f ,  %s " % (i + 1, tid, score, name))
         results.append({idk: tid, namek: name, scorek: float(score)})
+        if extra:
+            results[-1]["prob"] = float(t[3])
     return 200, {qkey: text, rkey: results}
 
 
@@ -209,12 +239,13 @@ def create_app(model_dir=None, index_file=None, device=0, ranker=None, batch=Tru
         ranker = Ranker(model_dir, index_file, device)
     batcher = MicroBatcher(ranker) if batch else None
 
-    def rank_fn(tokens, nbest, normalize, after=None):
+    def rank_fn(tokens, nbest, normalize, after=None, prob_scale=None):
+        extra = {} if prob_scale is None else {"prob_scale": prob_scale}
         if after is not None:                                # paged requests go past the micro-batcher
-            return ranker.rank([tokens], nbest, normalize, after=([after[0]], [after[1]]))[0]
+            return ranker.rank([tokens], nbest, normalize, after=([after[0]], [after[1]]), **extra)[0]
         if batcher is not None:
-            return batcher.submit(tokens, nbest, normalize)
-        return ranker.rank([tokens], nbest, normalize)[0]
+            return batcher.submit(tokens, nbest, normalize, **extra)
+        return ranker.rank([tokens], nbest, normalize, **extra)[0]
 
     def app(environ, start_response):
         args = {k: v[0] for k, v in parse_qs(environ.get("QUERY_STRING", ""), keep_blank_values=True).items()}

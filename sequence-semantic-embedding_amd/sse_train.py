@@ -44,6 +44,9 @@ FLAGS = flags.FlagSet("sse_train", [
                           "EvalPairs (each with its first verified target and one sampled negative)"),
     ("eval_ranks", int, 0, "1: after each epoch's task evaluation, log the mean reciprocal rank and the mean / median rank of the "
                            "best-ranked verified target of every evaluation source over the whole index"),
+    ("eval_nll", int, 0, "1: after each epoch's task evaluation, log the held-out full-softmax negative log-likelihood of every "
+                         "evaluation source's verified targets over the whole index, at the logit scale the run trains with "
+                         "(--loss_scale under --loss inbatch, 64 under the pair loss)"),
     ("loss", str, "pair", "pair (default): the reference's sigmoid cross-entropy on 64 cos(src, tgt) of every pair row; inbatch: "
                           "softmax over the batch -- every other row's target is a negative of a source, its own verified "
                           "targets and repeated targets masked out (library option train_loss)"),
@@ -191,6 +194,11 @@ def train(f):
                 rm = evaluator.rank_metrics()
                 logging.info("label ranks over the whole index: MRR %f, mean rank %f, median rank %f (%d sources)"
                              % (rm["mrr"], rm["mean_rank"], rm["median_rank"], len(evaluator.eval_Labels)))
+            if f.eval_nll:
+                nll_scale = f.loss_scale if f.loss == "inbatch" else 64
+                sm = evaluator.softmax_nll(scale=float(nll_scale))
+                logging.info("held-out full-softmax nll over the whole index: %f, label prob: %f (scale %d, %d sources)"
+                             % (sm["nll"], sm["label_prob"], nll_scale, len(evaluator.eval_Labels)))
             if f.eval_loss:
                 if eval_pairs is None:
                     eval_pairs = data.get_eval_pairs(seed=0, target_rows=table_tgt)
