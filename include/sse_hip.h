@@ -163,7 +163,17 @@ int sse_encode_dev(sse_handle *h, int side, const int32_t *ids_dev, int32_t B, i
  * the reference's 64.  Counter "train_inbatch_steps".  sse_eval_loss* evaluates the pair loss whatever train_loss says: its
  * result is independent of how the rows are chunked, which a softmax over the whole batch cannot be; the held-out measure of
  * the in-batch objective is sse_score_rank (MRR, recall@k), and sse_score_lse for the softmax over the whole INDEX, which
- * is chunk-independent: the full-softmax cross-entropy that the in-batch loss estimates. */
+ * is chunk-independent: the full-softmax cross-entropy that the in-batch loss estimates.
+ * "train_class_loss" (default 0, accepted 0 | 1): 1 = the loss stage of sse_train_step* / sse_train_grads* runs the class
+ * softmax loss of sse_class_loss_dev below: a softmax over EVERY row of the free target matrix
+ * target_embedding/tgt_seq_embedding, on every path, by ids and by corpus rows, with the logit scale of "train_loss_scale".
+ * Two rows carry the same source when their source token rows are equal.  The gradient of the matrix is dense (every class
+ * is a negative of every row) and enters clip_by_global_norm whole, like a projection matrix, instead of through the
+ * IndexedSlices slice norm; sse_train_apply takes that from the kind of step that left the pending gradients, not from the
+ * option's value at the time.  The objective decomposes over the rows of a batch, so a data-parallel step equals the
+ * single-rank step of the concatenated batch up to summation order, at any world size.  A step under this option is refused
+ * when the network mode has no free target matrix (dual-encoder, shared-encoder), or when "train_loss" = 1 is set as well
+ * (two objectives).  Counter "train_class_steps". */
 int sse_set_option(sse_handle *h, const char *name, int32_t value);
 /* Diagnostic counters (cumulative).  "score_bf16_second_chance_queries": queries whose bf16-candidate result missed
  * its certificate and were re-run with fp32 candidates.  "score_collect_queries": queries served by the collect path
@@ -187,6 +197,7 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value);
  * "train_split_repacks": steps that rebuilt their split-operand forms (options train_bwd_x3 + train_dk_x3).
  * "train_generic_repacks": packs of the any-shape path built, one per encoder side.
  * "train_inbatch_steps": train steps whose loss stage ran the in-batch softmax head (option train_loss = 1).
+ * "train_class_steps": train steps whose loss stage ran the class softmax head (option train_class_loss = 1).
  * "score_rank_band_rows" / "score_rank_bruteforce_pairs": see sse_score_rank.
  * "score_above_band_rows" / "score_above_bruteforce_pairs" / "score_above_long_segments": see sse_score_above.
  * "score_filtered_collected_rows" / "score_filtered_bruteforce_queries" / "score_filtered_tiles_skipped": see
@@ -221,6 +232,37 @@ int sse_inbatch_loss_dev(sse_handle *h, const float *src_raw_dev, const float *t
                          const int64_t *src_key_dev, const int64_t *tgt_key_dev, int32_t B, int32_t S, float scale,
                          float inv_rows, float *d_src_dev, float *d_tgt_dev, float *row_loss_dev, float *row_acc_dev,
                          void *stream);
+
+/* Class softmax loss: the full-softmax cross-entropy of B source encodings [B][S] against ALL N rows of a class table
+ * [N][S] (both un-normalised), with its gradient; the loss stage of the train step under option train_class_loss = 1, and
+ * usable with a caller's own encoder and table.  Row i names its class y_i = tgt_row_i in [0, N).
+ *   ns_i = s_i / sqrt(max(|s_i|^2, 1e-12)), nt_j likewise;  L_ij = scale * ns_i . nt_j, j over all N rows of the table
+ *   column j is excluded for row i when j != y_i and some row r has src_key_r == src_key_i, labels_r != 0, y_r == j: another
+ *       verified class of the same source is no negative, for any number of verified classes per source; a row with label 0
+ *       excludes nothing and its own class stays a negative column; y_i itself is always admitted
+ *   lse_i = log sum_{j admitted} exp(L_ij)  (running maximum subtracted; the excluded terms are never formed and subtracted)
+ *   row_loss_i = labels_i * (lse_i - L_{i,y_i})
+ *   row_acc_i = 1 when labels_i != 0 and no admitted j != y_i has L_ij > L_{i,y_i}, else 0
+ *   G_ij = labels_i * scale * inv_rows * (p_ij - [j == y_i]), p_ij = exp(L_ij - lse_i) on admitted columns, else 0
+ *   d(ns_i) = sum_j G_ij nt_j, d(nt_j) = sum_i G_ij ns_i for EVERY j, also classes no row names; d_src / d_table follow by
+ *       the l2_normalize backward (below 1e-12 the clamp passes no gradient to the norm)
+ * The loss of the batch is inv_rows * sum_i row_loss_i, its accuracy inv_rows * sum_i row_acc_i; the caller adds them up.
+ * tgt_row_dev: [B] int32 on the device.  A row outside [0, N) is found on the device: it raises the handle's error flag as a
+ * bad target row of a train step does (reported by sse_synchronize), its loss, accuracy and gradient share are 0.
+ * src_key_dev: [B] int64 on the device, equal values = the same source; NULL = every row a source of its own.
+ * d_src_dev [B][S] and d_table_dev [N][S] (every row written), or both NULL for loss and accuracy alone.  scale in (0, 256].
+ * All arithmetic is fp32 (logits and both gradient products on v_mfma_f32_32x32x2_f32); no B x N buffer exists, the logit
+ * tiles are recomputed by each of the three passes; where B or N alone leaves too few workgroups the other dimension is
+ * split over workgroups and the partial results are combined in index order; every sum is taken in an order fixed by
+ * (B, N, S), no atomics: the same inputs give the same bits.  Queued on `stream`, no host synchronisation; the scratch
+ * (O((B + N) * S + B), plus the partial gradients of a split walk: at most 512 * 32 * Sp floats per gradient, Sp = S rounded
+ * up to 32, i.e. 16 MiB each at S = 256) belongs to the handle and only grows.  Refused before anything is queued, each with
+ * its own text: B, N or S below 1; a NULL among the required pointers; one gradient pointer without the other; scale outside
+ * (0, 256]. */
+int sse_class_loss_dev(sse_handle *h, const float *src_raw_dev, const float *table_dev, const int32_t *tgt_row_dev,
+                       const float *labels_dev, const int64_t *src_key_dev, int32_t B, int32_t N, int32_t S, float scale,
+                       float inv_rows, float *d_src_dev, float *d_table_dev, float *row_loss_dev, float *row_acc_dev,
+                       void *stream);
 
 /* The target index (Evaluator.__init__ builds it from targetEncodingIndex.tsv,
  * sse_evaluator.py:80-92; sse_demo.py:79-90).  Rows are uploaded once and stay

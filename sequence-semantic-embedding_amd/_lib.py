@@ -43,6 +43,7 @@ SYMBOLS = {
     "sse_get_counter": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
     "sse_l2_normalize_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, _P]),
     "sse_inbatch_loss_dev": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
+    "sse_class_loss_dev": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
     "sse_index_upload": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64]),
     "sse_index_upload_f64": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64]),
     "sse_index_set_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, _P]),
@@ -269,6 +270,20 @@ class Handle(object):
         self.check(self.lib.sse_inbatch_loss_dev(self._h, dev(src_raw), dev(tgt_raw), dev(labels), dev(src_key), dev(tgt_key),
                                                  int(B), int(S), float(scale), float(inv_rows), dev(d_src), dev(d_tgt),
                                                  dev(row_loss), dev(row_acc), stream))
+
+    def class_loss_dev(self, src_raw, table, tgt_row, labels, src_key, B, N, S, scale, inv_rows, d_src, d_table, row_loss,
+                       row_acc, stream=0):
+        """sse_class_loss_dev: the class softmax loss head (softmax over all N rows of `table`) on device buffers.  Every
+        buffer is a torch CUDA tensor (contiguous; float32, tgt_row int32, src_key int64) or a raw device pointer; src_key
+        None = every row a source of its own; d_src and d_table both None = loss and accuracy only.  Queued on `stream`,
+        nothing is synchronised; a target row outside [0, N) raises the handle's error flag (reported by synchronize())."""
+        def dev(x):
+            if x is None:
+                return None
+            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        self.check(self.lib.sse_class_loss_dev(self._h, dev(src_raw), dev(table), dev(tgt_row), dev(labels), dev(src_key),
+                                               int(B), int(N), int(S), float(scale), float(inv_rows), dev(d_src), dev(d_table),
+                                               dev(row_loss), dev(row_acc), stream))
 
     # -- index / scoring -----------------------------------------------------
     def index_upload(self, rows, id_base=0):

@@ -149,7 +149,8 @@ struct sse_handle {
   int train_pair_dedup = 1; // option "train_pair_dedup": run the source encoder once per (pos, neg) pair of rows that share it
   int train_serial = 0; // option "train_serial": both encoders on one stream (profiling: isolated kernel times)
   int train_loss = 0;         // option "train_loss": 0 = the reference's pair loss, 1 = in-batch softmax (inbatch_loss.hip)
-  int train_loss_scale = 64;  // option "train_loss_scale": logit scale of the in-batch loss (the pair loss keeps the reference's 64)
+  int train_loss_scale = 64;  // option "train_loss_scale": logit scale of the in-batch and class losses (the pair loss keeps the reference's 64)
+  int train_class_loss = 0;   // option "train_class_loss": 1 = softmax over every row of the free target matrix (class_loss.hip)
   float *emb_pad = nullptr;  // [V][Ep]
   // source_only_cnn
   int cnn_W[4] = {-1, -1, -1, -1}, cnn_b[4] = {-1, -1, -1, -1}, cnn_M = -1, tgt_table = -1;
@@ -239,6 +240,10 @@ struct sse_handle {
   // in-batch softmax loss (sse_inbatch_loss_dev and the train step under option train_loss = 1): staged operands, row
   // statistics, un-normalised gradients (launch_inbatch_loss); the row keys [source | target | hash scratch] of a call
   DevBuf s_inbatch, s_inbatch_keys;
+  int64_t train_class_steps = 0;  // counter "train_class_steps": steps whose loss stage ran the class softmax head
+  // class softmax loss (sse_class_loss_dev and the train step under option train_class_loss = 1): the scratch of
+  // launch_class_loss; the source keys [keys | hash scratch] of a call
+  DevBuf s_class, s_class_keys;
   std::vector<hipEvent_t> events;
 };
 
@@ -2600,7 +2605,8 @@ int64_t sse_handle::*const HOST_COUNTERS[] = {&sse_handle::persist_fallbacks, &s
                                               &sse_handle::train_path_fused, &sse_handle::train_path_generic, &sse_handle::train_path_cnn,
                                               &sse_handle::train_paired_steps, &sse_handle::train_fp32_repacks,
                                               &sse_handle::train_split_repacks, &sse_handle::train_generic_repacks,
-                                              &sse_handle::train_inbatch_steps, &sse_handle::score_lse_calls};
+                                              &sse_handle::train_inbatch_steps, &sse_handle::score_lse_calls,
+                                              &sse_handle::train_class_steps};
 
 // every name sse_get_counter answers: its group and its word there (CG_HOST: entry of HOST_COUNTERS; CG_PATH: entry of
 // sse_handle::lstm_path_calls; a device group: the word the kernels of that family count in)
@@ -2622,6 +2628,7 @@ const struct {
     {"train_split_repacks", CG_HOST, 10},   // their split-operand forms KhT16 / KxT16
     {"train_generic_repacks", CG_HOST, 11}, // the any-shape path's packs, once per side
     {"train_inbatch_steps", CG_HOST, 12},   // steps whose loss stage ran the in-batch softmax head (option train_loss = 1)
+    {"train_class_steps", CG_HOST, 14},     // steps whose loss stage ran the class softmax head (option train_class_loss = 1)
     // LSTM inference encodes by kernel
     {"lstm_path_persist", CG_PATH, PATH_PERSIST},
     {"lstm_path_cluster", CG_PATH, PATH_CLUSTER},
@@ -2717,6 +2724,7 @@ const struct {
     {"lstm_x_table_mb", &sse_handle::lstm_x_table_mb, 0, INT32_MAX, "lstm_x_table_mb must be >= 0"},
     {"train_loss", &sse_handle::train_loss, 0, 1, "train_loss must be 0 (pair) or 1 (in-batch softmax)"},
     {"train_loss_scale", &sse_handle::train_loss_scale, 1, 256, "train_loss_scale must be in 1 .. 256"},
+    {"train_class_loss", &sse_handle::train_class_loss, 0, 1, "train_class_loss must be 0 (off) or 1 (softmax over the free target matrix)"},
 };
 
 }  // namespace
@@ -2802,6 +2810,30 @@ int sse_inbatch_loss_dev(sse_handle *h, const float *src_raw_dev, const float *t
   HIPCHECK(h, launch_inbatch_value_keys(tgt_key_dev, 64, B, kt, st));
   HIPCHECK(h, launch_inbatch_loss(src_raw_dev, tgt_raw_dev, labels_dev, ks, kt, B, B, S, scale, inv_rows, h->s_inbatch.p, d_src_dev,
                                   d_tgt_dev, row_loss_dev, row_acc_dev, st));
+  return 0;
+}
+
+// the handle's scratch of one class loss call; keys: [source keys | hash words], B each
+static int reserve_class(sse_handle *h, int B, int N, int S) {
+  return reserve(h, h->s_class, class_loss_scratch_bytes(B, N, S)) || reserve(h, h->s_class_keys, (size_t)2 * B * sizeof(int32_t));
+}
+
+int sse_class_loss_dev(sse_handle *h, const float *src_raw_dev, const float *table_dev, const int32_t *tgt_row_dev,
+                       const float *labels_dev, const int64_t *src_key_dev, int32_t B, int32_t N, int32_t S, float scale,
+                       float inv_rows, float *d_src_dev, float *d_table_dev, float *row_loss_dev, float *row_acc_dev, void *stream) {
+  SSE_ENTER(h);
+  if (B < 1 || N < 1 || S < 1) return fail(h, "sse_class_loss_dev: B, N and S must be >= 1");
+  if (!src_raw_dev || !table_dev || !tgt_row_dev || !labels_dev || !row_loss_dev || !row_acc_dev)
+    return fail(h, "sse_class_loss_dev: encodings, table, target rows, labels, row_loss and row_acc must not be NULL");
+  if ((d_src_dev == nullptr) != (d_table_dev == nullptr))
+    return fail(h, "sse_class_loss_dev: d_src and d_table must both be given, or both be NULL (forward only)");
+  if (!(scale > 0.0f && scale <= 256.0f)) return fail(h, "sse_class_loss_dev: scale must be in (0, 256]");
+  if (reserve_class(h, B, N, S)) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  int32_t *ks = (int32_t *)h->s_class_keys.p;
+  HIPCHECK(h, launch_inbatch_value_keys(src_key_dev, 64, B, ks, st));
+  HIPCHECK(h, launch_class_loss(src_raw_dev, table_dev, tgt_row_dev, labels_dev, ks, B, B, N, S, scale, inv_rows, h->s_class.p,
+                                h->err_flag, d_src_dev, d_table_dev, row_loss_dev, row_acc_dev, st));
   return 0;
 }
 
@@ -3438,6 +3470,7 @@ static int step_begin(sse_handle *h, const TrainCall &call, int row_tile, StepFr
   f.tail = f.ts->arena + grad_arena_count(h) - 4;
   f.inv_rows = 1.0f / (float)call.rows_global;
   f.n_sq = 0;
+  f.class_loss = h->train_class_loss != 0;
   return 0;
 }
 
@@ -3479,9 +3512,9 @@ static int step_stage_inputs(StepFrame &f, const int32_t *perm, int n_sq) {
   return reserve(h, ts.sq_part, (size_t)n_sq * sizeof(float));
 }
 
-// table target: raw[1] = the batch's rows of the free matrix
+// table target: raw[1] = the batch's rows of the free matrix (the class loss reads the whole matrix instead)
 static int step_table_forward(StepFrame &f) {
-  if (!f.table_tgt) return 0;
+  if (!f.table_tgt || f.class_loss) return 0;
   HIPCHECK(f.h, launch_rows_gather(f.table->dev, f.ids(1), f.B, f.Bp, f.table->rows, f.S, f.raw(1), f.h->err_flag, f.st));
   return 0;
 }
@@ -3507,6 +3540,24 @@ static int step_loss_inbatch(StepFrame &f) {
   return 0;
 }
 
+// option train_class_loss = 1: the class softmax head over raw[0] and the WHOLE free target matrix.  A row's source key is the
+// first row with the same source tokens (as step_loss_inbatch forms it); d(table) goes straight into the matrix's arena block,
+// every row of it, so nothing is zeroed or scattered there.  A target row out of range raises the error flag in the head.
+static int step_loss_class(StepFrame &f) {
+  sse_handle *h = f.h;
+  TrainState &ts = *f.ts;
+  if (reserve_class(h, f.B, f.table->rows, f.S)) return 1;
+  int32_t *ks = (int32_t *)h->s_class_keys.p;
+  uint32_t *hash = (uint32_t *)(ks + f.B);
+  HIPCHECK(h, launch_inbatch_token_keys(f.ids(0), f.B, f.T, hash, ks, f.st));
+  HIPCHECK(h, launch_class_loss(f.raw(0), f.table->dev, f.ids(1), (const float *)ts.labels.p, ks, f.B, f.Bp, f.table->rows, f.S,
+                                (float)h->train_loss_scale, f.inv_rows, h->s_class.p, h->err_flag, f.draw(0), f.table->grad,
+                                (float *)ts.row_loss.p, (float *)ts.row_acc.p, f.st));
+  HIPCHECK(h, launch_loss_reduce((const float *)ts.row_loss.p, (const float *)ts.row_acc.p, f.B, f.inv_rows, f.tail + 1, f.st));
+  h->train_class_steps += 1;
+  return 0;
+}
+
 // loss, train accuracy, d(raw encodings); then the two lookup tables' gradients zeroed for the scatters of the backward
 static int step_loss(StepFrame &f) {
   sse_handle *h = f.h;
@@ -3516,7 +3567,14 @@ static int step_loss(StepFrame &f) {
   // rows itself since round 5), so the fused step (sse_train_step) reads the flag once at its end -- train_apply_locked; a
   // flagged step cancels its own update on the device -- instead of stalling the queue here.  sse_train_grads reads it now,
   // on every path, so that a rank with a bad id fails here instead of only in its own sse_train_apply.
-  if (!f.call->defer_err && check_err_flag(h, f.st)) return 1;
+  // (the class head validates the target rows itself -- no gather ran -- so its step reads the flag after the head)
+  if (!f.call->defer_err && !f.class_loss && check_err_flag(h, f.st)) return 1;
+  if (f.class_loss) {
+    if (step_loss_class(f)) return 1;
+    if (!f.call->defer_err && check_err_flag(h, f.st)) return 1;
+    HIPCHECK(h, hipMemsetAsync(f.emb->grad, 0, f.emb->count * sizeof(float), f.st));
+    return 0;
+  }
   if (h->train_loss == 1) {
     if (step_loss_inbatch(f)) return 1;
   } else {
@@ -3531,6 +3589,10 @@ static int step_loss(StepFrame &f) {
 // table target: d(raw[1]) scattered onto the free matrix's gradient, its slice norms into the last B partial sums
 static int step_table_backward(StepFrame &f) {
   if (!f.table_tgt) return 0;
+  if (f.class_loss) {  // the matrix's gradient is dense and enters the global norm whole (train_apply_locked): no slice norms
+    HIPCHECK(f.h, hipMemsetAsync(f.sq() + (f.n_sq - f.B), 0, (size_t)f.B * sizeof(float), f.st));
+    return 0;
+  }
   HIPCHECK(f.h, launch_rows_scatter(f.draw(1), f.ids(1), f.B, f.S, f.table->rows, f.table->grad, f.sq() + (f.n_sq - f.B), f.st));
   return 0;
 }
@@ -3540,6 +3602,7 @@ static int step_table_backward(StepFrame &f) {
 static int step_finish(StepFrame &f) {
   HIPCHECK(f.h, launch_sum(f.sq(), f.n_sq, (float)f.B, f.tail, f.st));
   f.ts->grads_ready = true;
+  f.ts->grads_dense_table = f.class_loss;
   return 0;
 }
 
@@ -4046,6 +4109,12 @@ static int train_grads_locked(sse_handle *h, const TrainCall &call) {
   const sse_config &c = h->cfg;
   if (call.B < 1 || call.T < 1 || !call.src || !call.tgt || !call.labels || call.rows_global < call.B)
     return fail(h, "bad arguments to the train step");
+  if (h->train_class_loss) {
+    if (h->tgt_table < 0)
+      return fail(h, "train step: train_class_loss = 1 needs a network mode with a free target matrix (source-encoder-only or source_only_cnn)");
+    if (h->train_loss == 1)
+      return fail(h, "train step: train_class_loss = 1 and train_loss = 1 ask for two objectives; set one of them to 0");
+  }
   if (!h->train) h->train = new TrainState();
   if (c.network_mode == SSE_MODE_SOURCE_ONLY_CNN) return cnn_train_grads_locked(h, call);
   // shapes outside the fused training kernels (cell size > 256, embedding_size > 64; option train_generic forces it: tests)
@@ -4068,7 +4137,9 @@ static int train_apply_locked(sse_handle *h, float *loss, float *train_acc) {
   float *np_ = (float *)ts.norm_part.p;
   if (h->vars.size() > SSE_MAX_TENSORS) return fail(h, "too many variables");
   // dense tensors enter the global norm whole; the lookup tables (word_embedding, tgt_seq_embedding) through the raw
-  // slice norm in tail[0] (tf.clip_by_global_norm over IndexedSlices.values, sse_model.py:359-362)
+  // slice norm in tail[0] (tf.clip_by_global_norm over IndexedSlices.values, sse_model.py:359-362).  Gradients left by a
+  // class-loss step (ts.grads_dense_table, whatever the option says by now) carry a dense tgt_seq_embedding gradient: it
+  // enters whole, from the arena as it is now, i.e. after any all-reduce, and tail[0] covers word_embedding alone.
   MultiTensor dense, all;
   dense.n = all.n = 0;
   for (size_t i = 0; i < h->vars.size(); ++i) {
@@ -4077,7 +4148,7 @@ static int train_apply_locked(sse_handle *h, float *loss, float *train_acc) {
     all.slot[all.n] = v.slot;
     all.grad[all.n] = v.grad;
     all.count[all.n++] = v.count;
-    if (i == 0 || (int)i == h->tgt_table) continue;
+    if (i == 0 || ((int)i == h->tgt_table && !ts.grads_dense_table)) continue;
     dense.w[dense.n] = v.dev;
     dense.slot[dense.n] = v.slot;
     dense.grad[dense.n] = v.grad;

@@ -663,6 +663,16 @@ hipError_t launch_inbatch_loss(const float *src_raw, const float *tgt_raw, const
                                const int32_t *tgt_key, int B, int rows_out, int S, float scale, float inv_rows, void *scratch,
                                float *d_src, float *d_tgt, float *row_loss, float *row_acc, hipStream_t st);
 
+// ------------------------------ class softmax loss (class_loss.hip) -----------------------------
+// bytes of scratch launch_class_loss needs: O((B + N) * S + B), plus the bounded partials of the split walk
+size_t class_loss_scratch_bytes(int B, int N, int S);
+// The head (definition: DESIGN "Class softmax loss").  table: [N][S]; tgt_row: [B] rows of it (one out of range raises bit 1 of
+// *err and contributes nothing); src_key: [B] keys >= 0 as launch_inbatch_*_keys leave them.  d_src: [rows_out][S] with rows
+// B .. rows_out-1 zeroed, d_table: [N][S], every row written -- or both nullptr (forward only).  row_loss / row_acc: [B].
+hipError_t launch_class_loss(const float *src_raw, const float *table, const int32_t *tgt_row, const float *labels, const int32_t *src_key,
+                             int B, int rows_out, int N, int S, float scale, float inv_rows, void *scratch, int32_t *err, float *d_src,
+                             float *d_table, float *row_loss, float *row_acc, hipStream_t st);
+
 hipError_t launch_pack_lstm(const float *K, const float *b, int E, int H, int Ep, int Hp, int UB, float *Wp,
                             hipStream_t stream);
 // several re-layouts in one launch (the train step's: padded embedding table, packed kernels / projections, Kh^T / Kx^T)

@@ -42,6 +42,7 @@ struct TrainState {
   // ranks of a data-parallel job (one flat all-reduce)
   float *arena = nullptr;
   bool arena_external = false, grads_ready = false;
+  bool grads_dense_table = false;  // the pending gradients come from a class-loss step: tgt_seq_embedding's block is dense
   // corpus resident on the device (sse_corpus_upload): the *_rows train entry points ship row numbers, not token ids
   DevBuf corpus[2], rows[2];
   int64_t corpus_N[2] = {0, 0};
@@ -75,6 +76,7 @@ struct StepFrame {
   int B, T, S;
   int Bp;          // rows of raw[] / draw[]: B rounded up to the path's row tile
   bool table_tgt;  // target side = rows of the free target matrix
+  bool class_loss; // option train_class_loss: the loss stage runs the class softmax head over the whole matrix
   int nside;       // sequence encoders in the step
   Variable *emb, *table;
   float *tail, inv_rows;

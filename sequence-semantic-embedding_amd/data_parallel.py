@@ -24,6 +24,10 @@ class DataParallelTrainer(object):
         options: {name: value} set on this rank's engine (engine.set_option) before the first step, e.g.
         {"train_loss": 1, "train_loss_scale": 64} for the in-batch softmax loss: every rank passes the same dict, so every
         rank's handle computes the same objective (its negatives are the rank's own rows; the mean runs over rows_global).
+        {"train_class_loss": 1} selects the class softmax loss of the free-target-matrix modes instead.  That objective,
+        unlike the in-batch one, is identical at any world size: a softmax over the whole class table decomposes over the
+        rows of a batch, so the step equals the single-rank step of the concatenated batch up to summation order (the rows
+        of one source kept on one rank: the exclusion of its other verified classes is formed from the rank's own rows).
         sparse_embedding: exchange the word-embedding gradient as (row id, gradient row) pairs -- SURVEY 8e's shape for
         large vocabularies (the 1M-title ranking vocabulary, reference README.md:116) -- instead of all-reducing the
         dense [V,E] block; None = automatic (sparse when the GLOBAL batch touches fewer than V/4 rows: 2 * rows_global * T < V / 4)."""

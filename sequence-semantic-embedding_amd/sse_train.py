@@ -46,11 +46,14 @@ FLAGS = flags.FlagSet("sse_train", [
                            "best-ranked verified target of every evaluation source over the whole index"),
     ("eval_nll", int, 0, "1: after each epoch's task evaluation, log the held-out full-softmax negative log-likelihood of every "
                          "evaluation source's verified targets over the whole index, at the logit scale the run trains with "
-                         "(--loss_scale under --loss inbatch, 64 under the pair loss)"),
+                         "(--loss_scale under --loss inbatch and --loss softmax, 64 under the pair loss)"),
     ("loss", str, "pair", "pair (default): the reference's sigmoid cross-entropy on 64 cos(src, tgt) of every pair row; inbatch: "
                           "softmax over the batch -- every other row's target is a negative of a source, its own verified "
-                          "targets and repeated targets masked out (library option train_loss)"),
-    ("loss_scale", int, 64, "--loss inbatch: the logit scale, 1 .. 256 (library option train_loss_scale)"),
+                          "targets and repeated targets masked out (library option train_loss); softmax: the exact "
+                          "classification objective of source-encoder-only and source_only_cnn -- softmax over every row of "
+                          "the free target matrix, a source's other verified classes masked out (library option "
+                          "train_class_loss)"),
+    ("loss_scale", int, 64, "--loss inbatch, --loss softmax: the logit scale, 1 .. 256 (library option train_loss_scale)"),
     ("hard_learning", int, 0, "N > 0: at the start of every epoch from --hard_start_epoch on, mine up to N confusions per training "
                               "source (targets that are not verified for it and score near or above its best verified one) and draw "
                               "negatives from them; 0 (default): uniform negatives only, like the reference"),
@@ -58,6 +61,19 @@ FLAGS = flags.FlagSet("sse_train", [
     ("hard_fraction", float, 0.5, "hard learning: share of negatives drawn from the confusion table"),
     ("hard_start_epoch", int, 1, "hard learning: first epoch that uses the table"),
 ])
+
+
+def apply_loss_options(handle, f):
+    """--loss / --loss_scale onto the library options train_loss, train_loss_scale and train_class_loss."""
+    loss = getattr(f, "loss", "pair")
+    if loss not in ("pair", "inbatch", "softmax"):
+        raise ValueError("--loss must be pair, inbatch or softmax, not %r" % (loss,))
+    if loss == "softmax" and f.network_mode not in ("source-encoder-only", "source_only_cnn"):
+        raise ValueError("--loss softmax needs a network mode with a free target matrix (source-encoder-only or "
+                         "source_only_cnn), not %s: the classes of its softmax are the rows of that matrix" % f.network_mode)
+    handle.set_option("train_loss", 1 if loss == "inbatch" else 0)
+    handle.set_option("train_loss_scale", int(getattr(f, "loss_scale", 64)))
+    handle.set_option("train_class_loss", 1 if loss == "softmax" else 0)
 
 
 def create_model(f, session, targetSpaceSize, vocabsize, forward_only):
@@ -74,11 +90,7 @@ def create_model(f, session, targetSpaceSize, vocabsize, forward_only):
     if getattr(f, "train_x3", 0) and f.network_mode != "source_only_cnn":   # opt-in split-operand train step (library default: float32)
         for opt in ("train_dk_x3", "train_fwd_x3", "train_bwd_x3"):
             model.handle.set_option(opt, 1)
-    loss = getattr(f, "loss", "pair")
-    if loss not in ("pair", "inbatch"):
-        raise ValueError("--loss must be pair or inbatch, not %r" % (loss,))
-    model.handle.set_option("train_loss", 1 if loss == "inbatch" else 0)
-    model.handle.set_option("train_loss_scale", int(getattr(f, "loss_scale", 64)))
+    apply_loss_options(model.handle, f)
     ckpt =get_checkpoint_state(f.model_dir)
     if ckpt:
         logging.info("Reading model parameters from %s" % ckpt)
@@ -112,7 +124,7 @@ def train(f):
                          seed=None if f.seed < 0 else f.seed, log=logging.info)
     epoc_steps = len(data.rawTrainPosCorpus) / f.batch_size
     logging.info("Training Data: %d total positive samples, each epoch need %d steps; loss: %s%s"
-                 % (len(data.rawTrainPosCorpus), epoc_steps, f.loss, " (scale %d)" % f.loss_scale if f.loss == "inbatch" else ""))
+                 % (len(data.rawTrainPosCorpus), epoc_steps, f.loss, " (scale %d)" % f.loss_scale if f.loss in ("inbatch", "softmax") else ""))
     model = create_model(f, None, data.rawnegSetLen, data.vocab_size, False)
     sess = Session(model)
     summary_op = model.add_summaries()
@@ -195,7 +207,7 @@ def train(f):
                 logging.info("label ranks over the whole index: MRR %f, mean rank %f, median rank %f (%d sources)"
                              % (rm["mrr"], rm["mean_rank"], rm["median_rank"], len(evaluator.eval_Labels)))
             if f.eval_nll:
-                nll_scale = f.loss_scale if f.loss == "inbatch" else 64
+                nll_scale = f.loss_scale if f.loss in ("inbatch", "softmax") else 64
                 sm = evaluator.softmax_nll(scale=float(nll_scale))
                 logging.info("held-out full-softmax nll over the whole index: %f, label prob: %f (scale %d, %d sources)"
                              % (sm["nll"], sm["label_prob"], nll_scale, len(evaluator.eval_Labels)))
