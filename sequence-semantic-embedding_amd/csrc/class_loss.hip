@@ -4,12 +4,12 @@
 //
 // The rectangular (B x N) sibling of inbatch_loss.hip, on its scheme: no B x N buffer exists.  The normalised source
 // encodings ns [Bt][Sp] and the normalised class table nt [Nt][Sp] are staged once (Bt, Nt, Sp: B, N, S rounded up to 32, zero
-// padded), then three passes recompute the 32 x 32 logit tiles on v_mfma_f32_32x32x2_f32 where they need them:
+// padded), then three passes recompute the 32 x 32 logit tiles where they need them:
 //   rows pass      own = row i,    walk = class j:  the running (max, sum) of row i, L_{i,y_i}
 //   gradient pass  own = row i,    walk = class j:  d(ns_i) = sum_j G_ij nt_j
 //   gradient pass  own = class j,  walk = row i:    d(nt_j) = sum_i G_ij ns_i      for EVERY class j
-// with the OWN index on the lane and the WALK index in the 16 accumulator registers, so that the gradient tile G, written over
-// the accumulator, is the A operand of the product that sums over the walk index (inbatch_loss.hip explains the registers).
+// out of the pieces of softmax_head.h, which explains the register layout (OWN index on the lane, WALK index in the 16
+// accumulator registers).  This file adds the exclusion lists, the positive at j = y_i and the split walk.
 //
 // Split walk.  A workgroup owns 32 own rows (and, in a gradient pass, 128 or 256 columns of S); with few own tiles -- 4 at
 // B = 128, 18 at N = 571 -- such a grid leaves most of the machine idle, so the walk tiles are cut into `split` contiguous
@@ -23,17 +23,12 @@
 // of them inside one [B] array (a source's list starts where the lists of the sources with smaller keys end).  A row keeps
 // (begin, length, lowest, highest) and tests membership only for tiles that overlap [lowest, highest].
 #include <algorithm>
-#include <cmath>
 
-#include "sse_kernels.h"
+#include "softmax_head.h"
 
 namespace {
 
-constexpr int CL_NW = 8;        // waves per workgroup
-constexpr int CL_ST = 4;        // 32-column tiles of S per gradient workgroup: 4 up to 128 staged columns, 8 above
-constexpr int CL_ST_WIDE = 8;
 constexpr int CL_TARGET_WGS = 512;  // split the walk until a pass has about this many workgroups (2 per CU of an MI355X)
-constexpr float CL_NEG_INF = -INFINITY;
 
 struct ClassArgs {
   const float *src_raw, *table, *labels;  // [B][S], [N][S], [B]
@@ -77,17 +72,13 @@ __global__ __launch_bounds__(256) void class_prep_kernel(ClassArgs a) {
     }
     return;
   }
-  const float *x = (is_src ? a.src_raw : a.table) + (size_t)r * a.S;
-  float ss = 0.0f;
-  for (int d = lane; d < a.S; d += 64) ss += x[d] * x[d];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
-  const float rn = 1.0f / sqrtf(fmaxf(ss, 1e-12f));  // the clamp of loss_kernel (train.hip)
-  for (int d = lane; d < a.Sp; d += 64) n[d] = d < a.S ? x[d] * rn : 0.0f;
+  SmxStage st[1] = {{(is_src ? a.src_raw : a.table) + (size_t)r * a.S, n}};
+  smx_stage_rows(st, a.S, a.Sp, lane);
+  const float rn = st[0].rn, clamped = st[0].clamped;
   if (!is_src) {
     if (lane == 0) {
       a.rt[r] = rn;
-      a.ct[r] = ss < 1e-12f ? 1.0f : 0.0f;
+      a.ct[r] = clamped;
     }
     return;
   }
@@ -105,7 +96,7 @@ __global__ __launch_bounds__(256) void class_prep_kernel(ClassArgs a) {
     if (!valid) atomicOr(a.err, 1);  // a target row out of range, as rows_gather reports it; the row contributes nothing
     a.first[r] = first ? 1 : 0;
     a.rs[r] = rn;
-    a.cs[r] = ss < 1e-12f ? 1.0f : 0.0f;
+    a.cs[r] = clamped;
   }
 }
 
@@ -142,30 +133,6 @@ __global__ __launch_bounds__(256) void class_list_kernel(ClassArgs a) {
   if (a.first[i]) a.excl[before + below] = y;  // (first entries of one source carry distinct y: distinct positions, at most B in all)
 }
 
-// acc[r] = sum_k walk[wbase + mfma_row(r, lane)][k] * own[obase + (lane & 31)][k] over the Sp staged columns (the tile of
-// inbatch_loss.hip).  Every row read exists (Bt / Nt rows) and is 16-byte aligned (Sp % 32 == 0).
-__device__ __forceinline__ f32x16 class_logit_tile(const float *__restrict__ walk, int wbase, const float *__restrict__ own, int obase,
-                                                   int Sp, int lane) {
-  const float *pa = walk + (size_t)(wbase + (lane & 31)) * Sp + 4 * (lane >> 5);
-  const float *pb = own + (size_t)(obase + (lane & 31)) * Sp + 4 * (lane >> 5);
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-  for (int s0 = 0; s0 < Sp; s0 += 32) {
-    f32x4 av[4], bv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      av[u] = *reinterpret_cast<const f32x4 *>(pa + s0 + 8 * u);
-      bv[u] = *reinterpret_cast<const f32x4 *>(pb + s0 + 8 * u);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][e], bv[u][e], acc, 0, 0, 0);
-  }
-  return acc;
-}
-
 // first position in excl[begin .. begin + len) whose entry is >= j
 __device__ __forceinline__ int class_lower_bound(const int32_t *__restrict__ excl, int begin, int len, int j) {
   int lo = begin, hi = begin + len;
@@ -197,29 +164,17 @@ __device__ __forceinline__ bool class_excluded(const int32_t *__restrict__ excl,
   return p < m.y + m.z && excl[p] == j;
 }
 
-// (m, s) <- the running (max, sum of exp(. - max)) of two disjoint sets; an empty set is (-inf, 0)
-__device__ __forceinline__ void class_merge(float &m, float &s, float m2, float s2) {
-  const float M = fmaxf(m, m2);
-  if (M == CL_NEG_INF) {
-    s = 0.0f;
-  } else {
-    s = s * expf(m - M) + s2 * expf(m2 - M);
-  }
-  m = M;
-}
-
 // rows pass: block (x = own row tile, y = chunk of the class walk) leaves the chunk's (max, sum) over the admitted j != y_i and
 // L_{i,y_i} for its 32 rows
-__global__ __launch_bounds__(CL_NW * 64) void class_rows_kernel(ClassArgs a) {
-  __shared__ float sh_m[CL_NW][32], sh_s[CL_NW][32], sh_d[CL_NW][32];
+__global__ __launch_bounds__(SMX_NW * 64) void class_rows_kernel(ClassArgs a) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int obase = blockIdx.x * 32, i = obase + (lane & 31);
   const int4 mi = a.meta[i];
   const int2 rg = a.range[i];
   const int t0 = blockIdx.y * a.tiles_r, t1 = min(t0 + a.tiles_r, a.Nt / 32);
-  float m = CL_NEG_INF, s = 0.0f, lyy = CL_NEG_INF;
-  for (int wt = t0 + w; wt < t1; wt += CL_NW) {
-    const f32x16 acc = class_logit_tile(a.nt, wt * 32, a.ns, obase, a.Sp, lane);
+  float m = SMX_NEG_INF, s = 0.0f, lyy = SMX_NEG_INF;
+  for (int wt = t0 + w; wt < t1; wt += SMX_NW) {
+    const f32x16 acc = smx_logit_tile(a.nt, wt * 32, a.ns, obase, a.Sp, lane);
     const uint32_t ex = class_excluded_mask(a.excl, mi, rg, wt * 32);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -228,32 +183,11 @@ __global__ __launch_bounds__(CL_NW * 64) void class_rows_kernel(ClassArgs a) {
       if (j == mi.x) {
         lyy = x;
       } else if (j < a.N && !((ex >> c) & 1u)) {
-        if (x > m) {
-          s = s * expf(m - x) + 1.0f;
-          m = x;
-        } else {
-          s += expf(x - m);
-        }
+        smx_update(m, s, x);
       }
     }
   }
-  // the two lane halves of a row, then the waves in order
-  class_merge(m, s, __shfl_xor(m, 32), __shfl_xor(s, 32));
-  lyy = fmaxf(lyy, __shfl_xor(lyy, 32));
-  if (lane < 32) {
-    sh_m[w][lane] = m;
-    sh_s[w][lane] = s;
-    sh_d[w][lane] = lyy;
-  }
-  __syncthreads();
-  if (w != 0 || lane >= 32) return;
-  m = sh_m[0][lane];
-  s = sh_s[0][lane];
-  lyy = sh_d[0][lane];
-  for (int ww = 1; ww < CL_NW; ++ww) {
-    class_merge(m, s, sh_m[ww][lane], sh_s[ww][lane]);
-    lyy = fmaxf(lyy, sh_d[ww][lane]);
-  }
+  if (!smx_rows_reduce(m, s, lyy, lane, w)) return;
   const size_t at = (size_t)blockIdx.y * a.Bt + i;
   a.pm[at] = m;
   a.ps[at] = s;
@@ -267,7 +201,7 @@ __global__ __launch_bounds__(256) void class_rows_merge_kernel(ClassArgs a) {
   float m = a.pm[i], s = a.ps[i], lyy = a.pl[i];
   for (int c = 1; c < a.split_r; ++c) {
     const size_t at = (size_t)c * a.Bt + i;
-    class_merge(m, s, a.pm[at], a.ps[at]);
+    smx_merge(m, s, a.pm[at], a.ps[at]);
     lyy = fmaxf(lyy, a.pl[at]);
   }
   if (a.meta[i].x < 0) {  // target row out of range (flagged by class_prep_kernel): nothing
@@ -276,20 +210,13 @@ __global__ __launch_bounds__(256) void class_rows_merge_kernel(ClassArgs a) {
     a.row_acc[i] = 0.0f;
     return;
   }
-  const float M = fmaxf(m, lyy);
-  const float tot = (m == CL_NEG_INF ? 0.0f : s * expf(m - M)) + expf(lyy - M);
-  const float lse = M + logf(tot);
-  const float z = a.labels[i];
-  a.lse[i] = lse;
-  a.row_loss[i] = z * (lse - lyy);
-  a.row_acc[i] = (z != 0.0f && !(m > lyy)) ? 1.0f : 0.0f;
+  smx_row_close(m, s, lyy, a.labels[i], a.lse[i], a.row_loss[i], a.row_acc[i]);
 }
 
 // gradient pass, block (x = own tile, y = tile of S, z = chunk of the walk).  COLS == false: own = row i, walk = class j, out =
 // a partial of d(ns); COLS == true: own = class j, walk = row i, out = a partial of d(nt).
 template <bool COLS, int ST>
-__global__ __launch_bounds__(CL_NW * 64) void class_grad_kernel(ClassArgs a) {
-  __shared__ float red[ST][16][64];
+__global__ __launch_bounds__(SMX_NW * 64) void class_grad_kernel(ClassArgs a) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int obase = blockIdx.x * 32, o = obase + (lane & 31);
   const int sbase = blockIdx.y * (32 * ST);
@@ -308,12 +235,9 @@ __global__ __launch_bounds__(CL_NW * 64) void class_grad_kernel(ClassArgs a) {
     lse_o = a.lse[o];
   }
   f32x16 out[ST];
-#pragma unroll
-  for (int t = 0; t < ST; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) out[t][r] = 0.0f;
-  for (int wt = t0 + w; wt < t1; wt += CL_NW) {
-    f32x16 g = class_logit_tile(walkN, wt * 32, ownN, obase, a.Sp, lane);
+  smx_grad_zero(out);
+  for (int wt = t0 + w; wt < t1; wt += SMX_NW) {
+    f32x16 g = smx_logit_tile(walkN, wt * 32, ownN, obase, a.Sp, lane);
     uint32_t ex = 0u;
     if (!COLS) ex = class_excluded_mask(a.excl, mo, ro, wt * 32);
 #pragma unroll
@@ -324,43 +248,21 @@ __global__ __launch_bounds__(CL_NW * 64) void class_grad_kernel(ClassArgs a) {
         const int4 mi = a.meta[wi];
         const float coef = __int_as_float(mi.w);  // z_i * scale * inv_rows
         if (coef != 0.0f && o < a.N && !class_excluded(a.excl, mi, a.range[wi], o))
-          v = coef * (expf(a.scale * g[r] - a.lse[wi]) - (o == mi.x ? 1.0f : 0.0f));
+          v = smx_grad_entry(coef, a.scale, g[r], a.lse[wi], o == mi.x);
       } else {     // own row i = o, walk class j = wi
         const float coef = __int_as_float(mo.w);
-        if (coef != 0.0f && wi < a.N && !((ex >> c) & 1u)) v = coef * (expf(a.scale * g[r] - lse_o) - (wi == mo.x ? 1.0f : 0.0f));
+        if (coef != 0.0f && wi < a.N && !((ex >> c) & 1u)) v = smx_grad_entry(coef, a.scale, g[r], lse_o, wi == mo.x);
       }
       g[r] = v;
     }
-#pragma unroll
-    for (int t = 0; t < ST; ++t) {
-      if (t < nst) {
-        const float *pb = walkN + (size_t)(wt * 32) * a.Sp + sbase + 32 * t + (lane & 31);
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          out[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(g[r], pb[(size_t)mfma_row(r, lane) * a.Sp], out[t], 0, 0, 0);
-      }
-    }
+    SMX_GRAD_ACCUMULATE(ST, out, g, walkN + (size_t)(wt * 32) * a.Sp + sbase, a.Sp, nst, lane)
   }
-  // the waves' partial tiles, added in wave order
-  for (int ww = 0; ww < CL_NW; ++ww) {
-    if (w == ww) {
-#pragma unroll
-      for (int t = 0; t < ST; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) red[t][r][lane] = ww == 0 ? out[t][r] : red[t][r][lane] + out[t][r];
-    }
-    __syncthreads();
-  }
-  float *dst = (COLS ? a.dnt : a.dns) + (size_t)blockIdx.z * own_rows * a.Sp;
-  for (int e = threadIdx.x; e < nst * 16 * 64; e += CL_NW * 64) {
-    const int t = e >> 10, r = (e >> 6) & 15, l = e & 63;
-    dst[(size_t)(obase + mfma_row(r, l)) * a.Sp + sbase + 32 * t + (l & 31)] = red[t][r][l];
-  }
+  float *dst = (COLS ? a.dnt : a.dns) + (size_t)blockIdx.z * own_rows * a.Sp;  // this chunk's partial
+  smx_grad_reduce_store(out, dst + (size_t)obase * a.Sp + sbase, a.Sp, nst, lane, w);
 }
 
 // one wave per output row (rows_out source rows, then N classes): the chunks' partials added in chunk order, then the
-// l2_normalize backward d raw = r * (dn - n * (n . dn)), no n . dn term below the clamp (as loss_kernel); source rows
-// B .. rows_out-1 zeroed
+// l2_normalize backward; source rows B .. rows_out-1 zeroed
 __global__ __launch_bounds__(256) void class_finish_kernel(ClassArgs a) {
   const int lane = threadIdx.x & 63;
   const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -376,25 +278,22 @@ __global__ __launch_bounds__(256) void class_finish_kernel(ClassArgs a) {
   float *dn = (is_src ? a.dns : a.dnt) + (size_t)r * a.Sp;
   const int split = is_src ? a.split_s : a.split_t;
   const size_t stride = (size_t)(is_src ? a.Bt : a.Nt) * a.Sp;
-  float p = 0.0f;
-  for (int d = lane; d < a.S; d += 64) {
-    float v = dn[d];
-    for (int c = 1; c < split; ++c) v += dn[c * stride + d];
-    dn[d] = v;  // (this lane's own element: read back below)
-    p += n[d] * v;
+  if (split > 1) {
+    for (int d = lane; d < a.S; d += 64) {
+      float v = dn[d];
+      for (int c = 1; c < split; ++c) v += dn[c * stride + d];
+      dn[d] = v;  // (this lane's own element: the lane reads it back below)
+    }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o);
-  const float rn = is_src ? a.rs[r] : a.rt[r];
-  if ((is_src ? a.cs[r] : a.ct[r]) != 0.0f) p = 0.0f;
-  for (int d = lane; d < a.S; d += 64) out[d] = rn * (dn[d] - n[d] * p);
+  const SmxUnstage un[1] = {{n, dn, is_src ? a.rs[r] : a.rt[r], is_src ? a.cs[r] : a.ct[r], out}};
+  smx_normalize_backward(un, a.S, lane);
 }
 
 // the walk of `walk_tiles` tiles in chunks of `per` tiles (the result): one chunk when the own side fills the machine by itself,
 // else as many as bring the pass to about CL_TARGET_WGS workgroups, a chunk never below one tile per wave
 inline int class_split(int own_wgs, int walk_tiles, int *split) {
   int want = own_wgs >= CL_TARGET_WGS / 2 ? 1 : (CL_TARGET_WGS + own_wgs - 1) / own_wgs;
-  want = std::max(1, std::min(want, (walk_tiles + CL_NW - 1) / CL_NW));
+  want = std::max(1, std::min(want, (walk_tiles + SMX_NW - 1) / SMX_NW));
   const int per = (walk_tiles + want - 1) / want;
   *split = (walk_tiles + per - 1) / per;
   return per;
@@ -409,11 +308,11 @@ struct ClassPlan {
 
 inline ClassPlan class_plan(int B, int N, int S) {
   ClassPlan p;
-  p.Bt = (size_t)round_up(B, 32);
-  p.Nt = (size_t)round_up(N, 32);
-  p.Sp = (size_t)round_up(S, 32);
-  p.wide = p.Sp > 32 * CL_ST;
-  p.s_tiles = p.wide ? (int)((p.Sp + 32 * CL_ST_WIDE - 1) / (32 * CL_ST_WIDE)) : 1;
+  p.Bt = smx_round32(B);
+  p.Nt = smx_round32(N);
+  p.Sp = smx_round32(S);
+  p.wide = smx_wide(p.Sp);
+  p.s_tiles = (int)smx_s_tiles(p.Sp);
   const int bt = (int)(p.Bt / 32), nt = (int)(p.Nt / 32);
   p.tiles_r = class_split(bt, nt, &p.split_r);
   p.tiles_s = class_split(bt * p.s_tiles, nt, &p.split_s);
@@ -459,16 +358,16 @@ hipError_t launch_class_loss(const float *src_raw, const float *table, const int
   const unsigned bt = (unsigned)(Bt / 32), nt = (unsigned)(Nt / 32);
   hipLaunchKernelGGL(class_prep_kernel, dim3((unsigned)((Bt + Nt + 3) / 4)), dim3(256), 0, st, a);
   hipLaunchKernelGGL(class_list_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(class_rows_kernel, dim3(bt, (unsigned)p.split_r), dim3(CL_NW * 64), 0, st, a);
+  hipLaunchKernelGGL(class_rows_kernel, dim3(bt, (unsigned)p.split_r), dim3(SMX_NW * 64), 0, st, a);
   hipLaunchKernelGGL(class_rows_merge_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, a);
   if (d_src && d_table) {
     const dim3 gs(bt, (unsigned)p.s_tiles, (unsigned)p.split_s), gt(nt, (unsigned)p.s_tiles, (unsigned)p.split_t);
     if (!p.wide) {
-      hipLaunchKernelGGL((class_grad_kernel<false, CL_ST>), gs, dim3(CL_NW * 64), 0, st, a);
-      hipLaunchKernelGGL((class_grad_kernel<true, CL_ST>), gt, dim3(CL_NW * 64), 0, st, a);
+      hipLaunchKernelGGL((class_grad_kernel<false, SMX_ST>), gs, dim3(SMX_NW * 64), 0, st, a);
+      hipLaunchKernelGGL((class_grad_kernel<true, SMX_ST>), gt, dim3(SMX_NW * 64), 0, st, a);
     } else {
-      hipLaunchKernelGGL((class_grad_kernel<false, CL_ST_WIDE>), gs, dim3(CL_NW * 64), 0, st, a);
-      hipLaunchKernelGGL((class_grad_kernel<true, CL_ST_WIDE>), gt, dim3(CL_NW * 64), 0, st, a);
+      hipLaunchKernelGGL((class_grad_kernel<false, SMX_ST_WIDE>), gs, dim3(SMX_NW * 64), 0, st, a);
+      hipLaunchKernelGGL((class_grad_kernel<true, SMX_ST_WIDE>), gt, dim3(SMX_NW * 64), 0, st, a);
     }
     hipLaunchKernelGGL(class_finish_kernel, dim3((unsigned)(((size_t)rows_out + N + 3) / 4)), dim3(256), 0, st, a);
   }

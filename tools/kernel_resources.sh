@@ -17,8 +17,15 @@ for line in sys.stdin:
     elif cur is not None:
         cur[k.split(" ")[0].replace("Total", "")] = v   # (TotalSGPRs with newer compilers)
 names = subprocess.run(["c++filt"] + [r["name"] for r in rows], capture_output=True, text=True).stdout.split("\n")
+def strip_params(n):   # the trailing parameter list alone: "(anonymous namespace)::" also opens with a parenthesis
+    depth = 0
+    for i in range(len(n) - 1, -1, -1):
+        depth += (n[i] == ")") - (n[i] == "(")
+        if depth == 0:
+            return n[:i] if n.endswith(")") else n
+    return n
 print("%-78s %5s %5s %5s %7s %4s %7s" % ("kernel", "VGPR", "AGPR", "SGPR", "scratch", "occ", "LDS"))
 for r, n in zip(rows, names):
-    n = re.sub(r"\(.*\)$", "", n).replace("void ", "")
+    n = strip_params(n).replace("void ", "").replace("(anonymous namespace)::", "")
     print("%-78s %5s %5s %5s %7s %4s %7s" % (n[:78], r.get("VGPRs"), r.get("AGPRs"), r.get("SGPRs"), r.get("ScratchSize"), r.get("Occupancy"), r.get("LDS")))
 '
