@@ -18,6 +18,13 @@
  *     device, `stream` is a hipStream_t passed as void* (NULL = null stream);
  *   - token ids are row-major int32 [B,T] (sse_model.py:408-409,419-421,430,439),
  *     encodings row-major float32 [B,S];
+ *   - alignment: the natural alignment of the element type (4 bytes for float / int32, 8 for double / int64 / uint64) is all
+ *     any pointer needs, host or device -- a row of a larger tensor, an offset into an all-gather buffer and the arena of
+ *     sse_train_set_grad_arena included.  A 16-byte aligned device pointer lets some launchers take a 16-byte body where they
+ *     would take a scalar one; results are identical, except that sse_l2_normalize_dev then sums a row in another order;
+ *   - bounds: a call reads and writes only the elements its arguments name ([B,T], [Q,k], `cap` entries, `count` floats):
+ *     nothing before a pointer, nothing behind the last element, no input is written, and no memory outside the named
+ *     elements can reach a result (tests/guard_bands.py places every device pointer between guards to hold this);
  *   - a handle may be used from several threads for encode/score (calls are
  *     serialised internally, like tf.Session.run in webserver.py:108);
  *     sse_train_step is exclusive;
