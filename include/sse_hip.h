@@ -165,8 +165,9 @@ int sse_encode_dev(sse_handle *h, int side, const int32_t *ids_dev, int32_t B, i
  * sse_inbatch_loss_dev below over this call's rows, with keys the step forms itself: two rows carry the same source when
  * their source token rows are equal, the same target when their target token rows are equal (dual- and shared-encoder, by
  * ids or by corpus rows) or when they name the same row of the free target matrix (source-encoder-only, source_only_cnn).
- * In a data-parallel job the negatives are the rank's own rows; the mean still runs over rows_global.  Any other value is
- * refused.  "train_loss_scale" (default 64, accepted 1 .. 256): the logit scale c of the in-batch loss; the pair loss keeps
+ * In a data-parallel job that calls sse_train_grads* the negatives are the rank's own rows (the mean still runs over
+ * rows_global); the open step below (sse_train_forward + sse_train_backward_inbatch_global) takes them from the global
+ * batch of all ranks instead, and then equals the single-rank step of the concatenated batch.  Any other value is refused.  "train_loss_scale" (default 64, accepted 1 .. 256): the logit scale c of the in-batch loss; the pair loss keeps
  * the reference's 64.  Counter "train_inbatch_steps".  sse_eval_loss* evaluates the pair loss whatever train_loss says: its
  * result is independent of how the rows are chunked, which a softmax over the whole batch cannot be; the held-out measure of
  * the in-batch objective is sse_score_rank (MRR, recall@k), and sse_score_lse for the softmax over the whole INDEX, which
@@ -205,6 +206,8 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value);
  * "train_generic_repacks": packs of the any-shape path built, one per encoder side.
  * "train_inbatch_steps": train steps whose loss stage ran the in-batch softmax head (option train_loss = 1).
  * "train_class_steps": train steps whose loss stage ran the class softmax head (option train_class_loss = 1).
+ * "train_open_steps": sse_train_forward* calls that left a step open.
+ * "train_global_inbatch_steps": open steps closed by sse_train_backward_inbatch_global.
  * "score_rank_band_rows" / "score_rank_bruteforce_pairs": see sse_score_rank.
  * "score_above_band_rows" / "score_above_bruteforce_pairs" / "score_above_long_segments": see sse_score_above.
  * "score_filtered_collected_rows" / "score_filtered_bruteforce_queries" / "score_filtered_tiles_skipped": see
@@ -239,6 +242,26 @@ int sse_inbatch_loss_dev(sse_handle *h, const float *src_raw_dev, const float *t
                          const int64_t *src_key_dev, const int64_t *tgt_key_dev, int32_t B, int32_t S, float scale,
                          float inv_rows, float *d_src_dev, float *d_tgt_dev, float *row_loss_dev, float *row_acc_dev,
                          void *stream);
+
+/* The same head over the B rows of a batch with its OUTPUTS cut to the window of rows [row_lo, row_hi): what one rank of a
+ * data-parallel step runs over the gathered global batch (B = rows of all ranks, the window = the rank's own rows).
+ *   d_src_dev / d_tgt_dev: [row_hi - row_lo][S] (or both NULL), row_loss_dev / row_acc_dev: [row_hi - row_lo]; output row r
+ *   is row row_lo + r of the batch.  Everything else is an argument of sse_inbatch_loss_dev and means the same.
+ * Semantics are those of the full head restricted to the window: d(ns_i) of a window row sums over all B columns, d(nt_j) of
+ * a window column over all B rows.  So lse_i is formed for every row of the batch; only the two gradient passes, the
+ * l2_normalize backward and the loss outputs shrink, to the 32-row tiles of the batch's numbering that meet the window.  Every
+ * order of summation still depends on (B, S) alone: each output row is bit-identical to the same row of sse_inbatch_loss_dev on
+ * the same inputs, for windows not aligned to 32 and windows inside one tile alike, and the window [0, B) queues exactly the
+ * launches of sse_inbatch_loss_dev.
+ * Cost per call (per rank): one rows pass of B^2 * 2S flop, plus two gradient passes of (row_hi - row_lo) * B * 2S flop each
+ * (rounded up to whole 32-row tiles).  Only the gradient passes shrink with the world size; the rows pass is repeated on
+ * every rank.
+ * Refused before anything is queued, each with its own text: row_lo < 0, row_hi > B, an empty or inverted window
+ * (row_lo >= row_hi), and everything sse_inbatch_loss_dev refuses. */
+int sse_inbatch_loss_window_dev(sse_handle *h, const float *src_raw_dev, const float *tgt_raw_dev, const float *labels_dev,
+                                const int64_t *src_key_dev, const int64_t *tgt_key_dev, int32_t B, int32_t S,
+                                int32_t row_lo, int32_t row_hi, float scale, float inv_rows, float *d_src_dev,
+                                float *d_tgt_dev, float *row_loss_dev, float *row_acc_dev, void *stream);
 
 /* Class softmax loss: the full-softmax cross-entropy of B source encodings [B][S] against ALL N rows of a class table
  * [N][S] (both un-normalised), with its gradient; the loss stage of the train step under option train_class_loss = 1, and
@@ -686,6 +709,55 @@ int sse_train_apply(sse_handle *h, float *loss, float *train_acc);
 int64_t sse_train_packed_embedding_floats(sse_handle *h, int32_t cap);
 int sse_train_pack_embedding_grad(sse_handle *h, int32_t cap, float *packed_dev);
 int sse_train_unpack_embedding_grad(sse_handle *h, const float *gathered_dev, int32_t world, int32_t cap);
+/* The open train step: sse_train_grads* cut at its loss stage, so that the objective can see more than this rank's rows, or
+ * be the caller's own.  All calls take the handle's lock and run on the stream of sse_set_stream.
+ *   sse_train_forward[_rows]   the arguments, checks and forward of sse_train_grads[_rows] -- input staging, both encoders
+ *       with their tapes, the gather of the free target matrix's rows in the table modes -- on every path (fused LSTM,
+ *       any-shape LSTM, text-CNN) and in every network mode.  The step is then left OPEN: its encodings, tapes and staged
+ *       inputs stay in the handle, no pointer of the caller's is kept.  The options "train_loss" and "train_class_loss" are
+ *       NOT consulted: the closing call supplies the objective.  An open step does not apply the pair de-duplication: it
+ *       runs as with "train_pair_dedup" = 0 (its rows stay in the caller's order) and "train_paired_steps" does not rise.
+ *   sse_train_open_encodings_dev   copies the un-normalised encodings [B][S] of the open step, in the caller's row order, to
+ *       out_dev on `stream` (ordered behind the forward).  side 0 = source, 1 = target; in the table modes side 1 is the
+ *       gathered rows of the free target matrix.
+ *   sse_train_backward_dev   closes the step with the caller's gradients d_src_dev / d_tgt_dev [B][S]: the gradient of the
+ *       GLOBAL mean objective with respect to this rank's un-normalised encodings, already scaled by 1 / rows_global as the
+ *       loss heads produce them (read on the stream of sse_set_stream: the caller orders their production against it).
+ *       loss_part / acc_part go to tail[1] / tail[2] of the gradient arena, so that the arena's all-reduce adds the ranks'
+ *       shares up.  Then everything sse_train_grads does behind its loss head: the error-flag read, the zeroing of the
+ *       lookup-table gradients, the scatter onto the free target matrix, the path's backward, the tail.  The pending
+ *       gradients are IndexedSlices on both lookup tables (never the dense table of a class-loss step).
+ *       sse_train_apply (and the packed embedding exchange) follow as after sse_train_grads.
+ *   sse_train_pack_exchange   writes the open step's rows into ONE fixed-size block of 32-bit words for one all-gather,
+ *       sse_train_exchange_floats(cap, T) words for cap >= B row slots in the caller's row order (Tt = T words of a target
+ *       token row, or 1 in the table modes: the row number of the free target matrix; ids travel as their bit patterns):
+ *         [ rows (int32), S, T, Tt | src raw (cap x S) | tgt raw (cap x S) | labels (cap) | src ids (cap x T) | tgt ids (cap x Tt) ]
+ *       Slots B .. cap-1 are zeroed.  cap is IDENTICAL on all ranks (the largest row count of a rank).
+ *   sse_train_backward_inbatch_global   closes the step with the in-batch softmax loss over the GLOBAL batch.  gathered_dev:
+ *       the `world` blocks back to back in rank order; rank_rows (host, [world]): the ranks' row counts.  It compacts the
+ *       blocks into contiguous global arrays (global row = rows of the lower ranks + local row), forms the source and target
+ *       keys over the GLOBAL id rows exactly as a train_loss = 1 step forms them over its own (a source or a target repeated
+ *       on another rank is admitted or excluded as the single-rank step of the concatenated batch decides), runs
+ *       sse_inbatch_loss_window_dev's head on this rank's window with scale "train_loss_scale" and inv_rows = 1 / rows_global,
+ *       reduces the window's row losses and accuracies into the tail, and closes as sse_train_backward_dev does.  No host
+ *       synchronisation beyond that of sse_train_grads.  On the wire: 2S + 1 + T + Tt words per row slot, once, beside the
+ *       gradient exchange; on the device: the cost stated at sse_inbatch_loss_window_dev with B = rows_global.
+ * Lifetime: any sse_train_grads*, sse_train_step* or sse_train_forward* discards an open step.  A closing call (or
+ * sse_train_open_encodings_dev, sse_train_pack_exchange) without an open step is refused; so is one after the variables
+ * changed (sse_set_variable, an update), and a second closing call.  sse_train_backward_inbatch_global refuses, each with
+ * its own text and before anything is queued: world < 1, rank outside [0, world), rank_rows[rank] != B, a rank with more than
+ * cap rows, rank_rows not adding up to rows_global, NULL pointers.  After any refusal the handle stays usable.
+ * Counters "train_open_steps", "train_global_inbatch_steps". */
+int sse_train_forward(sse_handle *h, const int32_t *src_ids_host, const int32_t *tgt_ids_host, const float *labels_host,
+                      int32_t B, int32_t T, int64_t rows_global);
+int sse_train_forward_rows(sse_handle *h, const int32_t *src_rows_host, const int32_t *tgt_rows_host,
+                           const float *labels_host, int32_t B, int64_t rows_global);
+int sse_train_open_encodings_dev(sse_handle *h, int side, float *out_dev, void *stream);
+int sse_train_backward_dev(sse_handle *h, const float *d_src_dev, const float *d_tgt_dev, float loss_part, float acc_part);
+int64_t sse_train_exchange_floats(sse_handle *h, int32_t cap, int32_t T);
+int sse_train_pack_exchange(sse_handle *h, int32_t cap, float *block_dev);
+int sse_train_backward_inbatch_global(sse_handle *h, const float *gathered_dev, int32_t world, int32_t cap, int32_t rank,
+                                      const int32_t *rank_rows_host);
 /* Batches by row number: the padded source / target corpora (the token-id matrices Data builds
  * from TrainPairs / targetIDs, data.py:95-115) are uploaded once with sse_corpus_upload (side 0 = source corpus
  * [N,T], side 1 = target corpus) and a step ships 2*B row numbers instead of 2*B*T token ids; the batch's id matrix

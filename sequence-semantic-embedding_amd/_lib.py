@@ -43,6 +43,8 @@ SYMBOLS = {
     "sse_get_counter": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
     "sse_l2_normalize_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, _P]),
     "sse_inbatch_loss_dev": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
+    "sse_inbatch_loss_window_dev": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                              _P, _P, _P, _P, _P]),
     "sse_class_loss_dev": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
     "sse_index_upload": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64]),
     "sse_index_upload_f64": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64]),
@@ -94,6 +96,13 @@ SYMBOLS = {
     "sse_corpus_upload": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int32]),
     "sse_train_step_rows": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sse_train_grads_rows": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int64]),
+    "sse_train_forward": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int64]),
+    "sse_train_forward_rows": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int64]),
+    "sse_train_open_encodings_dev": (C.c_int, [_P, C.c_int, _P, _P]),
+    "sse_train_backward_dev": (C.c_int, [_P, _P, _P, C.c_float, C.c_float]),
+    "sse_train_exchange_floats": (C.c_int64, [_P, C.c_int32, C.c_int32]),
+    "sse_train_pack_exchange": (C.c_int, [_P, C.c_int32, _P]),
+    "sse_train_backward_inbatch_global": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "sse_eval_loss": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(C.c_double), _P]),
     "sse_eval_loss_rows": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(C.c_double), _P]),
     "sse_get_learning_rate": (C.c_int, [_P, C.POINTER(C.c_float)]),
@@ -270,6 +279,19 @@ class Handle(object):
         self.check(self.lib.sse_inbatch_loss_dev(self._h, dev(src_raw), dev(tgt_raw), dev(labels), dev(src_key), dev(tgt_key),
                                                  int(B), int(S), float(scale), float(inv_rows), dev(d_src), dev(d_tgt),
                                                  dev(row_loss), dev(row_acc), stream))
+
+    def inbatch_loss_window_dev(self, src_raw, tgt_raw, labels, src_key, tgt_key, B, S, row_lo, row_hi, scale, inv_rows, d_src,
+                                d_tgt, row_loss, row_acc, stream=0):
+        """sse_inbatch_loss_window_dev: inbatch_loss_dev over the B rows, its outputs cut to the rows [row_lo, row_hi): d_src /
+        d_tgt [row_hi - row_lo][S], row_loss / row_acc [row_hi - row_lo]; every output row carries the bits of the same row of
+        inbatch_loss_dev.  What a rank of a data-parallel step runs over the gathered global batch."""
+        def dev(x):
+            if x is None:
+                return None
+            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        self.check(self.lib.sse_inbatch_loss_window_dev(self._h, dev(src_raw), dev(tgt_raw), dev(labels), dev(src_key), dev(tgt_key),
+                                                        int(B), int(S), int(row_lo), int(row_hi), float(scale), float(inv_rows),
+                                                        dev(d_src), dev(d_tgt), dev(row_loss), dev(row_acc), stream))
 
     def class_loss_dev(self, src_raw, table, tgt_row, labels, src_key, B, N, S, scale, inv_rows, d_src, d_table, row_loss,
                        row_acc, stream=0):
@@ -802,6 +824,48 @@ class Handle(object):
         loss, acc = C.c_float(), C.c_float()
         self.check(self.lib.sse_train_apply(self._h, C.byref(loss), C.byref(acc)))
         return float(loss.value), float(acc.value)
+
+    # ---- the open train step: forward -> (the caller's objective over the raw encodings) -> backward -> [exchange] -> apply
+    def train_forward(self, src_ids, tgt_ids, labels, rows_global=None):
+        """sse_train_forward: the forward half of train_grads; the step stays open for ONE closing call (train_backward,
+        train_backward_inbatch_global).  The options train_loss / train_class_loss are not consulted."""
+        s, t, z = self._train_batch(src_ids, tgt_ids, labels)
+        self._check_tgt_kind(t)
+        self.check(self.lib.sse_train_forward(self._h, _ptr(s), _ptr(t), _ptr(z), s.shape[0], s.shape[1],
+                                              int(rows_global if rows_global is not None else s.shape[0])))
+
+    def train_forward_rows(self, src_rows, tgt_rows, labels, rows_global=None):
+        s, t, z = self._rows_batch(src_rows, tgt_rows, labels)
+        self.check(self.lib.sse_train_forward_rows(self._h, _ptr(s), _ptr(t), _ptr(z), s.shape[0],
+                                                   int(rows_global if rows_global is not None else s.shape[0])))
+
+    def train_open_encodings(self, side, out, stream=0):
+        """The un-normalised encodings [B][S] of the open step (side 0 source, 1 target; table modes: the gathered rows of
+        the free target matrix) into `out`, a contiguous float32 CUDA tensor; queued on `stream`."""
+        self.check(self.lib.sse_train_open_encodings_dev(self._h, int(side), C.c_void_p(out.data_ptr()), stream))
+
+    def train_backward(self, d_src, d_tgt, loss_part=0.0, acc_part=0.0):
+        """Closes the open step with the caller's gradients [B][S] of the GLOBAL mean objective with respect to this rank's
+        un-normalised encodings (float32 CUDA tensors); loss_part / acc_part: this rank's share of the global loss and
+        accuracy, summed over the ranks by the arena's all-reduce.  train_apply follows as after train_grads."""
+        self.check(self.lib.sse_train_backward_dev(self._h, C.c_void_p(d_src.data_ptr()), C.c_void_p(d_tgt.data_ptr()),
+                                                   float(loss_part), float(acc_part)))
+
+    def train_exchange_floats(self, cap, T=None):
+        return int(self.lib.sse_train_exchange_floats(self._h, int(cap), int(T if T is not None else self.cfg.max_seq_length)))
+
+    def train_pack_exchange(self, cap, block):
+        """block: contiguous float32 CUDA tensor of train_exchange_floats(cap, T) elements; the open step's rows for one all-gather."""
+        self.check(self.lib.sse_train_pack_exchange(self._h, int(cap), C.c_void_p(block.data_ptr())))
+
+    def train_backward_inbatch_global(self, gathered, world, cap, rank, rank_rows):
+        """Closes the open step with the in-batch softmax loss over the GLOBAL batch: gathered = the `world` exchange blocks
+        back to back (float32 CUDA), rank_rows = the ranks' row counts (host)."""
+        rr = np.ascontiguousarray(rank_rows, dtype=np.int32).reshape(-1)
+        if rr.size < int(world):                    # (the library reads `world` entries; it refuses every other mismatch itself)
+            raise ValueError("rank_rows must hold one row count per rank")
+        self.check(self.lib.sse_train_backward_inbatch_global(self._h, C.c_void_p(gathered.data_ptr()), int(world), int(cap),
+                                                              int(rank), _ptr(rr)))
 
     # ---- forward-only loss / accuracy / cosines of held-out pairs (sse_eval_loss*): no update, inference kernels
     def _eval_call(self, by_rows, src, tgt, labels, want_cos):

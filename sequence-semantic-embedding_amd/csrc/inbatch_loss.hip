@@ -10,6 +10,13 @@
 // shared with class_loss.hip; that header explains the register layout (OWN index on the lane, WALK index in the 16 accumulator
 // registers) and why every order depends on (B, S) alone.  This file adds the keys, the admission rule (inbatch_admits) and the
 // positive on the diagonal.
+//
+// The head can be cut to a window of rows [row_lo, row_hi) of the batch (sse_inbatch_loss_window_dev; the global closing of a
+// data-parallel step, where a rank owns a window of the gathered global batch).  The staging and the rows pass still cover every
+// row -- d(nt_j) of a window column needs lse_i of every row i -- while the two gradient passes, the finish kernel and the loss
+// outputs shrink to the 32-row tiles of the batch's own numbering that meet the window: a workgroup owns the same tile, walks the
+// same tiles in the same order and adds its waves up the same way as in the full head, so a row's bits do not depend on the
+// window.  The window [0, B) is the full head, launch for launch.
 #include "softmax_head.h"
 
 namespace {
@@ -20,9 +27,11 @@ struct InbatchArgs {
   float *ns, *nt, *dns, *dnt;               // [Bt][Sp]
   float *rs, *rt, *cs, *ct, *lse;           // [Bt]: 1 / norm, clamp flag (sum of squares below 1e-12), log-sum-exp
   int4 *meta;                               // [Bt]: {target key, source key, source key or -1 when the label is 0, bits of z * scale * inv_rows}
-  float *d_src, *d_tgt;                     // [rows_out][S]
-  float *row_loss, *row_acc;                // [B]
+  float *d_src, *d_tgt;                     // [rows_out][S]: row r is batch row row_lo + r
+  float *row_loss, *row_acc;                // [row_hi - row_lo]
   int32_t B, Bt, rows_out, S, Sp;
+  int32_t row_lo, row_hi;                   // the window of batch rows whose outputs are written; tile_lo = row_lo / 32
+  int32_t tile_lo;
   float scale, coef;                        // coef = scale * inv_rows
 };
 
@@ -82,14 +91,20 @@ __global__ __launch_bounds__(SMX_NW * 64) void inbatch_rows_kernel(InbatchArgs a
     }
   }
   if (!smx_rows_reduce(m, s, lii, lane, w) || i >= a.B) return;
-  smx_row_close(m, s, lii, a.labels[i], a.lse[i], a.row_loss[i], a.row_acc[i]);
+  float row_loss, row_acc;
+  smx_row_close(m, s, lii, a.labels[i], a.lse[i], row_loss, row_acc);
+  if (i >= a.row_lo && i < a.row_hi) {
+    a.row_loss[i - a.row_lo] = row_loss;
+    a.row_acc[i - a.row_lo] = row_acc;
+  }
 }
 
 // gradient pass.  COLS == false: own = row i, walk = column j, out = d(ns); COLS == true: own = column j, walk = row i, out = d(nt).
+// Workgroup x owns tile tile_lo + x of the batch: the grid covers the tiles that meet the window.
 template <bool COLS, int ST>
 __global__ __launch_bounds__(SMX_NW * 64) void inbatch_grad_kernel(InbatchArgs a) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int obase = blockIdx.x * 32, o = obase + (lane & 31);
+  const int obase = (a.tile_lo + blockIdx.x) * 32, o = obase + (lane & 31);
   const int sbase = blockIdx.y * (32 * ST);
   const int nst = min(ST, (a.Sp - sbase) / 32);
   const float *__restrict__ ownN = COLS ? a.nt : a.ns;
@@ -120,13 +135,15 @@ __global__ __launch_bounds__(SMX_NW * 64) void inbatch_grad_kernel(InbatchArgs a
   smx_grad_reduce_store(out, (COLS ? a.dnt : a.dns) + (size_t)obase * a.Sp + sbase, a.Sp, nst, lane, w);
 }
 
-// l2_normalize backward of both sides, one wave per output row; rows B .. rows_out-1 zeroed
+// l2_normalize backward of both sides, one wave per output row (batch row row_lo + output row); the output rows behind the
+// window, up to rows_out, zeroed
 __global__ __launch_bounds__(256) void inbatch_finish_kernel(InbatchArgs a) {
   const int lane = threadIdx.x & 63;
-  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (row >= a.rows_out) return;
-  float *ds = a.d_src + (size_t)row * a.S, *dt = a.d_tgt + (size_t)row * a.S;
-  if (row >= a.B) {
+  const int orow = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (orow >= a.rows_out) return;
+  float *ds = a.d_src + (size_t)orow * a.S, *dt = a.d_tgt + (size_t)orow * a.S;
+  const int row = a.row_lo + orow;
+  if (row >= a.row_hi) {
     for (int d = lane; d < a.S; d += 64) {
       ds[d] = 0.0f;
       dt[d] = 0.0f;
@@ -217,9 +234,10 @@ size_t inbatch_scratch_bytes(int B, int S) {
   return (4 * Bt * Sp + 5 * Bt) * sizeof(float) + Bt * sizeof(int4);
 }
 
-hipError_t launch_inbatch_loss(const float *src_raw, const float *tgt_raw, const float *labels, const int32_t *src_key,
-                               const int32_t *tgt_key, int B, int rows_out, int S, float scale, float inv_rows, void *scratch,
-                               float *d_src, float *d_tgt, float *row_loss, float *row_acc, hipStream_t st) {
+hipError_t launch_inbatch_loss_window(const float *src_raw, const float *tgt_raw, const float *labels, const int32_t *src_key,
+                                      const int32_t *tgt_key, int B, int row_lo, int row_hi, int rows_out, int S, float scale,
+                                      float inv_rows, void *scratch, float *d_src, float *d_tgt, float *row_loss, float *row_acc,
+                                      hipStream_t st) {
   const size_t Bt = smx_round32(B), Sp = smx_round32(S);
   InbatchArgs a;
   a.src_raw = src_raw;  a.tgt_raw = tgt_raw;  a.labels = labels;  a.ks = src_key;  a.kt = tgt_key;
@@ -231,11 +249,12 @@ hipError_t launch_inbatch_loss(const float *src_raw, const float *tgt_raw, const
   a.d_src = d_src;  a.d_tgt = d_tgt;  a.row_loss = row_loss;  a.row_acc = row_acc;
   a.B = B;  a.Bt = (int32_t)Bt;  a.rows_out = rows_out;  a.S = S;  a.Sp = (int32_t)Sp;
   a.scale = scale;  a.coef = scale * inv_rows;
-  const int NT = (int)(Bt / 32);
+  a.row_lo = row_lo;  a.row_hi = row_hi;  a.tile_lo = row_lo / 32;
+  const int NT = (int)(Bt / 32), NTw = (row_hi - 1) / 32 - a.tile_lo + 1;
   hipLaunchKernelGGL(inbatch_prep_kernel, dim3((unsigned)((Bt + 3) / 4)), dim3(256), 0, st, a);
   hipLaunchKernelGGL(inbatch_rows_kernel, dim3(NT), dim3(SMX_NW * 64), 0, st, a);
   if (d_src && d_tgt) {
-    const dim3 grid(NT, smx_s_tiles(Sp));
+    const dim3 grid(NTw, smx_s_tiles(Sp));
     if (!smx_wide(Sp)) {
       hipLaunchKernelGGL((inbatch_grad_kernel<false, SMX_ST>), grid, dim3(SMX_NW * 64), 0, st, a);
       hipLaunchKernelGGL((inbatch_grad_kernel<true, SMX_ST>), grid, dim3(SMX_NW * 64), 0, st, a);
@@ -246,4 +265,11 @@ hipError_t launch_inbatch_loss(const float *src_raw, const float *tgt_raw, const
     hipLaunchKernelGGL(inbatch_finish_kernel, dim3((rows_out + 3) / 4), dim3(256), 0, st, a);
   }
   return hipGetLastError();
+}
+
+hipError_t launch_inbatch_loss(const float *src_raw, const float *tgt_raw, const float *labels, const int32_t *src_key,
+                               const int32_t *tgt_key, int B, int rows_out, int S, float scale, float inv_rows, void *scratch,
+                               float *d_src, float *d_tgt, float *row_loss, float *row_acc, hipStream_t st) {
+  return launch_inbatch_loss_window(src_raw, tgt_raw, labels, src_key, tgt_key, B, 0, B, rows_out, S, scale, inv_rows, scratch, d_src,
+                                    d_tgt, row_loss, row_acc, st);
 }

@@ -237,6 +237,8 @@ struct sse_handle {
   int64_t train_path_fused = 0, train_path_generic = 0, train_path_cnn = 0, train_paired_steps = 0;
   int64_t train_fp32_repacks = 0, train_split_repacks = 0, train_generic_repacks = 0;
   int64_t train_inbatch_steps = 0;  // counter "train_inbatch_steps": steps whose loss stage ran the in-batch softmax head
+  int64_t train_open_steps = 0;            // counter "train_open_steps": sse_train_forward* calls that left a step open
+  int64_t train_global_inbatch_steps = 0;  // counter "train_global_inbatch_steps": steps closed by sse_train_backward_inbatch_global
   // in-batch softmax loss (sse_inbatch_loss_dev and the train step under option train_loss = 1): staged operands, row
   // statistics, un-normalised gradients (launch_inbatch_loss); the row keys [source | target | hash scratch] of a call
   DevBuf s_inbatch, s_inbatch_keys;
@@ -2606,7 +2608,8 @@ int64_t sse_handle::*const HOST_COUNTERS[] = {&sse_handle::persist_fallbacks, &s
                                               &sse_handle::train_paired_steps, &sse_handle::train_fp32_repacks,
                                               &sse_handle::train_split_repacks, &sse_handle::train_generic_repacks,
                                               &sse_handle::train_inbatch_steps, &sse_handle::score_lse_calls,
-                                              &sse_handle::train_class_steps};
+                                              &sse_handle::train_class_steps, &sse_handle::train_open_steps,
+                                              &sse_handle::train_global_inbatch_steps};
 
 // every name sse_get_counter answers: its group and its word there (CG_HOST: entry of HOST_COUNTERS; CG_PATH: entry of
 // sse_handle::lstm_path_calls; a device group: the word the kernels of that family count in)
@@ -2629,6 +2632,8 @@ const struct {
     {"train_generic_repacks", CG_HOST, 11}, // the any-shape path's packs, once per side
     {"train_inbatch_steps", CG_HOST, 12},   // steps whose loss stage ran the in-batch softmax head (option train_loss = 1)
     {"train_class_steps", CG_HOST, 14},     // steps whose loss stage ran the class softmax head (option train_class_loss = 1)
+    {"train_open_steps", CG_HOST, 15},      // sse_train_forward* calls that left a step open
+    {"train_global_inbatch_steps", CG_HOST, 16},  // steps closed by sse_train_backward_inbatch_global
     // LSTM inference encodes by kernel
     {"lstm_path_persist", CG_PATH, PATH_PERSIST},
     {"lstm_path_cluster", CG_PATH, PATH_CLUSTER},
@@ -2810,6 +2815,30 @@ int sse_inbatch_loss_dev(sse_handle *h, const float *src_raw_dev, const float *t
   HIPCHECK(h, launch_inbatch_value_keys(tgt_key_dev, 64, B, kt, st));
   HIPCHECK(h, launch_inbatch_loss(src_raw_dev, tgt_raw_dev, labels_dev, ks, kt, B, B, S, scale, inv_rows, h->s_inbatch.p, d_src_dev,
                                   d_tgt_dev, row_loss_dev, row_acc_dev, st));
+  return 0;
+}
+
+int sse_inbatch_loss_window_dev(sse_handle *h, const float *src_raw_dev, const float *tgt_raw_dev, const float *labels_dev,
+                                const int64_t *src_key_dev, const int64_t *tgt_key_dev, int32_t B, int32_t S, int32_t row_lo,
+                                int32_t row_hi, float scale, float inv_rows, float *d_src_dev, float *d_tgt_dev, float *row_loss_dev,
+                                float *row_acc_dev, void *stream) {
+  SSE_ENTER(h);
+  if (B < 1 || S < 1) return fail(h, "sse_inbatch_loss_window_dev: B and S must be >= 1");
+  if (row_lo < 0) return fail(h, "sse_inbatch_loss_window_dev: row_lo = %d is negative", row_lo);
+  if (row_hi > B) return fail(h, "sse_inbatch_loss_window_dev: row_hi = %d lies behind the %d rows of the batch", row_hi, B);
+  if (row_lo >= row_hi) return fail(h, "sse_inbatch_loss_window_dev: the window [%d, %d) is empty or inverted", row_lo, row_hi);
+  if (!src_raw_dev || !tgt_raw_dev || !labels_dev || !row_loss_dev || !row_acc_dev)
+    return fail(h, "sse_inbatch_loss_window_dev: encodings, labels, row_loss and row_acc must not be NULL");
+  if ((d_src_dev == nullptr) != (d_tgt_dev == nullptr))
+    return fail(h, "sse_inbatch_loss_window_dev: d_src and d_tgt must both be given, or both be NULL (forward only)");
+  if (!(scale > 0.0f && scale <= 256.0f)) return fail(h, "sse_inbatch_loss_window_dev: scale must be in (0, 256]");
+  if (reserve_inbatch(h, B, S)) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  int32_t *ks = (int32_t *)h->s_inbatch_keys.p, *kt = ks + B;
+  HIPCHECK(h, launch_inbatch_value_keys(src_key_dev, 64, B, ks, st));
+  HIPCHECK(h, launch_inbatch_value_keys(tgt_key_dev, 64, B, kt, st));
+  HIPCHECK(h, launch_inbatch_loss_window(src_raw_dev, tgt_raw_dev, labels_dev, ks, kt, B, row_lo, row_hi, row_hi - row_lo, S, scale, inv_rows,
+                                         h->s_inbatch.p, d_src_dev, d_tgt_dev, row_loss_dev, row_acc_dev, st));
   return 0;
 }
 
@@ -3470,7 +3499,7 @@ static int step_begin(sse_handle *h, const TrainCall &call, int row_tile, StepFr
   f.tail = f.ts->arena + grad_arena_count(h) - 4;
   f.inv_rows = 1.0f / (float)call.rows_global;
   f.n_sq = 0;
-  f.class_loss = h->train_class_loss != 0;
+  f.class_loss = h->train_class_loss != 0 && call.phase == STEP_WHOLE;  // (an open step takes its objective from the closing call)
   return 0;
 }
 
@@ -3586,6 +3615,16 @@ static int step_loss(StepFrame &f) {
   return 0;
 }
 
+// the loss stage of a closing call (STEP_CLOSE): draw[] and tail[1..2] are written already; what step_loss does around its head
+static int step_loss_closing(StepFrame &f) {
+  sse_handle *h = f.h;
+  if (check_err_flag(h, f.st)) return 1;
+  HIPCHECK(h, hipMemsetAsync(f.emb->grad, 0, f.emb->count * sizeof(float), f.st));
+  if (f.table_tgt) HIPCHECK(h, hipMemsetAsync(f.table->grad, 0, f.table->count * sizeof(float), f.st));
+  return 0;
+}
+static int step_loss_of(StepFrame &f) { return f.call->phase == STEP_CLOSE ? step_loss_closing(f) : step_loss(f); }
+
 // table target: d(raw[1]) scattered onto the free matrix's gradient, its slice norms into the last B partial sums
 static int step_table_backward(StepFrame &f) {
   if (!f.table_tgt) return 0;
@@ -3652,6 +3691,13 @@ static int cnn_backward(StepFrame &f) {
 static int cnn_train_grads_locked(sse_handle *h, const TrainCall &call) {
   const sse_config &c = h->cfg;
   const int B = call.B, T = call.T, E = c.embedding_size, S = c.encoding_size;
+  const bool closing = call.phase == STEP_CLOSE;  // the checks passed and the buffers were reserved when the step was opened
+  if (closing) {
+    StepFrame f;
+    if (step_begin(h, call, 64, f)) return 1;
+    f.n_sq = 2 * B;
+    return step_loss_of(f) || cnn_backward(f) || step_table_backward(f) || step_finish(f);
+  }
   if (T < 5) return fail(h, "source_only_cnn needs max_seq_length >= 5 (widest filter)");
   if (E > 64) return fail(h, "train step: embedding_size %d > 64 not supported yet", E);
   if ((h->cnn_bf16 ? cnn_bf16_lds_bytes(T, round_up(E, 8), 1) : cnn_lds_bytes(T, emb_cols(c), 1)) > 160 * 1024)
@@ -3674,7 +3720,9 @@ static int cnn_train_grads_locked(sse_handle *h, const TrainCall &call) {
       reserve(h, ts.hot_part[0], (size_t)std::max(B, cnn_dx_mfma_blocks(B)) * 2 * 64 * sizeof(float)) ||
       reserve(h, ts.dm_part[0], (size_t)proj_bwd_chunks(Bp) * 576 * S * sizeof(float)))
     return 1;
-  return cnn_forward(f) || step_table_forward(f) || step_loss(f) || cnn_backward(f) || step_table_backward(f) || step_finish(f);
+  if (cnn_forward(f) || step_table_forward(f)) return 1;
+  if (call.phase == STEP_OPEN) return 0;
+  return step_loss(f) || cnn_backward(f) || step_table_backward(f) || step_finish(f);
 }
 
 // ---- The LSTM modes at shapes the fused training kernels are not laid out for (cell size > 256, embedding_size > 64): the same
@@ -3724,11 +3772,13 @@ static int generic_backward_side(StepFrame &f, const GenLstmDims &d, int s) {
 
 static int train_grads_generic_locked(sse_handle *h, const TrainCall &call) {
   StepFrame f;
-  h->train_path_generic += 1;
+  const bool closing = call.phase == STEP_CLOSE;  // the inputs are staged, the forward has run
+  if (!closing) h->train_path_generic += 1;
   if (step_begin(h, call, 32, f)) return 1;
   const int B = f.B, T = f.T, nside = f.nside;
   // sq_part: one partial sum per (side, step, row), one per target row in source-encoder-only mode
-  if (step_stage_inputs(f, nullptr, nside * T * B + (f.table_tgt ? B : 0))) return 1;
+  f.n_sq = nside * T * B + (f.table_tgt ? B : 0);
+  if (!closing && step_stage_inputs(f, nullptr, f.n_sq)) return 1;
   TrainState &ts = *f.ts;
   GenLstmDims dims[2];
   size_t g_max = 0, c_max = 0, da_max = 0, dkp_max = 0;
@@ -3744,10 +3794,13 @@ static int train_grads_generic_locked(sse_handle *h, const TrainCall &call) {
       reserve(h, ts.gen_dA, da_max * sizeof(float)) || reserve(h, ts.gen_dc, c_max * sizeof(float)) ||
       reserve(h, ts.gen_dkp, dkp_max * sizeof(float)))
     return 1;
-  if (step_table_forward(f)) return 1;
-  for (int s = 0; s < nside; ++s)
-    if (generic_forward_side(f, dims[s], s)) return 1;
-  if (step_loss(f) || step_table_backward(f)) return 1;
+  if (!closing) {
+    if (step_table_forward(f)) return 1;
+    for (int s = 0; s < nside; ++s)
+      if (generic_forward_side(f, dims[s], s)) return 1;
+    if (call.phase == STEP_OPEN) return 0;
+  }
+  if (step_loss_of(f) || step_table_backward(f)) return 1;
   for (int s = 0; s < nside; ++s)
     if (generic_backward_side(f, dims[s], s)) return 1;
   return step_finish(f);
@@ -3790,7 +3843,8 @@ static FusedPlan fused_plan(const StepFrame &f) {
   // its positive and once with a sampled negative target): the rows are taken in the order [0,2,4,.. | 1,3,5,..], the
   // source encoder runs on the first half only, and its tapes serve both halves of the backward pass.  The backward
   // itself stays per row: clip_by_global_norm sees the two rows' embedding slices separately (sse_model.py:359-362).
-  p.paired = h->train_pair_dedup && f.B % 128 == 0 &&  // both halves whole 64-row tiles
+  // (an open step runs without the de-duplication: its closing call hands over gradients in the caller's row order)
+  p.paired = f.call->phase == STEP_WHOLE && h->train_pair_dedup && f.B % 128 == 0 &&  // both halves whole 64-row tiles
              batch_is_paired(f.call->src, f.B, f.T, f.call->by_rows);
   p.NT32 = f.Bp / 32;
   p.NT_half = p.NT32 / 2;
@@ -4084,19 +4138,25 @@ static int train_grads_fused_locked(sse_handle *h, const TrainCall &call) {
   StepFrame f;
   if (step_begin(h, call, 64, f)) return 1;
   TrainState &ts = *f.ts;
-  const FusedPlan p = fused_plan(f);
-  h->train_path_fused += 1;
-  if (p.paired) h->train_paired_steps += 1;
-  if (fused_refresh_layouts(f, p) || fused_check_tape(f, p)) return 1;
-  const int32_t *perm = nullptr;
-  if (p.paired && pair_permutation(f, &perm)) return 1;
-  if (step_stage_inputs(f, perm, p.n_sq) || fused_pack_split_inputs(f)) return 1;
-  // the two encoders are independent: fork onto two side streams, join before the loss
-  HIPCHECK(h, hipEventRecord(ts.ev_fork, f.st));
-  if (step_table_forward(f)) return 1;
-  for (int s = 0; s < f.nside; ++s)
-    if (fused_forward_side(f, p, s)) return 1;
-  if (step_loss(f) || step_table_backward(f)) return 1;
+  const FusedPlan p = call.phase == STEP_CLOSE ? ts.open.plan : fused_plan(f);
+  if (call.phase == STEP_OPEN) ts.open.plan = p;
+  if (call.phase != STEP_CLOSE) {
+    h->train_path_fused += 1;
+    if (p.paired) h->train_paired_steps += 1;
+    if (fused_refresh_layouts(f, p) || fused_check_tape(f, p)) return 1;
+    const int32_t *perm = nullptr;
+    if (p.paired && pair_permutation(f, &perm)) return 1;
+    if (step_stage_inputs(f, perm, p.n_sq) || fused_pack_split_inputs(f)) return 1;
+    // the two encoders are independent: fork onto two side streams, join before the loss
+    HIPCHECK(h, hipEventRecord(ts.ev_fork, f.st));
+    if (step_table_forward(f)) return 1;
+    for (int s = 0; s < f.nside; ++s)
+      if (fused_forward_side(f, p, s)) return 1;
+    if (call.phase == STEP_OPEN) return 0;
+  } else {
+    f.n_sq = p.n_sq;
+  }
+  if (step_loss_of(f) || step_table_backward(f)) return 1;
   HIPCHECK(h, hipEventRecord(ts.ev_fork, f.st));  // loss + zeroed embedding gradient are ready
   for (int s = 0; s < f.nside; ++s)
     if (fused_backward_side(f, p, s)) return 1;
@@ -4107,21 +4167,62 @@ static int train_grads_fused_locked(sse_handle *h, const TrainCall &call) {
 // the arena (with the tail sums), nothing is updated.
 static int train_grads_locked(sse_handle *h, const TrainCall &call) {
   const sse_config &c = h->cfg;
+  if (h->train) h->train->open.valid = false;  // whatever step was left open is discarded
   if (call.B < 1 || call.T < 1 || !call.src || !call.tgt || !call.labels || call.rows_global < call.B)
     return fail(h, "bad arguments to the train step");
-  if (h->train_class_loss) {
+  if (call.phase == STEP_WHOLE && h->train_class_loss) {
     if (h->tgt_table < 0)
       return fail(h, "train step: train_class_loss = 1 needs a network mode with a free target matrix (source-encoder-only or source_only_cnn)");
     if (h->train_loss == 1)
       return fail(h, "train step: train_class_loss = 1 and train_loss = 1 ask for two objectives; set one of them to 0");
   }
   if (!h->train) h->train = new TrainState();
-  if (c.network_mode == SSE_MODE_SOURCE_ONLY_CNN) return cnn_train_grads_locked(h, call);
+  int &path = h->train->open.path;  // (read by the closing call of an open step)
+  if (c.network_mode == SSE_MODE_SOURCE_ONLY_CNN) return path = OPEN_CNN, cnn_train_grads_locked(h, call);
   // shapes outside the fused training kernels (cell size > 256, embedding_size > 64; option train_generic forces it: tests)
   bool generic = h->train_generic || c.embedding_size > 64;
   for (int s = 0; s < (c.network_mode == SSE_MODE_SOURCE_ENCODER_ONLY ? 1 : 2); ++s)
     generic = generic || h->enc[s].Hp > 256 || h->enc[s].generic;
+  path = generic ? OPEN_GENERIC : OPEN_FUSED;
   return generic ? train_grads_generic_locked(h, call) : train_grads_fused_locked(h, call);
+}
+
+// ---- the open step: sse_train_forward* stops behind the forward (STEP_OPEN), one closing call supplies d(raw encodings) and
+// the loss tail and runs the rest (STEP_CLOSE).  An open step keeps the caller's row order (no pair de-duplication).
+
+static int train_forward_locked(sse_handle *h, TrainCall call) {
+  call.phase = STEP_OPEN;
+  if (train_grads_locked(h, call)) return 1;
+  TrainState::Open &o = h->train->open;
+  o.B = call.B;  o.T = call.T;  o.rows_global = call.rows_global;  o.by_rows = call.by_rows;
+  o.weights_version = h->weights_version;
+  o.valid = true;
+  h->train_open_steps += 1;
+  return 0;
+}
+
+// the open step a closing or reading call refers to, or nullptr with the refusal's text set
+static TrainState::Open *open_step(sse_handle *h, const char *who) {
+  if (!h->train || !h->train->open.valid) {
+    fail(h, "%s: no step is open (sse_train_forward opens one; a closing call or any other train step ends it)", who);
+    return nullptr;
+  }
+  if (h->train->open.weights_version != h->weights_version) {
+    fail(h, "%s: the variables changed since sse_train_forward (sse_set_variable or an update): run the forward again", who);
+    return nullptr;
+  }
+  return &h->train->open;
+}
+
+static int open_row_tile(const TrainState::Open &o) { return o.path == OPEN_GENERIC ? 32 : 64; }
+
+// the rest of the open step; draw[] (pad rows zeroed) and tail[1..2] have been queued by the caller
+static int train_close_locked(sse_handle *h) {
+  TrainState::Open &o = h->train->open;
+  o.valid = false;
+  const TrainCall call{nullptr, nullptr, nullptr, o.B, o.T, o.rows_global, o.by_rows, false, STEP_CLOSE};
+  return o.path == OPEN_CNN ? cnn_train_grads_locked(h, call)
+         : o.path == OPEN_GENERIC ? train_grads_generic_locked(h, call) : train_grads_fused_locked(h, call);
 }
 
 // clip_by_global_norm over the (possibly all-reduced) arena + Adagrad + global_step (sse_model.py:355-364)
@@ -4184,6 +4285,131 @@ int sse_train_grads(sse_handle *h, const int32_t *src_ids_host, const int32_t *t
                     int32_t B, int32_t T, int64_t rows_global) {
   SSE_ENTER(h);
   return train_grads_locked(h, TrainCall{src_ids_host, tgt_ids_host, labels_host, B, T, rows_global, false, false});
+}
+
+int sse_train_forward(sse_handle *h, const int32_t *src_ids_host, const int32_t *tgt_ids_host, const float *labels_host, int32_t B,
+                      int32_t T, int64_t rows_global) {
+  SSE_ENTER(h);
+  return train_forward_locked(h, TrainCall{src_ids_host, tgt_ids_host, labels_host, B, T, rows_global, false, false});
+}
+
+int sse_train_forward_rows(sse_handle *h, const int32_t *src_rows_host, const int32_t *tgt_rows_host, const float *labels_host,
+                           int32_t B, int64_t rows_global) {
+  SSE_ENTER(h);
+  if (!h->train || !h->train->corpus[0].p) return fail(h, "train step by rows: no source corpus on the device (sse_corpus_upload)");
+  return train_forward_locked(h, TrainCall{src_rows_host, tgt_rows_host, labels_host, B, h->train->corpus_T[0], rows_global, true, false});
+}
+
+int sse_train_open_encodings_dev(sse_handle *h, int side, float *out_dev, void *stream) {
+  SSE_ENTER(h);
+  if ((side != 0 && side != 1) || !out_dev) return fail(h, "bad arguments to sse_train_open_encodings_dev");
+  const TrainState::Open *o = open_step(h, "sse_train_open_encodings_dev");
+  if (!o) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  if (st != h->stream) {  // the forward was queued on the stream of sse_set_stream: the copy waits for it
+    hipEvent_t ev;
+    HIPCHECK(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HIPCHECK(h, hipEventRecord(ev, h->stream));
+    HIPCHECK(h, hipStreamWaitEvent(st, ev, 0));
+    HIPCHECK(h, hipEventDestroy(ev));
+  }
+  HIPCHECK(h, hipMemcpyAsync(out_dev, h->train->raw[side].p, (size_t)o->B * h->cfg.encoding_size * sizeof(float), hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
+int sse_train_backward_dev(sse_handle *h, const float *d_src_dev, const float *d_tgt_dev, float loss_part, float acc_part) {
+  SSE_ENTER(h);
+  if (!d_src_dev || !d_tgt_dev) return fail(h, "sse_train_backward_dev: d_src and d_tgt must not be NULL");
+  const TrainState::Open *o = open_step(h, "sse_train_backward_dev");
+  if (!o) return 1;
+  TrainState &ts = *h->train;
+  if (ensure_arena(h)) return 1;
+  const int B = o->B, S = h->cfg.encoding_size, Bp = round_up(B, open_row_tile(*o));
+  const float *d[2] = {d_src_dev, d_tgt_dev};
+  for (int s = 0; s < 2; ++s) {
+    HIPCHECK(h, hipMemcpyAsync(ts.draw[s].p, d[s], (size_t)B * S * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    if (Bp > B) HIPCHECK(h, hipMemsetAsync((float *)ts.draw[s].p + (size_t)B * S, 0, (size_t)(Bp - B) * S * sizeof(float), h->stream));
+  }
+  HIPCHECK(h, launch_set_pair(ts.arena + grad_arena_count(h) - 4 + 1, loss_part, acc_part, h->stream));
+  return train_close_locked(h);
+}
+
+static int exchange_target_words(sse_handle *h, int T) { return h->tgt_table >= 0 ? 1 : T; }
+
+int64_t sse_train_exchange_floats(sse_handle *h, int32_t cap, int32_t T) {
+  if (!h || cap < 1 || T < 1) return 0;
+  return (int64_t)train_exchange_floats(cap, h->cfg.encoding_size, T, exchange_target_words(h, T));
+}
+
+int sse_train_pack_exchange(sse_handle *h, int32_t cap, float *block_dev) {
+  SSE_ENTER(h);
+  if (!block_dev) return fail(h, "sse_train_pack_exchange: block must not be NULL");
+  const TrainState::Open *o = open_step(h, "sse_train_pack_exchange");
+  if (!o) return 1;
+  if (cap < o->B) return fail(h, "sse_train_pack_exchange: cap = %d row slots, the open step holds %d rows", cap, o->B);
+  TrainState &ts = *h->train;
+  HIPCHECK(h, launch_train_exchange_pack((const float *)ts.raw[0].p, (const float *)ts.raw[1].p, (const float *)ts.labels.p,
+                                         (const int32_t *)ts.ids[0].p, (const int32_t *)ts.ids[1].p, o->B, cap, h->cfg.encoding_size, o->T,
+                                         exchange_target_words(h, o->T), block_dev, h->stream));
+  return 0;
+}
+
+int sse_train_backward_inbatch_global(sse_handle *h, const float *gathered_dev, int32_t world, int32_t cap, int32_t rank,
+                                      const int32_t *rank_rows_host) {
+  SSE_ENTER(h);
+  const char *who = "sse_train_backward_inbatch_global";
+  if (!gathered_dev || !rank_rows_host) return fail(h, "%s: the gathered blocks and rank_rows must not be NULL", who);
+  if (world < 1) return fail(h, "%s: world = %d, must be >= 1", who, world);
+  if (rank < 0 || rank >= world) return fail(h, "%s: rank %d outside [0, %d)", who, rank, world);
+  const TrainState::Open *o = open_step(h, who);
+  if (!o) return 1;
+  int64_t sum = 0;
+  int32_t most = 0;
+  for (int r = 0; r < world; ++r) {
+    if (rank_rows_host[r] < 0) return fail(h, "%s: rank_rows[%d] = %d is negative", who, r, rank_rows_host[r]);
+    sum += rank_rows_host[r];
+    most = std::max(most, rank_rows_host[r]);
+  }
+  if (rank_rows_host[rank] != o->B)
+    return fail(h, "%s: rank_rows[%d] = %d, the open step of this rank holds %d rows", who, rank, rank_rows_host[rank], o->B);
+  if (most > cap) return fail(h, "%s: a rank holds %d rows, more than the cap = %d row slots of a block", who, most, cap);
+  if (sum != o->rows_global)
+    return fail(h, "%s: rank_rows add up to %lld rows, the step was opened with rows_global = %lld", who, (long long)sum, (long long)o->rows_global);
+  TrainState &ts = *h->train;
+  hipStream_t st = h->stream;
+  const int B = o->B, G = (int)sum, S = h->cfg.encoding_size, T = o->T, Tt = exchange_target_words(h, T);
+  const int Bp = round_up(B, open_row_tile(*o));
+  if (ensure_arena(h) || reserve_inbatch(h, G, S)) return 1;
+  for (int s = 0; s < 2; ++s)
+    if (reserve(h, ts.xg_raw[s], (size_t)G * S * sizeof(float))) return 1;
+  if (reserve(h, ts.xg_labels, (size_t)G * sizeof(float)) || reserve(h, ts.xg_ids[0], (size_t)G * T * sizeof(int32_t)) ||
+      reserve(h, ts.xg_ids[1], (size_t)G * Tt * sizeof(int32_t)) || reserve(h, ts.xg_off, (size_t)(world + 1) * sizeof(int32_t)))
+    return 1;
+  // global row = rows of the lower ranks + local row
+  ts.h_off.assign(world + 1, 0);
+  for (int r = 0; r < world; ++r) ts.h_off[r + 1] = ts.h_off[r] + rank_rows_host[r];
+  const int row_lo = ts.h_off[rank];
+  HIPCHECK(h, hipMemcpyAsync(ts.xg_off.p, ts.h_off.data(), (size_t)(world + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  float *gsrc = (float *)ts.xg_raw[0].p, *gtgt = (float *)ts.xg_raw[1].p, *glab = (float *)ts.xg_labels.p;
+  int32_t *gid0 = (int32_t *)ts.xg_ids[0].p, *gid1 = (int32_t *)ts.xg_ids[1].p;
+  HIPCHECK(h, launch_train_exchange_compact(gathered_dev, (const int32_t *)ts.xg_off.p, world, G, cap, S, T, Tt, gsrc, gtgt, glab, gid0, gid1, st));
+  // the keys over the GLOBAL id rows, as step_loss_inbatch forms them over a rank's own: a source or a target repeated on
+  // another rank is admitted or excluded as the single-rank step of the concatenated batch decides
+  int32_t *ks = (int32_t *)h->s_inbatch_keys.p, *kt = ks + G;
+  uint32_t *hash = (uint32_t *)(kt + G);
+  HIPCHECK(h, launch_inbatch_token_keys(gid0, G, T, hash, ks, st));
+  if (Tt == 1 && h->tgt_table >= 0)
+    HIPCHECK(h, launch_inbatch_value_keys(gid1, 32, G, kt, st));
+  else
+    HIPCHECK(h, launch_inbatch_token_keys(gid1, G, T, hash, kt, st));
+  const float inv_rows = 1.0f / (float)o->rows_global;
+  HIPCHECK(h, launch_inbatch_loss_window(gsrc, gtgt, glab, ks, kt, G, row_lo, row_lo + B, Bp, S, (float)h->train_loss_scale, inv_rows,
+                                         h->s_inbatch.p, (float *)ts.draw[0].p, (float *)ts.draw[1].p, (float *)ts.row_loss.p,
+                                         (float *)ts.row_acc.p, st));
+  HIPCHECK(h, launch_loss_reduce((const float *)ts.row_loss.p, (const float *)ts.row_acc.p, B, inv_rows,
+                                 ts.arena + grad_arena_count(h) - 4 + 1, st));
+  h->train_global_inbatch_steps += 1;
+  return train_close_locked(h);
 }
 
 int sse_corpus_upload(sse_handle *h, int side, const int32_t *ids_host, int64_t N, int32_t T) {

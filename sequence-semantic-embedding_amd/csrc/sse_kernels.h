@@ -662,6 +662,27 @@ size_t inbatch_scratch_bytes(int B, int S);
 hipError_t launch_inbatch_loss(const float *src_raw, const float *tgt_raw, const float *labels, const int32_t *src_key,
                                const int32_t *tgt_key, int B, int rows_out, int S, float scale, float inv_rows, void *scratch,
                                float *d_src, float *d_tgt, float *row_loss, float *row_acc, hipStream_t st);
+// The head cut to the window [row_lo, row_hi) of the B rows, 0 <= row_lo < row_hi <= B: the same staging, keys and rows pass over
+// all B rows, the gradient passes over the 32-row tiles of the batch that meet the window.  d_src / d_tgt: [rows_out][S], output
+// row r = batch row row_lo + r, rows row_hi - row_lo .. rows_out-1 zeroed; row_loss / row_acc: [row_hi - row_lo].  Every output
+// row carries the bits of the same row of the full head; the window [0, B) IS the full head (launch_inbatch_loss calls this).
+hipError_t launch_inbatch_loss_window(const float *src_raw, const float *tgt_raw, const float *labels, const int32_t *src_key,
+                                      const int32_t *tgt_key, int B, int row_lo, int row_hi, int rows_out, int S, float scale,
+                                      float inv_rows, void *scratch, float *d_src, float *d_tgt, float *row_loss, float *row_acc,
+                                      hipStream_t st);
+
+// ------------------------------ exchange block of an open train step (train_exchange.hip) ------------
+// 32-bit words of one rank's block for cap row slots (layout: include/sse_hip.h, sse_train_pack_exchange); Tt = words of a
+// target id row: T, or 1 when the target is a row of the free target matrix
+size_t train_exchange_floats(int cap, int S, int T, int Tt);
+// B <= cap rows of raw encodings [B][S], labels [B] and id rows [B][T] / [B][Tt] into `block`; slots B .. cap-1 zeroed
+hipError_t launch_train_exchange_pack(const float *src_raw, const float *tgt_raw, const float *labels, const int32_t *ids0,
+                                      const int32_t *ids1, int B, int cap, int S, int T, int Tt, float *block, hipStream_t st);
+// `world` gathered blocks into contiguous [rows_global] arrays in rank order; row_off: [world + 1] device, first global row of each rank
+hipError_t launch_train_exchange_compact(const float *gathered, const int32_t *row_off, int world, int rows_global, int cap, int S, int T,
+                                         int Tt, float *src_raw, float *tgt_raw, float *labels, int32_t *ids0, int32_t *ids1,
+                                         hipStream_t st);
+hipError_t launch_set_pair(float *dst, float a, float b, hipStream_t st);  // dst[0] = a, dst[1] = b
 
 // ------------------------------ class softmax loss (class_loss.hip) -----------------------------
 // bytes of scratch launch_class_loss needs: O((B + N) * S + B), plus the bounded partials of the split walk

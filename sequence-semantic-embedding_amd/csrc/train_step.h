@@ -23,6 +23,17 @@ struct DevBuf {  // grow-only device scratch; freed with its owner (handle / Tra
   }
 };
 
+// Which kernels one fused LSTM step runs and what follows from it; decided once per call (fused_plan), const afterwards.
+struct FusedPlan {
+  // which kernel families run on split bf16 operands (options train_fwd_x3 / train_bwd_x3 / train_dk_x3), per encoder
+  bool fwd_x3[2], bwd_x3[2], all_x3, any_bwd_x3;
+  bool bwd2;    // second-generation fp32 kernels
+  bool paired;  // paired batch: the source encoder runs on the first half of the rows
+  int NT32, NT_half;  // 32-row tiles of the batch; paired: of one half (B % 128 == 0: Bp = B, NT_half even)
+  int sq_off[3];      // where each encoder's partial sums of dx^2 start in sq_part
+  int n_sq;
+};
+
 // device buffers of the training path, grown on demand
 struct TrainState {
   DevBuf ids[2], labels, raw[2], draw[2], tape_g[2], tape_a[2], h_last[2], dh_last[2], dg_a[2], dg_b[2], db_part[2],
@@ -53,7 +64,23 @@ struct TrainState {
   int perm_B = 0;
   std::vector<int32_t> h_perm, h_rows[2], h_tgt;
   std::vector<float> h_labels;
+  // the open step (sse_train_forward*): what its closing call needs to rebuild the frame -- no pointer of the caller's
+  struct Open {
+    bool valid = false;
+    int path = 0;                  // OPEN_CNN | OPEN_GENERIC | OPEN_FUSED
+    int32_t B = 0, T = 0;
+    int64_t rows_global = 0;
+    bool by_rows = false;
+    uint64_t weights_version = 0;  // the variables the forward ran on; a closing call after they changed is refused
+    FusedPlan plan = {};           // OPEN_FUSED: the plan the forward ran under (the options may have changed since)
+  } open;
+  DevBuf xg_raw[2], xg_labels, xg_ids[2], xg_off;  // the global batch of sse_train_backward_inbatch_global, compacted
+  std::vector<int32_t> h_off;
 };
+enum { OPEN_CNN, OPEN_GENERIC, OPEN_FUSED };
+// a train step whole, or cut at its loss stage: STEP_OPEN stops behind the forward, STEP_CLOSE resumes there with d(raw
+// encodings) and the loss tail already written by the closing call
+enum { STEP_WHOLE, STEP_OPEN, STEP_CLOSE };
 
 // One call of the train step as its entry point received it.  src / tgt: id matrices [B][T], or -- by_rows -- row numbers
 // into the corpora of sse_corpus_upload; tgt is rows of the free target matrix in the table modes either way.
@@ -65,6 +92,7 @@ struct TrainCall {
   bool by_rows;
   bool defer_err;  // the fused step entry points: the device error flag is read once, with the loss, after the whole step
                    // has been queued (a flagged step cancels its own update on the device)
+  int phase;       // STEP_WHOLE (the default of the brace initialisers), STEP_OPEN, STEP_CLOSE (src / tgt / labels are null)
 };
 
 // What the three paths of a step (text-CNN, any-shape LSTM, fused LSTM) share: filled by step_begin, n_sq by step_stage_inputs
@@ -85,17 +113,6 @@ struct StepFrame {
   float *draw(int s) const { return (float *)ts->draw[s].p; }
   const int32_t *ids(int s) const { return (const int32_t *)ts->ids[s].p; }
   float *sq() const { return (float *)ts->sq_part.p; }
-};
-
-// Which kernels one fused LSTM step runs and what follows from it; decided once per call (fused_plan), const afterwards.
-struct FusedPlan {
-  // which kernel families run on split bf16 operands (options train_fwd_x3 / train_bwd_x3 / train_dk_x3), per encoder
-  bool fwd_x3[2], bwd_x3[2], all_x3, any_bwd_x3;
-  bool bwd2;    // second-generation fp32 kernels
-  bool paired;  // paired batch: the source encoder runs on the first half of the rows
-  int NT32, NT_half;  // 32-row tiles of the batch; paired: of one half (B % 128 == 0: Bp = B, NT_half even)
-  int sq_off[3];      // where each encoder's partial sums of dx^2 start in sq_part
-  int n_sq;
 };
 
 // one encoder's backward of the fused path as its three bodies see it

@@ -6,6 +6,9 @@ norm of the raw embedding-gradient slices that `tf.clip_by_global_norm` sees, lo
 arena" of include/sse_hip.h), then clips by the global norm of the REDUCED gradients and applies Adagrad: the update is
 bit-identical on every rank and equals the single-process step on the concatenated batch up to fp32 summation order.
 
+With global_negatives=True the in-batch softmax loss sees the rows of ALL ranks as negatives: one more all-gather, of the ranks'
+encodings, ahead of the loss (DataParallelTrainer.__init__).
+
 The reference trains in one process (sse_train.py:170-172); this is the exchange step a multi-GPU job adds.
 The engine is anything with train_grad_count / train_bind_arena / train_grads / train_apply (and, for eval_loss,
 eval_loss_sums / eval_loss_rows_sums): the HIP handle
@@ -19,11 +22,21 @@ leaves the step before the all-reduce while its peers wait in it until the proce
 
 
 class DataParallelTrainer(object):
-    def __init__(self, engine, device=None, group=None, always_reduce=False, sparse_embedding=None, options=None):
+    def __init__(self, engine, device=None, group=None, always_reduce=False, sparse_embedding=None, options=None,
+                 global_negatives=False):
         """always_reduce: issue the collective even in a 1-rank group (exercises the RCCL path on one GPU).
         options: {name: value} set on this rank's engine (engine.set_option) before the first step, e.g.
         {"train_loss": 1, "train_loss_scale": 64} for the in-batch softmax loss: every rank passes the same dict, so every
-        rank's handle computes the same objective (its negatives are the rank's own rows; the mean runs over rows_global).
+        rank's handle computes the same objective.  By default its negatives are the rank's own rows (the mean runs over
+        rows_global), so the objective depends on the world size: 8 ranks of 128 rows see 127 negatives per row, not 1023.
+        global_negatives=True: the in-batch softmax loss over the GLOBAL batch instead, whatever "train_loss" says (the scale
+        is "train_loss_scale").  Every rank runs the forward alone (engine.train_forward), the ranks' encodings, labels and
+        id rows cross the wire in ONE all-gather of fixed-size blocks (engine.train_pack_exchange: 2S + 1 + 2T words per row
+        slot, T + 1 in the free-target-matrix modes), and every rank closes its step with the head over the gathered batch
+        cut to its own rows (engine.train_backward_inbatch_global: one rows pass over rows_global^2 logits on every rank,
+        two gradient passes over its rows x rows_global).  The step then equals the single-rank train_loss = 1 step of the
+        concatenated batch up to summation order, at any world size and for any split of the rows.  The gradient exchange
+        and the update follow as without it.
         {"train_class_loss": 1} selects the class softmax loss of the free-target-matrix modes instead.  That objective,
         unlike the in-batch one, is identical at any world size: a softmax over the whole class table decomposes over the
         rows of a batch, so the step equals the single-rank step of the concatenated batch up to summation order (the rows
@@ -34,6 +47,12 @@ class DataParallelTrainer(object):
         import torch
         self.engine, self.group, self.always_reduce = engine, group, bool(always_reduce)
         self.sparse_embedding = sparse_embedding
+        self.global_negatives = bool(global_negatives)
+        if self.global_negatives and not all(hasattr(engine, n) for n in ("train_forward", "train_exchange_floats", "train_pack_exchange",
+                                                                          "train_backward_inbatch_global")):
+            raise ValueError("global_negatives=True needs an engine with the open train step (train_forward, train_exchange_floats, "
+                             "train_pack_exchange, train_backward_inbatch_global)")
+        self._block = self._blocks = None      # this rank's exchange block and the gathered ones
         for name, value in (options or {}).items():
             engine.set_option(name, value)
         self.arena =torch.zeros(engine.train_grad_count(), dtype=torch.float32, device=device or "cpu")
@@ -58,15 +77,24 @@ class DataParallelTrainer(object):
     def _rows_sum_max(self, local_rows):
         """(sum, max) of the ranks' row counts: one tiny all-gather (both are needed: the loss is a mean over the sum,
         the packed embedding exchange is sized by the max)."""
+        rows = self._rank_rows(local_rows)
+        return sum(rows), max(rows)
+
+    def _rank_rows(self, local_rows):
+        """The ranks' row counts, in rank order: one tiny all-gather."""
         import torch
         from .collectives import all_gather_into
         if self.world == 1:
-            return int(local_rows), int(local_rows)
+            return [int(local_rows)]
         t = torch.tensor([int(local_rows)], dtype=torch.int64, device=self.arena.device)
         out = torch.empty(self.world, dtype=torch.int64, device=self.arena.device)
         all_gather_into(out, t, group=self.group)
-        out = out.cpu()
-        return int(out.sum()), int(out.max())
+        return [int(v) for v in out.cpu()]
+
+    @property
+    def rank(self):
+        import torch.distributed as dist
+        return dist.get_rank(self.group) if dist.is_available() and dist.is_initialized() else 0
 
     def train_step(self, src_ids, tgt_ids, labels, rows_global=None, by_rows=False):
         """One step on this rank's rows; returns the GLOBAL (loss, train_acc), evaluated before the update.
@@ -83,14 +111,24 @@ class DataParallelTrainer(object):
             if cur != self._stream:
                 self.engine.set_stream(cur)
                 self._stream = cur
+        rank_rows = None
         if rows_global is None:
-            rows_global, rows_cap = self._rows_sum_max(len(labels))
+            rank_rows = self._rank_rows(len(labels))
+            rows_global, rows_cap = sum(rank_rows), max(rank_rows)
         else:
             rows_cap = -(-int(rows_global) // self.world)
             if len(labels) > rows_cap:
                 raise ValueError("rank holds %d rows, more than ceil(rows_global / world) = %d: leave rows_global=None for "
                                  "unevenly split batches" % (len(labels), rows_cap))
-        if by_rows:
+        if self.global_negatives:
+            if rank_rows is None:                      # the even split of split_batch
+                from .sharded import shard_bounds
+                rank_rows = [e - s for s, e in shard_bounds(int(rows_global), self.world)]
+                if rank_rows[self.rank] != len(labels):
+                    raise ValueError("rank %d holds %d rows, split_batch gives it %d of %d: leave rows_global=None for other splits"
+                                     % (self.rank, len(labels), rank_rows[self.rank], rows_global))
+            self._global_inbatch_grads(src_ids, tgt_ids, labels, rows_global, rows_cap, rank_rows, by_rows)
+        elif by_rows:
             self.engine.train_grads_rows(src_ids, tgt_ids, labels, rows_global)
         else:
             self.engine.train_grads(src_ids, tgt_ids, labels, rows_global)
@@ -101,6 +139,26 @@ class DataParallelTrainer(object):
                 all_reduce_(self.arena, group=self.group)          # ONE collective per step (sum)
                 self.last_exchange = "dense"
         return self.engine.train_apply()
+
+    def _global_inbatch_grads(self, src_ids, tgt_ids, labels, rows_global, rows_cap, rank_rows, by_rows):
+        """forward -> pack -> ONE all-gather of the ranks' blocks -> the in-batch head over the global batch, cut to this rank's
+        rows, and the backward.  Leaves the arena as train_grads does."""
+        import torch
+        from .collectives import all_gather_into
+        if by_rows:
+            self.engine.train_forward_rows(src_ids, tgt_ids, labels, rows_global)
+        else:
+            self.engine.train_forward(src_ids, tgt_ids, labels, rows_global)
+        n = self.engine.train_exchange_floats(rows_cap, self._seq_len(src_ids, by_rows))
+        if self._block is None or self._block.numel() != n or self._blocks.numel() != n * self.world:
+            self._block = torch.zeros(n, dtype=torch.float32, device=self.arena.device)
+            self._blocks = torch.zeros(n * self.world, dtype=torch.float32, device=self.arena.device)
+        self.engine.train_pack_exchange(rows_cap, self._block)
+        if self.world == 1 and not self.always_reduce:
+            self._blocks.copy_(self._block)
+        else:
+            all_gather_into(self._blocks, self._block, group=self.group)
+        self.engine.train_backward_inbatch_global(self._blocks, self.world, rows_cap, self.rank, rank_rows)
 
     def eval_loss(self, src_ids, tgt_ids, labels, by_rows=False):
         """Forward-only GLOBAL (loss, train_acc) of held-out pairs split over the ranks (any row counts, a rank may hold none):

@@ -1,0 +1,173 @@
+"""The in-batch softmax step over the GLOBAL batch as two REAL ranks: two processes on the one GPU of a test box, a `gloo` group
+between them (host-staged collectives), DataParallelTrainer(global_negatives=True) on 5 + 9 pair rows of a dual-encoder model,
+one source and one target shared across the ranks.  Every rank runs its forward, ONE all-gather moves the ranks' encodings,
+labels and id rows, and every rank closes its step with the head over the 14 gathered rows cut to its own window
+(sse_train_backward_inbatch_global).  The variables after the step must be identical on both ranks, bit for bit, and equal those
+of ONE handle stepping the concatenated 14 rows under train_loss = 1 up to summation order: util.GRAD_BARS_EXACT on the variables
+and on the update itself, the loss within util.LOSS_REL_EXACT.  The same job with global_negatives=False (the rank's own rows
+as negatives) must NOT meet that comparison, so the test cannot pass vacuously.  A 20-step run of both ranks against the one
+handle free-running from the same weights is recorded, not held: two free runs drift apart by summation order.
+
+One launch of tests/inbatch_global_two_rank_worker.py per rank, each under its own time limit; a child that fails ends the
+launch and the other child is killed; a child that died of a signal ends the pytest session -- nothing more starts on the GPU
+after a fault."""
+import json
+import os
+import socket
+import subprocess
+import sys
+import time
+
+import numpy as np
+import pytest
+
+from tests import inbatch_cases as IC
+from tests.util import GRAD_BARS_EXACT, LOSS_REL_EXACT, check_grads
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+WORKER = os.path.join(HERE, "inbatch_global_two_rank_worker.py")
+CHILD_CAP_S = 100                       # each child's own limit (timeout -k): safety, not a measurement
+LAUNCH_CAP_S = 120
+FAULT_CODES = (134, 139, 124, 137)
+ROWS = (5, 9)
+STEPS = 20
+SCALE = 64
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _tail(path, n=25):
+    try:
+        with open(path, errors="replace") as f:
+            return "".join(f.readlines()[-n:])
+    except OSError:
+        return "(no output)"
+
+
+def _launch(tmp, world, job):
+    job_path = os.path.join(tmp, "job.json")
+    with open(job_path, "w") as f:
+        json.dump(job, f)
+    procs, logs = [], []
+    for r in range(world):
+        logs.append((os.path.join(tmp, "rank%d.out" % r), os.path.join(tmp, "rank%d.err" % r)))
+        with open(logs[r][0], "w") as fo, open(logs[r][1], "w") as fe:
+            procs.append(subprocess.Popen(["timeout", "-k", "10", str(CHILD_CAP_S), sys.executable, WORKER, job_path, str(r)],
+                                          stdout=fo, stderr=fe, stdin=subprocess.DEVNULL, cwd=os.path.dirname(HERE)))
+    deadline = time.monotonic() + LAUNCH_CAP_S
+    ended, why = {}, None
+    while len(ended) < world and why is None:
+        for r, p in enumerate(procs):
+            if r not in ended and p.poll() is not None:
+                ended[r] = p.returncode
+                if p.returncode != 0:
+                    why = "rank %d ended with code %d" % (r, p.returncode)        # the first non-zero exit stops the launch
+        if why is None and len(ended) < world:
+            if time.monotonic() > deadline:
+                why = "no result after %d s" % LAUNCH_CAP_S
+            else:
+                time.sleep(0.1)
+    for p in procs:                                              # nothing is left running, whatever happened
+        if p.poll() is None:
+            p.kill()
+    for p in procs:
+        p.wait()
+    if why is not None:
+        text = "launch of %d ranks: %s\n" % (world, why) + "".join(
+            "---- rank %d (%s) stderr:\n%s---- stdout:\n%s" % (r, ended.get(r, "killed"), _tail(logs[r][1]), _tail(logs[r][0], 5))
+            for r in range(world))
+        if any(rc < 0 or rc in FAULT_CODES for rc in ended.values()):
+            pytest.exit("a rank died of a signal or at its time limit; nothing more is started on the GPU\n" + text, returncode=3)
+        pytest.fail(text, pytrace=False)
+    return [np.load(os.path.join(tmp, "rank%d.npz" % r)) for r in range(world)]
+
+
+def _batch(c):
+    """Rank slices of 5 and 9 rows with a verified source of rank 0 repeated, verified, on rank 1 and a target of rank 0 repeated on
+    rank 1, at the first seed whose concatenation meets the accuracy precondition of tests/inbatch_cases.py."""
+    params, p = IC.step_params(c)
+    for seed in range(32):
+        parts = [[a.copy() for a in IC.step_batch(dict(c, B=B), seed=seed + 10 * r)] for r, B in enumerate(ROWS)]
+        parts[1][0][8] = parts[0][0][1]
+        parts[0][2][1] = parts[1][2][8] = 1.0
+        parts[1][1][0] = parts[0][1][0]
+        parts[1][2][0] = 1.0
+        src, tgt, z = (np.concatenate([part[k] for part in parts]) for k in range(3))
+        r = IC.step_reference(p, params, src, tgt, z, len(z), SCALE)[2]
+        L, adm = r["logits"], r["adm"]
+        others = np.where(adm & ~np.eye(len(z), dtype=bool), L, -np.inf).max(axis=1)
+        if np.abs(np.diag(L) - others)[z != 0].min() > IC.accuracy_gap_bound(SCALE, c["S"]):
+            return params, p, parts, (src, tgt, z)
+    raise AssertionError("no seed meets the accuracy precondition")
+
+
+def test_two_uneven_ranks_with_global_negatives_equal_one_handle_on_the_concatenated_batch(tmp_path):
+    """Recorded on an MI355X (the GLOBAL TWO RANKS line this test prints): variables norm 3.7e-07 element 4.8e-07, update norm
+    2.0e-06 element 2.9e-06 (bars 1e-5 / 2e-5); the update under local negatives is off by 6.2e-01; after 20 steps the loss
+    fell 2.61614 -> 1.71697 on both sides and the variables of the two ranks lie within 6.1e-06 of the one handle's."""
+    import sse_amd
+    tmp = str(tmp_path)
+    c = IC.STEP_CASES_BY_ID["dual-unpaired-b40"]
+    params, p, parts, (src, tgt, z) = _batch(c)
+    ks, kt = IC._row_keys(src), IC._row_keys(tgt)
+    assert (ks[ROWS[0]:] < ROWS[0]).any() and (kt[ROWS[0]:] < ROWS[0]).any()       # a source and a target shared across the ranks
+    inputs = {"p/" + k: v for k, v in p.items()}
+    for r, part in enumerate(parts):
+        inputs.update({"rank%d/src" % r: part[0], "rank%d/tgt" % r: part[1], "rank%d/z" % r: part[2]})
+    np.savez(os.path.join(tmp, "inputs.npz"), **inputs)
+    job = dict(world=2, port=_free_port(), inputs=os.path.join(tmp, "inputs.npz"), out_dir=tmp, params=params, steps=STEPS,
+               options={"train_loss": 1, "train_loss_scale": SCALE})
+    out = _launch(tmp, 2, job)
+    # one handle, the 14 rows at once
+    m = sse_amd.SSEModel(params)
+    m.set_variables(p)
+    m.handle.set_option("train_loss", 1)
+    m.handle.set_option("train_loss_scale", SCALE)
+    before = m.get_variables(with_slots=True)
+    loss, acc = m.train_step(src, tgt, z)
+    after = m.get_variables(with_slots=True)
+    names = sorted(after)
+    want = {n: after[n].astype(np.float64) for n in names}
+    moved_want = {n: want[n] - before[n] for n in names}
+    assert all(np.abs(moved_want[n]).max() > 0 for n in names)
+    for r in range(2):
+        assert int(out[r]["global/counter/train_open_steps"]) == 1 and int(out[r]["global/counter/train_global_inbatch_steps"]) == 1
+        assert int(out[r]["global/counter/train_inbatch_steps"]) == 0 and int(out[r]["global/counter/train_path_fused"]) == 1
+        assert int(out[r]["local/counter/train_open_steps"]) == 0 and int(out[r]["local/counter/train_inbatch_steps"]) == 1
+        for run in ("global", "local", "long"):
+            for n in names:                                      # the update is the same on every rank, bit for bit
+                assert out[r]["%s/v/%s" % (run, n)].tobytes() == out[0]["%s/v/%s" % (run, n)].tobytes(), (run, n)
+        h = out[r]["global/hist"][0]
+        assert abs(h[0] - loss) <= LOSS_REL_EXACT * abs(loss) + 1e-7 and abs(h[1] - acc) <= 1e-6, (h, loss, acc)
+    got = {n: out[0]["global/v/" + n] for n in names}
+    errs = check_grads(got, want, GRAD_BARS_EXACT, what="variables after the step: ")
+    moved = {n: got[n].astype(np.float64) - before[n] for n in names}
+    derrs = check_grads(moved, moved_want, GRAD_BARS_EXACT, what="the update itself: ")
+    # the rank's own rows as negatives: another objective, and the comparison shows it
+    local = {n: out[0]["local/v/" + n].astype(np.float64) - before[n] for n in names}
+    with pytest.raises(AssertionError):
+        check_grads(local, moved_want, GRAD_BARS_EXACT, what="local negatives: ")
+    lerr = max(np.linalg.norm(local[n] - moved_want[n]) / np.linalg.norm(moved_want[n]) for n in names)
+    assert lerr > GRAD_BARS_EXACT[0] and abs(out[0]["local/hist"][0][0] - loss) > LOSS_REL_EXACT * abs(loss) + 1e-7
+    # 20 steps of both ranks against the one handle free-running from the same weights: recorded
+    m2 = sse_amd.SSEModel(params)
+    m2.set_variables(p)
+    m2.handle.set_option("train_loss", 1)
+    m2.handle.set_option("train_loss_scale", SCALE)
+    free = [m2.train_step(src, tgt, z) for _ in range(STEPS)]
+    final = m2.get_variables()
+    gap = max(float(np.abs(out[0]["long/v/" + n].astype(np.float64) - final[n]).max()) for n in final)
+    assert int(out[0]["long/counter/train_global_inbatch_steps"]) == STEPS
+    print("GLOBAL TWO RANKS: variables norm %.2e element %.2e; update norm %.2e element %.2e; local-negatives update off by %.2e; "
+          "%d steps: loss %.5f -> %.5f (one handle %.5f -> %.5f), max |two ranks - one handle| over the variables %.2e"
+          % (max(e[0] for e in errs.values()), max(e[1] for e in errs.values()), max(e[0] for e in derrs.values()),
+             max(e[1] for e in derrs.values()), lerr, STEPS, out[0]["long/hist"][0][0], out[0]["long/hist"][-1][0], free[0][0],
+             free[-1][0], gap))
