@@ -1237,26 +1237,61 @@ __global__ __launch_bounds__(256) void score_small_index_x3_kernel(SmallIndexArg
     const int row = qt * 32 + (lane & 31), kb0 = (lane >> 5) * 8;
     const float *src = a.q_rows + (size_t)(row < a.Q ? row : 0) * a.S + kb0;
     const bool vec = (a.S & 3) == 0 && (reinterpret_cast<uintptr_t>(a.q_rows) & 15) == 0 && KB * 16 <= a.S;  // (uniform)
+    // The four waves want the same 32 rows, each lane 32 bytes of a row per k-block, lanes 1 KiB apart: 2 KB loads per wave
+    // of 64 pieces each.  With whole rows (S = 16 KB) the tile is staged ONCE instead: wave w loads rows 8w .. 8w+7 with its
+    // lanes along a row and writes them into the score tile's LDS, which nobody needs before the first tile's stores (row
+    // stride + 16 bytes: the rows of a fragment read start in different banks); every wave then takes its fragments from
+    // there.  The values are the ones the direct loads return (rows >= Q: zeros), so the split and the scores are the same bits.
+    constexpr int QS = KB * 16 + 4;                          // staged row stride, floats
+    const bool stage = vec && a.S == KB * 16 && QS <= NP;  // (uniform; the tile [32][NP] holds [32][QS])
+    if (stage) {
+      constexpr int LPR = KB * 4, RPI = 64 / LPR;  // lanes per row, rows per load instruction
+      f32x4 t[8 / RPI];
 #pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-      float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (vec) {
-        const f32x4 v0 = *reinterpret_cast<const f32x4 *>(src + kb * 16), v1 = *reinterpret_cast<const f32x4 *>(src + kb * 16 + 4);
+      for (int it = 0; it < 8 / RPI; ++it) {
+        const int grow = qt * 32 + w * 8 + it * RPI + lane / LPR;
+        t[it] = *reinterpret_cast<const f32x4 *>(a.q_rows + (size_t)(grow < a.Q ? grow : 0) * a.S + (lane % LPR) * 4);
+        if (grow >= a.Q) t[it] = f32x4{0, 0, 0, 0};
+      }
+#pragma unroll
+      for (int it = 0; it < 8 / RPI; ++it)
+        *reinterpret_cast<f32x4 *>(sc + (w * 8 + it * RPI + lane / LPR) * QS + (lane % LPR) * 4) = t[it];
+      __syncthreads();
+      const float *mine = sc + (lane & 31) * QS + kb0;
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb) {
+        const f32x4 v0 = *reinterpret_cast<const f32x4 *>(mine + kb * 16), v1 = *reinterpret_cast<const f32x4 *>(mine + kb * 16 + 4);
+        float v[8];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           v[e] = v0[e];
           v[4 + e] = v1[e];
         }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (kb * 16 + kb0 + e < a.S) v[e] = src[kb * 16 + e];
+        sse_split8(v, bh[kb], bl[kb]);
       }
-      if (row >= a.Q) {
+      __syncthreads();  // every wave has its fragments: the tile is free for the scores
+    } else {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = 0.0f;
+      for (int kb = 0; kb < KB; ++kb) {
+        float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (vec) {
+          const f32x4 v0 = *reinterpret_cast<const f32x4 *>(src + kb * 16), v1 = *reinterpret_cast<const f32x4 *>(src + kb * 16 + 4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            v[e] = v0[e];
+            v[4 + e] = v1[e];
+          }
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            if (kb * 16 + kb0 + e < a.S) v[e] = src[kb * 16 + e];
+        }
+        if (row >= a.Q) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[e] = 0.0f;
+        }
+        sse_split8(v, bh[kb], bl[kb]);
       }
-      sse_split8(v, bh[kb], bl[kb]);
     }
   }
   SC_CLK(0)
@@ -1783,8 +1818,275 @@ __global__ __launch_bounds__(256) void rescore_small_kernel(RescoreArgs a) {
   }
 }
 
+// The same pass once more for the device-resident many-queries call of one split (NC = 16, no host mirror, no compacted
+// slots): FOUR queries per wave, one per 16-lane DPP row -- lane c of row g owns candidate c of query 4 * wave + g.  The
+// one-query wave above idles 48 lanes through its rank loops and runs every cross-lane step once per query; here the rank
+// loops are 15 row rotations for four queries at once, and nothing leaves the row: no v_readlane, no LDS but the one
+// ds_permute that compacts the window.  A row past Q runs on the last query's inputs and stores nothing: it has to stay in
+// every cross-lane operation (a DPP read of a lane that has left is undefined), so nothing returns early.
+//
+// Float64 scores, bit for bit wave_exact_dot's: a row's lane l plays the virtual lanes l, l + 16, l + 32, l + 48 of the
+// 64-lane form with one accumulator each (the same loads, the same expression in the same order, the same d < S guards; a
+// virtual lane without dimensions stays an explicit +0.0), combines them as (acc0 + acc2) + (acc1 + acc3) -- the 64-lane
+// butterfly's xor-32 step, then its xor-16 step -- and finishes with xor 8, 4, 2, 1 inside the row.  IEEE addition
+// commutes, so every partial sum is the one the 64-lane butterfly forms.  |q| likewise.
+template <int CTRL>
+__device__ __forceinline__ int row_dpp(int v) {  // (all source lanes exist in a row permutation: bound_ctrl is moot)
+  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false);
+}
+template <int CTRL>
+__device__ __forceinline__ double row_dpp_f64(double v) {
+  const long long b = __double_as_longlong(v);
+  const int lo = row_dpp<CTRL>((int)b), hi = row_dpp<CTRL>((int)(b >> 32));
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+#define RS4_ROR1 0x121         // row_ror:1 (a lane reads its neighbour; 15 of them visit the whole row)
+#define RS4_XOR1 0xB1          // quad_perm:[1,0,3,2]
+#define RS4_XOR2 0x4E          // quad_perm:[2,3,0,1]
+#define RS4_QUAD_MIRROR 0x1B   // quad_perm:[3,2,1,0] (lane ^ 3)
+#define RS4_HALF_MIRROR 0x141  // row_half_mirror (lane ^ 7): with the quad mirror, lane ^ 4
+#define RS4_XOR8 0x128         // row_ror:8
+#define RS4_BCAST 0x150        // row_newbcast:0 (+ n: lane n of the row to all of it)
+// value + the value of row lane (l ^ 8), then ^ 4, ^ 2, ^ 1: the total in every lane of the row
+__device__ __forceinline__ double row_butterfly_sum(double v) {
+  v += row_dpp_f64<RS4_XOR8>(v);
+  v += row_dpp_f64<RS4_QUAD_MIRROR>(row_dpp_f64<RS4_HALF_MIRROR>(v));
+  v += row_dpp_f64<RS4_XOR2>(v);
+  v += row_dpp_f64<RS4_XOR1>(v);
+  return v;
+}
+__device__ __forceinline__ int row_or(int v) {  // OR over the row (any rotation direction)
+  v |= row_dpp<0x128>(v);
+  v |= row_dpp<0x124>(v);
+  v |= row_dpp<0x122>(v);
+  v |= row_dpp<0x121>(v);
+  return v;
+}
+// float64 scores of the row's window members M0 .. M0 + 3 (idm: member ids in row lanes 0 .. nwin - 1, else -1) into exm of
+// the members' lanes.  Padding re-scores member 0 (row 0 for an empty window): loads stay in bounds, results are dropped.
+template <int M0>
+__device__ __forceinline__ void rescore4_batch(const RescoreArgs &a, const float (&qf)[16], const float *qrow, int KG, int l, int idm,
+                                               double &exm) {
+  const int n0 = max(row_dpp<RS4_BCAST>(idm), 0);
+  int64_t n[RS_NB];
+  {
+    const int m0 = row_dpp<RS4_BCAST + M0>(idm), m1 = row_dpp<RS4_BCAST + M0 + 1>(idm);
+    const int m2 = row_dpp<RS4_BCAST + M0 + 2>(idm), m3 = row_dpp<RS4_BCAST + M0 + 3>(idm);
+    n[0] = m0 >= 0 ? m0 : n0;
+    n[1] = m1 >= 0 ? m1 : n0;
+    n[2] = m2 >= 0 ? m2 : n0;
+    n[3] = m3 >= 0 ? m3 : n0;
+  }
+  double acc[RS_NB][4];
+#pragma unroll
+  for (int b = 0; b < RS_NB; ++b)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[b][i] = 0.0;
+  if (a.idx64) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      for (int d = l + 16 * i; d < a.S; d += 64) {  // virtual lane l + 16 i
+        double rv[RS_NB];
+#pragma unroll
+        for (int b = 0; b < RS_NB; ++b) rv[b] = a.idx64[(size_t)n[b] * a.S + d];
+#pragma unroll
+        for (int b = 0; b < RS_NB; ++b) acc[b][i] += (double)qrow[d] * rv[b];
+      }
+  } else {
+    // (S <= 256: one pass of the 64-lane loop, j = virtual lane.)  Every load is issued in front of the first use; a virtual
+    // lane past the row's k-groups reads the last group again and its guard below drops the products
+    // (the address of dimensions 4j .. 4j+3 of row n, row-major copy or fragment order, without a branch per load)
+    f32x4 v[4][RS_NB];
+    const bool rm = a.idx_rm != nullptr;
+    const float *base = rm ? a.idx_rm : a.idx32;
+    const int jlast = rm ? (a.S >> 2) - 1 : KG * 2 - 1;
+    size_t on[RS_NB];
+#pragma unroll
+    for (int b = 0; b < RS_NB; ++b) on[b] = rm ? (size_t)n[b] * a.S : (size_t)(n[b] >> 5) * KG * 256 + (size_t)(n[b] & 31) * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (a.S > 64 * i) {  // (uniform: the four virtual lanes of a lane hold dimensions from 64 i on)
+        const int j = min(l + 16 * i, jlast);
+        const int oj = rm ? j * 4 : (j >> 1) * 256 + (j & 1) * 128;
+#pragma unroll
+        for (int b = 0; b < RS_NB; ++b) v[i][b] = *reinterpret_cast<const f32x4 *>(base + on[b] + oj);
+      }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int d0 = (l + 16 * i) * 4;
+      if (a.S >= 64 * (i + 1)) {  // (uniform) every lane's four dimensions exist: the guard holds everywhere
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int b = 0; b < RS_NB; ++b) acc[b][i] += (double)qf[i * 4 + e] * (double)v[i][b][e];
+      } else if (a.S > 64 * i) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (d0 + e < a.S) {
+#pragma unroll
+            for (int b = 0; b < RS_NB; ++b) acc[b][i] += (double)qf[i * 4 + e] * (double)v[i][b][e];
+          }
+      }
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < RS_NB; ++b) {
+    const double tot = row_butterfly_sum((acc[b][0] + acc[b][2]) + (acc[b][1] + acc[b][3]));
+    if (l == M0 + b && idm >= 0) exm = tot;
+  }
+}
+__global__ __launch_bounds__(256) void rescore_small4_kernel(RescoreArgs a) {
+  static_assert(RS_NB == 4, "rescore4_batch names its four members");
+  const int lane = threadIdx.x & 63, l = lane & 15, g = lane >> 4;
+  const int q = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + g;
+  if (a.uncert_clear && blockIdx.x == 0 && threadIdx.x == 0) *a.uncert_clear = 0;  // the next call's word (see RescoreArgs::uncert)
+  const bool valid = q < a.Q;
+  const int qc = valid ? q : a.Q - 1;
+  const float *qrow = a.q + (size_t)qc * a.S;
+  const int KG = (a.S + 7) / 8;
+#ifdef SSE_SCORE_CLOCK
+  long long rk_[6] = {0, 0, 0, 0, 0, 0}, rk_t = clock64();
+#endif
+  const int id = a.part_ids[(size_t)qc * 16 + l];
+  const float sc = a.part_scores[(size_t)qc * 16 + l];
+  const float mmax = fmaxf(NEG_INF, a.part_bnd[qc]);  // one split: its bound (rows outside the candidates score <= M)
+  // the query's dimensions 4 (l + 16 i) + e, i, e = 0 .. 3, for every float64 dot of the row
+  float qf[16];
+  if ((a.S & 3) == 0 && (reinterpret_cast<uintptr_t>(a.q) & 15) == 0) {  // (uniform)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const f32x4 t = *reinterpret_cast<const f32x4 *>(qrow + min(l + 16 * i, (a.S >> 2) - 1) * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) qf[i * 4 + e] = t[e];
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) qf[i] = qrow[min((l + 16 * (i >> 2)) * 4 + (i & 3), a.S - 1)];
+  }
+  // |q| as the 64-lane form sums it: virtual lane v takes d = v, v + 64, v + 128, v + 192 (S <= 256).  All 16 loads are
+  // issued at once; a dimension past S enters as x = +0.0, which leaves the sum's bits alone: a sum of squares that starts
+  // at +0.0 is never -0.0, and s + (+0.0) = s for every other s
+  double qn;
+  {
+    float x[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) x[i][t] = qrow[min(l + 16 * i + 64 * t, a.S - 1)];
+    double qa[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      qa[i] = 0.0;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const float xv = (l + 16 * i + 64 * t < a.S) ? x[i][t] : 0.0f;
+        qa[i] += (double)xv * xv;
+      }
+    }
+    qn = row_butterfly_sum((qa[0] + qa[2]) + (qa[1] + qa[3]));
+  }
+  const float qnorm = (float)sqrt(qn);
+  const float eps_q = a.eps * qnorm;
+  RS_CLK(0)
+
+  unsigned u = __float_as_uint(sc);
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  const unsigned long long key = (id < 0) ? 0ull : (((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)id));
+  int rank = 0;
+  {
+    int lo = (int)(unsigned)key, hi = (int)(unsigned)(key >> 32);
+#pragma unroll
+    for (int j = 1; j < 16; ++j) {
+      lo = row_dpp<RS4_ROR1>(lo);
+      hi = row_dpp<RS4_ROR1>(hi);
+      const unsigned long long kj = ((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo;
+      rank += (kj > key) ? 1 : 0;
+    }
+  }
+  // fp32 score of the k-th best candidate (keys are unique: one lane of the row at most holds rank k - 1)
+  const bool is_kth = key != 0ull && rank == a.k - 1;
+  const bool any_kth = ((__ballot(is_kth) >> (16 * g)) & 0xFFFFull) != 0ull;
+  const int kth_bits = row_or(is_kth ? __float_as_int(sc) : 0);
+  const float kth = any_kth ? __int_as_float(kth_bits) : NEG_INF;
+  // window: candidates within 2*eps of the k-th; its members to row lanes 0 .. nwin-1, in candidate order
+  const bool in_win = (id >= 0) && (sc >= kth - 2.0f * eps_q);
+  const unsigned wrow = (unsigned)((__ballot(in_win) >> (16 * g)) & 0xFFFFull);
+  const int nwin = __popc(wrow);
+  const int mi = __popc(wrow & ((1u << l) - 1u));
+  int idm = __builtin_amdgcn_ds_permute((g * 16 + (in_win ? mi : 15)) * 4, id);  // (row lane 15 is a member's only with all 16 in the window)
+  idm = (l < nwin) ? idm : -1;
+  RS_CLK(1)
+  // exact float64 scores, RS_NB members at a time; a batch is skipped when no row of the wave has a member in it
+  double exm = -__builtin_inf();
+  rescore4_batch<0>(a, qf, qrow, KG, l, idm, exm);
+  if (__ballot(nwin > 4) != 0ull) rescore4_batch<4>(a, qf, qrow, KG, l, idm, exm);
+  if (__ballot(nwin > 8) != 0ull) rescore4_batch<8>(a, qf, qrow, KG, l, idm, exm);
+  if (__ballot(nwin > 12) != 0ull) rescore4_batch<12>(a, qf, qrow, KG, l, idm, exm);
+  RS_CLK(2)
+  // exact rank inside the window (score descending, then lower row id)
+  const bool member = idm >= 0;
+  int r2 = 0;
+  {
+    const long long b = __double_as_longlong(exm);
+    int lo = (int)b, hi = (int)(b >> 32), ij = idm;
+#pragma unroll
+    for (int j = 1; j < 16; ++j) {
+      lo = row_dpp<RS4_ROR1>(lo);
+      hi = row_dpp<RS4_ROR1>(hi);
+      ij = row_dpp<RS4_ROR1>(ij);
+      const double ej = __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+      r2 += (ij >= 0 && before(ej, (int64_t)ij, exm, (int64_t)idm)) ? 1 : 0;
+    }
+  }
+  if (valid && member && r2 < a.k) {
+    a.out_scores[(size_t)q * a.k + r2] = exm;
+    a.out_ids[(size_t)q * a.k + r2] = a.id_base + idm;
+  }
+  const bool is_theta = member && r2 == a.k - 1;
+  const bool any_theta = ((__ballot(is_theta) >> (16 * g)) & 0xFFFFull) != 0ull;
+  const long long eb = __double_as_longlong(exm);
+  const int th_lo = row_or(is_theta ? (int)eb : 0), th_hi = row_or(is_theta ? (int)(eb >> 32) : 0);
+  const double theta = any_theta ? __longlong_as_double(((long long)th_hi << 32) | (unsigned int)th_lo) : -__builtin_inf();
+  RS_CLK(3)
+#ifdef SSE_SCORE_CLOCK
+  if (q == a.Q / 2 && l == 0) {
+    rk_[4] = nwin;
+    for (int i = 0; i < 6; ++i) g_score_clk[i] = rk_[i];
+  }
+#endif
+  if (valid && l == 0) {
+    const bool ok = (nwin >= a.k) && ((double)mmax + (double)eps_q < theta);
+    a.cert[q] = ok ? 1 : 0;
+    if (!ok && a.uncert) atomicAdd(a.uncert, 1);
+    if (a.col_thr) a.col_thr[q] = ok ? __builtin_inff() : __double2float_rd(theta - (double)(a.eps32 * qnorm));
+    if (a.col_slot) {
+      a.col_slot[q] = ok ? -1 : q;
+      a.col_cnt[q] = 0;
+    }
+  }
+}
+
 hipError_t launch_rescore(const RescoreArgs &a, hipStream_t stream) {
   if (a.NC > RS_MAXNC) return hipErrorInvalidValue;
+  if (a.NC == 16 && a.S <= 256 && a.host_flag == nullptr && a.qmap == nullptr && a.q_count == nullptr) {
+    const char *ev = getenv("SSE_RESCORE_SMALL4");  // measurement and test aid: 0 = rescore_small_kernel
+    if (!(ev && atoi(ev) == 0)) {
+      hipLaunchKernelGGL(rescore_small4_kernel, dim3((a.Q + 15) / 16), dim3(256), 0, stream, a);
+#ifdef SSE_SCORE_CLOCK
+      if (a.Q >= 8192) {
+        static int n = 0;
+        if (n++ % 8 == 3) {
+          long long v[8];
+          (void)hipStreamSynchronize(stream);
+          (void)hipMemcpyFromSymbol(v, HIP_SYMBOL(g_score_clk), sizeof v);
+          fprintf(stderr, "[rescore_small4 clock Q=%d NC=%d] cycles: query norm %lld | candidates, rank, k-th, window %lld | float64 dots %lld (window of %lld) | exact rank + outputs %lld\n",
+                  a.Q, a.NC, v[0], v[1], v[2], v[4], v[3]);
+        }
+      }
+#endif
+      return hipGetLastError();
+    }
+  }
   if (a.NC <= 64) {
     hipLaunchKernelGGL(rescore_small_kernel, dim3((a.Q + 3) / 4), dim3(256), 0, stream, a);
 #ifdef SSE_SCORE_CLOCK
