@@ -171,6 +171,48 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+# The argument checks and output buffers the host forms of the scoring family share (score_topk_filtered, _grouped, _after,
+# _biased, score_lse, score_confusions, score_rank, score_above): one copy of each message.
+
+def _opt(a):
+    return _ptr(a) if a is not None else None
+
+
+def _queries(queries):
+    q = np.ascontiguousarray(queries, dtype=np.float32)
+    if q.ndim != 2:
+        raise ValueError("queries must be [Q,S]")
+    return q
+
+
+def _masks(any_of, none_of, Q):
+    """[any_of, none_of] as uint64 [Q] arrays (None stays None), any_of checked first."""
+    masks = []
+    for m in (any_of, none_of):
+        if m is not None:
+            m = np.ascontiguousarray(m, dtype=np.uint64).reshape(-1)
+            if m.shape[0] != Q:
+                raise ValueError("any_of / none_of must be uint64 [Q]")
+        masks.append(m)
+    return masks
+
+
+def _weights(weight, Q):
+    """None, a scalar or float32 [Q] -> None or float32 [Q]."""
+    if weight is None:
+        return None
+    w = np.asarray(weight, dtype=np.float32)
+    w = np.full(Q, w, np.float32) if w.ndim == 0 else np.ascontiguousarray(w.reshape(-1))
+    if w.shape[0] != Q:
+        raise ValueError("weight must be a scalar or float32 [Q]")
+    return w
+
+
+def _topk_out(Q, k):
+    """(scores float64 [Q,k], ids int64 [Q,k], counts int32 [Q]); a negative k is left to the library to refuse."""
+    return np.empty((Q, max(k, 0)), np.float64), np.empty((Q, max(k, 0)), np.int64), np.empty(Q, np.int32)
+
+
 class SSEError(RuntimeError):
     pass
 
@@ -357,9 +399,7 @@ class Handle(object):
         their 0-based rank and their float64 score.  pair_score given: rows before the threshold (pair_score[p],
         pair_id[p]), any id -- what a shard counts for a label of another shard.  Returns (before int64 [L], score
         float64 [L]); the output arrays are handed back untouched (zeros) only on success -- an error raises."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2:
-            raise ValueError("queries must be [Q,S]")
+        q = _queries(queries)
         pq = np.ascontiguousarray(pair_q, dtype=np.int32).reshape(-1)
         pid = np.ascontiguousarray(pair_id, dtype=np.int64).reshape(-1)
         if pq.shape != pid.shape:
@@ -373,7 +413,7 @@ class Handle(object):
         before = np.zeros(L, np.int64)
         score = np.zeros(L, np.float64) if ps is None else ps.copy()
         self.check(self.lib.sse_score_rank(self._h, _ptr(q), q.shape[0], _ptr(pq), _ptr(pid), L,
-                                           _ptr(ps) if ps is not None else None, _ptr(before), _ptr(score)))
+                                           _opt(ps), _ptr(before), _ptr(score)))
         return before, score
 
     def score_rank_dev(self, q_ptr, Q, pair_q_ptr, pair_id_ptr, L, pair_score_ptr, before_ptr, score_ptr, stream=0):
@@ -383,9 +423,7 @@ class Handle(object):
                                                before_ptr, score_ptr or None, stream))
 
     def _above_args(self, queries, thr, pair_q):
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2:
-            raise ValueError("queries must be [Q,S]")
+        q = _queries(queries)
         t = np.ascontiguousarray(thr, dtype=np.float64).reshape(-1)
         pq = np.arange(q.shape[0], dtype=np.int32) if pair_q is None else np.ascontiguousarray(pair_q, dtype=np.int32).reshape(-1)
         if pq.shape != t.shape:
@@ -431,11 +469,15 @@ class Handle(object):
 
     def index_set_tags(self, tags):
         """One uint64 tag word per row of the resident index (tags=None clears them); a new index clears them too."""
-        if tags is None:
-            self.check(self.lib.sse_index_set_tags(self._h, None, 0))
+        self._index_set_column(self.lib.sse_index_set_tags, tags, np.uint64)
+
+    def _index_set_column(self, fn, values, dtype):
+        """index_set_tags / _groups / _bias: one value of `dtype` per row of the resident index; None clears the column."""
+        if values is None:
+            self.check(fn(self._h, None, 0))
             return
-        t = np.ascontiguousarray(tags, dtype=np.uint64).reshape(-1)
-        self.check(self.lib.sse_index_set_tags(self._h, _ptr(t), t.shape[0]))
+        v = np.ascontiguousarray(values, dtype=dtype).reshape(-1)
+        self.check(fn(self._h, _ptr(v), v.shape[0]))
 
     def index_set_tags_dev(self, tags_ptr, N, stream=0):
         """index_set_tags from a device pointer of N uint64 words (None / 0 clears), copied on `stream`."""
@@ -447,17 +489,9 @@ class Handle(object):
         must not return (n <= 64; ids outside the index, e.g. -1 padding, are ignored).  Returns (scores float64 [Q,k],
         ids int64 [Q,k], counts int32 [Q]): the first counts[q] columns are score_topk's columns with the ineligible rows
         removed, the rest hold (-inf, INT64_MAX)."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2:
-            raise ValueError("queries must be [Q,S]")
+        q = _queries(queries)
         Q, k = q.shape[0], int(k)
-        masks = []
-        for m in (any_of, none_of):
-            if m is not None:
-                m = np.ascontiguousarray(m, dtype=np.uint64).reshape(-1)
-                if m.shape[0] != Q:
-                    raise ValueError("any_of / none_of must be uint64 [Q]")
-            masks.append(m)
+        masks = _masks(any_of, none_of, Q)
         ex, n_excl = None, 0
         if exclude is not None:
             ex = np.ascontiguousarray(exclude, dtype=np.int64)
@@ -466,12 +500,9 @@ class Handle(object):
             n_excl = ex.shape[1]
             if n_excl == 0:
                 ex = None
-        scores = np.empty((Q, max(k, 0)), np.float64)
-        ids = np.empty((Q, max(k, 0)), np.int64)
-        counts = np.empty(Q, np.int32)
-        self.check(self.lib.sse_score_topk_filtered(self._h, _ptr(q), Q, k, _ptr(masks[0]) if masks[0] is not None else None,
-                                                    _ptr(masks[1]) if masks[1] is not None else None,
-                                                    _ptr(ex) if ex is not None else None, n_excl, _ptr(scores), _ptr(ids), _ptr(counts)))
+        scores, ids, counts = _topk_out(Q, k)
+        self.check(self.lib.sse_score_topk_filtered(self._h, _ptr(q), Q, k, _opt(masks[0]), _opt(masks[1]), _opt(ex), n_excl,
+                                                    _ptr(scores), _ptr(ids), _ptr(counts)))
         return scores, ids, counts
 
     def score_topk_filtered_dev(self, q_ptr, Q, k, any_ptr, none_ptr, excl_ptr, n_excl, scores_ptr, ids_ptr, counts_ptr, stream=0):
@@ -481,11 +512,7 @@ class Handle(object):
 
     def index_set_groups(self, groups):
         """One int64 group key per row of the resident index (groups=None clears them); a new index clears them too."""
-        if groups is None:
-            self.check(self.lib.sse_index_set_groups(self._h, None, 0))
-            return
-        g = np.ascontiguousarray(groups, dtype=np.int64).reshape(-1)
-        self.check(self.lib.sse_index_set_groups(self._h, _ptr(g), g.shape[0]))
+        self._index_set_column(self.lib.sse_index_set_groups, groups, np.int64)
 
     def index_set_groups_dev(self, groups_ptr, N, stream=0):
         """index_set_groups from a device pointer of N int64 keys (None / 0 clears), copied on `stream`."""
@@ -496,23 +523,12 @@ class Handle(object):
         eligibility rule of score_topk_filtered.  Returns (scores float64 [Q,k], ids int64 [Q,k], groups int64 [Q,k], counts
         int32 [Q]): the first counts[q] columns hold each group once, represented by its best eligible row (the lowest id
         among equal bests), best group first; the rest hold (-inf, INT64_MAX, INT64_MAX)."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2:
-            raise ValueError("queries must be [Q,S]")
+        q = _queries(queries)
         Q, k = q.shape[0], int(k)
-        masks = []
-        for m in (any_of, none_of):
-            if m is not None:
-                m = np.ascontiguousarray(m, dtype=np.uint64).reshape(-1)
-                if m.shape[0] != Q:
-                    raise ValueError("any_of / none_of must be uint64 [Q]")
-            masks.append(m)
-        scores = np.empty((Q, max(k, 0)), np.float64)
-        ids = np.empty((Q, max(k, 0)), np.int64)
+        masks = _masks(any_of, none_of, Q)
+        scores, ids, counts = _topk_out(Q, k)
         groups = np.empty((Q, max(k, 0)), np.int64)
-        counts = np.empty(Q, np.int32)
-        self.check(self.lib.sse_score_topk_grouped(self._h, _ptr(q), Q, k, _ptr(masks[0]) if masks[0] is not None else None,
-                                                   _ptr(masks[1]) if masks[1] is not None else None,
+        self.check(self.lib.sse_score_topk_grouped(self._h, _ptr(q), Q, k, _opt(masks[0]), _opt(masks[1]),
                                                    _ptr(scores), _ptr(ids), _ptr(groups), _ptr(counts)))
         return scores, ids, groups, counts
 
@@ -528,9 +544,7 @@ class Handle(object):
         masks, the eligibility rule of score_topk_filtered.  Returns (scores float64 [Q,k], ids int64 [Q,k], counts int32
         [Q]): the first counts[q] columns are score_topk's columns with the ineligible rows and the rows not after the cursor
         removed, the rest hold (-inf, INT64_MAX)."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2:
-            raise ValueError("queries must be [Q,S]")
+        q = _queries(queries)
         Q, k = q.shape[0], int(k)
         cs = ci = None
         if after is not None:
@@ -538,20 +552,9 @@ class Handle(object):
             ci = np.ascontiguousarray(after[1], dtype=np.int64).reshape(-1)
             if cs.shape[0] != Q or ci.shape[0] != Q:
                 raise ValueError("after must be (scores float64 [Q], ids int64 [Q])")
-        masks = []
-        for m in (any_of, none_of):
-            if m is not None:
-                m = np.ascontiguousarray(m, dtype=np.uint64).reshape(-1)
-                if m.shape[0] != Q:
-                    raise ValueError("any_of / none_of must be uint64 [Q]")
-            masks.append(m)
-        scores = np.empty((Q, max(k, 0)), np.float64)
-        ids = np.empty((Q, max(k, 0)), np.int64)
-        counts = np.empty(Q, np.int32)
-        self.check(self.lib.sse_score_topk_after(self._h, _ptr(q), Q, k, _ptr(cs) if cs is not None else None,
-                                                 _ptr(ci) if ci is not None else None,
-                                                 _ptr(masks[0]) if masks[0] is not None else None,
-                                                 _ptr(masks[1]) if masks[1] is not None else None,
+        masks = _masks(any_of, none_of, Q)
+        scores, ids, counts = _topk_out(Q, k)
+        self.check(self.lib.sse_score_topk_after(self._h, _ptr(q), Q, k, _opt(cs), _opt(ci), _opt(masks[0]), _opt(masks[1]),
                                                  _ptr(scores), _ptr(ids), _ptr(counts)))
         return scores, ids, counts
 
@@ -569,9 +572,7 @@ class Handle(object):
         +inf (no cut).  Returns (scores float64 [Q,k], ids int64 [Q,k], counts int32 [Q], pos_scores float64 [Q], pos_ids
         int64 [Q]): the first counts[q] columns are score_topk's columns with the positives and the rows below the floor
         removed, the rest hold (-inf, INT64_MAX); (pos_scores, pos_ids) is the best positive, (-inf, INT64_MAX) without one."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2:
-            raise ValueError("queries must be [Q,S]")
+        q = _queries(queries)
         Q, k = q.shape[0], int(k)
         if isinstance(positives, np.ndarray) and positives.ndim == 2:
             pos = np.ascontiguousarray(positives, dtype=np.int64)
@@ -582,9 +583,7 @@ class Handle(object):
                 pos[i, :len(r)] = r
         if pos.shape[0] != Q:
             raise ValueError("positives must be int64 [Q, n_pos]")
-        scores = np.empty((Q, max(k, 0)), np.float64)
-        ids = np.empty((Q, max(k, 0)), np.int64)
-        counts = np.empty(Q, np.int32)
+        scores, ids, counts = _topk_out(Q, k)
         pos_scores = np.empty(Q, np.float64)
         pos_ids = np.empty(Q, np.int64)
         self.check(self.lib.sse_score_confusions(self._h, _ptr(q), Q, k, _ptr(pos), pos.shape[1], float(margin), _ptr(scores),
@@ -601,11 +600,7 @@ class Handle(object):
     def index_set_bias(self, bias):
         """One float32 bias per row of the resident index (bias=None clears it); a new index clears it too.  A non-finite
         value is refused."""
-        if bias is None:
-            self.check(self.lib.sse_index_set_bias(self._h, None, 0))
-            return
-        b = np.ascontiguousarray(bias, dtype=np.float32).reshape(-1)
-        self.check(self.lib.sse_index_set_bias(self._h, _ptr(b), b.shape[0]))
+        self._index_set_column(self.lib.sse_index_set_bias, bias, np.float32)
 
     def index_set_bias_dev(self, bias_ptr, N, stream=0):
         """index_set_bias from a device pointer of N float32 values (None / 0 clears), copied on `stream`."""
@@ -617,29 +612,12 @@ class Handle(object):
         ids int64 [Q,k], counts int32 [Q]): the first counts[q] columns are the eligible rows by biased score descending,
         equal scores by ascending id, scores holding score_topk's float64 score + float64(weight) * float64(bias); the rest
         hold (-inf, INT64_MAX)."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2:
-            raise ValueError("queries must be [Q,S]")
+        q = _queries(queries)
         Q, k = q.shape[0], int(k)
-        w = None
-        if weight is not None:
-            w = np.asarray(weight, dtype=np.float32)
-            w = np.full(Q, w, np.float32) if w.ndim == 0 else np.ascontiguousarray(w.reshape(-1))
-            if w.shape[0] != Q:
-                raise ValueError("weight must be a scalar or float32 [Q]")
-        masks = []
-        for m in (any_of, none_of):
-            if m is not None:
-                m = np.ascontiguousarray(m, dtype=np.uint64).reshape(-1)
-                if m.shape[0] != Q:
-                    raise ValueError("any_of / none_of must be uint64 [Q]")
-            masks.append(m)
-        scores = np.empty((Q, max(k, 0)), np.float64)
-        ids = np.empty((Q, max(k, 0)), np.int64)
-        counts = np.empty(Q, np.int32)
-        self.check(self.lib.sse_score_topk_biased(self._h, _ptr(q), Q, k, _ptr(w) if w is not None else None,
-                                                  _ptr(masks[0]) if masks[0] is not None else None,
-                                                  _ptr(masks[1]) if masks[1] is not None else None,
+        w = _weights(weight, Q)
+        masks = _masks(any_of, none_of, Q)
+        scores, ids, counts = _topk_out(Q, k)
+        self.check(self.lib.sse_score_topk_biased(self._h, _ptr(q), Q, k, _opt(w), _opt(masks[0]), _opt(masks[1]),
                                                   _ptr(scores), _ptr(ids), _ptr(counts)))
         return scores, ids, counts
 
@@ -656,29 +634,15 @@ class Handle(object):
         or float32 [Q]; any_of / none_of: uint64 [Q] tag masks, the eligibility rule of score_topk_filtered; 0 < scale <= 256.
         Returns (lse float64 [Q], -inf where no row is eligible; count int64 [Q], the eligible rows; bound float64 [Q], a
         certified bound on |lse - its float64 value|)."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2:
-            raise ValueError("queries must be [Q,S]")
+        q = _queries(queries)
         Q = q.shape[0]
-        w = None
-        if weight is not None:
-            w = np.asarray(weight, dtype=np.float32)
-            w = np.full(Q, w, np.float32) if w.ndim == 0 else np.ascontiguousarray(w.reshape(-1))
-            if w.shape[0] != Q:
-                raise ValueError("weight must be a scalar or float32 [Q]")
-        masks = []
-        for m in (any_of, none_of):
-            if m is not None:
-                m = np.ascontiguousarray(m, dtype=np.uint64).reshape(-1)
-                if m.shape[0] != Q:
-                    raise ValueError("any_of / none_of must be uint64 [Q]")
-            masks.append(m)
+        w = _weights(weight, Q)
+        masks = _masks(any_of, none_of, Q)
         lse = np.empty(Q, np.float64)
         count = np.empty(Q, np.int64)
         bound = np.empty(Q, np.float64)
-        self.check(self.lib.sse_score_lse(self._h, _ptr(q), Q, float(scale), _ptr(w) if w is not None else None,
-                                          _ptr(masks[0]) if masks[0] is not None else None,
-                                          _ptr(masks[1]) if masks[1] is not None else None, _ptr(lse), _ptr(count), _ptr(bound)))
+        self.check(self.lib.sse_score_lse(self._h, _ptr(q), Q, float(scale), _opt(w), _opt(masks[0]), _opt(masks[1]),
+                                          _ptr(lse), _ptr(count), _ptr(bound)))
         return lse, count, bound
 
     def score_lse_dev(self, q_ptr, Q, scale, weight_ptr, any_ptr, none_ptr, lse_ptr, count_ptr, bound_ptr=None, stream=0):

@@ -188,10 +188,10 @@ class ShardedIndex(object):
             raise ValueError("k=%d must be in [1, n_total=%d]" % (k, self.n_total))
         Q = queries.shape[0]
         dev = queries.device
-        stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
+        stream = self._stream(queries)
         out = torch.empty((2, Q, k), dtype=torch.int64, device=dev)        # [0] = float64 score bits, [1] = row ids
         fs, fi = out[0].view(torch.float64), out[1]
-        if self.world == 1 and not self.always_gather:
+        if self._single():
             self.handle.score_topk_dev(queries.data_ptr(), Q, k, fs.data_ptr(), fi.data_ptr(), stream)
             return fs, fi
         world = dist.get_world_size(self.group)
@@ -227,20 +227,124 @@ class ShardedIndex(object):
             pending = nxt
         return fs, fi
 
+    # -- the eligible-rows family (filtered, after, biased, grouped, lse, confusions): one copy of the checks, of the local
+    # lists and of the exchange.  Every check raises before any device call and any collective, on every rank alike.
+
+    def _single(self):
+        """One shard and no forced gather: the local call is the result, no collective runs."""
+        return self.world == 1 and not self.always_gather
+
+    @staticmethod
+    def _stream(t):
+        """torch's current stream on t's device as the library takes it (0 for a CPU tensor)."""
+        import torch
+        return torch.cuda.current_stream(t.device).cuda_stream if t.is_cuda else 0
+
+    @staticmethod
+    def _opt_ptr(t):
+        return t.data_ptr() if t is not None else None
+
+    @staticmethod
+    def _check_k(k):
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise ValueError("k=%d must be in [1, 1024]" % k)
+        return k
+
+    @staticmethod
+    def _check_masks(any_of, none_of, Q):
+        """Both masks checked, then both contiguous (None stays None)."""
+        import torch
+        for m in (any_of, none_of):
+            if m is not None and (m.shape[0] != Q or m.dtype != torch.int64):
+                raise ValueError("any_of / none_of must be int64 [Q] tensors of mask bits")
+        return [m.contiguous() if m is not None else None for m in (any_of, none_of)]
+
+    @staticmethod
+    def _weight_tensor(weight, Q, dev):
+        """None, a number or a float32 [Q] tensor -> None or the contiguous float32 [Q] tensor."""
+        import torch
+        if weight is None:
+            return None
+        if not torch.is_tensor(weight):
+            weight = torch.full((Q,), float(weight), dtype=torch.float32, device=dev)
+        if weight.shape[0] != Q or weight.dtype != torch.float32:
+            raise ValueError("weight must be a number or a float32 [Q] tensor")
+        return weight.contiguous()
+
+    def _set_local_column(self, values, what, dtype, setter):
+        """set_local_tags / _groups / _bias: one value per row of this rank goes to `setter`, the handle's index_set_*_dev.
+        what = (the values' name in the length error, the whole dtype error); dtype = the torch dtype's name, None: any."""
+        if values is not None and values.shape[0] != self.end - self.start:
+            raise ValueError("rank %d holds %d rows, got %d %s" % (self.rank, self.end - self.start, values.shape[0], what[0]))
+        if self.end == self.start:
+            return
+        if values is None:
+            setter(None, 0)
+            return
+        import torch
+        if dtype is not None and values.dtype != getattr(torch, dtype):
+            raise ValueError(what[1])
+        values = values.contiguous()
+        setter(values.data_ptr(), values.shape[0], self._stream(values))
+
+    def _local_lists(self, planes, queries, k, stream, call):
+        """This rank's lists: (loc int64 [planes, Q, k] -- plane 0 float64 score bits, plane 1 row ids, plane 2 group keys --
+        and counts int32 [Q]).  With rows and Q > 0, call(one pointer per plane, counts pointer, stream) makes the device
+        call; otherwise no handle call is made and the lists are all padding, (-inf, INT64_MAX)."""
+        import torch
+        Q = int(queries.shape[0])
+        loc = torch.empty((planes, Q, k), dtype=torch.int64, device=queries.device)
+        cnt = torch.zeros(Q, dtype=torch.int32, device=queries.device)
+        if self.end > self.start and Q > 0:
+            call(*([loc[p].data_ptr() for p in range(planes)] + [cnt.data_ptr(), stream]))
+        else:
+            loc[0].view(torch.float64).fill_(float("-inf"))
+            loc[1:].fill_(torch.iinfo(torch.int64).max)
+        return loc, cnt
+
+    def _gather(self, loc):
+        """ONE all-gather of every rank's `loc`: (world, the ranks' tensors concatenated along dim 0)."""
+        import torch
+        import torch.distributed as dist
+        from .collectives import all_gather_into
+        world = dist.get_world_size(self.group)
+        g = torch.empty((world * loc.shape[0],) + tuple(loc.shape[1:]), dtype=loc.dtype, device=loc.device)
+        all_gather_into(g, loc, group=self.group)
+        return world, g
+
+    def _merged_topk(self, queries, k, call):
+        """What score_topk_filtered, _after and _biased do once their arguments are checked: the local lists (`call` is
+        their one differing device call), ONE all-gather, the k-way (score, id) merge, ONE all-reduce of the counts, cut
+        at k.  A single shard, or Q == 0, returns the local lists."""
+        import torch
+        from .collectives import all_reduce_
+        Q = int(queries.shape[0])
+        stream = self._stream(queries)
+        loc, cnt = self._local_lists(2, queries, k, stream, call)
+        if Q == 0 or self._single():
+            return loc[0].view(torch.float64), loc[1], cnt
+        world, g = self._gather(loc)
+        out = torch.empty((2, Q, k), dtype=torch.int64, device=queries.device)
+        self.handle.merge_topk_strided_dev(g.data_ptr(), g[1].data_ptr(), 2 * Q * k, world, Q, k, out[0].data_ptr(), out[1].data_ptr(), stream)
+        total = cnt.to(torch.int64)
+        all_reduce_(total, group=self.group)
+        return out[0].view(torch.float64), out[1], torch.clamp(total, max=k).to(torch.int32)
+
     def set_local_tags(self, tags):
         """tags: CUDA uint64 (or int64 holding the same bits) tensor [end-start] -- the tag words of this rank's rows, set
         after set_local_rows.  None clears them; a rank without rows has nothing to tag."""
-        if tags is not None and tags.shape[0] != self.end - self.start:
-            raise ValueError("rank %d holds %d rows, got %d tags" % (self.rank, self.end - self.start, tags.shape[0]))
-        if self.end == self.start:
-            return
-        if tags is None:
-            self.handle.index_set_tags_dev(None, 0)
-            return
-        import torch
-        tags = tags.contiguous()
-        stream = torch.cuda.current_stream(tags.device).cuda_stream if tags.is_cuda else 0
-        self.handle.index_set_tags_dev(tags.data_ptr(), tags.shape[0], stream)
+        self._set_local_column(tags, ("tags", None), None, self.handle.index_set_tags_dev)
+
+    def set_local_groups(self, groups):
+        """groups: CUDA int64 tensor [end-start] -- the group keys of this rank's rows, set after set_local_rows.  None
+        clears them; a rank without rows has nothing to group."""
+        self._set_local_column(groups, ("group keys", "group keys must be an int64 tensor"), "int64", self.handle.index_set_groups_dev)
+
+    def set_local_bias(self, bias):
+        """bias: CUDA float32 tensor [end-start] -- the bias of this rank's rows (Handle.index_set_bias), set after
+        set_local_rows.  None clears it; a rank without rows has nothing to bias."""
+        self._set_local_column(bias, ("bias values", "bias must be a float32 tensor"), "float32", self.handle.index_set_bias_dev)
 
     def score_topk_filtered(self, queries, k, any_of=None, none_of=None, exclude=None):
         """Handle.score_topk_filtered over the whole sharded index: queries CUDA float32 [Q,S], any_of / none_of int64 [Q]
@@ -250,46 +354,18 @@ class ShardedIndex(object):
         without rows contributes all padding), ONE all-gather exchanges the lists, the k-way merge ranks padding behind
         every real entry and fills the slots past the real entries with it, ONE all-reduce adds the counts."""
         import torch
-        import torch.distributed as dist
-        from .collectives import all_gather_into, all_reduce_
-        k = int(k)
-        if not 1 <= k <= 1024:
-            raise ValueError("k=%d must be in [1, 1024]" % k)
+        k = self._check_k(k)
         Q = int(queries.shape[0])
-        dev = queries.device
         n_excl = 0
         if exclude is not None:
             if exclude.dim() != 2 or exclude.shape[0] != Q or exclude.dtype != torch.int64 or exclude.shape[1] > 64:
                 raise ValueError("exclude must be int64 [Q, n <= 64]")
             n_excl = int(exclude.shape[1])
             exclude = exclude.contiguous() if n_excl else None
-        for m in (any_of, none_of):
-            if m is not None and (m.shape[0] != Q or m.dtype != torch.int64):
-                raise ValueError("any_of / none_of must be int64 [Q] tensors of mask bits")
-        queries = queries.contiguous()
-        any_of = any_of.contiguous() if any_of is not None else None
-        none_of = none_of.contiguous() if none_of is not None else None
-        stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
-        loc = torch.empty((2, Q, k), dtype=torch.int64, device=dev)        # [0] = float64 score bits, [1] = row ids
-        cnt = torch.zeros(Q, dtype=torch.int32, device=dev)
-        if self.end > self.start and Q > 0:
-            self.handle.score_topk_filtered_dev(queries.data_ptr(), Q, k, any_of.data_ptr() if any_of is not None else None,
-                                                none_of.data_ptr() if none_of is not None else None,
-                                                exclude.data_ptr() if exclude is not None else None, n_excl,
-                                                loc[0].data_ptr(), loc[1].data_ptr(), cnt.data_ptr(), stream)
-        else:
-            loc[0].view(torch.float64).fill_(float("-inf"))
-            loc[1].fill_(torch.iinfo(torch.int64).max)
-        if Q == 0 or (self.world == 1 and not self.always_gather):
-            return loc[0].view(torch.float64), loc[1], cnt
-        world = dist.get_world_size(self.group)
-        g = torch.empty((world * 2, Q, k), dtype=torch.int64, device=dev)
-        all_gather_into(g, loc, group=self.group)
-        out = torch.empty((2, Q, k), dtype=torch.int64, device=dev)
-        self.handle.merge_topk_strided_dev(g.data_ptr(), g[1].data_ptr(), 2 * Q * k, world, Q, k, out[0].data_ptr(), out[1].data_ptr(), stream)
-        total = cnt.to(torch.int64)
-        all_reduce_(total, group=self.group)
-        return out[0].view(torch.float64), out[1], torch.clamp(total, max=k).to(torch.int32)
+        any_of, none_of = self._check_masks(any_of, none_of, Q)
+        queries, p = queries.contiguous(), self._opt_ptr
+        return self._merged_topk(queries, k, lambda s, i, c, stream: self.handle.score_topk_filtered_dev(
+            queries.data_ptr(), Q, k, p(any_of), p(none_of), p(exclude), n_excl, s, i, c, stream))
 
     def score_topk_after(self, queries, k, after=None, any_of=None, none_of=None):
         """Handle.score_topk_after over the whole sharded index: queries CUDA float32 [Q,S], after = None or (scores float64
@@ -300,64 +376,18 @@ class ShardedIndex(object):
         padded to k, ONE all-gather exchanges the lists, the k-way merge ranks padding behind every real entry, ONE
         all-reduce adds the counts."""
         import torch
-        import torch.distributed as dist
-        from .collectives import all_gather_into, all_reduce_
-        k = int(k)
-        if not 1 <= k <= 1024:
-            raise ValueError("k=%d must be in [1, 1024]" % k)
+        k = self._check_k(k)
         Q = int(queries.shape[0])
-        dev = queries.device
         cs = ci = None
         if after is not None:
             cs, ci = after
             if cs.shape[0] != Q or ci.shape[0] != Q or cs.dtype != torch.float64 or ci.dtype != torch.int64:
                 raise ValueError("after must be (float64 [Q], int64 [Q]) tensors")
             cs, ci = cs.contiguous(), ci.contiguous()
-        for m in (any_of, none_of):
-            if m is not None and (m.shape[0] != Q or m.dtype != torch.int64):
-                raise ValueError("any_of / none_of must be int64 [Q] tensors of mask bits")
-        queries = queries.contiguous()
-        any_of = any_of.contiguous() if any_of is not None else None
-        none_of = none_of.contiguous() if none_of is not None else None
-        stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
-        loc = torch.empty((2, Q, k), dtype=torch.int64, device=dev)        # [0] = float64 score bits, [1] = row ids
-        cnt = torch.zeros(Q, dtype=torch.int32, device=dev)
-        if self.end > self.start and Q > 0:
-            self.handle.score_topk_after_dev(queries.data_ptr(), Q, k, cs.data_ptr() if cs is not None else None,
-                                             ci.data_ptr() if ci is not None else None,
-                                             any_of.data_ptr() if any_of is not None else None,
-                                             none_of.data_ptr() if none_of is not None else None,
-                                             loc[0].data_ptr(), loc[1].data_ptr(), cnt.data_ptr(), stream)
-        else:
-            loc[0].view(torch.float64).fill_(float("-inf"))
-            loc[1].fill_(torch.iinfo(torch.int64).max)
-        if Q == 0 or (self.world == 1 and not self.always_gather):
-            return loc[0].view(torch.float64), loc[1], cnt
-        world = dist.get_world_size(self.group)
-        g = torch.empty((world * 2, Q, k), dtype=torch.int64, device=dev)
-        all_gather_into(g, loc, group=self.group)
-        out = torch.empty((2, Q, k), dtype=torch.int64, device=dev)
-        self.handle.merge_topk_strided_dev(g.data_ptr(), g[1].data_ptr(), 2 * Q * k, world, Q, k, out[0].data_ptr(), out[1].data_ptr(), stream)
-        total = cnt.to(torch.int64)
-        all_reduce_(total, group=self.group)
-        return out[0].view(torch.float64), out[1], torch.clamp(total, max=k).to(torch.int32)
-
-    def set_local_bias(self, bias):
-        """bias: CUDA float32 tensor [end-start] -- the bias of this rank's rows (Handle.index_set_bias), set after
-        set_local_rows.  None clears it; a rank without rows has nothing to bias."""
-        if bias is not None and bias.shape[0] != self.end - self.start:
-            raise ValueError("rank %d holds %d rows, got %d bias values" % (self.rank, self.end - self.start, bias.shape[0]))
-        if self.end == self.start:
-            return
-        if bias is None:
-            self.handle.index_set_bias_dev(None, 0)
-            return
-        import torch
-        if bias.dtype != torch.float32:
-            raise ValueError("bias must be a float32 tensor")
-        bias = bias.contiguous()
-        stream = torch.cuda.current_stream(bias.device).cuda_stream if bias.is_cuda else 0
-        self.handle.index_set_bias_dev(bias.data_ptr(), bias.shape[0], stream)
+        any_of, none_of = self._check_masks(any_of, none_of, Q)
+        queries, p = queries.contiguous(), self._opt_ptr
+        return self._merged_topk(queries, k, lambda s, i, c, stream: self.handle.score_topk_after_dev(
+            queries.data_ptr(), Q, k, p(cs), p(ci), p(any_of), p(none_of), s, i, c, stream))
 
     def score_topk_biased(self, queries, k, weight=None, any_of=None, none_of=None):
         """Handle.score_topk_biased over the whole sharded index: queries CUDA float32 [Q,S], weight None, a number or a
@@ -366,47 +396,33 @@ class ShardedIndex(object):
         returns.  A biased score depends on the query and the row alone, so it is a global quantity: every rank makes the
         local call with the full k, ONE all-gather exchanges the lists, the plain (score, id) merge of score_topk_filtered
         ranks padding behind every real entry, ONE all-reduce adds the counts."""
-        import torch
-        import torch.distributed as dist
-        from .collectives import all_gather_into, all_reduce_
-        k = int(k)
-        if not 1 <= k <= 1024:
-            raise ValueError("k=%d must be in [1, 1024]" % k)
+        k = self._check_k(k)
         Q = int(queries.shape[0])
-        dev = queries.device
-        if weight is not None:
-            if not torch.is_tensor(weight):
-                weight = torch.full((Q,), float(weight), dtype=torch.float32, device=dev)
-            if weight.shape[0] != Q or weight.dtype != torch.float32:
-                raise ValueError("weight must be a number or a float32 [Q] tensor")
-            weight = weight.contiguous()
-        for m in (any_of, none_of):
-            if m is not None and (m.shape[0] != Q or m.dtype != torch.int64):
-                raise ValueError("any_of / none_of must be int64 [Q] tensors of mask bits")
-        queries = queries.contiguous()
-        any_of = any_of.contiguous() if any_of is not None else None
-        none_of = none_of.contiguous() if none_of is not None else None
-        stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
-        loc = torch.empty((2, Q, k), dtype=torch.int64, device=dev)        # [0] = float64 score bits, [1] = row ids
-        cnt = torch.zeros(Q, dtype=torch.int32, device=dev)
-        if self.end > self.start and Q > 0:
-            self.handle.score_topk_biased_dev(queries.data_ptr(), Q, k, weight.data_ptr() if weight is not None else None,
-                                              any_of.data_ptr() if any_of is not None else None,
-                                              none_of.data_ptr() if none_of is not None else None,
-                                              loc[0].data_ptr(), loc[1].data_ptr(), cnt.data_ptr(), stream)
-        else:
-            loc[0].view(torch.float64).fill_(float("-inf"))
-            loc[1].fill_(torch.iinfo(torch.int64).max)
-        if Q == 0 or (self.world == 1 and not self.always_gather):
-            return loc[0].view(torch.float64), loc[1], cnt
-        world = dist.get_world_size(self.group)
-        g = torch.empty((world * 2, Q, k), dtype=torch.int64, device=dev)
-        all_gather_into(g, loc, group=self.group)
-        out = torch.empty((2, Q, k), dtype=torch.int64, device=dev)
-        self.handle.merge_topk_strided_dev(g.data_ptr(), g[1].data_ptr(), 2 * Q * k, world, Q, k, out[0].data_ptr(), out[1].data_ptr(), stream)
-        total = cnt.to(torch.int64)
-        all_reduce_(total, group=self.group)
-        return out[0].view(torch.float64), out[1], torch.clamp(total, max=k).to(torch.int32)
+        weight = self._weight_tensor(weight, Q, queries.device)
+        any_of, none_of = self._check_masks(any_of, none_of, Q)
+        queries, p = queries.contiguous(), self._opt_ptr
+        return self._merged_topk(queries, k, lambda s, i, c, stream: self.handle.score_topk_biased_dev(
+            queries.data_ptr(), Q, k, p(weight), p(any_of), p(none_of), s, i, c, stream))
+
+    def score_topk_grouped(self, queries, k, any_of=None, none_of=None):
+        """Handle.score_topk_grouped over the whole sharded index: queries CUDA float32 [Q,S], any_of / none_of int64 [Q]
+        tensors holding the uint64 mask bits (or None), identical on every rank.  Returns (scores float64 [Q,k], ids int64
+        [Q,k], groups int64 [Q,k], counts int32 [Q]) on every rank: what the unsharded call returns.  Every rank makes the
+        local call with the full k (a rank without rows contributes all padding), ONE all-gather carries scores, ids and
+        groups, merge_grouped_lists collapses the groups again.  Exact: were the representative of an answer group missing
+        from its rank's local top-k, k other groups would beat it on that rank alone."""
+        import torch
+        k = self._check_k(k)
+        Q = int(queries.shape[0])
+        any_of, none_of = self._check_masks(any_of, none_of, Q)
+        queries, p = queries.contiguous(), self._opt_ptr
+        loc, cnt = self._local_lists(3, queries, k, self._stream(queries), lambda s, i, g, c, stream: self.handle.score_topk_grouped_dev(
+            queries.data_ptr(), Q, k, p(any_of), p(none_of), s, i, g, c, stream))
+        if Q == 0 or self._single():
+            return loc[0].view(torch.float64), loc[1], loc[2], cnt
+        world, g = self._gather(loc)
+        g = g.view(world, 3, Q, k).permute(1, 2, 0, 3).reshape(3, Q, world * k)   # the shards' lists side by side
+        return merge_grouped_lists(g[0].view(torch.float64), g[1], g[2], k)
 
     def score_lse(self, queries, scale, weight=None, any_of=None, none_of=None):
         """Handle.score_lse over the whole sharded index: queries CUDA float32 [Q,S], weight None, a number or a float32 [Q]
@@ -416,35 +432,18 @@ class ShardedIndex(object):
         logaddexp over the ranks in rank order, adds the counts and takes the largest bound.  A rank without rows, or
         without an eligible row, contributes (-inf, 0)."""
         import torch
-        import torch.distributed as dist
-        from .collectives import all_gather_into
         Q = int(queries.shape[0])
-        dev = queries.device
-        if weight is not None:
-            if not torch.is_tensor(weight):
-                weight = torch.full((Q,), float(weight), dtype=torch.float32, device=dev)
-            if weight.shape[0] != Q or weight.dtype != torch.float32:
-                raise ValueError("weight must be a number or a float32 [Q] tensor")
-            weight = weight.contiguous()
-        for m in (any_of, none_of):
-            if m is not None and (m.shape[0] != Q or m.dtype != torch.int64):
-                raise ValueError("any_of / none_of must be int64 [Q] tensors of mask bits")
-        queries = queries.contiguous()
-        any_of = any_of.contiguous() if any_of is not None else None
-        none_of = none_of.contiguous() if none_of is not None else None
-        stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
-        loc = torch.zeros((3, Q), dtype=torch.int64, device=dev)           # [0] = lse bits, [1] = count, [2] = bound bits
+        weight = self._weight_tensor(weight, Q, queries.device)
+        any_of, none_of = self._check_masks(any_of, none_of, Q)
+        queries, p = queries.contiguous(), self._opt_ptr
+        loc = torch.zeros((3, Q), dtype=torch.int64, device=queries.device)   # [0] = lse bits, [1] = count, [2] = bound bits
         loc[0].view(torch.float64).fill_(float("-inf"))
         if self.end > self.start and Q > 0:
-            self.handle.score_lse_dev(queries.data_ptr(), Q, float(scale), weight.data_ptr() if weight is not None else None,
-                                      any_of.data_ptr() if any_of is not None else None,
-                                      none_of.data_ptr() if none_of is not None else None,
-                                      loc[0].data_ptr(), loc[1].data_ptr(), loc[2].data_ptr(), stream)
-        if Q == 0 or (self.world == 1 and not self.always_gather):
+            self.handle.score_lse_dev(queries.data_ptr(), Q, float(scale), p(weight), p(any_of), p(none_of),
+                                      loc[0].data_ptr(), loc[1].data_ptr(), loc[2].data_ptr(), self._stream(queries))
+        if Q == 0 or self._single():
             return loc[0].view(torch.float64), loc[1], loc[2].view(torch.float64)
-        world = dist.get_world_size(self.group)
-        g = torch.empty((world * 3, Q), dtype=torch.int64, device=dev)
-        all_gather_into(g, loc, group=self.group)
+        world, g = self._gather(loc)
         g = g.view(world, 3, Q)
         return merge_lse_lists(g[:, 0].contiguous().view(torch.float64), g[:, 1], g[:, 2].contiguous().view(torch.float64))
 
@@ -457,11 +456,7 @@ class ShardedIndex(object):
         positive over the ranks, forms the floor and cuts the merged lists at it.  No second device pass."""
         import math
         import torch
-        import torch.distributed as dist
-        from .collectives import all_gather_into
-        k, margin = int(k), float(margin)
-        if not 1 <= k <= 1024:
-            raise ValueError("k=%d must be in [1, 1024]" % k)
+        k, margin = self._check_k(k), float(margin)
         if math.isnan(margin) or margin == float("-inf"):
             raise ValueError("margin=%r must be finite or +inf" % margin)
         Q = int(queries.shape[0])
@@ -469,8 +464,7 @@ class ShardedIndex(object):
         if positives.dim() != 2 or positives.shape[0] != Q or positives.dtype != torch.int64 or not 1 <= positives.shape[1] <= 64:
             raise ValueError("positives must be int64 [Q, 1 <= n_pos <= 64]")
         queries, positives = queries.contiguous(), positives.contiguous()
-        stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
-        single = self.world == 1 and not self.always_gather
+        single = self._single()
         pad = torch.iinfo(torch.int64).max
         loc = torch.empty(2 * Q * k + 2 * Q, dtype=torch.int64, device=dev)   # score bits [Q,k] | ids [Q,k] | m bits [Q] | b [Q]
         ls, li = loc[:Q * k].view(Q, k), loc[Q * k:2 * Q * k].view(Q, k)
@@ -479,7 +473,7 @@ class ShardedIndex(object):
         if self.end > self.start and Q > 0:
             self.handle.score_confusions_dev(queries.data_ptr(), Q, k, positives.data_ptr(), positives.shape[1],
                                              margin if single else float("inf"), ls.data_ptr(), li.data_ptr(), cnt.data_ptr(),
-                                             lm.data_ptr(), lb.data_ptr(), stream)
+                                             lm.data_ptr(), lb.data_ptr(), self._stream(queries))
         else:
             ls.view(torch.float64).fill_(float("-inf"))
             li.fill_(pad)
@@ -487,71 +481,13 @@ class ShardedIndex(object):
             lb.fill_(pad)
         if Q == 0 or single:
             return ls.view(torch.float64), li, cnt, lm.view(torch.float64), lb
-        world = dist.get_world_size(self.group)
-        g = torch.empty(world * loc.shape[0], dtype=torch.int64, device=dev)
-        all_gather_into(g, loc, group=self.group)
+        world, g = self._gather(loc)
         g = g.view(world, -1)
         gs = g[:, :Q * k].view(torch.float64).view(world, Q, k).permute(1, 0, 2).reshape(Q, world * k)
         gi = g[:, Q * k:2 * Q * k].view(world, Q, k).permute(1, 0, 2).reshape(Q, world * k)
         gm = g[:, 2 * Q * k:2 * Q * k + Q].contiguous().view(torch.float64)
         gb = g[:, 2 * Q * k + Q:]
         return merge_confusion_lists(gs, gi, gm, gb, margin, k)
-
-    def set_local_groups(self, groups):
-        """groups: CUDA int64 tensor [end-start] -- the group keys of this rank's rows, set after set_local_rows.  None
-        clears them; a rank without rows has nothing to group."""
-        if groups is not None and groups.shape[0] != self.end - self.start:
-            raise ValueError("rank %d holds %d rows, got %d group keys" % (self.rank, self.end - self.start, groups.shape[0]))
-        if self.end == self.start:
-            return
-        if groups is None:
-            self.handle.index_set_groups_dev(None, 0)
-            return
-        import torch
-        if groups.dtype != torch.int64:
-            raise ValueError("group keys must be an int64 tensor")
-        groups = groups.contiguous()
-        stream = torch.cuda.current_stream(groups.device).cuda_stream if groups.is_cuda else 0
-        self.handle.index_set_groups_dev(groups.data_ptr(), groups.shape[0], stream)
-
-    def score_topk_grouped(self, queries, k, any_of=None, none_of=None):
-        """Handle.score_topk_grouped over the whole sharded index: queries CUDA float32 [Q,S], any_of / none_of int64 [Q]
-        tensors holding the uint64 mask bits (or None), identical on every rank.  Returns (scores float64 [Q,k], ids int64
-        [Q,k], groups int64 [Q,k], counts int32 [Q]) on every rank: what the unsharded call returns.  Every rank makes the
-        local call with the full k (a rank without rows contributes all padding), ONE all-gather carries scores, ids and
-        groups, merge_grouped_lists collapses the groups again.  Exact: were the representative of an answer group missing
-        from its rank's local top-k, k other groups would beat it on that rank alone."""
-        import torch
-        import torch.distributed as dist
-        from .collectives import all_gather_into
-        k = int(k)
-        if not 1 <= k <= 1024:
-            raise ValueError("k=%d must be in [1, 1024]" % k)
-        Q = int(queries.shape[0])
-        dev = queries.device
-        for m in (any_of, none_of):
-            if m is not None and (m.shape[0] != Q or m.dtype != torch.int64):
-                raise ValueError("any_of / none_of must be int64 [Q] tensors of mask bits")
-        queries = queries.contiguous()
-        any_of = any_of.contiguous() if any_of is not None else None
-        none_of = none_of.contiguous() if none_of is not None else None
-        stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
-        loc = torch.empty((3, Q, k), dtype=torch.int64, device=dev)        # float64 score bits | row ids | group keys
-        cnt = torch.zeros(Q, dtype=torch.int32, device=dev)
-        if self.end > self.start and Q > 0:
-            self.handle.score_topk_grouped_dev(queries.data_ptr(), Q, k, any_of.data_ptr() if any_of is not None else None,
-                                               none_of.data_ptr() if none_of is not None else None,
-                                               loc[0].data_ptr(), loc[1].data_ptr(), loc[2].data_ptr(), cnt.data_ptr(), stream)
-        else:
-            loc[0].view(torch.float64).fill_(float("-inf"))
-            loc[1:].fill_(torch.iinfo(torch.int64).max)
-        if Q == 0 or (self.world == 1 and not self.always_gather):
-            return loc[0].view(torch.float64), loc[1], loc[2], cnt
-        world = dist.get_world_size(self.group)
-        g = torch.empty((world * 3, Q, k), dtype=torch.int64, device=dev)
-        all_gather_into(g, loc, group=self.group)
-        g = g.view(world, 3, Q, k).permute(1, 2, 0, 3).reshape(3, Q, world * k)   # the shards' lists side by side
-        return merge_grouped_lists(g[0].view(torch.float64), g[1], g[2], k)
 
     def rank_of(self, queries, pair_q, pair_id):
         """Exact global rank of labelled rows: queries CUDA float32 [Q,S], pair_q int32 [L] (query row of pair p), pair_id
@@ -573,10 +509,10 @@ class ShardedIndex(object):
             return out
         if bool(((pair_q < 0) | (pair_q >= Q) | (pair_id < 0) | (pair_id >= self.n_total)).any().item()):
             raise ValueError("pair_q must be in [0, Q=%d) and pair_id in [0, n_total=%d)" % (Q, self.n_total))
-        stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
+        stream = self._stream(queries)
         queries, pair_q, pair_id = queries.contiguous(), pair_q.contiguous(), pair_id.contiguous()
         have_rows = self.end > self.start
-        if self.world == 1 and not self.always_gather:
+        if self._single():
             self.handle.score_rank_dev(queries.data_ptr(), Q, pair_q.data_ptr(), pair_id.data_ptr(), L, None, out.data_ptr(), None, stream)
             return out
         world = dist.get_world_size(self.group)
@@ -617,7 +553,7 @@ class ShardedIndex(object):
         call sizes the lists (one read-back of the total); an empty shard has no index and contributes nothing."""
         import torch
         dev = queries.device
-        stream = torch.cuda.current_stream(dev).cuda_stream if queries.is_cuda else 0
+        stream = self._stream(queries)
         off = torch.zeros(L + 1, dtype=torch.int64, device=dev)
         empty = (torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.float64, device=dev))
         if self.end == self.start or L == 0:
@@ -643,7 +579,7 @@ class ShardedIndex(object):
         queries, pair_q, pair_thr = queries.contiguous(), pair_q.contiguous(), pair_thr.contiguous()
         off, _, _ = self._above_local(queries, pair_q, pair_thr, Q, L, False)
         cnt = (off[1:] - off[:-1]).contiguous()
-        if L > 0 and not (self.world == 1 and not self.always_gather):
+        if L > 0 and not self._single():
             all_reduce_(cnt, group=self.group)
         return cnt
 
@@ -661,7 +597,7 @@ class ShardedIndex(object):
         dev = queries.device
         queries, pair_q, pair_thr = queries.contiguous(), pair_q.contiguous(), pair_thr.contiguous()
         off, ids, sc = self._above_local(queries, pair_q, pair_thr, Q, L, True)
-        if L == 0 or (self.world == 1 and not self.always_gather):
+        if L == 0 or self._single():
             return off, ids, sc
         world = dist.get_world_size(self.group)
         cnt = (off[1:] - off[:-1]).contiguous()

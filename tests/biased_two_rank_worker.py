@@ -3,8 +3,6 @@
 A fresh process that joins a `gloo` group on 127.0.0.1 with its peers, all on device 0 (the collectives are staged through the
 host, sse_amd/collectives.py), holds ITS rows, tag words and bias values of the index only, runs ShardedIndex.score_topk_biased
 and writes rank<RANK>.npz.  It asserts nothing about numbers: the parent does."""
-import datetime
-import json
 import os
 import sys
 
@@ -16,30 +14,14 @@ if ROOT not in sys.path:
 
 
 def main(job_path, rank):
-    with open(job_path) as f:
-        job = json.load(f)
-    z = np.load(job["inputs"])
     import torch
-    import torch.distributed as dist
-    import sse_amd
-    from tests.util import make_pair, model_params
-    world = job["world"]
-    torch.cuda.set_device(0)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(job["port"]))
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=60))
-    t, q = z["t"], z["q"]
-    m, _ = make_pair(model_params("dual-encoder", 50, 8, 16, 16, 8, 4))
-    h = m.handle
-    sh = sse_amd.ShardedIndex(h, rank, world, t.shape[0])
-    assert (sh.start, sh.end) == tuple(job["bounds"][rank])
-    sh.set_local_rows(torch.from_numpy(t[sh.start:sh.end].copy()).cuda())
-    sh.set_local_tags(torch.from_numpy(z["tags"][sh.start:sh.end].copy().view(np.int64)).cuda())
+    from tests import rank_worker as RW
+    job, z = RW.open_job(job_path)
+    RW.join_group(job, rank)
+    h, sh = RW.sharded_index(job, z, rank)
+    q = z["q"]
     res = {}
-    try:
-        sh.set_local_bias(torch.from_numpy(z["bias"][:sh.end - sh.start + 1].copy()).cuda())
-        res["bad_len"] = np.array("no error")
-    except ValueError as e:
-        res["bad_len"] = np.array("ValueError: %s" % e)
+    res["bad_len"] = RW.error_text(lambda: sh.set_local_bias(torch.from_numpy(z["bias"][:sh.end - sh.start + 1].copy()).cuda()))
     sh.set_local_bias(torch.from_numpy(z["bias"][sh.start:sh.end].copy()).cuda())
     qd = torch.from_numpy(q).cuda()
     any_of = torch.from_numpy(z["any"].view(np.int64).copy()).cuda()
@@ -47,18 +29,9 @@ def main(job_path, rank):
     w = torch.from_numpy(z["w"]).cuda()
     sc, ids, cnt = sh.score_topk_biased(qd, int(job["k"]), weight=w, any_of=any_of, none_of=none_of)
     res.update(scores=sc.cpu().numpy(), ids=ids.cpu().numpy(), counts=cnt.cpu().numpy())
-    try:
-        sh.score_topk_biased(qd, 1025)
-        res["bad_k"] = np.array("no error")
-    except ValueError as e:
-        res["bad_k"] = np.array("ValueError: %s" % e)
+    res["bad_k"] = RW.error_text(lambda: sh.score_topk_biased(qd, 1025))
     res["bruteforce"] = np.array(h.get_counter("score_biased_bruteforce_queries"))
-    torch.cuda.synchronize()
-    h.close()
-    np.savez(os.path.join(job["out_dir"], "rank%d.npz" % rank), **res)
-    print("rank %d done" % rank, flush=True)
-    dist.barrier()
-    dist.destroy_process_group()
+    RW.finish(job, rank, res, h)
 
 
 if __name__ == "__main__":

@@ -4,8 +4,6 @@ A fresh process (the pytest process has initialised the GPU already) that joins 
 on device 0, loads the job's weights, takes ONE step of its own rows through the product's DataParallelTrainer under the job's
 options and writes rank<RANK>.npz: the variables and slots afterwards, the step's (loss, accuracy), the exchange it used and the
 train_* counters.  It asserts nothing about numbers: the parent does."""
-import datetime
-import json
 import os
 import sys
 
@@ -17,15 +15,11 @@ if ROOT not in sys.path:
 
 
 def main(job_path, rank):
-    with open(job_path) as f:
-        job = json.load(f)
-    z = np.load(job["inputs"])
     import torch
-    import torch.distributed as dist
     import sse_amd
-    torch.cuda.set_device(0)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(job["port"]))
-    dist.init_process_group("gloo", rank=rank, world_size=job["world"], timeout=datetime.timedelta(seconds=60))
+    from tests import rank_worker as RW
+    job, z = RW.open_job(job_path)
+    RW.join_group(job, rank)
     m = sse_amd.SSEModel(job["params"])
     m.set_variables({k[2:]: z[k] for k in z.files if k.startswith("p/")})
     tr = sse_amd.DataParallelTrainer(m.handle, device="cuda:0", options=job["options"])
@@ -37,10 +31,7 @@ def main(job_path, rank):
     res["exchange"] = np.array(tr.last_exchange)
     for n in ("train_class_steps", "train_inbatch_steps", "train_path_fused"):
         res["counter/" + n] = np.array(m.handle.get_counter(n))
-    np.savez(os.path.join(job["out_dir"], "rank%d.npz" % rank), **res)
-    print("rank %d done" % rank, flush=True)
-    dist.barrier()
-    dist.destroy_process_group()
+    RW.finish(job, rank, res)
     m.handle.close()
 
 

@@ -5,8 +5,6 @@ on device 0.  Three runs of its own rows through the product's DataParallelTrain
 handle with the job's weights: ONE step with global_negatives=True, ONE step with global_negatives=False, and job["steps"]
 steps with global_negatives=True.  It writes rank<RANK>.npz: per run the variables and slots afterwards and the (loss,
 accuracy) of every step, the exchange used and the train_* counters.  It asserts nothing about numbers: the parent does."""
-import datetime
-import json
 import os
 import sys
 
@@ -20,15 +18,12 @@ COUNTERS = ("train_open_steps", "train_global_inbatch_steps", "train_inbatch_ste
 
 
 def main(job_path, rank):
-    with open(job_path) as f:
-        job = json.load(f)
-    z = np.load(job["inputs"])
     import torch
     import torch.distributed as dist
     import sse_amd
-    torch.cuda.set_device(0)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(job["port"]))
-    dist.init_process_group("gloo", rank=rank, world_size=job["world"], timeout=datetime.timedelta(seconds=60))
+    from tests import rank_worker as RW
+    job, z = RW.open_job(job_path)
+    RW.join_group(job, rank)
     key = "rank%d/" % rank
     res = {}
     for run, global_negatives, steps in (("global", True, 1), ("local", False, 1), ("long", True, int(job["steps"]))):
@@ -44,10 +39,7 @@ def main(job_path, rank):
             res["%s/counter/%s" % (run, n)] = np.array(m.handle.get_counter(n))
         dist.barrier()
         m.handle.close()
-    np.savez(os.path.join(job["out_dir"], "rank%d.npz" % rank), **res)
-    print("rank %d done" % rank, flush=True)
-    dist.barrier()
-    dist.destroy_process_group()
+    RW.finish(job, rank, res)
 
 
 if __name__ == "__main__":

@@ -3,8 +3,6 @@
 A fresh process that joins a `gloo` group on 127.0.0.1 with its peer, both on device 0 (the collectives are staged through the
 host, sse_amd/collectives.py), holds ITS rows of the index only, runs ShardedIndex.rank_of and writes rank<RANK>.npz.  It
 asserts nothing about numbers: the parent does."""
-import datetime
-import json
 import os
 import sys
 
@@ -16,39 +14,19 @@ if ROOT not in sys.path:
 
 
 def main(job_path, rank):
-    with open(job_path) as f:
-        job = json.load(f)
-    z = np.load(job["inputs"])
     import torch
-    import torch.distributed as dist
-    import sse_amd
-    from tests.util import make_pair, model_params
-    world = job["world"]
-    torch.cuda.set_device(0)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(job["port"]))
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=60))
+    from tests import rank_worker as RW
+    job, z = RW.open_job(job_path)
+    RW.join_group(job, rank)
+    h, sh = RW.sharded_index(job, z, rank)
     t, q = z["t"], z["q"]
-    m, _ = make_pair(model_params("dual-encoder", 50, 8, 16, 16, 8, 4))
-    h = m.handle
-    sh = sse_amd.ShardedIndex(h, rank, world, t.shape[0])
-    assert (sh.start, sh.end) == tuple(job["bounds"][rank])
-    sh.set_local_rows(torch.from_numpy(t[sh.start:sh.end].copy()).cuda())
     qd = torch.from_numpy(q).cuda()
     pq, pi = torch.from_numpy(z["pair_q"]).cuda(), torch.from_numpy(z["pair_id"]).cuda()
     res = {"ranks": sh.rank_of(qd, pq, pi).cpu().numpy()}
-    try:
-        sh.rank_of(qd, pq, pi + t.shape[0])
-        res["bad_id"] = np.array("no error")
-    except ValueError as e:
-        res["bad_id"] = np.array("ValueError: %s" % e)
+    res["bad_id"] = RW.error_text(lambda: sh.rank_of(qd, pq, pi + t.shape[0]))
     res["empty"] = sh.rank_of(qd, pq[:0], pi[:0]).cpu().numpy()
     res["bruteforce"] = np.array(h.get_counter("score_rank_bruteforce_pairs"))
-    torch.cuda.synchronize()
-    h.close()
-    np.savez(os.path.join(job["out_dir"], "rank%d.npz" % rank), **res)
-    print("rank %d done" % rank, flush=True)
-    dist.barrier()
-    dist.destroy_process_group()
+    RW.finish(job, rank, res, h)
 
 
 if __name__ == "__main__":

@@ -4,7 +4,6 @@ sharded.py); the per-shard top-k and the k-way merge are done by the oracle here
 (on the GPU they are sse_score_topk_dev / sse_merge_topk_dev, covered by
 tests/test_gpu_score.py::test_sharded_index_equals_unsharded)."""
 import os
-import socket
 import sys
 
 import numpy as np
@@ -13,15 +12,9 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from tests.rank_launch import free_port
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, q_np, t_np, k, out_dir):
@@ -62,7 +55,7 @@ def test_two_rank_sharded_topk_equals_unsharded(tmp_path):
     q = rng.standard_normal((Q, S)).astype(np.float32)
     t = rng.standard_normal((N, S)).astype(np.float32)
     t[400] = t[7]                                                  # an exact tie across the two shards
-    port = _free_port()
+    port = free_port()
     mp.spawn(_worker, args=(world, port, q, t, k, str(tmp_path)), nprocs=world, join=True)
     wsc, wids = O.topk(O.scores_f64(q, t.astype(np.float64)), k)
     for r in range(world):
@@ -132,7 +125,7 @@ def test_two_rank_sharded_index_class_blocks_and_packed_gather(tmp_path):
     q = rng.standard_normal((Q, S)).astype(np.float32)
     t = rng.standard_normal((N, S)).astype(np.float32)
     t[300] = t[5]
-    port = _free_port()
+    port = free_port()
     mp.spawn(_sharded_worker, args=(world, port, q, t, k, str(tmp_path)), nprocs=world, join=True)
     wsc, wids = O.topk(O.scores_f64(q, t.astype(np.float64)), k)
     for r in range(world):
@@ -151,7 +144,7 @@ def test_eight_rank_sharded_index_uneven_blocks_and_shards(tmp_path):
     t[300] = t[5]
     t[51] = t[50]                                                  # a tie across the boundary of shards 0 | 1
     q[3] = t[50]
-    port = _free_port()
+    port = free_port()
     mp.spawn(_sharded_worker, args=(world, port, q, t, k, str(tmp_path), 7), nprocs=world, join=True)
     wsc, wids = O.topk(O.scores_f64(q, t.astype(np.float64)), k)
     assert wids[3, :2].tolist() == [50, 51]
@@ -171,7 +164,7 @@ def test_three_rank_shards_shorter_than_k(tmp_path, Q, N, k, block):
     S, world = 16, 3
     q = rng.standard_normal((Q, S)).astype(np.float32)
     t = rng.standard_normal((N, S)).astype(np.float32)
-    port = _free_port()
+    port = free_port()
     mp.spawn(_sharded_worker, args=(world, port, q, t, k, str(tmp_path), block), nprocs=world, join=True)
     wsc, wids = O.topk(O.scores_f64(q, t.astype(np.float64)), k)
     for r in range(world):
@@ -313,7 +306,7 @@ def test_two_rank_data_parallel_step_equals_single_process(tmp_path, uneven, spa
     gradient travels as (row id, gradient row) pairs instead of the dense [V,E] block."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from oracle import sse_oracle as O
-    world, port = 2, _free_port()
+    world, port = 2, free_port()
     mp.spawn(_dp_worker, args=(world, port, str(tmp_path), uneven, sparse), nprocs=world, join=True)
     cfg = _dp_cfg()
     p = O.init_params(cfg, seed=3)
@@ -359,7 +352,7 @@ def test_sparse_or_dense_is_decided_identically_on_every_rank(tmp_path):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from oracle import sse_oracle as O
     from util import model_params
-    world, port = 2, _free_port()
+    world, port = 2, free_port()
     mp.spawn(_dp_threshold_worker, args=(world, port, str(tmp_path)), nprocs=world, join=True)
     z0, z1 = (np.load(os.path.join(str(tmp_path), "thr%d.npz" % r)) for r in range(2))
     assert z0["kinds"].tolist() == z1["kinds"].tolist() == ["sparse", "dense"]

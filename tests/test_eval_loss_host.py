@@ -1,7 +1,6 @@
 """Host side of the forward-only loss, no GPU: Data.get_eval_pairs on the rawdata-qna fixture, and
 DataParallelTrainer.eval_loss as two gloo ranks with the numpy oracle as the engine."""
 import os
-import socket
 import sys
 
 import numpy as np
@@ -10,6 +9,7 @@ import torch.multiprocessing as mp
 
 import sse_amd  # noqa: F401
 from sse_amd import sse_data
+from tests.rank_launch import free_port
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(ROOT, "tests", "golden")
@@ -57,14 +57,6 @@ def test_get_eval_pairs_leaves_the_training_stream_alone(tmp_path):
 
 
 # ---- DataParallelTrainer.eval_loss: two gloo ranks, the oracle as the engine ----------------------------------------
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _dp_cfg():
     from util import model_params
     return model_params("dual-encoder", 60, 8, 12, 16, 16, 6)
@@ -135,7 +127,7 @@ def _dp_worker(rank, world, port, out_dir):
 def test_two_rank_eval_loss_is_the_loss_of_the_whole_batch(tmp_path):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from oracle import sse_oracle as O
-    world, port = 2, _free_port()
+    world, port = 2, free_port()
     mp.spawn(_dp_worker, args=(world, port, str(tmp_path)), nprocs=world, join=True)
     cfg = _dp_cfg()
     p = O.init_params(cfg, seed=3)

@@ -4,7 +4,7 @@ collectives), each holding its rows and tag words only and all of them the same 
 the first row after it lives on rank 1; cursors that are rows of either shard, +inf, NaN; a second page chained from the first
 on every rank.  Three ranks over a two-row index (rank 2 holds nothing, k exceeds the rows).  The result on EVERY rank must equal
 the single-handle call on the whole index -- including the (-inf, INT64_MAX) padding the merge writes into every slot past the
-real entries.  One launch of tests/after_two_rank_worker.py per rank under the launch cap of the filtered two-rank test; a child
+real entries.  One launch of tests/after_two_rank_worker.py per rank (tests/rank_launch.py); a child
 that fails ends the launch and the other children are killed; a child that died of a signal ends the pytest session."""
 import os
 
@@ -15,19 +15,14 @@ from oracle import sse_oracle as O
 from tests import after_cases as AC
 from tests import filtered_cases as FC
 from tests import rank_cases as RC
-from tests import test_gpu_filtered_two_ranks as F2
 from tests.after_two_rank_worker import next_cursors
 from tests.util import make_pair, model_params
+from tests.rank_launch import free_port, launch
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 WORKER = os.path.join(HERE, "after_two_rank_worker.py")
-
-
-def _launch(tmp, world, job, monkeypatch):
-    monkeypatch.setattr(F2, "WORKER", WORKER)                    # the launcher of the filtered pair, this worker
-    return F2._launch(tmp, world, job)
 
 
 def _single_handle(q, t, tags, any_, cs, ci, k):
@@ -65,7 +60,7 @@ def _check_ranks(out, want):
         assert int(out[r]["bruteforce"]) == 0
 
 
-def test_after_on_two_ranks_equals_the_single_handle(tmp_path, monkeypatch):
+def test_after_on_two_ranks_equals_the_single_handle(tmp_path):
     from sse_amd.sharded import shard_bounds
     tmp = str(tmp_path)
     q, t = RC.shard_case()                                       # multiples of 1/4: exact in any order; row 4000 == row 10
@@ -96,11 +91,11 @@ def test_after_on_two_ranks_equals_the_single_handle(tmp_path, monkeypatch):
     assert np.array_equal(want[1][1][1], want[0][1][1]) and want[1][2][2] == 0 and want[2][2][2] == 0
     assert (want[2][2][[0, 1] + list(range(3, Q))] == k).all()
     np.savez(os.path.join(tmp, "inputs.npz"), t=t, q=q, tags=tags, any=any_, cs=cs, ci=ci)
-    job = dict(world=2, port=F2._free_port(), inputs=os.path.join(tmp, "inputs.npz"), out_dir=tmp, bounds=[list(x) for x in bounds], k=k)
-    _check_ranks(_launch(tmp, 2, job, monkeypatch), want)
+    job = dict(world=2, port=free_port(), inputs=os.path.join(tmp, "inputs.npz"), out_dir=tmp, bounds=[list(x) for x in bounds], k=k)
+    _check_ranks(launch(WORKER, tmp, 2, job), want)
 
 
-def test_after_with_an_empty_shard(tmp_path, monkeypatch):
+def test_after_with_an_empty_shard(tmp_path):
     from sse_amd.sharded import shard_bounds
     tmp = str(tmp_path)
     q, t = RC.quarter_set(52, 3, 2, 16)
@@ -116,5 +111,5 @@ def test_after_with_an_empty_shard(tmp_path, monkeypatch):
     want = _single_handle(q, t, tags, any_, cs, ci, k)
     assert want[1][2].tolist() == [2, 1, 0] and want[2][2].tolist() == [0, 0, 0] and want[0][2].tolist() == [2, 2, 2]
     np.savez(os.path.join(tmp, "inputs.npz"), t=t, q=q, tags=tags, any=any_, cs=cs, ci=ci)
-    job = dict(world=3, port=F2._free_port(), inputs=os.path.join(tmp, "inputs.npz"), out_dir=tmp, bounds=[list(x) for x in bounds], k=k)
-    _check_ranks(_launch(tmp, 3, job, monkeypatch), want)
+    job = dict(world=3, port=free_port(), inputs=os.path.join(tmp, "inputs.npz"), out_dir=tmp, bounds=[list(x) for x in bounds], k=k)
+    _check_ranks(launch(WORKER, tmp, 3, job), want)

@@ -8,12 +8,7 @@ whole index and the float64 oracle bit for bit -- including the (-inf, INT64_MAX
 past the real entries.  One launch of tests/biased_two_rank_worker.py per rank; a child that fails, or the cap, ends the launch
 and the other children are killed; a child that died of a signal ends the pytest session -- nothing more starts on the GPU
 after a fault."""
-import json
 import os
-import socket
-import subprocess
-import sys
-import time
 
 import numpy as np
 import pytest
@@ -22,67 +17,12 @@ from oracle import sse_oracle as O
 from tests import filtered_cases as FC
 from tests import rank_cases as RC
 from tests.util import make_pair, model_params
+from tests.rank_launch import free_port, launch
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 WORKER = os.path.join(HERE, "biased_two_rank_worker.py")
-LAUNCH_CAP_S = 120                      # safety limit of the launch, not a measurement
-FAULT_CODES = (134, 139, 124, 137)
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _tail(path, n=25):
-    try:
-        with open(path, errors="replace") as f:
-            return "".join(f.readlines()[-n:])
-    except OSError:
-        return "(no output)"
-
-
-def _launch(tmp, world, job):
-    job_path = os.path.join(tmp, "job.json")
-    with open(job_path, "w") as f:
-        json.dump(job, f)
-    procs, logs = [], []
-    for r in range(world):
-        logs.append((os.path.join(tmp, "rank%d.out" % r), os.path.join(tmp, "rank%d.err" % r)))
-        with open(logs[r][0], "w") as fo, open(logs[r][1], "w") as fe:
-            procs.append(subprocess.Popen([sys.executable, WORKER, job_path, str(r)], stdout=fo, stderr=fe,
-                                          stdin=subprocess.DEVNULL, cwd=os.path.dirname(HERE)))
-    deadline = time.monotonic() + LAUNCH_CAP_S
-    ended, why = {}, None
-    while len(ended) < world and why is None:
-        for r, p in enumerate(procs):
-            if r not in ended and p.poll() is not None:
-                ended[r] = p.returncode
-                if p.returncode != 0:
-                    why = "rank %d ended with code %d" % (r, p.returncode)
-        if why is None and len(ended) < world:
-            if time.monotonic() > deadline:
-                why = "no result after %d s" % LAUNCH_CAP_S
-            else:
-                time.sleep(0.1)
-    for p in procs:                                              # nothing is left running, whatever happened
-        if p.poll() is None:
-            p.kill()
-    for p in procs:
-        p.wait()
-    if why is not None:
-        text = "launch of %d ranks: %s\n" % (world, why) + "".join(
-            "---- rank %d (%s) stderr:\n%s---- stdout:\n%s" % (r, ended.get(r, "killed"), _tail(logs[r][1]), _tail(logs[r][0], 5))
-            for r in range(world))
-        if any(rc < 0 or rc in FAULT_CODES for rc in ended.values()):
-            pytest.exit("a rank died of a signal; nothing more is started on the GPU\n" + text, returncode=3)
-        pytest.fail(text, pytrace=False)
-    return [np.load(os.path.join(tmp, "rank%d.npz" % r)) for r in range(world)]
 
 
 def _reference(q, t, tags, any_, none_, bias, w, k):
@@ -156,8 +96,8 @@ def test_biased_topk_on_two_ranks_equals_the_single_handle(tmp_path):
     unbiased = _reference(q, t, tags, any_, none_, np.zeros(N, np.float32), w, k)
     assert (unbiased[1] != want[1]).any(), "the bias changes nothing"
     np.savez(os.path.join(tmp, "inputs.npz"), t=t, q=q, tags=tags, any=any_, none=none_, bias=bias, w=w)
-    job = dict(world=2, port=_free_port(), inputs=os.path.join(tmp, "inputs.npz"), out_dir=tmp, bounds=[list(x) for x in bounds], k=k)
-    _check_ranks(_launch(tmp, 2, job), want)
+    job = dict(world=2, port=free_port(), inputs=os.path.join(tmp, "inputs.npz"), out_dir=tmp, bounds=[list(x) for x in bounds], k=k)
+    _check_ranks(launch(WORKER, tmp, 2, job), want)
 
 
 def test_biased_topk_with_an_empty_shard(tmp_path):
@@ -175,5 +115,5 @@ def test_biased_topk_with_an_empty_shard(tmp_path):
     want = _single_handle(q, t, tags, any_, none_, bias, w, k)
     assert want[2].tolist() == [1, 2, 0]
     np.savez(os.path.join(tmp, "inputs.npz"), t=t, q=q, tags=tags, any=any_, none=none_, bias=bias, w=w)
-    job = dict(world=3, port=_free_port(), inputs=os.path.join(tmp, "inputs.npz"), out_dir=tmp, bounds=[list(x) for x in bounds], k=k)
-    _check_ranks(_launch(tmp, 3, job), want)
+    job = dict(world=3, port=free_port(), inputs=os.path.join(tmp, "inputs.npz"), out_dir=tmp, bounds=[list(x) for x in bounds], k=k)
+    _check_ranks(launch(WORKER, tmp, 3, job), want)

@@ -4,7 +4,7 @@
 copy on rank 1, margin 0); positives on rank 0 only, on rank 1 only, on both, on none; margins 0, 2.5 and +inf.  The result on
 EVERY rank must equal the single-handle call on the whole index bit for bit -- lists, counts, best positive and the
 (-inf, INT64_MAX) padding -- and that call the float64 oracle (scores exact in any order: the quarter construction).  One launch
-of tests/confusions_two_rank_worker.py per rank under the launch cap of the filtered two-rank test."""
+of tests/confusions_two_rank_worker.py per rank (tests/rank_launch.py)."""
 import os
 
 import numpy as np
@@ -12,8 +12,8 @@ import pytest
 
 from oracle import sse_oracle as O
 from tests import rank_cases as RC
-from tests import test_gpu_filtered_two_ranks as F2
 from tests.util import make_pair, model_params
+from tests.rank_launch import free_port, launch
 
 pytestmark = pytest.mark.gpu
 
@@ -43,7 +43,7 @@ def _oracle(q, t, pos, margin, k):
     return ws, wi, wc, wm, wb
 
 
-def test_confusions_on_two_ranks_equal_the_single_handle(tmp_path, monkeypatch):
+def test_confusions_on_two_ranks_equal_the_single_handle(tmp_path):
     from sse_amd.sharded import shard_bounds
     tmp = str(tmp_path)
     q, t = RC.shard_case()                                       # multiples of 1/4: exact in any order
@@ -82,10 +82,9 @@ def test_confusions_on_two_ranks_equal_the_single_handle(tmp_path, monkeypatch):
     assert (want[2][2] == k).all() and (want[0][4][3::4] == PAD).all() and (want[0][2][3::4] == k).all()
     assert (want[0][2] < k).any() and (want[1][2] > want[0][2]).any()
     np.savez(os.path.join(tmp, "inputs.npz"), t=t, q=q, pos=pos)
-    job = dict(world=2, port=F2._free_port(), inputs=os.path.join(tmp, "inputs.npz"), out_dir=tmp, bounds=[list(x) for x in bounds], k=k,
+    job = dict(world=2, port=free_port(), inputs=os.path.join(tmp, "inputs.npz"), out_dir=tmp, bounds=[list(x) for x in bounds], k=k,
                margins=[repr(x) for x in MARGINS])
-    monkeypatch.setattr(F2, "WORKER", WORKER)                    # the launcher of the filtered pair, this worker
-    out = F2._launch(tmp, 2, job)
+    out = launch(WORKER, tmp, 2, job)
     for r in range(2):
         for i in range(len(MARGINS)):
             for name, w in zip(("scores", "ids", "counts", "pos_scores", "pos_ids"), want[i]):

@@ -5,79 +5,18 @@ unrestricted, a weight per query.  Both ranks must hold the same (lse, count, bo
 lse_cases.check() against the float64 reference of the WHOLE index.  One launch of tests/lse_two_rank_worker.py per rank, each
 under its own time limit; a child that fails ends the launch and the other child is killed; a child that died of a signal ends
 the pytest session -- nothing more starts on the GPU after a fault."""
-import json
 import os
-import socket
-import subprocess
-import sys
-import time
 
 import numpy as np
 import pytest
 
 from tests import lse_cases as LC
+from tests.rank_launch import free_port, launch
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 WORKER = os.path.join(HERE, "lse_two_rank_worker.py")
-CHILD_CAP_S = 100                       # each child's own limit (timeout -k): safety, not a measurement
-LAUNCH_CAP_S = 120
-FAULT_CODES = (134, 139, 124, 137)
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _tail(path, n=25):
-    try:
-        with open(path, errors="replace") as f:
-            return "".join(f.readlines()[-n:])
-    except OSError:
-        return "(no output)"
-
-
-def _launch(tmp, world, job):
-    job_path = os.path.join(tmp, "job.json")
-    with open(job_path, "w") as f:
-        json.dump(job, f)
-    procs, logs = [], []
-    for r in range(world):
-        logs.append((os.path.join(tmp, "rank%d.out" % r), os.path.join(tmp, "rank%d.err" % r)))
-        with open(logs[r][0], "w") as fo, open(logs[r][1], "w") as fe:
-            procs.append(subprocess.Popen(["timeout", "-k", "10", str(CHILD_CAP_S), sys.executable, WORKER, job_path, str(r)],
-                                          stdout=fo, stderr=fe, stdin=subprocess.DEVNULL, cwd=os.path.dirname(HERE)))
-    deadline = time.monotonic() + LAUNCH_CAP_S
-    ended, why = {}, None
-    while len(ended) < world and why is None:
-        for r, p in enumerate(procs):
-            if r not in ended and p.poll() is not None:
-                ended[r] = p.returncode
-                if p.returncode != 0:
-                    why = "rank %d ended with code %d" % (r, p.returncode)        # the first non-zero exit stops the launch
-        if why is None and len(ended) < world:
-            if time.monotonic() > deadline:
-                why = "no result after %d s" % LAUNCH_CAP_S
-            else:
-                time.sleep(0.1)
-    for p in procs:                                              # nothing is left running, whatever happened
-        if p.poll() is None:
-            p.kill()
-    for p in procs:
-        p.wait()
-    if why is not None:
-        text = "launch of %d ranks: %s\n" % (world, why) + "".join(
-            "---- rank %d (%s) stderr:\n%s---- stdout:\n%s" % (r, ended.get(r, "killed"), _tail(logs[r][1]), _tail(logs[r][0], 5))
-            for r in range(world))
-        if any(rc < 0 or rc in FAULT_CODES for rc in ended.values()):
-            pytest.exit("a rank died of a signal or at its time limit; nothing more is started on the GPU\n" + text, returncode=3)
-        pytest.fail(text, pytrace=False)
-    return [np.load(os.path.join(tmp, "rank%d.npz" % r)) for r in range(world)]
 
 
 CUT = 601
@@ -110,9 +49,9 @@ def test_lse_on_two_ranks_passes_the_check_of_the_whole_index(tmp_path):
     assert e[1, :CUT].any() and e[1, CUT:].any() and I["any"][1] == 0
     assert np.array_equal(LC.inputs(PLAIN)["q"], I["q"]) and np.array_equal(LC.inputs(PLAIN)["t"], I["t"])
     np.savez(os.path.join(tmp, "inputs.npz"), t=I["t"], q=I["q"], tags=I["tags"], any=I["any"], none=I["none"], bias=I["bias"], w=I["w"])
-    job = dict(world=2, port=_free_port(), inputs=os.path.join(tmp, "inputs.npz"), out_dir=tmp, bounds=[list(x) for x in bounds],
+    job = dict(world=2, port=free_port(), inputs=os.path.join(tmp, "inputs.npz"), out_dir=tmp, bounds=[list(x) for x in bounds],
                scale=CASE.scale)
-    out = _launch(tmp, 2, job)
+    out = launch(WORKER, tmp, 2, job)
     for key in ("lse", "count", "bound", "plain_lse", "plain_count", "plain_bound"):
         assert out[0][key].tobytes() == out[1][key].tobytes(), key
     for r in range(2):

@@ -17,11 +17,7 @@ arena at util.GRAD_BARS_EXACT / LOSS_REL_EXACT against the float64 gradient of t
 of a float64 clip + Adagrad of that arena (tests/test_gpu_train_grads.py); on the `even` shape the bars of
 tests/test_gpu_train.py::test_data_parallel_two_logical_ranks; three free-running oracle steps at the bars of
 tests/test_gpu_rccl.py::test_data_parallel_step_through_rccl_all_reduce on `even` and `three`."""
-import json
 import os
-import socket
-import subprocess
-import sys
 import time
 
 import numpy as np
@@ -31,74 +27,24 @@ from oracle import sse_oracle as O
 from tests.test_gpu_train_grads import case_batch, cnn_min_pool_gap
 from tests.util import (GRAD_BARS_EXACT, LOSS_REL_EXACT, check_grads, check_tail, make_pair, model_params, oracle_params,
                         random_ids, reference_apply, reference_grads)
+from tests.rank_launch import free_port, run_ranks
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 WORKER = os.path.join(HERE, "two_rank_worker.py")
 LAUNCH_CAP_S = 300                      # safety limit of one launch, not a measurement
-FAULT_CODES = (134, 139, 124, 137)      # abort, segmentation fault, time limits: as good as a signal
 
 
 # ---- launching ---------------------------------------------------------------------------------------------------------
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _tail(path, n=25):
-    try:
-        with open(path, errors="replace") as f:
-            return "".join(f.readlines()[-n:])
-    except OSError:
-        return "(no output)"
-
-
 def _launch(tmp, kind, world, cases, inputs):
     """Runs `world` workers on one job; returns [{case id: loaded npz} per rank].  Fails with every rank's stderr tail when a
     rank fails or the cap passes; ends the session when a rank died of a signal."""
     assert world <= 3, "three children plus pytest is the most this module puts on the GPU"
     tmp = str(tmp)
     np.savez(os.path.join(tmp, "inputs.npz"), **inputs)
-    job = dict(kind=kind, world=world, port=_free_port(), cases=cases, inputs=os.path.join(tmp, "inputs.npz"), out_dir=tmp)
-    job_path = os.path.join(tmp, "job.json")
-    with open(job_path, "w") as f:
-        json.dump(job, f)
-    procs, logs = [], []
-    for r in range(world):
-        logs.append((os.path.join(tmp, "rank%d.out" % r), os.path.join(tmp, "rank%d.err" % r)))
-        with open(logs[r][0], "w") as fo, open(logs[r][1], "w") as fe:
-            procs.append(subprocess.Popen([sys.executable, WORKER, job_path, str(r)], stdout=fo, stderr=fe,
-                                          stdin=subprocess.DEVNULL, cwd=os.path.dirname(HERE)))
-    deadline = time.monotonic() + LAUNCH_CAP_S
-    ended = {}                                                   # rank -> return code of a child that ended BY ITSELF
-    why = None
-    while len(ended) < world and why is None:
-        for r, p in enumerate(procs):
-            if r not in ended and p.poll() is not None:
-                ended[r] = p.returncode
-                if p.returncode != 0:
-                    why = "rank %d ended with code %d" % (r, p.returncode)
-        if why is None and len(ended) < world:
-            if time.monotonic() > deadline:
-                why = "no result after %d s" % LAUNCH_CAP_S
-            else:
-                time.sleep(0.1)
-    for p in procs:                                              # nothing is left running, whatever happened
-        if p.poll() is None:
-            p.kill()
-    for p in procs:
-        p.wait()
-    if why is not None:
-        text = "%s launch of %d ranks: %s\n" % (kind, world, why) + "".join(
-            "---- rank %d (%s) stderr:\n%s---- stdout:\n%s" % (r, ended.get(r, "killed"), _tail(logs[r][1]), _tail(logs[r][0], 5))
-            for r in range(world))
-        if any(rc < 0 or rc in FAULT_CODES for rc in ended.values()):
-            pytest.exit("a rank died of a signal; nothing more is started on the GPU\n" + text, returncode=3)
-        pytest.fail(text, pytrace=False)
+    job = dict(kind=kind, world=world, port=free_port(), cases=cases, inputs=os.path.join(tmp, "inputs.npz"), out_dir=tmp)
+    run_ranks(WORKER, tmp, world, job, LAUNCH_CAP_S)
     return [{c["id"]: np.load(os.path.join(tmp, "%s_rank%d.npz" % (c["id"], r))) for c in cases} for r in range(world)]
 
 

@@ -8,7 +8,6 @@
 (2) Two `gloo` ranks: that engine behind the product's DataParallelTrainer(global_negatives=True); the updated variables equal
     ONE engine's in-batch step on the concatenated batch, and the default (local negatives) does not."""
 import os
-import socket
 import sys
 
 import numpy as np
@@ -19,6 +18,7 @@ import torch.multiprocessing as mp
 
 from oracle import sse_oracle as O
 from tests import inbatch_cases as IC
+from tests.rank_launch import free_port
 from tests.test_distributed_gloo import OracleEngine
 from tests.util import GRAD_BARS_EXACT, LOSS_REL_EXACT, check_grads, oracle_float64
 
@@ -235,14 +235,6 @@ def test_planted_defects_are_rejected(rows, defect):
 
 
 # ---- (2) two gloo ranks behind the product's DataParallelTrainer -------------------------------------------------------------
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _worker(rank, world, port, out_dir, rows, global_negatives):
     sys.path.insert(0, ROOT)
     os.environ["SSE_NO_TORCH"] = "1"
@@ -275,7 +267,7 @@ def test_two_gloo_ranks_with_global_negatives_equal_one_engine_on_the_concatenat
     moved_want = {n: want[n] - before[n] for n in names}
     assert all(np.abs(moved_want[n]).max() > 0 for n in names)
     for global_negatives in (True, False):
-        mp.spawn(_worker, args=(2, _free_port(), str(tmp_path), rows, global_negatives), nprocs=2, join=True)
+        mp.spawn(_worker, args=(2, free_port(), str(tmp_path), rows, global_negatives), nprocs=2, join=True)
         out = [np.load(os.path.join(str(tmp_path), "g%d_rank%d.npz" % (int(global_negatives), r))) for r in range(2)]
         for n in names:
             assert np.array_equal(out[0][n], out[1][n]), n         # the ranks stay in lock-step, bit for bit
