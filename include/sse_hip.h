@@ -213,7 +213,8 @@ int sse_set_option(sse_handle *h, const char *name, int32_t value);
  * "score_filtered_collected_rows" / "score_filtered_bruteforce_queries" / "score_filtered_tiles_skipped": see
  * sse_score_topk_filtered.
  * "score_grouped_collected_rows" / "score_grouped_bruteforce_queries": see sse_score_topk_grouped.
- * "score_lse_calls" / "score_lse_tiles_skipped": see sse_score_lse. */
+ * "score_lse_calls" / "score_lse_tiles_skipped": see sse_score_lse.
+ * "index_update_calls" / "index_update_rows" / "index_append_rows" / "index_grow_copies": see sse_index_update. */
 int sse_get_counter(sse_handle *h, const char *name, int64_t *value);
 
 /* tf.nn.l2_normalize(x, dim=-1) on device rows (sse_model.py:282-283). */
@@ -306,6 +307,51 @@ int sse_index_upload(sse_handle *h, const float *rows_host, int64_t N, int32_t S
 int sse_index_upload_f64(sse_handle *h, const double *rows_host, int64_t N, int32_t S, int64_t id_base);
 int sse_index_set_dev(sse_handle *h, const float *rows_dev, int64_t N, int32_t S, int64_t id_base,
                       void *stream);
+
+/* Rows, dimension and id_base of the resident index, and norm_max, the largest row norm as the library formed it in fp32 (the
+ * bound every certificate of the scorer scales with); zeros when no index is resident; any pointer may be NULL.  The id an
+ * append will give its first row is id_base + N. */
+int sse_index_shape(sse_handle *h, int64_t *N, int32_t *S, int64_t *id_base, float *norm_max);
+
+/* Update and append rows of the resident index in place (DESIGN K6n).  The contract: after any sequence of these calls the
+ * handle answers every scoring entry point, bit for bit and counter for counter, as a fresh handle that was given the final
+ * rows through the same upload entry and then the final tags, group keys and bias.  The cost is O(M S) plus one pass over N
+ * floats (the norm bound and max |bias| can fall as well as rise), never O(N S) -- except the copy of an append that
+ * outgrows its allocation (storage grows geometrically on that path only; counter "index_grow_copies").
+ *
+ * update: ids [M] are global ids in [id_base, id_base + N), strictly increasing; rows [M][S] replace those rows.  rows may
+ * be NULL when at least one column is given: then only the rows' tag words, group keys or bias values change.  A non-NULL
+ * column must be set on the resident index (sse_index_set_tags / _groups / _bias); a NULL column keeps every row's value.
+ * append: the M new rows take the ids id_base + N .. id_base + N + M - 1 (N grows by M; id_base and S never change); each
+ * column must be given exactly when it is set on the resident index (no default key or tag is invented).
+ * The _f64 forms serve an index uploaded with sse_index_upload_f64: they patch its float64 rows and form the fp32 images
+ * from (float) of them as that upload does.  A float form with rows on such an index, and an _f64 form on any other, is
+ * refused: there is one source of truth.
+ * Refused with a message before anything is touched: no resident index, a wrong column combination, an id out of range or
+ * ids not strictly increasing (host forms), N + M > 2147483000, a non-finite host bias.  M == 0 succeeds and changes
+ * nothing.  The _dev forms take every operand from device memory and run on `stream`; sse_index_update_dev checks the ids
+ * on the device: a bad list raises the handle's error word, every later kernel of the call that takes the list reads it and
+ * writes nothing, and the call fails having changed nothing (the tile sums and max |bias| are formed again from the unchanged
+ * columns).  Both _dev forms synchronise `stream` once (the norm bound lives on the host), and an append that
+ * reallocates frees the old storage: work queued on OTHER streams must have finished with the index before it.
+ *
+ * There is no removal and no compaction: a row's id is id_base + its position, and compaction would renumber other rows
+ * behind the caller's back.  To hide a row, reserve one tag bit for "hidden", set it on that row with a columns-only update
+ * (rows == NULL, tags = the row's word with the bit), and pass the bit as none_of to sse_score_topk_filtered / _grouped /
+ * _after; clearing the bit brings the row back.
+ * Counters: "index_update_calls", "index_update_rows", "index_append_rows", "index_grow_copies". */
+int sse_index_update(sse_handle *h, const int64_t *ids, const float *rows, int64_t M, const uint64_t *tags,
+                     const int64_t *groups, const float *bias);
+int sse_index_update_f64(sse_handle *h, const int64_t *ids, const double *rows, int64_t M, const uint64_t *tags,
+                         const int64_t *groups, const float *bias);
+int sse_index_update_dev(sse_handle *h, const int64_t *ids_dev, const float *rows_dev, int64_t M, const uint64_t *tags_dev,
+                         const int64_t *groups_dev, const float *bias_dev, void *stream);
+int sse_index_append(sse_handle *h, const float *rows, int64_t M, const uint64_t *tags, const int64_t *groups,
+                     const float *bias);
+int sse_index_append_f64(sse_handle *h, const double *rows, int64_t M, const uint64_t *tags, const int64_t *groups,
+                         const float *bias);
+int sse_index_append_dev(sse_handle *h, const float *rows_dev, int64_t M, const uint64_t *tags_dev,
+                         const int64_t *groups_dev, const float *bias_dev, void *stream);
 
 /* np.dot(srcEnc, tgtEnc.T) + data_utils.getSortedResults, first k columns only
  * (sse_evaluator.py:110-112, data_utils.py:263-267, sse_demo.py:126-129).

@@ -49,6 +49,13 @@ SYMBOLS = {
     "sse_index_upload": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64]),
     "sse_index_upload_f64": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64]),
     "sse_index_set_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, _P]),
+    "sse_index_shape": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float)]),
+    "sse_index_update": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P]),
+    "sse_index_update_f64": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P]),
+    "sse_index_update_dev": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "sse_index_append": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
+    "sse_index_append_f64": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
+    "sse_index_append_dev": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P]),
     "sse_score_topk": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     "sse_score_topk_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     "sse_score_rank": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P]),
@@ -365,6 +372,87 @@ class Handle(object):
     def index_set_dev(self, rows_ptr, N, S, id_base=0, stream=0):
         self.check(self.lib.sse_index_set_dev(self._h, rows_ptr, N, S, id_base, stream))
         self.index_gen += 1
+
+    def index_shape(self):
+        """(rows, dimension, id_base) of the resident index as the library holds them; zeros when none is resident."""
+        n, s, b = C.c_int64(), C.c_int32(), C.c_int64()
+        self.check(self.lib.sse_index_shape(self._h, C.byref(n), C.byref(s), C.byref(b), None))
+        return int(n.value), int(s.value), int(b.value)
+
+    def index_norm_max(self):
+        """The largest row norm of the resident index as the library formed it (float32), the bound its certificates use."""
+        v = C.c_float()
+        self.check(self.lib.sse_index_shape(self._h, None, None, None, C.byref(v)))
+        return np.float32(v.value)
+
+    index_rows = property(lambda self: self.index_shape()[0])
+    index_base = property(lambda self: self.index_shape()[2])
+
+    # In-place updates (sse_index_update* / sse_index_append*).  They change the holder's own index, so index_gen stays.
+    @staticmethod
+    def _index_delta_args(rows, M, tags, groups, bias):
+        """rows [M,S] float32 / float64 (or None) and the three optional columns of M values, contiguous."""
+        if rows is not None:
+            rows = np.ascontiguousarray(rows)
+            if rows.dtype != np.float64:
+                rows = np.ascontiguousarray(rows, dtype=np.float32)
+            if rows.ndim != 2 or (M is not None and rows.shape[0] != M):
+                raise ValueError("rows must be [M,S], one row per id")
+            M = rows.shape[0]
+        cols = []
+        for name, v, dt in (("tags", tags, np.uint64), ("groups", groups, np.int64), ("bias", bias, np.float32)):
+            if v is not None:
+                v = np.ascontiguousarray(v, dtype=dt).reshape(-1)
+                if M is not None and v.shape[0] != M:
+                    raise ValueError("%s must hold one value per row (%d), got %d" % (name, M, v.shape[0]))
+                M = v.shape[0]
+            cols.append(v)
+        return rows, cols, M
+
+    def index_update(self, ids, rows=None, tags=None, groups=None, bias=None):
+        """Replace rows of the resident index in place: ids int64 [M] global ids (any order; of a repeated id the LAST
+        entry wins), rows [M,S] (float64 selects the _f64 form, for an index uploaded as float64) and / or one tag word,
+        group key or bias value per id.  rows=None changes the given columns only.  After the call the handle answers as
+        one freshly given the final rows and columns."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        rows, cols, M = self._index_delta_args(rows, ids.shape[0], tags, groups, bias)
+        # sorted, the last of equal ids kept: a stable sort of the reversed list puts it first in its run
+        order = (ids.shape[0] - 1 - np.argsort(ids[::-1], kind="stable")).astype(np.int64)
+        keep = np.ones(order.shape[0], bool)
+        keep[1:] = ids[order][1:] != ids[order][:-1]
+        order = order[keep]
+        if order.shape[0] != ids.shape[0] or (order[1:] < order[:-1]).any():   # (ids already strictly increasing: no copies)
+            ids = np.ascontiguousarray(ids[order])
+            if rows is not None:
+                rows = np.ascontiguousarray(rows[order])
+            cols = [None if c is None else np.ascontiguousarray(c[order]) for c in cols]
+        fn = self.lib.sse_index_update_f64 if rows is not None and rows.dtype == np.float64 else self.lib.sse_index_update
+        self.check(fn(self._h, _ptr(ids), _opt(rows), ids.shape[0], _opt(cols[0]), _opt(cols[1]), _opt(cols[2])))
+
+    def index_update_dev(self, ids_ptr, rows_ptr, M, tags_ptr=None, groups_ptr=None, bias_ptr=None, stream=0):
+        """index_update on device pointers: ids int64 [M] strictly increasing (checked on the device: a bad list changes
+        nothing and raises), rows float32 [M,S] or None / 0.  Runs on `stream`, which is synchronised once."""
+        self.check(self.lib.sse_index_update_dev(self._h, ids_ptr, rows_ptr or None, int(M), tags_ptr or None, groups_ptr or None,
+                                                 bias_ptr or None, stream))
+
+    def index_append(self, rows, tags=None, groups=None, bias=None):
+        """Append rows [M,S] behind the resident index (float64 selects the _f64 form); each column must be given exactly
+        when it is set on the index.  Returns the id of the first new row."""
+        rows, cols, M = self._index_delta_args(rows, None, tags, groups, bias)
+        if rows is None:
+            raise ValueError("rows must be [M,S]")
+        first = self.index_base + self.index_rows
+        fn = self.lib.sse_index_append_f64 if rows.dtype == np.float64 else self.lib.sse_index_append
+        self.check(fn(self._h, _ptr(rows), M, _opt(cols[0]), _opt(cols[1]), _opt(cols[2])))
+        return first
+
+    def index_append_dev(self, rows_ptr, M, tags_ptr=None, groups_ptr=None, bias_ptr=None, stream=0):
+        """index_append on device pointers (rows float32 [M,S]), on `stream`, which is synchronised once.  Returns the id
+        of the first new row."""
+        first = self.index_base + self.index_rows
+        self.check(self.lib.sse_index_append_dev(self._h, rows_ptr, int(M), tags_ptr or None, groups_ptr or None, bias_ptr or None,
+                                                 stream))
+        return first
 
     def score_topk(self, queries, k):
         q = np.ascontiguousarray(queries, dtype=np.float32)

@@ -48,12 +48,10 @@ __global__ __launch_bounds__(256) void pack_rows_vec_kernel(const f32x4 *__restr
     for (int q = qq; q < Q4; q += 8) {
       f32x4 v = {0, 0, 0, 0};
       if (r < R && q < C4) v = rows[(size_t)r * C4 + q];
-      ss += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+      ss = row_sumsq_add4(ss, v);
       out[((size_t)rt * KG + (q >> 1)) * 64 + (q & 1) * 32 + rl] = v;
     }
-    ss += __shfl_xor(ss, 1);
-    ss += __shfl_xor(ss, 2);
-    ss += __shfl_xor(ss, 4);
+    ss = row_sumsq_reduce8(ss);
     best = fmaxf(best, ss);
   }
   if (norm_bits) {
@@ -288,9 +286,8 @@ __global__ void row_norm2_max_kernel_k(const float *__restrict__ x, int64_t rows
   float best = 0.0f;
   for (int64_t r = wave0; r < rows; r += nwaves) {
     float ss = 0.0f;
-    for (int c = lane; c < cols; c += 64) ss += x[(size_t)r * cols + c] * x[(size_t)r * cols + c];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+    for (int c = lane; c < cols; c += 64) ss = row_sumsq_add1(ss, x[(size_t)r * cols + c]);
+    ss = row_sumsq_reduce64(ss);
     best = fmaxf(best, ss);
   }
   if (lane == 0) atomicMax(out, __float_as_uint(best));

@@ -945,31 +945,55 @@ hipError_t launch_pack_rows_bf16(const float *rows, int64_t R, int C, void *out,
   return hipGetLastError();
 }
 
-// the resident fp32 fragment index [NT][KG][256 floats] -> bf16 fragment copy [NT][ceil(KG/2)][1 KiB]
+// the resident fp32 fragment index [NT][KG][256 floats] -> bf16 fragment copy [NT][ceil(KG/2)][1 KiB]: the 16 bytes lane l
+// of block (tile, kg16) holds
+__device__ __forceinline__ f32x4 frag32_to_bf16_piece(const f32x4 *__restrict__ in, int KG, int64_t tile, int kg16, int l) {
+  const int kg = kg16 * 2 + (l >> 5), r = l & 31;
+  f32x4 lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
+  if (kg < KG) {
+    lo = in[((size_t)tile * KG + kg) * 64 + r];
+    hi = in[((size_t)tile * KG + kg) * 64 + 32 + r];
+  }
+  unsigned w[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float a = (j < 2) ? lo[2 * j] : hi[2 * (j - 2)], b = (j < 2) ? lo[2 * j + 1] : hi[2 * (j - 2) + 1];
+    unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
+    ua += 0x7FFFu + ((ua >> 16) & 1u);
+    ub += 0x7FFFu + ((ub >> 16) & 1u);
+    w[j] = (ua >> 16) | (ub & 0xFFFF0000u);
+  }
+  return __builtin_bit_cast(f32x4, u32x4{w[0], w[1], w[2], w[3]});
+}
 __global__ void frag32_to_bf16_kernel(const f32x4 *__restrict__ in, int64_t NT, int KG, int KG16, int64_t total8,
                                       f32x4 *__restrict__ out) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total8; i += (int64_t)gridDim.x * blockDim.x) {
-    const int l = (int)(i & 63);
     const int64_t blk = i >> 6;
-    const int kg16 = (int)(blk % KG16);
-    const int64_t tile = blk / KG16;
-    const int kg = kg16 * 2 + (l >> 5), r = l & 31;
-    f32x4 lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
-    if (kg < KG) {
-      lo = in[((size_t)tile * KG + kg) * 64 + r];
-      hi = in[((size_t)tile * KG + kg) * 64 + 32 + r];
-    }
-    unsigned w[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float a = (j < 2) ? lo[2 * j] : hi[2 * (j - 2)], b = (j < 2) ? lo[2 * j + 1] : hi[2 * (j - 2) + 1];
-      unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
-      ua += 0x7FFFu + ((ua >> 16) & 1u);
-      ub += 0x7FFFu + ((ub >> 16) & 1u);
-      w[j] = (ua >> 16) | (ub & 0xFFFF0000u);
-    }
-    out[i] = __builtin_bit_cast(f32x4, u32x4{w[0], w[1], w[2], w[3]});
+    out[i] = frag32_to_bf16_piece(in, KG, blk / KG16, (int)(blk % KG16), (int)(i & 63));
   }
+}
+// ... for the tiles of a row list (an index update): item = (list entry, kg16, lane); entries that are not the first of
+// their tile do nothing
+__global__ void frag32_to_bf16_rows_kernel(IndexRowList rl, const f32x4 *__restrict__ in, int KG, int KG16, int64_t total8,
+                                           f32x4 *__restrict__ out) {
+  if (index_list_refused(rl)) return;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total8; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t blk = i >> 6, m = blk / KG16;
+    if (!index_list_tile_head(rl, m)) continue;
+    const int64_t tile = index_list_row(rl, m) >> 5;
+    const int kg16 = (int)(blk % KG16), l = (int)(i & 63);
+    out[((size_t)tile * KG16 + kg16) * 64 + l] = frag32_to_bf16_piece(in, KG, tile, kg16, l);
+  }
+}
+
+hipError_t launch_frag32_to_bf16_rows(const IndexRowList &l, const float *idxp, int KG, void *out, hipStream_t st) {
+  const int KG16 = (KG + 1) / 2;
+  const int64_t total8 = l.M * KG16 * 64;
+  if (total8 == 0) return hipSuccess;
+  const int64_t blocks = (total8 + 255) / 256;
+  hipLaunchKernelGGL(frag32_to_bf16_rows_kernel, dim3((int)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, st, l,
+                     reinterpret_cast<const f32x4 *>(idxp), KG, KG16, total8, reinterpret_cast<f32x4 *>(out));
+  return hipGetLastError();
 }
 
 hipError_t launch_frag32_to_bf16(const float *idxp, int64_t NT, int KG, void *out, hipStream_t stream) {
@@ -984,24 +1008,46 @@ hipError_t launch_frag32_to_bf16(const float *idxp, int64_t NT, int KG, void *ou
 
 // the resident fp32 fragment index -> split-bf16 image [NT][KB][hi 1 KiB | lo 1 KiB], KB = ceil(KG/2): lane (row, k octet)
 // owns k = 16 kb + 8 (lane >> 5) + 0 .. 7 of its row, the A operand of v_mfma_f32_32x32x16_bf16 (k-groups past KG: zeros)
+__device__ __forceinline__ void frag32_to_split_bf16_piece(const f32x4 *__restrict__ in, int KG, int KB, int64_t tile, int kb, int l,
+                                                           sse_u32x4 *__restrict__ out) {
+  const int kg = kb * 2 + (l >> 5), r = l & 31;
+  f32x4 lo4 = {0, 0, 0, 0}, hi4 = {0, 0, 0, 0};
+  if (kg < KG) {
+    lo4 = in[((size_t)tile * KG + kg) * 64 + r];
+    hi4 = in[((size_t)tile * KG + kg) * 64 + 32 + r];
+  }
+  const float v[8] = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
+  sse_u32x4 h, lw;
+  sse_split8(v, h, lw);
+  const size_t blk = (size_t)tile * KB + kb;
+  out[blk * 128 + l] = h;
+  out[blk * 128 + 64 + l] = lw;
+}
 __global__ void frag32_to_split_bf16_kernel(const f32x4 *__restrict__ in, int KG, int KB, int64_t total8, sse_u32x4 *__restrict__ out) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total8; i += (int64_t)gridDim.x * blockDim.x) {
-    const int l = (int)(i & 63);
     const int64_t blk = i >> 6;
-    const int kb = (int)(blk % KB);
-    const int64_t tile = blk / KB;
-    const int kg = kb * 2 + (l >> 5), r = l & 31;
-    f32x4 lo4 = {0, 0, 0, 0}, hi4 = {0, 0, 0, 0};
-    if (kg < KG) {
-      lo4 = in[((size_t)tile * KG + kg) * 64 + r];
-      hi4 = in[((size_t)tile * KG + kg) * 64 + 32 + r];
-    }
-    const float v[8] = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-    sse_u32x4 h, lw;
-    sse_split8(v, h, lw);
-    out[(size_t)blk * 128 + l] = h;
-    out[(size_t)blk * 128 + 64 + l] = lw;
+    frag32_to_split_bf16_piece(in, KG, KB, blk / KB, (int)(blk % KB), (int)(i & 63), out);
   }
+}
+// ... for the tiles of a row list (an index update), as frag32_to_bf16_rows_kernel
+__global__ void frag32_to_split_bf16_rows_kernel(IndexRowList rl, const f32x4 *__restrict__ in, int KG, int KB, int64_t total8,
+                                                 sse_u32x4 *__restrict__ out) {
+  if (index_list_refused(rl)) return;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total8; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t blk = i >> 6, m = blk / KB;
+    if (!index_list_tile_head(rl, m)) continue;
+    frag32_to_split_bf16_piece(in, KG, KB, index_list_row(rl, m) >> 5, (int)(blk % KB), (int)(i & 63), out);
+  }
+}
+
+hipError_t launch_frag32_to_split_bf16_rows(const IndexRowList &l, const float *idxp, int KG, void *out, hipStream_t st) {
+  const int KB = (KG + 1) / 2;
+  const int64_t total8 = l.M * KB * 64;
+  if (total8 == 0) return hipSuccess;
+  const int64_t blocks = (total8 + 255) / 256;
+  hipLaunchKernelGGL(frag32_to_split_bf16_rows_kernel, dim3((int)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, st, l,
+                     reinterpret_cast<const f32x4 *>(idxp), KG, KB, total8, reinterpret_cast<sse_u32x4 *>(out));
+  return hipGetLastError();
 }
 
 hipError_t launch_frag32_to_split_bf16(const float *idxp, int64_t NT, int KG, void *out, hipStream_t stream) {

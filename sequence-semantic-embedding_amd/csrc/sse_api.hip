@@ -167,6 +167,14 @@ struct sse_handle {
   int64_t idx_N = 0, idx_base = 0;
   int idx_S = 0;
   float idx_norm_max = 1.0f;
+  // in-place updates (sse_index_update* / sse_index_append*, DESIGN K6n): the per-row sums of squares behind idx_norm_max
+  // (built from idxp by the first update after an upload; valid: idx_norm2_valid), which of the two pack paths formed that
+  // bound (idx_norm_vec: pack_rows_vec_kernel), the bytes idx64 was allocated with, the staged operands of the host forms,
+  // the counters "index_update_calls" / "index_update_rows" / "index_append_rows" / "index_grow_copies"
+  DevBuf idx_norm2, s_upd;
+  bool idx_norm2_valid = false, idx_norm_vec = false;
+  size_t idx64_cap = 0;
+  int64_t index_update_calls = 0, index_update_rows = 0, index_append_rows = 0, index_grow_copies = 0;
   // scratch
   DevBuf s_ids, s_out, s_q, s_qp, s_ps, s_pi, s_cert, s_os, s_oi, s_tmp, s_tmp2, s_feat, s_zero, s_map;
   DevBuf s_qmap, s_qc;     // fp32 second chance of the bf16 candidate pass: the uncertified queries as a dense set
@@ -1009,6 +1017,8 @@ int check_err_flag(sse_handle *h, hipStream_t st, int32_t *bits = nullptr) {
                                   "this index; the call wrote no output");
     if (flag & 32) return fail(h, "sse_score_above_dev: a pair_q out of [0, Q); the call wrote no output");
     if (flag & 64) return fail(h, "sse_score_above: the emitting pass found other rows than the counting pass; the lists of the call are not valid");
+    if (flag & SSE_ERR_INDEX_IDS) return fail(h, "sse_index_update_dev: an id outside the index, or ids not strictly increasing; the "
+                                                 "call changed nothing");
     if (flag & 4) return fail(h, "LSTM cluster kernel: a workgroup of a cluster did not arrive (device oversubscribed?); the "
                                  "host-buffer entry points fall back to the few-sequences kernel by themselves, for "
                                  "sse_encode_dev set option lstm_persist_rows to 0");
@@ -1045,6 +1055,8 @@ int index_from_dev_rows(sse_handle *h, const float *rows_dev, int64_t N, int S, 
   if (reserve(h, h->s_tmp2, 16)) return 1;
   HIPCHECK(h, hipMemsetAsync(h->s_tmp2.p, 0, 4, st));
   HIPCHECK(h, launch_pack_rows_norm(rows_dev, N, S, h->idxp, (float *)h->s_tmp2.p, st));
+  h->idx_norm_vec = (S & 3) == 0 && (reinterpret_cast<uintptr_t>(rows_dev) & 15) == 0;  // (the path launch_pack_rows_norm took)
+  h->idx_norm2_valid = false;
   // the small-index scorer's split-bf16 image: once per index, from the fragment copy just written (the index is resident
   // and constant from call to call); an index it cannot serve leaves no image behind
   h->idx_x3_valid = false;
@@ -1071,6 +1083,209 @@ int index_from_dev_rows(sse_handle *h, const float *rows_dev, int64_t N, int S, 
   h->idx_S = S;
   h->idx_base = id_base;
   return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// sse_index_update* / sse_index_append* (DESIGN K6n).  After any sequence of them the handle answers as a fresh handle given
+// the final rows, tags, keys and bias.
+
+// an allocation of at least `need` bytes that still holds its first `used` bytes (reserve() drops the contents); the growth
+// is geometric; *grew reports a reallocation
+int grow_keep(sse_handle *h, void **p, size_t *cap, size_t used, size_t need, hipStream_t st, bool *grew = nullptr) {
+  if (need <= *cap) return 0;
+  const size_t ncap = std::max(need, *cap * 2) + 256;
+  void *np = nullptr;
+  HIPCHECK(h, hipMalloc(&np, ncap));
+  if (*p && used) {
+    const hipError_t e = hipMemcpyAsync(np, *p, used, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) {
+      (void)hipFree(np);
+      return fail(h, "index growth: copy failed: %s", hipGetErrorString(e));
+    }
+  }
+  HIPCHECK(h, hipStreamSynchronize(st));
+  if (*p) HIPCHECK(h, hipFree(*p));
+  *p = np;
+  *cap = ncap;
+  if (grew) *grew = true;
+  return 0;
+}
+int grow_keep(sse_handle *h, DevBuf &b, size_t used, size_t need, hipStream_t st) { return grow_keep(h, &b.p, &b.cap, used, need, st); }
+
+struct IndexDelta {
+  const char *name;        // the entry point, for messages
+  bool append;
+  const int64_t *ids;      // update: [M] global ids on the device (already checked, or checked on the device: check_ids)
+  bool check_ids;
+  const float *rows32;     // [M][S] on the device; at most one of the two
+  const double *rows64;
+  int64_t M;
+  const uint64_t *tags;    // [M] on the device, or nullptr
+  const int64_t *groups;
+  const float *bias;
+};
+
+// every refusal that needs no look at the operands' contents; nothing has been touched when one fires
+int index_delta_check(sse_handle *h, const char *name, bool append, bool f64, bool has_rows, int64_t M, const void *tags,
+                      const void *groups, const void *bias) {
+  if (!h->idxp || h->idx_N <= 0) return fail(h, "%s: no index uploaded", name);
+  if (M < 0) return fail(h, "%s: M = %lld", name, (long long)M);
+  if (has_rows && f64 != (h->idx64 != nullptr))
+    return fail(h, f64 ? "%s: the resident index holds no float64 rows (it was not uploaded with sse_index_upload_f64); use the float form"
+                       : "%s: the resident index holds float64 rows (sse_index_upload_f64); use the _f64 form", name);
+  if (append) {
+    if (!has_rows) return fail(h, "%s: rows must not be NULL", name);
+    if ((tags != nullptr) != h->tags_set || (groups != nullptr) != h->groups_set || (bias != nullptr) != h->bias_set)
+      return fail(h, "%s: tags, groups and bias must be given exactly when the resident index has them set (tags %s, groups %s, bias %s); "
+                     "the index is unchanged", name, h->tags_set ? "set" : "not set", h->groups_set ? "set" : "not set",
+                  h->bias_set ? "set" : "not set");
+    if (h->idx_N + M > (int64_t)2147483000) return fail(h, "%s: %lld + %lld rows: index shard too large for int32 row ids", name,
+                                                         (long long)h->idx_N, (long long)M);
+  } else {
+    if (!has_rows && !tags && !groups && !bias) return fail(h, "%s: rows is NULL and so is every column: nothing to update", name);
+    if ((tags && !h->tags_set) || (groups && !h->groups_set) || (bias && !h->bias_set))
+      return fail(h, "%s: a column was given that is not set on the resident index (sse_index_set_tags / _groups / _bias first); "
+                     "the index is unchanged", name);
+  }
+  return 0;
+}
+
+// room for `newN` rows in every per-index buffer, contents kept; new tiles of idxp, the tags and the bias start as zeros
+int index_grow(sse_handle *h, int64_t newN, hipStream_t st) {
+  const int64_t N = h->idx_N, NT = (N + 31) / 32, newNT = (newN + 31) / 32;
+  const size_t S = (size_t)h->idx_S, KG = (S + 7) / 8, KB = (KG + 1) / 2;
+  bool grew = false;
+  if (grow_keep(h, (void **)&h->idxp, &h->idxp_cap, (size_t)NT * KG * 1024, (size_t)newNT * KG * 1024, st, &grew)) return 1;
+  if (grew) h->index_grow_copies += 1;
+  if (newNT > NT) HIPCHECK(h, hipMemsetAsync(h->idxp + (size_t)NT * KG * 256, 0, (size_t)(newNT - NT) * KG * 1024, st));
+  // (an upload of that many rows keeps no row-major copy / no split image; the two flags fall only after the last
+  // allocation that can fail, so a refused append leaves the routes as they were)
+  const bool drop_rm = h->idx_rm_valid && (size_t)newN * S * sizeof(float) > ((size_t)64 << 20);
+  const bool drop_x3 = h->idx_x3_valid && !score_small_index_applies(1024, (int)KG, newNT);
+  if (h->idx_rm_valid && !drop_rm && grow_keep(h, h->idx_rm, (size_t)N * S * 4, (size_t)newN * S * 4, st)) return 1;
+  if (h->idx64) {
+    if (h->idx64_cap < (size_t)N * S * 8) h->idx64_cap = (size_t)N * S * 8;
+    if (grow_keep(h, (void **)&h->idx64, &h->idx64_cap, (size_t)N * S * 8, (size_t)newN * S * 8, st)) return 1;
+  }
+  if (h->idx_x3_valid && !drop_x3 && grow_keep(h, h->idx_x3, (size_t)NT * KB * 2048, (size_t)newNT * KB * 2048, st)) return 1;
+  if (h->idxp16_valid && grow_keep(h, &h->idxp16, &h->idxp16_cap, (size_t)NT * KB * 1024, (size_t)newNT * KB * 1024, st)) return 1;
+  if (h->tags_set) {
+    if (grow_keep(h, h->idx_tags, (size_t)NT * 32 * 8, (size_t)newNT * 32 * 8, st)) return 1;
+    if (grow_keep(h, h->idx_tag_sum, (size_t)NT * 8, (size_t)newNT * 8, st)) return 1;
+    if (newNT > NT) HIPCHECK(h, hipMemsetAsync((uint64_t *)h->idx_tags.p + NT * 32, 0, (size_t)(newNT - NT) * 32 * 8, st));
+  }
+  if (h->groups_set && grow_keep(h, h->idx_groups, (size_t)N * 8, (size_t)newN * 8, st)) return 1;
+  if (h->bias_set && grow_keep(h, h->idx_bias, (size_t)NT * 32 * 4, (size_t)newNT * 32 * 4, st)) return 1;  // (launch_bias_prepare zeroes the padding)
+  if (grow_keep(h, h->idx_norm2, h->idx_norm2_valid ? (size_t)N * 4 : 0, (size_t)newN * 4, st)) return 1;
+  if (drop_rm) h->idx_rm_valid = false;
+  if (drop_x3) h->idx_x3_valid = false;
+  return 0;
+}
+
+// the device half of every form: operands on the device, index_delta_check passed.  One synchronisation of `st` at the end
+// (idx_norm_max lives on the host, and the device's verdict on the ids is read with it).
+int index_apply_delta(sse_handle *h, const IndexDelta &d, hipStream_t st) {
+  if (d.M == 0) return 0;
+  const int S = h->idx_S, KG = (S + 7) / 8;
+  const int64_t N = h->idx_N, newN = d.append ? N + d.M : N;
+  const bool rows = d.rows32 || d.rows64;
+  if (d.append) {
+    if (index_grow(h, newN, st)) return 1;
+  } else if (rows && reserve(h, h->idx_norm2, (size_t)N * sizeof(float))) {  // (not valid yet whenever this reallocates)
+    return 1;
+  }
+  if (reserve(h, h->s_tmp2, 16)) return 1;
+  if (d.check_ids) HIPCHECK(h, launch_index_ids_check(d.ids, d.M, h->idx_base, h->idx_base + N, h->err_flag, st));
+  const IndexRowList rl{d.append ? nullptr : d.ids, h->idx_base, N, d.M, d.check_ids ? h->err_flag : nullptr};
+  if (rows) {
+    float *norm2 = (float *)h->idx_norm2.p;
+    if (!h->idx_norm2_valid) {  // first update after an upload: every row's sum from the fragment copy, as the pack formed it
+      const IndexRowList all{nullptr, h->idx_base, 0, N, nullptr};
+      HIPCHECK(h, launch_index_row_norms(all, h->idxp, S, h->idx_norm_vec, norm2, st));
+      h->idx_norm2_valid = true;
+    }
+    HIPCHECK(h, launch_index_scatter_rows(rl, d.rows32, d.rows64, S, h->idxp, h->idx_rm_valid ? (float *)h->idx_rm.p : nullptr,
+                                          h->idx64, st));
+    HIPCHECK(h, launch_index_row_norms(rl, h->idxp, S, h->idx_norm_vec, norm2, st));
+    HIPCHECK(h, hipMemsetAsync(h->s_tmp2.p, 0, 4, st));
+    HIPCHECK(h, launch_index_norm_max(norm2, newN, rl.err, (float *)h->s_tmp2.p, st));
+    if (h->idx_x3_valid) HIPCHECK(h, launch_frag32_to_split_bf16_rows(rl, h->idxp, KG, h->idx_x3.p, st));
+    if (h->idxp16_valid) HIPCHECK(h, launch_frag32_to_bf16_rows(rl, h->idxp, KG, h->idxp16, st));
+  }
+  if (d.tags || d.groups || d.bias) {
+    const int64_t newNT = (newN + 31) / 32;
+    HIPCHECK(h, launch_index_scatter_cols(rl, d.tags, (uint64_t *)h->idx_tags.p, d.groups, (int64_t *)h->idx_groups.p, d.bias,
+                                          (float *)h->idx_bias.p, st));
+    // the touched tiles' ORs and max |bias| fall as well as rise: both are formed again from the columns (O(N) words)
+    if (d.tags) HIPCHECK(h, launch_tag_tile_summary((const uint64_t *)h->idx_tags.p, newNT, (uint64_t *)h->idx_tag_sum.p, st));
+    if (d.bias) {
+      HIPCHECK(h, hipMemsetAsync(h->idx_bias_absmax.p, 0, sizeof(float), st));
+      HIPCHECK(h, launch_bias_prepare((float *)h->idx_bias.p, newN, newNT, (float *)h->idx_bias_absmax.p, st));
+    }
+  }
+  if (rows) HIPCHECK(h, hipMemcpyAsync(h->pin_small + 1, h->s_tmp2.p, 4, hipMemcpyDeviceToHost, st));
+  if (d.check_ids) {
+    int32_t bits = 0;
+    if (check_err_flag(h, st, &bits)) return 1;
+  } else {
+    HIPCHECK(h, sync_stream(st));
+  }
+  if (rows) {
+    float n2;
+    memcpy(&n2, h->pin_small + 1, 4);
+    h->idx_norm_max = std::sqrt(n2);
+  }
+  h->idx_N = newN;
+  if (d.append) h->index_append_rows += d.M;
+  else h->index_update_calls += 1, h->index_update_rows += d.M;
+  return 0;
+}
+
+// the host forms: ids in range and strictly increasing, a finite bias (both before anything is touched), then every operand
+// staged on the device in one buffer
+template <typename T>
+int index_delta_host(sse_handle *h, const char *name, bool append, const int64_t *ids, const T *rows, int64_t M,
+                     const uint64_t *tags, const int64_t *groups, const float *bias) {
+  if (index_delta_check(h, name, append, sizeof(T) == 8, rows != nullptr, M, tags, groups, bias)) return 1;
+  if (M == 0) return 0;
+  if (!append) {
+    if (!ids) return fail(h, "%s: ids must not be NULL", name);
+    for (int64_t m = 0; m < M; ++m) {
+      if (ids[m] < h->idx_base || ids[m] >= h->idx_base + h->idx_N)
+        return fail(h, "%s: ids[%lld] = %lld is outside the index [%lld, %lld); the index is unchanged", name, (long long)m,
+                    (long long)ids[m], (long long)h->idx_base, (long long)(h->idx_base + h->idx_N));
+      if (m > 0 && ids[m - 1] >= ids[m])
+        return fail(h, "%s: ids must be strictly increasing (ids[%lld] = %lld after %lld); the index is unchanged", name, (long long)m,
+                    (long long)ids[m], (long long)ids[m - 1]);
+    }
+  }
+  if (bias)
+    for (int64_t m = 0; m < M; ++m)
+      if (!std::isfinite(bias[m]))
+        return fail(h, "%s: bias[%lld] = %g is not finite; the index is unchanged", name, (long long)m, (double)bias[m]);
+  const size_t S = (size_t)h->idx_S;
+  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_rows = rows ? pad((size_t)M * S * sizeof(T)) : 0, b8 = pad((size_t)M * 8), b4 = pad((size_t)M * 4);
+  if (reserve(h, h->s_upd, b_rows + 3 * b8 + b4)) return 1;
+  char *base = (char *)h->s_upd.p;
+  auto put = [&](size_t off, const void *src, size_t bytes) -> const void * {
+    if (!src) return nullptr;
+    return hipMemcpy(base + off, src, bytes, hipMemcpyHostToDevice) == hipSuccess ? base + off : (const void *)-1;
+  };
+  IndexDelta d{};
+  d.name = name;
+  d.append = append;
+  d.M = M;
+  const void *r = put(0, rows, (size_t)M * S * sizeof(T));
+  d.ids = (const int64_t *)put(b_rows, append ? nullptr : ids, (size_t)M * 8);
+  d.tags = (const uint64_t *)put(b_rows + b8, tags, (size_t)M * 8);
+  d.groups = (const int64_t *)put(b_rows + 2 * b8, groups, (size_t)M * 8);
+  d.bias = (const float *)put(b_rows + 3 * b8, bias, (size_t)M * 4);
+  const void *bad = (const void *)-1;
+  if (r == bad || d.ids == bad || d.tags == bad || d.groups == bad || d.bias == bad) return fail(h, "%s: staging copy failed", name);
+  if (sizeof(T) == 8) d.rows64 = (const double *)r;
+  else d.rows32 = (const float *)r;
+  return index_apply_delta(h, d, nullptr);
 }
 
 // splits of the index range for a candidate / collect sweep (see score_dev_locked)
@@ -2609,7 +2824,9 @@ int64_t sse_handle::*const HOST_COUNTERS[] = {&sse_handle::persist_fallbacks, &s
                                               &sse_handle::train_split_repacks, &sse_handle::train_generic_repacks,
                                               &sse_handle::train_inbatch_steps, &sse_handle::score_lse_calls,
                                               &sse_handle::train_class_steps, &sse_handle::train_open_steps,
-                                              &sse_handle::train_global_inbatch_steps};
+                                              &sse_handle::train_global_inbatch_steps,
+                                              &sse_handle::index_update_calls, &sse_handle::index_update_rows,
+                                              &sse_handle::index_append_rows, &sse_handle::index_grow_copies};
 
 // every name sse_get_counter answers: its group and its word there (CG_HOST: entry of HOST_COUNTERS; CG_PATH: entry of
 // sse_handle::lstm_path_calls; a device group: the word the kernels of that family count in)
@@ -2679,6 +2896,12 @@ const struct {
     // sse_score_lse* (score_lse.hip): calls that passed their checks, index tiles its sweep skipped
     {"score_lse_calls", CG_HOST, 13},
     {"score_lse_tiles_skipped", CG_LSE, 0},
+    // sse_index_update* / sse_index_append*: update calls and the rows they named, rows appended, appends that reallocated
+    // the fragment copy
+    {"index_update_calls", CG_HOST, 17},
+    {"index_update_rows", CG_HOST, 18},
+    {"index_append_rows", CG_HOST, 19},
+    {"index_grow_copies", CG_HOST, 20},
 };
 
 static int read_dev_counter(sse_handle *h, const DevCounters &g, int word, int64_t *value) {
@@ -2900,10 +3123,61 @@ int sse_index_upload_f64(sse_handle *h, const double *rows_host, int64_t N, int3
     h->idx64 = nullptr;
   }
   HIPCHECK(h, hipMalloc((void **)&h->idx64, (size_t)N * S * sizeof(double)));
+  h->idx64_cap = (size_t)N * S * sizeof(double);
   HIPCHECK(h, hipMemcpy(h->idx64, rows_host, (size_t)N * S * sizeof(double), hipMemcpyHostToDevice));
   if (reserve(h, h->s_tmp, (size_t)N * S * sizeof(float))) return 1;
   HIPCHECK(h, launch_f64_to_f32(h->idx64, (float *)h->s_tmp.p, N * S, nullptr));
   return index_from_dev_rows(h, (const float *)h->s_tmp.p, N, S, id_base, nullptr);
+}
+
+int sse_index_shape(sse_handle *h, int64_t *N, int32_t *S, int64_t *id_base, float *norm_max) {
+  SSE_ENTER(h);
+  const bool resident = h->idxp != nullptr && h->idx_N > 0;
+  if (N) *N = resident ? h->idx_N : 0;
+  if (S) *S = resident ? h->idx_S : 0;
+  if (id_base) *id_base = resident ? h->idx_base : 0;
+  if (norm_max) *norm_max = resident ? h->idx_norm_max : 0.0f;
+  return 0;
+}
+
+int sse_index_update(sse_handle *h, const int64_t *ids, const float *rows, int64_t M, const uint64_t *tags, const int64_t *groups,
+                     const float *bias) {
+  SSE_ENTER(h);
+  return index_delta_host<float>(h, "sse_index_update", false, ids, rows, M, tags, groups, bias);
+}
+
+int sse_index_update_f64(sse_handle *h, const int64_t *ids, const double *rows, int64_t M, const uint64_t *tags,
+                         const int64_t *groups, const float *bias) {
+  SSE_ENTER(h);
+  return index_delta_host<double>(h, "sse_index_update_f64", false, ids, rows, M, tags, groups, bias);
+}
+
+int sse_index_append(sse_handle *h, const float *rows, int64_t M, const uint64_t *tags, const int64_t *groups, const float *bias) {
+  SSE_ENTER(h);
+  return index_delta_host<float>(h, "sse_index_append", true, nullptr, rows, M, tags, groups, bias);
+}
+
+int sse_index_append_f64(sse_handle *h, const double *rows, int64_t M, const uint64_t *tags, const int64_t *groups,
+                         const float *bias) {
+  SSE_ENTER(h);
+  return index_delta_host<double>(h, "sse_index_append_f64", true, nullptr, rows, M, tags, groups, bias);
+}
+
+int sse_index_update_dev(sse_handle *h, const int64_t *ids_dev, const float *rows_dev, int64_t M, const uint64_t *tags_dev,
+                         const int64_t *groups_dev, const float *bias_dev, void *stream) {
+  SSE_ENTER(h);
+  if (index_delta_check(h, "sse_index_update_dev", false, false, rows_dev != nullptr, M, tags_dev, groups_dev, bias_dev)) return 1;
+  if (M > 0 && !ids_dev) return fail(h, "sse_index_update_dev: ids must not be NULL");
+  IndexDelta d{"sse_index_update_dev", false, ids_dev, true, rows_dev, nullptr, M, tags_dev, groups_dev, bias_dev};
+  return index_apply_delta(h, d, (hipStream_t)stream);
+}
+
+int sse_index_append_dev(sse_handle *h, const float *rows_dev, int64_t M, const uint64_t *tags_dev, const int64_t *groups_dev,
+                         const float *bias_dev, void *stream) {
+  SSE_ENTER(h);
+  if (index_delta_check(h, "sse_index_append_dev", true, false, rows_dev != nullptr, M, tags_dev, groups_dev, bias_dev)) return 1;
+  IndexDelta d{"sse_index_append_dev", true, nullptr, false, rows_dev, nullptr, M, tags_dev, groups_dev, bias_dev};
+  return index_apply_delta(h, d, (hipStream_t)stream);
 }
 
 int sse_score_topk_dev(sse_handle *h, const float *q_dev, int32_t Q, int32_t k, double *out_scores_dev,

@@ -344,6 +344,62 @@ hipError_t launch_frag32_to_bf16(const float *idxp, int64_t NT, int KG, void *ou
 // lo = bf16(x - hi)): the A operand of the small-index scorer's split candidate pass (SmallIndexArgs::idx_x3)
 hipError_t launch_frag32_to_split_bf16(const float *idxp, int64_t NT, int KG, void *out, hipStream_t stream);
 
+// ---------------------------------------------------------------------------
+// In-place updates of the resident index (index_update.hip; the tile-list converters stand beside the whole-index ones in
+// score_topk.hip).  A row list is M rows given either by `ids` (global ids, strictly increasing: row = ids[m] - id_base) or,
+// with ids == nullptr, as the run row0 .. row0 + M - 1 (an append).  Every kernel that writes reads the handle's error word
+// first and writes nothing once SSE_ERR_INDEX_IDS is set in it.
+#define SSE_ERR_INDEX_IDS 128
+struct IndexRowList {
+  const int64_t *ids;  // [M] global ids or nullptr
+  int64_t id_base, row0, M;
+  const int32_t *err;  // the error word, or nullptr: never gated
+};
+__device__ __forceinline__ int64_t index_list_row(const IndexRowList &l, int64_t m) { return l.ids ? l.ids[m] - l.id_base : l.row0 + m; }
+__device__ __forceinline__ bool index_list_refused(const IndexRowList &l) { return l.err && (*l.err & SSE_ERR_INDEX_IDS) != 0; }
+// first row of its tile in the list (the rows are increasing): the tile converters run once per touched tile
+__device__ __forceinline__ bool index_list_tile_head(const IndexRowList &l, int64_t m) {
+  return m == 0 || (index_list_row(l, m - 1) >> 5) != (index_list_row(l, m) >> 5);
+}
+// The per-row sum of squares behind idx_norm_max, one copy for the pack (pack.hip) and the update: the 16-byte-piece form
+// (8 lanes of a row take the pieces q = lane, lane + 8, ...; C % 4 == 0 and aligned rows) and the element form (64 lanes of
+// a row take the elements c = lane, lane + 64, ...).
+__device__ __forceinline__ float row_sumsq_add4(float ss, const f32x4 &v) {
+  ss += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+  return ss;
+}
+__device__ __forceinline__ float row_sumsq_reduce8(float ss) {
+  ss += __shfl_xor(ss, 1);
+  ss += __shfl_xor(ss, 2);
+  ss += __shfl_xor(ss, 4);
+  return ss;
+}
+__device__ __forceinline__ float row_sumsq_add1(float ss, float x) {
+  ss += x * x;
+  return ss;
+}
+__device__ __forceinline__ float row_sumsq_reduce64(float ss) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+  return ss;
+}
+// ids[M] inside [lo, hi) and strictly increasing, else SSE_ERR_INDEX_IDS is raised in *err
+hipError_t launch_index_ids_check(const int64_t *ids, int64_t M, int64_t lo, int64_t hi, int32_t *err, hipStream_t st);
+// rows [M][S] (float, or double: idx64 patched and the fp32 images formed from (float) of it) -> the listed rows of idxp
+// (16-byte pieces, zero padded to KG * 8), of idx_rm and of idx64 (each may be nullptr)
+hipError_t launch_index_scatter_rows(const IndexRowList &l, const float *rows32, const double *rows64, int S, float *idxp,
+                                     float *idx_rm, double *idx64, hipStream_t st);
+// norm2[row] = the sum of squares the pack formed for that row, from idxp; vec: the 16-byte-piece form
+hipError_t launch_index_row_norms(const IndexRowList &l, const float *idxp, int S, bool vec, float *norm2, hipStream_t st);
+// *out_bits (zeroed by the caller) = max norm2[0 .. N)
+hipError_t launch_index_norm_max(const float *norm2, int64_t N, const int32_t *err, float *out_bits, hipStream_t st);
+// the listed rows' tag words, group keys and bias values (a nullptr source leaves that column alone)
+hipError_t launch_index_scatter_cols(const IndexRowList &l, const uint64_t *tags_in, uint64_t *tags, const int64_t *groups_in,
+                                     int64_t *groups, const float *bias_in, float *bias, hipStream_t st);
+// launch_frag32_to_bf16 / launch_frag32_to_split_bf16 for the tiles of the listed rows only (the same per-tile device code)
+hipError_t launch_frag32_to_bf16_rows(const IndexRowList &l, const float *idxp, int KG, void *out, hipStream_t st);
+hipError_t launch_frag32_to_split_bf16_rows(const IndexRowList &l, const float *idxp, int KG, void *out, hipStream_t st);
+
 #define SSE_COLLECT_CAP 4096   // rows one query can collect (exact path); more -> float64 brute force
 #define SSE_MAX_SELECT_K 1024  // largest k the collect path serves
 

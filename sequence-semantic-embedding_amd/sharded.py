@@ -176,6 +176,21 @@ class ShardedIndex(object):
         if rows.shape[0] > 0:
             self.handle.index_set_dev(rows.data_ptr(), rows.shape[0], rows.shape[1], id_base=self.start)
 
+    def update_rows(self, ids, rows=None, tags=None, groups=None, bias=None):
+        """Replace rows (and / or their tag words, group keys, bias values) of the sharded index in place: ids int64 [M]
+        GLOBAL ids, rows [M,S] and the columns as Handle.index_update takes them (host arrays, identical on every rank).
+        Each rank applies the ids that fall in its shard: global ids make this a filter, nothing is exchanged.  Returns
+        the number of ids this rank applied.  There is no sharded append: the shard bounds are fixed at construction."""
+        import numpy as np
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        if ((ids < 0) | (ids >= self.n_total)).any():
+            raise ValueError("update_rows: ids must be in [0, %d)" % self.n_total)
+        mine = np.flatnonzero((ids >= self.start) & (ids < self.end))
+        if mine.size:
+            pick = lambda x: None if x is None else np.asarray(x)[mine]
+            self.handle.index_update(ids[mine], pick(rows), pick(tags), pick(groups), pick(bias))
+        return int(mine.size)
+
     def score_topk(self, queries, k, block=8192):
         """queries: CUDA float32 [Q,S] (identical on every rank).  Returns the global
         top-k (scores float64 [Q,k], row ids int64 [Q,k]) on every rank, for any 1 <= k <= n_total (ValueError

@@ -150,6 +150,38 @@ def hard_negatives(handle, queries, positives, n):
     return ids, scores
 
 
+def refresh_rows(model, handle, ids, token_rows, tags=None, groups=None, bias=None, normalize=True):
+    """Re-encode changed targets and patch them into the resident index in place: ids int64 [M] global ids (any order, the
+    last of a repeated id wins), token_rows int32 [M,T] their padded token rows.  The rows are encoded on the device
+    (Handle.encode_dev, target side of `model`) and handed to Handle.index_update_dev as they lie there: the encodings never
+    leave the device.  tags / groups / bias: optional new column values per id.  What hard-learning mining and a serving
+    process call when targets change; `handle` is the handle holding the index (model.handle unless sharded)."""
+    import torch
+    ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+    toks = np.ascontiguousarray(token_rows, dtype=np.int32)
+    if toks.ndim != 2 or toks.shape[0] != ids.shape[0]:
+        raise ValueError("token_rows must be [M,T], one row per id")
+    order = (ids.shape[0] - 1 - np.argsort(ids[::-1], kind="stable")).astype(np.int64)   # sorted; of equal ids the last first
+    order = order[np.concatenate([[True], ids[order][1:] != ids[order][:-1]])] if ids.shape[0] else order
+    M = int(order.shape[0])
+    if M == 0:
+        return 0
+    dev = torch.device("cuda:%d" % model.handle.cfg.device)
+    up = lambda x, dt: None if x is None else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dt).reshape(-1)[order])).to(dev)
+    d_ids = torch.from_numpy(np.ascontiguousarray(ids[order])).to(dev)
+    d_tok = torch.from_numpy(np.ascontiguousarray(toks[order])).to(dev)
+    enc = torch.empty((M, model.handle.cfg.encoding_size), dtype=torch.float32, device=dev)
+    d_tags = up(None if tags is None else np.asarray(tags, np.uint64).view(np.int64), np.int64)
+    d_groups, d_bias = up(groups, np.int64), up(bias, np.float32)
+    torch.cuda.synchronize(dev)
+    model.handle.encode_dev(1, d_tok.data_ptr(), M, toks.shape[1], normalize, enc.data_ptr())
+    if handle is not model.handle:
+        model.handle.synchronize()
+    ptr = lambda t: None if t is None else t.data_ptr()
+    handle.index_update_dev(d_ids.data_ptr(), enc.data_ptr(), M, ptr(d_tags), ptr(d_groups), ptr(d_bias))
+    return M
+
+
 def csls_bias(handle, target_rows, source_rows, k=10, block=4096):
     """The per-row bias that turns Handle.score_topk_biased (weight 1.0) into the CSLS ranking of cross-lingual retrieval.
     CSLS ranks a source x against targets t by 2 cos(x,t) - r_T(x) - r_S(t), r_S(t) the mean score of t's k nearest SOURCE

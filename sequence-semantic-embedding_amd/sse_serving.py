@@ -71,11 +71,39 @@ class Ranker(object):
         self._index_gen = self.model.handle.index_gen
         self._encodings = encodings
 
+    def _guard(self):
+        """the lock rank() and update_targets() share: the micro-batcher's worker ranks under it, so an update never lands
+        between a rank's index check and its sweep (created on first use: a Ranker may be assembled without __init__)"""
+        return self.__dict__.setdefault("_lock", threading.RLock())
+
+    def update_targets(self, ids, token_rows, normalize=True):
+        """Re-encode the targets at row ids `ids` from their padded token rows and patch the resident index in place
+        (Handle.index_update): the next rank() returns the new rows.  The index of a model directory holds the float64 rows
+        parsed from its file, so the new encodings go in through the float64 form, and into the copy that is re-uploaded
+        when another index was scored on this handle (sse_index.refresh_rows is the device-resident path, for float32
+        indexes).  Runs under the lock rank() takes; no HTTP route calls it."""
+        with self._guard():
+            h = self.model.handle
+            if not self.__dict__.get("_encodings_owned"):      # once: the rows may be the loader's (or read-only)
+                self._encodings = np.array(self._encodings)
+                self._encodings_owned = True
+            if h.index_gen != self._index_gen:
+                h.index_upload(self._encodings)
+                self._index_gen = h.index_gen
+            ids = np.asarray(ids, np.int64).reshape(-1)
+            rows = h.encode(1, np.asarray(token_rows, np.int32), normalize).astype(self._encodings.dtype)
+            self._encodings[ids] = rows                        # first the copy a re-upload would use, then the device
+            h.index_update(ids, rows)
+
     def tokens(self, text):
         """webserver.py:135-142: encode(lower-cased text), left-pad / truncate to max_seq_length."""
         return sse_text.pad_tokens(self.encoder.encode(text.lower()), self.max_seq_length)
 
     def rank(self, token_rows, nbest, normalize, after=None, prob_scale=None):
+        with self._guard():
+            return self._rank(token_rows, nbest, normalize, after, prob_scale)
+
+    def _rank(self, token_rows, nbest, normalize, after=None, prob_scale=None):
         """Top-`nbest` (score, target id, target name) per token row; one encode + one sweep for all rows.
         after = (scores [B], row ids [B]): the next `nbest` (at most 1024) after each row's (score, row id) cursor instead, in
         the same order (Handle.score_topk_after), as (score, target id, target name, row id) -- a list may be shorter than
